@@ -3,8 +3,13 @@
 missions (start/end time factor 1.5), minimum-snap solve + sampling followed by 10 000 fused
 controller + dynamics ticks, on synthetic missions (SURVEY.md 8(d) generator).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs when `--dump-outputs DIR` is given
+(`dump_outputs`) and prints the line.  Everything else -- the untimed diagnostics, the config-4 leg, the CPU baseline with
+its oracle comparison -- runs with `--full` only (each can still be left out there with `--no-extras`, `--no-config4`,
+`--no-cpu-baseline`).
 
 Started WITHOUT a launcher (`python bench.py --gpus N`, N > 1, no WORLD_SIZE in the environment) it launches its N ranks
 itself: the parent touches no GPU, checks that N GPUs are visible (exit 2 with a message otherwise), starts N children
@@ -17,10 +22,10 @@ sampler; ONE call into the C ABI), vehicle reset, then 10 000 control ticks as 1
 shards by mission index over ranks with no data-path collective (weak scaling: 65 536 UAVs per GPU).
 
 Prints ONE JSON line on rank 0.  `value` = UAV control ticks of all ranks / wall time of the K timed steps
-(planning time included in the denominator).  `roofline` prices the dominant kernel (control_rollout) against
-the HBM peak with the algorithmic 112.8 B per UAV tick of SURVEY.md 8(d), on the average launch duration
-measured with HIP events on the launch stream inside the timed region; `cpu_baseline` is the CPU oracle timed
-on this box's host cores on a bounded sample.  `config4` is BASELINE.json configs[3] run on the same N GPUs
+(planning time included in the denominator); `ms_per_step` = that wall time / K.  `roofline` prices the dominant kernel
+(control_rollout) against the HBM peak with the algorithmic 112.8 B per UAV tick of SURVEY.md 8(d), on the average launch
+duration measured with HIP events on the launch stream inside the timed region.  With `--full`: `cpu_baseline` is the CPU
+oracle timed on this box's host cores on a bounded sample.  `config4` is BASELINE.json configs[3] run on the same N GPUs
 (262 144 UAVs in total = strong scaling, 8-segment missions, 5 000 ticks, final gather of the trajectories to
 rank 0 over RCCL timed and verified) with compute-only and compute+gather rates side by side, for the gather of the
 ROWS (20.8 GB into the root's links) and for the gather of the PLAN (0.4 GB; the root re-samples the peers' rows from
@@ -48,7 +53,7 @@ for p in (ROOT, PKG):
         sys.path.insert(0, p)
 os.environ.setdefault("UAVAC_AUTOBUILD", "1")       # a never-built checkout compiles the HIP library on first use (no fallback)
 _LIB = os.path.join(PKG, "lib", "libuavac.so")
-if not os.path.exists(_LIB) and int(os.environ.get("LOCAL_RANK", "0")) != 0:
+if not os.path.exists(_LIB) and int(os.environ.get("LOCAL_RANK", "0")) != 0 and "--launch-check" not in sys.argv:   # (no library used there)
     for _ in range(1200):                           # ... once: the other ranks of the node wait for local rank 0's build
         if os.path.exists(_LIB):                    # (the Makefile links to a temporary name and renames: it is complete)
             break
@@ -68,6 +73,7 @@ GATHER_STALL_EXIT = 3 if os.environ.get("UAVAC_BENCH_STRICT") == "1" else 0     
 GATHER_FAILURE_EXIT = 3                                                          # wrong data, a failed collective: never rc 0
 C4_TOTAL, C4_SEGMENTS, C4_TICKS = 262144, 8, 5000           # BASELINE.json configs[3]
 ROLLOUT_SOURCES = ("csrc/control_rollout.hip", "csrc/control_law.h", "csrc/minsnap_eval.h", "csrc/minsnap_yaw.h", "csrc/uavac_internal.h")
+DUMP_SEED, DUMP_MISSIONS, DUMP_ROWS, DUMP_LANES = 20261016, 4096, 65536, 64     # --dump-outputs: the fixed samples (~44 MB in all)
 
 
 def missions(B_total, m, lo, hi):
@@ -136,6 +142,29 @@ def planning_traffic():
 def nat_build_info():
     from uav_ac import _native as nat
     return nat.lib().uavac_build_info().decode()
+
+
+def dump_outputs(out_dir, plan, fleet, log):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as float64 DIR/<name>.npy.  The plan's per-mission
+    arrays and the fleet's final state whole; of the larger outputs a fixed sample (DUMP_SEED), stored beside the indices it
+    took: the coefficients of DUMP_MISSIONS missions, DUMP_ROWS trajectory rows, the last launch's state log of DUMP_LANES
+    vehicles.  The inputs depend on the arguments alone, so two builds of the project compare file for file."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    missions_ = np.sort(rng.choice(plan.B, min(plan.B, DUMP_MISSIONS), replace=False))
+    rows = np.sort(rng.integers(0, plan.total_rows, DUMP_ROWS))
+    lanes = np.sort(rng.choice(plan.B, min(plan.B, DUMP_LANES), replace=False))
+    on_dev = lambda a: torch.as_tensor(a, device=plan.traj.device)      # noqa: E731
+    arrays = {"times": plan.times, "seg_rows": plan.seg_rows, "row_offsets": plan.row_offsets, "status": plan.status,
+              "first_yaw": plan.first_yaw,
+              "coeffs_sample": plan.coeffs.index_select(0, on_dev(missions_)), "coeffs_sample_missions": missions_,
+              "traj_sample": plan.traj.index_select(0, on_dev(rows)), "traj_sample_rows": rows,
+              "state": fleet.X, "trajectory_index": fleet.trajectory_index,
+              "state_log_sample": log.index_select(2, on_dev(lanes)), "state_log_sample_lanes": lanes}
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if torch.is_tensor(a) else a
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
 
 
 def cpu_baseline(eng=None, wps=None):
@@ -284,9 +313,15 @@ def main():
                                                              "flyable-distribution rate)")
     ap.add_argument("--launch-check", action="store_true", help="rendezvous + one JSON line, no GPU work (tests of the "
                                                                 "self-launcher)")
+    ap.add_argument("--full", action="store_true", help="after the headline also run the untimed diagnostics, the BASELINE "
+                                                        "configs[3] leg and the CPU baseline (each unless its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float64, "
+                                                          "fixed samples of the large ones)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 or os.environ.get("UAVAC_BENCH_FORCE_DIST") == "1":
         # HIP maps a process's streams round-robin onto a few hardware queues (default 4), and two streams that share a queue run
         # one after the other.  The config-4 leg of a multi-rank run uses a handful of them at once on the root -- its flight, the
@@ -376,6 +411,8 @@ def main():
         elapsed = float(t.item())
     flags = eng.take_flags()
     assert flags == [0, 0, 0, 0], f"planning flags raised: {flags}"
+    if args.dump_outputs and rank == 0:                  # (before any untimed pass of --full writes into these buffers again)
+        dump_outputs(args.dump_outputs, plan, fleet, log)
 
     plan_ms = [a.elapsed_time(b) for a, b, _ in rec]
     # e1 -> e2 spans reset (a 5 us kernel) + the n_chunks rollout launches (each preceded by its ~2 us aligner launch);
@@ -492,14 +529,14 @@ def main():
 
     # The headline exists: say so on stderr at once, before the diagnostics and before any config-4 collective -- a crash inside
     # RCCL on first contact with real peers cannot lose it (stdout still carries exactly ONE line, at the end).
-    if rank == 0:
+    if rank == 0 and args.full:
         print(json.dumps({"early": True, "note": "headline measured; diagnostics and the config-4 leg follow; the full line goes to stdout",
                           **{k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "scaling", "dtype")},
                           "roofline_frac": out["roofline"]["frac"], "minsnap_segments_per_s": out["minsnap"]["value"]}),
               file=sys.stderr, flush=True)
 
     # ---- untimed diagnostics: per-launch durations of one more step, and the rollout on a flyable distribution -------
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         for attempt in range(2):                      # the first pass creates its 20 events (slow) and is thrown away
             eng.replan(plan)
             fleet.reset()
@@ -594,7 +631,7 @@ def main():
     #            (`config4.end_to_end`).  Same rows on rank 0, bit for bit -- verified against the literal row gather in this run.
     gather_err = None
     comm = None
-    if not args.no_config4:
+    if args.full and not args.no_config4:
         del plan, fleet, log
         torch.cuda.empty_cache()
         from uav_ac.sharding import balanced_root_share, candidate_shard_sizes, measure_tick_table, shard_bounds, shard_sizes
@@ -959,7 +996,7 @@ def main():
     if gather_err is not None:
         out["gather_error"] = gather_err
         out["gather_error_kind"] = "mismatch" if ("do not match" in gather_err or "differ" in gather_err) else "collective"
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(eng, wps)
         out["checks"]["yaw_2pi_forks"] = yaw_fork_census(eng)
     print(json.dumps(out), flush=True)

@@ -43,6 +43,12 @@ def test_fewer_gpus_than_asked_for_is_an_error_not_a_line():
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def test_steps_below_one_are_refused_before_any_gpu_work():
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+    assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
 def test_world_size_must_match_gpus():
     """Under a launcher with another world size the bench refuses instead of printing a line for the wrong N."""
     e = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
@@ -62,7 +68,7 @@ def test_rehearsal_ranks_through_the_self_launcher_plan_gather_equals_row_gather
     # test injects.  Either way the line says which table was used and the cut follows from it.
     table = [[30000, 0.9, 0.02], [90000, 1.7, 0.018], [140000, 2.7, 0.018]]
     extra = {} if n == 2 else {"UAVAC_BENCH_TICK_TABLE": json.dumps(table)}
-    r = _run(["--gpus", str(n), "--steps", "1", "--warmup", "1", "--no-extras"], UAVAC_BENCH_REHEARSAL="1", **extra)
+    r = _run(["--gpus", str(n), "--steps", "1", "--warmup", "1", "--full", "--no-extras"], UAVAC_BENCH_REHEARSAL="1", **extra)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == n and "REHEARSAL" in line and "gather_error" not in line
@@ -84,7 +90,7 @@ def test_rehearsal_ranks_through_the_self_launcher_plan_gather_equals_row_gather
     assert c4["pipelined_plan_gather_verified"] is True and c4["compute_rows_free_ms"] > 0
     assert c4["plan_gather_ms"] > 0 and c4["steps_per_s_with_plan_gather"] > 0
     if n == 2:                                  # the same with equal blocks
-        r = _run(["--gpus", "2", "--steps", "1", "--warmup", "1", "--no-extras", "--equal-shards"], UAVAC_BENCH_REHEARSAL="1")
+        r = _run(["--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--no-extras", "--equal-shards"], UAVAC_BENCH_REHEARSAL="1")
         assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
         c4 = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])["config4"]
         assert c4["shard_sizes"] == [131072, 131072] and c4["root_share"] is None
@@ -97,7 +103,7 @@ def test_rehearsal_with_a_root_that_flies_nothing():
     flight beside its own sampler runs a quarter slower): `shard_sizes[0] == 0`.  Two ranks on one GPU with `--root-share 0`: rank 0
     plans and flies nothing, takes part in every gather with an empty block, and holds all rows at the end -- row gather, one-shot
     plan gather and the pipelined order all verified."""
-    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "1", "--no-extras", "--root-share", "0"], UAVAC_BENCH_REHEARSAL="1")
+    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--no-extras", "--root-share", "0"], UAVAC_BENCH_REHEARSAL="1")
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     c4 = line["config4"]
@@ -113,7 +119,7 @@ def test_rehearsal_with_one_wrong_gathered_value_exits_3():
     forced-world-1 runs only): the re-sampled plan no longer equals the gathered rows, the line is still printed with the
     headline and says `mismatch`, every rank exits 3 and so does the launcher -- without UAVAC_BENCH_STRICT."""
     table = [[30000, 0.9, 0.02], [140000, 2.7, 0.018]]
-    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "1", "--no-extras", "--equal-shards"], UAVAC_BENCH_REHEARSAL="1",
+    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--no-extras", "--equal-shards"], UAVAC_BENCH_REHEARSAL="1",
              UAVAC_BENCH_CORRUPT_GATHER="1", UAVAC_BENCH_TICK_TABLE=json.dumps(table))
     assert r.returncode == 3, (r.returncode, (r.stdout + r.stderr)[-3000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -130,7 +136,7 @@ def test_two_real_gpus_over_rccl_when_the_box_has_them():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("one GPU visible")
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-extras"])
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-extras"])
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and "REHEARSAL" not in line and "gather_error" not in line

@@ -36,7 +36,7 @@ def test_bench_multi_gpu_path_on_real_rccl_at_world_1():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert "gather_error" not in line and "FORCED_DIST" in line and line["n_gpus"] == 1
@@ -57,7 +57,7 @@ def test_bench_multi_gpu_path_on_real_rccl_at_world_1():
     assert c4["log_pitch"] == 262144 and c4["tick_table"] is None and c4["root_share"] is None      # one rank: nothing to balance
     # ... and ONE wrong value among the gathered rows ends in exit status 3 with the line still printed (round-4 VERDICT 3)
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-extras"], env=dict(env, UAVAC_BENCH_CORRUPT_GATHER="1", MASTER_PORT="29534"),
+                          "--full", "--no-cpu-baseline", "--no-extras"], env=dict(env, UAVAC_BENCH_CORRUPT_GATHER="1", MASTER_PORT="29534"),
                          capture_output=True, text=True, timeout=900)
     assert bad.returncode == 3, (bad.returncode, bad.stderr[-1500:])
     line = json.loads([l for l in bad.stdout.splitlines() if l.startswith("{")][-1])

@@ -512,7 +512,8 @@ def test_bench_line_schema_with_extras():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-config4"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+                        "--no-config4"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -537,6 +538,44 @@ def test_bench_line_schema_with_extras():
     assert m["clock_ghz"] == ck["clock_ghz"] and 0.9 < m["leg_to_leg"] < 1.1
     if rf["traffic"] is not None:                                        # profiles/hbm_traffic.json was measured on these sources
         assert 0.85 < rf["traffic"] / rf["algorithmic_bytes_per_launch"] < 1.05 and rf["frac_counter_bytes"] < rf["frac"]
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """`python bench.py` without --full: the headline of exactly --steps timed steps and nothing after it (no diagnostics, no
+    config-4 leg, no CPU baseline); --dump-outputs leaves the last timed step's outputs as float64 .npy files, 64 MB at most, that
+    agree with the line and with each other."""
+    import json, os, subprocess, sys
+    from bench import missions
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    B, rows = d["config"]["batch_per_gpu"], d["config"]["rows"]
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True and d["value"] > 1e10
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 / (B * d["config"]["ticks"]) - 1) < 1e-9      # value and ms_per_step: one clock
+    assert not {"config4", "cpu_baseline", "rollout_only_flyable"} & set(d) and "per_launch_ms_one_step" not in d["roofline"]
+    assert "clocked_steps" not in d["minsnap"] and '"early"' not in r.stderr
+    files = sorted(out.glob("*.npy"))
+    assert sum(p.stat().st_size for p in files) <= 64 << 20
+    f = {p.stem: np.load(p) for p in files}
+    assert set(f) == {"times", "seg_rows", "row_offsets", "status", "first_yaw", "coeffs_sample", "coeffs_sample_missions",
+                      "traj_sample", "traj_sample_rows", "state", "trajectory_index", "state_log_sample", "state_log_sample_lanes"}
+    assert all(a.dtype == np.float64 for a in f.values())
+    assert f["row_offsets"].shape == (B + 1,) and f["row_offsets"][-1] == rows and not f["status"].any()
+    assert f["traj_sample"].shape == (len(f["traj_sample_rows"]), 11) and f["traj_sample_rows"].max() < rows
+    # the cursors where the line's check says they are; the first coefficient of every sampled mission is its first waypoint
+    assert np.array_equal(f["trajectory_index"], np.minimum(d["config"]["ticks"] // d["config"]["inner_per_outer"], np.diff(f["row_offsets"]) - 1))
+    b = f["coeffs_sample_missions"].astype(np.int64)
+    assert np.allclose(f["coeffs_sample"][:, 0, :], missions(B, d["config"]["segments"], 0, B)[b, 0, :], rtol=0, atol=1e-9)
+    # the last logged tick of the sampled vehicles is their final state
+    lanes = f["state_log_sample_lanes"].astype(np.int64)
+    assert f["state"].shape == (13, B) and f["state_log_sample"].shape == (d["config"]["ticks_per_launch"], 13, len(lanes))
+    assert np.array_equal(f["state_log_sample"][-1], f["state"][:, lanes])
 
 
 def test_full_size_planning_chain_is_the_same_under_every_launch_shape(eng):

@@ -10,14 +10,14 @@ rm -rf "$OUT"; mkdir -p "$OUT"
 export TMPDIR=/tmp
 bash tools/box_mode.sh 2>&1 | grep -E "Unique|sampler" | head -2 > "$OUT/box.txt"
 # 1. kernel trace + stats of the bench command (HIP-event average in the JSON line must agree with the trace average)
-timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-config4 > "$OUT/${TAG}_bench_profiled.json" 2> "$OUT/trace.err"
+timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-config4 > "$OUT/${TAG}_bench_profiled.json" 2> "$OUT/trace.err"
 python3 tools/summarize_trace.py "$(ls $OUT/trace/*kernel_trace.csv | head -1)" "$OUT/${TAG}_bench" > "$OUT/per_dispatch_summary.txt"
 # 2. PMC traffic (three passes) -> hbm_traffic.json + pmc summary
 timeout -s KILL 900 python3 tools/pmc_traffic.py > "$OUT/pmc_traffic.log" 2>&1
 cp gpurun_out/hbm_traffic.json "$OUT/hbm_traffic.json"; cp gpurun_out/${TAG}_pmc_summary.csv "$OUT/${TAG}_pmc_summary.csv"
 cp gpurun_out/hbm_traffic.json profiles/hbm_traffic.json      # so that the bench of step 3 quotes it
-# 3. the plain bench line (what the driver runs)
-python3 bench.py > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err"
+# 3. the bench line with every leg
+python3 bench.py --full > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err"
 # 4. other BASELINE configurations
 python3 tools/config_sweep.py > "$OUT/${TAG}_config_sweep.jsonl" 2>/dev/null
 # 5. small batch: where the cycles go
