@@ -112,6 +112,10 @@ const char *uavac_last_rollout_kernel(const uavac_ctx *ctx);
  * 1.96 ms instead of 1.27 ms.  __graft_entry__.build() refuses a build that crosses the line; this is the same number seen
  * from the running process. */
 int uavac_last_rollout_vgprs(const uavac_ctx *ctx);
+/* Shape of that launch, out[6] = grid (workgroups), threads per workgroup, dynamic LDS bytes per workgroup (the cu_balance /
+ * lds_pad pad included), log pitch (doubles between log rows), 64-UAV tiles, persistent passes (tiles walked per workgroup,
+ * rounded up).  All 0 before the first rollout.  Read-only diagnostics: tests prove which launch form they reached with it. */
+int uavac_last_rollout_launch(const uavac_ctx *ctx, int64_t out[6]);
 /* "libuavac <version>; gfx950; HIP <x.y.z>; <compiler version>" of the build (static string). */
 const char *uavac_build_info(void);
 /* Which physical GPU the ctx runs on: "uuid=<32 hex digits>;pci=<domain:bus:device.function>;name=<gcnArchName>" into buf
@@ -216,6 +220,14 @@ int uavac_minsnap_sample_hits_dev(uavac_ctx *ctx, const double *coeffs, const do
 int uavac_minsnap_sample_derivs_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows,
                                     const int64_t *row_offsets, int B, int m, double dt, double *traj,
                                     double *yaw, double *first_yaw, double *jerk, double *snap);
+/* uavac_minsnap_sample_derivs_dev (rows, optional yaw column, optional first headings) into a row buffer of
+ * traj_capacity_rows rows (yaw, when given, as many values): when row_offsets[B] exceeds it the launch writes nothing and
+ * raises flag 2 (uavac_take_flags), like uavac_minsnap_plan_dev.  row_offsets may point into a larger table (a sub-range of
+ * missions whose offsets stay absolute): the capacity is then that of the whole buffer.  UAVAC_EINVAL for a negative
+ * capacity.  The form every caller should use whose buffer was sized from a row count it did not just read. */
+int uavac_minsnap_sample_capped_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows,
+                                    const int64_t *row_offsets, int B, int m, double dt, double *traj,
+                                    int64_t traj_capacity_rows, double *yaw, double *first_yaw);
 /* The whole planning chain of MinimumSnap.get_trajectory() (obstacles=None; minimum_snap.py:59-61,
  * 97-124) enqueued by ONE call: times + row counts, row offsets, coefficient solve, sampler (+ yaw
  * column when yaw != NULL, + the missions' first headings when first_yaw != NULL) -- four kernel

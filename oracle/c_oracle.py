@@ -59,6 +59,9 @@ def lib():
         _lib.oracle_bench_threads.restype = C.c_int64
         _lib.oracle_bench_threads.argtypes = [C.POINTER(Vehicle), _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                               C.c_int, C.c_double, _P]
+        _lib.oracle_fleet_threads.restype = C.c_int
+        _lib.oracle_fleet_threads.argtypes = [C.POINTER(Vehicle), _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _P, C.c_int,
+                                              _P, C.c_int, _P, C.c_int, C.c_int] + [_P] * 8
         _lib.oracle_segment_intersects_cuboid.restype = C.c_int
         _lib.oracle_segment_intersects_cuboid.argtypes = [_P, _P, _P]
         _lib.oracle_rrt_distances.restype = None
@@ -124,6 +127,45 @@ def bench_threads(wps, velocity: float, dt: float, ticks: int, n_threads: int, b
     done = lib().oracle_bench_threads(C.byref(V), _p(wps), wps.shape[0], wps.shape[1] - 1, float(velocity), float(dt),
                                       int(ticks), int(n_threads), float(budget_s), C.addressof(elapsed))
     return int(done), elapsed.value
+
+
+def default_threads() -> int:
+    """Threads for the whole-batch oracle: the CPUs this process may run on, at most 16 and at most OMP_NUM_THREADS."""
+    n = min(len(os.sched_getaffinity(0)), 16)
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.strip().isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
+def fleet(wps, velocity: float, dt: float, K: int, sel_ticks=(), log_lanes=(), aabbs=None, n_threads: int = None,
+          V: Vehicle | None = None, cmd: bool = False, plan: bool = True):
+    """Every mission of wps (B, m+1, 3) planned by the oracle itself and flown K ticks from hover at its first waypoint, on
+    POSIX threads (`oracle_fleet_threads`).  -> dict: state (B, 26), istate (B, 4), and with `plan` seg_rows (B, m),
+    coeffs (B, 8m, 3), first_yaw (B,); sel_log (n_sel, 13, B) = the state after each tick of `sel_ticks` (the GPU's log layout),
+    with `cmd` also sel_cmd (n_sel, 12, B); lane_log (n_ll, K, 13) = every tick of each lane of `log_lanes`.  Bit for bit what
+    `plan` + `rollout` give lane by lane."""
+    V = V or Vehicle.default()
+    wps = np.ascontiguousarray(wps, dtype=np.float64)
+    B, m = wps.shape[0], wps.shape[1] - 1
+    sel = np.ascontiguousarray(sel_ticks, dtype=np.int32).reshape(-1)
+    lanes = np.ascontiguousarray(log_lanes, dtype=np.int64).reshape(-1)
+    if len(np.unique(sel)) != len(sel) or len(np.unique(lanes)) != len(lanes):
+        raise ValueError("sel_ticks and log_lanes must not repeat")
+    ab = None if aabbs is None else np.ascontiguousarray(aabbs, dtype=np.float64).reshape(-1, 6)
+    out = {"state": np.empty((B, 26)), "istate": np.empty((B, 4), dtype=np.int32),
+           "sel_log": np.empty((len(sel), 13, B)), "lane_log": np.empty((len(lanes), int(K), 13))}
+    if plan:
+        out.update(seg_rows=np.empty((B, m), dtype=np.int32), coeffs=np.empty((B, 8 * m, 3)), first_yaw=np.empty(B))
+    if cmd:
+        out["sel_cmd"] = np.empty((len(sel), 12, B))
+    rc = lib().oracle_fleet_threads(C.byref(V), _p(wps), B, m, float(velocity), float(dt), int(K), _p(ab), 0 if ab is None else len(ab),
+                                    _p(sel), len(sel), _p(lanes), len(lanes), int(n_threads or default_threads()),
+                                    _p(out["state"]), _p(out["istate"]), _p(out.get("seg_rows")), _p(out.get("coeffs")),
+                                    _p(out.get("first_yaw")), _p(out["sel_log"]), _p(out.get("sel_cmd")), _p(out["lane_log"]))
+    if rc != 0:
+        raise RuntimeError(f"oracle_fleet_threads failed ({rc})")
+    return out
 
 
 # ---------------------------------------------------------------------------------------- RRT* (rrt_oracle.c)

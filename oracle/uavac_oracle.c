@@ -418,3 +418,122 @@ int64_t oracle_bench_threads(const oracle_vehicle *V, const double *wps, int n, 
     free(th); free(args);
     return done;
 }
+
+/* ------------------------------------------------------------------ whole-batch reference (tests only)
+ * B missions wps[B][m+1][3], each planned by oracle_solve / oracle_sample (never from a GPU plan) and flown K ticks by
+ * oracle_rollout from hover at its first waypoint, on n_threads POSIX threads (lanes handed out 64 at a time).  Outputs
+ * (every one may be NULL): out_state [B][26], out_istate [B][4], out_seg_rows [B][m], out_coeffs [B][8m][3], out_first_yaw [B]
+ * (the yaw of the mission's first row), out_sel_log [n_sel][13][B] = the state after tick sel_ticks[i] in the GPU's log layout,
+ * out_sel_cmd [n_sel][12][B] the same for the command log, out_lane_log [n_ll][K][13] = every tick of lane log_lanes[j].
+ * Per-thread buffers only, freed on return.  Returns 0, -1 when a mission's system is singular, -2 when out of memory, -3 on
+ * bad arguments. */
+typedef struct {
+    const oracle_vehicle *V;
+    const double *wps, *aabbs;
+    int B, m, K, n_obs, n_sel;
+    double velocity, dt;
+    const int *tick_sel;           /* [K]: index into sel_ticks or -1 */
+    const int *lane_sel;           /* [B]: index into log_lanes or -1 */
+    int *next;                     /* shared lane counter */
+    double *out_state, *out_coeffs, *out_first_yaw, *out_sel_log, *out_sel_cmd, *out_lane_log;
+    int32_t *out_istate, *out_seg_rows;
+    int rc;
+} fleet_arg;
+
+static void *fleet_worker(void *p) {
+    fleet_arg *a = (fleet_arg *)p;
+    const int m = a->m, K = a->K, B = a->B;
+    double *coeffs = (double *)malloc(sizeof(double) * 24 * (size_t)m);
+    double *times = (double *)malloc(sizeof(double) * (size_t)m);
+    double *slog = (double *)malloc(sizeof(double) * 13 * (size_t)(K > 0 ? K : 1));
+    double *clog = a->out_sel_cmd ? (double *)malloc(sizeof(double) * 12 * (size_t)(K > 0 ? K : 1)) : NULL;
+    double *traj = NULL;
+    int64_t cap = 0;
+    if (!coeffs || !times || !slog || (a->out_sel_cmd && !clog)) { a->rc = -2; goto done; }
+    for (;;) {
+        const int b0 = __atomic_fetch_add(a->next, 64, __ATOMIC_RELAXED);
+        if (b0 >= B) break;
+        const int b1 = b0 + 64 < B ? b0 + 64 : B;
+        for (int b = b0; b < b1; ++b) {
+            const double *wp = a->wps + (size_t)b * (size_t)(m + 1) * 3;
+            if (oracle_solve(wp, m, a->velocity, coeffs, times) != 0) { a->rc = -1; goto done; }
+            int64_t rows = 0;
+            for (int s = 0; s < m; ++s) {
+                const int64_t cnt = (int64_t)ceil(times[s] / a->dt);
+                if (a->out_seg_rows) a->out_seg_rows[(size_t)b * m + s] = (int32_t)cnt;
+                rows += cnt;
+            }
+            if (rows > cap) {
+                free(traj);
+                cap = rows + rows / 4;
+                traj = (double *)malloc(sizeof(double) * 11 * (size_t)cap);
+                if (!traj) { a->rc = -2; goto done; }
+            }
+            oracle_sample(coeffs, times, m, a->dt, traj);
+            if (a->out_coeffs) memcpy(a->out_coeffs + (size_t)b * 24 * m, coeffs, sizeof(double) * 24 * (size_t)m);
+            if (a->out_first_yaw) a->out_first_yaw[b] = rows > 0 ? traj[9] : 0.0;
+            double state[26] = {0};
+            int32_t istate[4] = {0, 0, 0, 0};
+            state[0] = wp[0]; state[1] = wp[1]; state[2] = wp[2]; state[3] = 1.0;
+            const double hover = sqrt(a->V->mass * a->V->g / (4.0 * a->V->kf));
+            for (int r = 13; r < 21; ++r) state[r] = hover;
+            oracle_rollout(a->V, traj, rows, state, istate, K, slog, clog, a->aabbs, a->n_obs);
+            if (a->out_state) memcpy(a->out_state + (size_t)b * 26, state, sizeof state);
+            if (a->out_istate) memcpy(a->out_istate + (size_t)b * 4, istate, sizeof istate);
+            for (int k = 0; k < K; ++k) {
+                const int i = a->tick_sel[k];
+                if (i < 0) continue;
+                if (a->out_sel_log)
+                    for (int c = 0; c < 13; ++c) a->out_sel_log[((size_t)i * 13 + c) * B + b] = slog[(size_t)k * 13 + c];
+                if (a->out_sel_cmd)
+                    for (int c = 0; c < 12; ++c) a->out_sel_cmd[((size_t)i * 12 + c) * B + b] = clog[(size_t)k * 12 + c];
+            }
+            const int j = a->lane_sel[b];
+            if (j >= 0 && a->out_lane_log) memcpy(a->out_lane_log + (size_t)j * K * 13, slog, sizeof(double) * 13 * (size_t)K);
+        }
+    }
+done:
+    free(coeffs); free(times); free(slog); free(clog); free(traj);
+    return NULL;
+}
+
+int oracle_fleet_threads(const oracle_vehicle *V, const double *wps, int B, int m, double velocity, double dt, int K,
+                         const double *aabbs, int n_obs, const int32_t *sel_ticks, int n_sel, const int64_t *log_lanes, int n_ll,
+                         int n_threads, double *out_state, int32_t *out_istate, int32_t *out_seg_rows, double *out_coeffs,
+                         double *out_first_yaw, double *out_sel_log, double *out_sel_cmd, double *out_lane_log) {
+    if (!V || !wps || B < 0 || m < 1 || K < 0 || n_sel < 0 || n_ll < 0 || n_obs < 0 || (n_obs > 0 && !aabbs) ||
+        (n_sel > 0 && !sel_ticks) || (n_ll > 0 && !log_lanes))
+        return -3;
+    if (n_threads < 1) n_threads = 1;
+    int *tick_sel = (int *)malloc(sizeof(int) * (size_t)(K > 0 ? K : 1));
+    int *lane_sel = (int *)malloc(sizeof(int) * (size_t)(B > 0 ? B : 1));
+    pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)n_threads);
+    fleet_arg *args = (fleet_arg *)malloc(sizeof(fleet_arg) * (size_t)n_threads);
+    int rc = 0, next = 0;
+    if (!tick_sel || !lane_sel || !th || !args) { rc = -2; goto out; }
+    for (int k = 0; k < K; ++k) tick_sel[k] = -1;
+    for (int i = 0; i < n_sel; ++i) {
+        if (sel_ticks[i] < 0 || sel_ticks[i] >= K) { rc = -3; goto out; }
+        tick_sel[sel_ticks[i]] = i;
+    }
+    for (int b = 0; b < B; ++b) lane_sel[b] = -1;
+    for (int j = 0; j < n_ll; ++j) {
+        if (log_lanes[j] < 0 || log_lanes[j] >= B) { rc = -3; goto out; }
+        lane_sel[log_lanes[j]] = j;
+    }
+    int started = 0;
+    for (int t = 0; t < n_threads; ++t) {
+        fleet_arg a = {V, wps, aabbs, B, m, K, n_obs, n_sel, velocity, dt, tick_sel, lane_sel, &next, out_state, out_coeffs,
+                       out_first_yaw, out_sel_log, out_sel_cmd, out_lane_log, out_istate, out_seg_rows, 0};
+        args[t] = a;
+        if (pthread_create(&th[t], NULL, fleet_worker, &args[t]) != 0) { rc = -2; break; }
+        ++started;
+    }
+    for (int t = 0; t < started; ++t) {
+        pthread_join(th[t], NULL);
+        if (args[t].rc != 0 && (rc == 0 || args[t].rc == -1)) rc = args[t].rc;
+    }
+out:
+    free(tick_sel); free(lane_sel); free(th); free(args);
+    return rc;
+}

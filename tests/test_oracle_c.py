@@ -68,3 +68,35 @@ def test_cpu_baseline_leg_runs_bounded():
     from oracle import cpu_baseline as cb
     r = cb.run(segments=8, ticks=500, velocity=3.0, dt=0.01, budget_s=1.0, max_missions=3)
     assert r["kind"] == "port" and r["cores"] == 1 and r["value"] > 0 and r["unit"] == "UAV control-steps/s"
+
+
+@pytest.mark.parametrize("with_boxes", [False, True])
+def test_fleet_threads_equals_lane_by_lane_oracle(with_boxes):
+    """oracle_fleet_threads (the whole-batch reference of tests/test_gpu_whole_batch_parity.py) is oracle_solve + oracle_sample +
+    oracle_rollout lane by lane, bit for bit, whatever the thread count -- B = 37 is a multiple of none of them."""
+    from oracle import minsnap_oracle as mo
+    B, m, K = 37, 3, 437
+    wps = mo.synthetic_missions(B, m)
+    aabbs = load_golden("fixed_missions.npz")["lab_aabbs"] if with_boxes else None
+    sel, lanes = [0, 1, 10, 200, K - 1], [0, 5, 36]
+    state = np.empty((B, 26)); istate = np.empty((B, 4), np.int32); slog = np.empty((K, 13, B)); clog = np.empty((K, 12, B))
+    seg_rows = np.empty((B, m), np.int32); coeffs = np.empty((B, 8 * m, 3)); fy = np.empty(B)
+    for b in range(B):
+        traj, coeffs[b], _ = cc.plan(wps[b], 3.0, 0.01)
+        seg_rows[b] = np.bincount(traj[:, 10].astype(int), minlength=m)
+        fy[b] = traj[0, 9]
+        s, i = cc.initial_state(wps[b, 0])
+        sl, cl = cc.rollout(traj, s, i, K, aabbs=aabbs)
+        state[b], istate[b], slog[:, :, b], clog[:, :, b] = s, i, sl, cl
+    if with_boxes:
+        assert 0 < istate[:, 2].sum() < B, "the boxes should stop some missions and not others"
+    for n_threads in (1, 3, 16):
+        got = cc.fleet(wps, 3.0, 0.01, K, sel_ticks=sel, log_lanes=lanes, aabbs=aabbs, n_threads=n_threads, cmd=True)
+        assert np.array_equal(got["state"], state) and np.array_equal(got["istate"], istate)
+        assert np.array_equal(got["seg_rows"], seg_rows) and np.array_equal(got["coeffs"], coeffs)
+        assert np.array_equal(got["first_yaw"], fy)
+        assert np.array_equal(got["sel_log"], slog[sel]) and np.array_equal(got["sel_cmd"], clog[sel])
+        assert np.array_equal(got["lane_log"], slog[:, :, lanes].transpose(2, 0, 1))
+    with pytest.raises(RuntimeError):
+        cc.fleet(wps, 3.0, 0.01, K, sel_ticks=[K])                 # a tick the flight never reaches
+    assert 1 <= cc.default_threads() <= 16

@@ -873,6 +873,8 @@ void launch_shape(uavac_ctx *ctx, const VehK &V, const double *traj, const int64
     snprintf(name, sizeof name, "control_rollout_kernel<%d, %d, %s, %s, %s, %s, %s, %s, %d>", CW, SW, tf(LS), tf(LC), tf(AB), tf(POLY),
              tf(GR), tf(YS), PMODE);                       // the name rocprofv3 prints, argument for argument
     ctx->last_rollout = name;
+    const int64_t shape[6] = {grid, threads, (int64_t)(lds + pad), (int64_t)pitch, n_tiles, grid > 0 ? (n_tiles + grid - 1) / grid : 0};
+    for (int i = 0; i < 6; ++i) ctx->last_rollout_launch[i] = shape[i];
     // vector registers of that kernel as the loaded code object has them (once per variant): above 256 a SIMD holds ONE
     // wave of it and the launch runs at 0.65x -- a toolchain that crosses the line shows up here and in bench.py's line
     // (one value per kernel variant, the same from every ctx: an atomic, since distinct ctxs may launch from distinct threads)

@@ -360,6 +360,12 @@ const char *uavac_last_rollout_kernel(const uavac_ctx *ctx) { return ctx ? ctx->
 
 int uavac_last_rollout_vgprs(const uavac_ctx *ctx) { return ctx ? ctx->last_rollout_vgprs : UAVAC_EINVAL; }
 
+int uavac_last_rollout_launch(const uavac_ctx *ctx, int64_t out[6]) {
+    if (!ctx || !out) return UAVAC_EINVAL;
+    for (int i = 0; i < 6; ++i) out[i] = ctx->last_rollout_launch[i];
+    return UAVAC_OK;
+}
+
 #define UAVAC_STR2(x) #x
 #define UAVAC_STR(x) UAVAC_STR2(x)
 const char *uavac_build_info(void) {
@@ -480,6 +486,19 @@ int uavac_minsnap_sample_derivs_dev(uavac_ctx *ctx, const double *coeffs, const 
     x.first_yaw = first_yaw;
     x.jerk = jerk;
     x.snap = snap;
+    return uavac_launch_sample(ctx, coeffs, seg_rows, row_offsets, B, m, dt, traj, x);
+}
+
+int uavac_minsnap_sample_capped_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *row_offsets,
+                                    int B, int m, double dt, double *traj, int64_t traj_capacity_rows, double *yaw,
+                                    double *first_yaw) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_sample_args(ctx, coeffs, seg_rows, row_offsets, B, m, dt, traj)) return rc;
+    if (traj_capacity_rows < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative capacity");
+    SampleExtras x;
+    x.yaw_dense = yaw;
+    x.first_yaw = first_yaw;
+    x.capacity_rows = traj_capacity_rows;
     return uavac_launch_sample(ctx, coeffs, seg_rows, row_offsets, B, m, dt, traj, x);
 }
 

@@ -47,6 +47,7 @@ struct uavac_ctx {
     int n_simds = 1024;              // SIMDs of the device (4 per CU): the logged rollout launches one workgroup per SIMD at most
     std::string last_rollout;        // name and template arguments of the rollout kernel launched last (diagnostics)
     int last_rollout_vgprs = 0;      // ... and its vector registers per lane (hipFuncGetAttributes); 0 = unknown
+    int64_t last_rollout_launch[6] = {0, 0, 0, 0, 0, 0};   // ... and its shape: grid, threads, dynamic LDS, log pitch, tiles, passes
     int launch_rc = UAVAC_OK;        // set by a rollout launcher that had to give up before the launch (text in err)
 };
 

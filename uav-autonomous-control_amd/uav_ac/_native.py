@@ -65,6 +65,7 @@ _SIGNATURES = {
     "uavac_device": (C.c_int, [_P]),
     "uavac_last_rollout_kernel": (C.c_char_p, [_P]),
     "uavac_last_rollout_vgprs": (C.c_int, [_P]),
+    "uavac_last_rollout_launch": (C.c_int, [_P, _P]),
     "uavac_device_identity": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "uavac_clock_probe_dev": (C.c_int, [_P, C.c_int, _P]),
     "uavac_build_info": (C.c_char_p, []),
@@ -78,6 +79,7 @@ _SIGNATURES = {
     "uavac_minsnap_sample_yaw_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P]),
     "uavac_minsnap_sample_hits_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P]),
     "uavac_minsnap_sample_derivs_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P, _P]),
+    "uavac_minsnap_sample_capped_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int64, _P, _P]),
     "uavac_minsnap_plan_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,
                                           C.c_int64, _P, _P]),
     "uavac_minsnap_first_yaw_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P]),
@@ -268,6 +270,12 @@ class Context:
 
     def last_rollout_vgprs(self) -> int:
         return int(lib().uavac_last_rollout_vgprs(self._h))
+
+    def last_rollout_launch(self) -> dict:
+        """Shape of the rollout launched last: grid, threads, lds (dynamic bytes, pad included), pitch, n_tiles, passes."""
+        out = (C.c_int64 * 6)()
+        self.check(lib().uavac_last_rollout_launch(self._h, out))
+        return dict(zip(("grid", "threads", "lds", "pitch", "n_tiles", "passes"), (int(v) for v in out)))
 
     def device_identity(self) -> str:
         """"uuid=...;pci=...;name=..." of the GPU this ctx runs on."""

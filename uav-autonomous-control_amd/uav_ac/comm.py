@@ -266,10 +266,18 @@ class RcclComm:
         """Wait for a gather started with `gather_rows_begin` / `gather_plan_begin` -> (result on dst | None, counts)."""
         e, torch = self.engine, self.engine._torch
         stream, out, counts, _rows = ticket
+        refused = False
         with torch.cuda.stream(stream):
             e._bind_stream()
             e.ctx.call("uavac_comm_finish", self._h)
+            if out is not None and not torch.is_tensor(out):
+                # a plan gather's root: a row buffer sized from row counts that no longer matched the gathered plan was refused by
+                # the sampler (flag 2) -- say so here rather than hand back rows that were never written
+                refused = bool(e.take_flags()[2])
         e._bind_stream()                                      # back on the caller's stream
+        if refused:
+            raise nat.UavacError(nat.EINVAL, f"plan gather: the gathered plan needs more rows than the {out.traj.shape[0]} the row "
+                                             "counts announced (a stale total_rows?); nothing was sampled past the buffer")
         here = torch.cuda.current_stream(e.device)
         if stream is not here and out is not None:
             # the result was allocated under the side stream and is consumed on the caller's: tell the caching allocator

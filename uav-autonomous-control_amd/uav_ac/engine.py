@@ -40,7 +40,8 @@ class Plan:
     coeffs: "object"         # (B, 8m, 3) f64
     status: "object"         # (B,) i32: 0 ok, 1 singular
     traj: "object"           # (N, 11) f64, missions back to back; None for a rows-free plan (Engine.plan(..., rows=False))
-    total_rows: int          # N (known for a rows-free plan too: what the root of a plan gather will sample)
+    total_rows: int          # N (known for a rows-free plan too: what the root of a plan gather will sample; after
+                             # `Engine.replan` it is re-read from the device on first use, see _plan_total_rows)
     yaw: "object" = None     # (N,) f64 or None: the yaw column on its own (== traj[:, 9]); one way to feed the plan-fed rollout
     first_yaw: "object" = None   # (B,) f64: heading of each mission's first row that has one; lets the rollout scan the yaw itself
     placement_ms: "object" = None    # sampler times of the candidate row buffers when plan(..., placement_trials > 1) chose one
@@ -61,6 +62,23 @@ class Plan:
         first heading, 8 B per mission, instead of the rows)."""
         rows = 88 * self.total_rows if self.traj is not None else 8 * self.B
         return self.B * (24 * (self.m + 1) + 192 * self.m) + rows
+
+
+def _plan_total_rows(self) -> int:
+    # `Engine.replan` leaves the new row count on the device only (replan does not synchronise): the first reader after it --
+    # `RcclComm.plan_counts`, whose all-gather sizes the root's row buffer, among them -- takes it from there.
+    if self.__dict__.get("_rows_stale"):
+        self.__dict__["_total_rows"] = int(self.row_offsets[-1].item())
+        self.__dict__["_rows_stale"] = False
+    return self.__dict__["_total_rows"]
+
+
+def _set_plan_total_rows(self, value):
+    self.__dict__["_total_rows"] = int(value)
+    self.__dict__["_rows_stale"] = False
+
+
+Plan.total_rows = property(_plan_total_rows, _set_plan_total_rows)
 
 
 @dataclass
@@ -341,7 +359,8 @@ class Engine:
         the four launches.  The buffers keep their size: a plan that would need more rows than `plan.traj` holds is
         refused on the device AS A WHOLE (flag 2, see `take_flags`): every array of the plan keeps what it held, so the
         previous plan stays consistent and flyable.  A rows-free plan (`plan.traj` is None) runs the rows-free chain: times + row
-        counts, offsets, solve, first headings -- nothing to refuse."""
+        counts, offsets, solve, first headings -- nothing to refuse.  Either way `plan.total_rows` is re-read from the device by
+        whoever reads it next: the new waypoints may need more rows (rows-free) or fewer (rows that fit) than the old ones."""
         if plan.B == 0:
             return                                               # (`empty_plan`: nothing to plan)
         self._bind_stream()
@@ -349,11 +368,12 @@ class Engine:
         self.ctx.call("uavac_minsnap_plan_dev", _ptr(plan.waypoints), plan.B, plan.m, plan.velocity, plan.dt,
                       _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets), _ptr(plan.coeffs), _ptr(plan.status),
                       _ptr(plan.traj), cap, _ptr(plan.yaw), _ptr(plan.first_yaw))
+        plan.__dict__["_rows_stale"] = True                      # (no sync here: Plan.total_rows reads it when asked)
         plan.epoch += 1
 
     def sample_rows(self, plan: Plan, traj=None):
-        """Give a rows-free plan its rows: allocate (or take `traj`, >= plan.total_rows rows) and sample -- the same rows, bit for
-        bit, as `plan(..., rows=True)` would have written."""
+        """Give a rows-free plan (or a rows-free RaggedBatch, `plan_ragged(..., rows=False)`) its rows: allocate (or take `traj`,
+        >= plan.total_rows rows) and sample -- the same rows, bit for bit, as `plan(..., rows=True)` would have written."""
         torch = self._torch
         total = int(plan.row_offsets[-1].item())
         if traj is None:
@@ -361,7 +381,13 @@ class Engine:
         elif traj.shape[0] < total or traj.dtype != torch.float64 or not traj.is_contiguous():
             raise ValueError("traj must be a contiguous float64 tensor with at least total_rows rows")
         plan.traj, plan.total_rows = traj[:total], total
-        self.sample(plan)
+        if hasattr(plan, "seg_offsets"):                         # a ragged batch: its own sampler entry, segments back to back
+            self._bind_stream()
+            self.ctx.call("uavac_minsnap_sample_ragged_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets),
+                          _ptr(plan.row_offsets), plan.B, plan.max_m, int(plan.seg_offsets_host[-1]), float(plan.dt),
+                          _ptr(plan.traj), total, None, None, _ptr(plan.first_yaw))
+        else:
+            self.sample(plan)
         return plan
 
     def first_yaw(self, plan):
@@ -389,8 +415,10 @@ class Engine:
             return
         self._bind_stream()
         fy = getattr(plan, "first_yaw", None)
-        self.ctx.call("uavac_minsnap_sample_derivs_dev", _ptr(plan.coeffs[b0:b1]), _ptr(plan.seg_rows[b0:b1]), _ptr(plan.row_offsets[b0:]),
-                      b1 - b0, plan.m, plan.dt, _ptr(plan.traj), _ptr(plan.yaw), _ptr(None if fy is None else fy[b0:b1]), None, None)
+        # (the offsets are absolute: the capacity is the whole buffer's; a range that would end past it writes nothing, flag 2)
+        self.ctx.call("uavac_minsnap_sample_capped_dev", _ptr(plan.coeffs[b0:b1]), _ptr(plan.seg_rows[b0:b1]), _ptr(plan.row_offsets[b0:]),
+                      b1 - b0, plan.m, plan.dt, _ptr(plan.traj), int(plan.traj.shape[0]), _ptr(plan.yaw),
+                      _ptr(None if fy is None else fy[b0:b1]))
 
     def plan_from_parts(self, coeffs, times, seg_rows, m: int, velocity: float, dt: float, total_rows: int = None,
                         traj=None, sample: bool = True) -> Plan:
@@ -754,13 +782,10 @@ class Engine:
         if plan.traj is None:
             raise ValueError("a rows-free plan has no row buffer: Engine.sample_rows(plan) allocates one and samples")
         self._bind_stream()
-        if plan.yaw is None and getattr(plan, "first_yaw", None) is None:
-            self.ctx.call("uavac_minsnap_sample_dev", _ptr(plan.coeffs), _ptr(plan.times), _ptr(plan.seg_rows),
-                          _ptr(plan.row_offsets), plan.B, plan.m, plan.dt, _ptr(plan.traj))
-        else:
-            self.ctx.call("uavac_minsnap_sample_derivs_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.row_offsets),
-                          plan.B, plan.m, plan.dt, _ptr(plan.traj), _ptr(plan.yaw), _ptr(getattr(plan, "first_yaw", None)),
-                          None, None)
+        # with the capacity of plan.traj: rows that would not fit are refused as a whole on the device (flag 2, `take_flags`)
+        self.ctx.call("uavac_minsnap_sample_capped_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.row_offsets),
+                      plan.B, plan.m, plan.dt, _ptr(plan.traj), int(plan.traj.shape[0]), _ptr(plan.yaw),
+                      _ptr(getattr(plan, "first_yaw", None)))
 
     def check(self, plan: Plan):
         """Raise like the C ABI's host twins would: singular knot systems (repeated waypoints)."""
