@@ -116,6 +116,16 @@ int uavac_last_rollout_vgprs(const uavac_ctx *ctx);
  * lds_pad pad included), log pitch (doubles between log rows), 64-UAV tiles, persistent passes (tiles walked per workgroup,
  * rounded up).  All 0 before the first rollout.  Read-only diagnostics: tests prove which launch form they reached with it. */
 int uavac_last_rollout_launch(const uavac_ctx *ctx, int64_t out[6]);
+/* Name and template arguments of the coefficient-solve kernel the ctx launched last -- "minsnap_solve_tw_kernel<ragged, parked
+ * in LDS, missions per wave, blocks kept in registers>", "minsnap_solve_bt_kernel<...>" (the one-ended form) or
+ * "minsnap_solve_kernel" (banded) -- and of the sampler kernel launched last: "minsnap_sample_stream_kernel<waves, hits,
+ * derivatives, ragged>" or "minsnap_sample_kernel<hits, derivatives, yaw chunks per store[, ragged]>".  "" before the first.
+ * Read-only diagnostics like uavac_last_rollout_kernel: tests prove which form they reached with them. */
+const char *uavac_last_solve_kernel(const uavac_ctx *ctx);
+const char *uavac_last_sample_kernel(const uavac_ctx *ctx);
+/* Shape of that sampler launch, out[5] = grid, threads per workgroup, dynamic LDS bytes, missions per workgroup (the
+ * "sampler_group" after it shrank to fit LDS), address phase of the chunk grid (0 .. 63; -1 for the one-wave form). */
+int uavac_last_sample_launch(const uavac_ctx *ctx, int64_t out[5]);
 /* "libuavac <version>; gfx950; HIP <x.y.z>; <compiler version>" of the build (static string). */
 const char *uavac_build_info(void);
 /* Which physical GPU the ctx runs on: "uuid=<32 hex digits>;pci=<domain:bus:device.function>;name=<gcnArchName>" into buf

@@ -62,6 +62,13 @@ def lib():
         _lib.oracle_fleet_threads.restype = C.c_int
         _lib.oracle_fleet_threads.argtypes = [C.POINTER(Vehicle), _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _P, C.c_int,
                                               _P, C.c_int, _P, C.c_int, C.c_int] + [_P] * 8
+        _lib.oracle_plan_threads.restype = C.c_int
+        _lib.oracle_plan_threads.argtypes = [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_double, _P, C.c_int,
+                                             _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]
+        _lib.oracle_solve_ld.restype = C.c_int
+        _lib.oracle_solve_ld.argtypes = [_P, C.c_int, C.c_double, _P, _P]
+        _lib.oracle_ldbl_mant_dig.restype = C.c_int
+        _lib.oracle_ldbl_mant_dig.argtypes = []
         _lib.oracle_segment_intersects_cuboid.restype = C.c_int
         _lib.oracle_segment_intersects_cuboid.argtypes = [_P, _P, _P]
         _lib.oracle_rrt_distances.restype = None
@@ -166,6 +173,74 @@ def fleet(wps, velocity: float, dt: float, K: int, sel_ticks=(), log_lanes=(), a
     if rc != 0:
         raise RuntimeError(f"oracle_fleet_threads failed ({rc})")
     return out
+
+
+def plan_threads(wps, velocity: float, dt: float, b0: int = 0, b1: int = None, seg_offsets=None, rows: bool = True,
+                 derivs: bool = False, cuboid=None, n_threads: int = None, out_rows=None):
+    """Missions [b0, b1) of a batch planned by the oracle itself (`oracle_plan_threads`: oracle_solve + oracle_sample mission by
+    mission, bit for bit, on POSIX threads).  Uniform: wps (B, m+1, 3).  Ragged: seg_offsets (B+1,) and wps (S+B, 3) back to back
+    (include/uavac.h's layout).  -> dict, everything relative to the range: times / seg_rows per segment ((n, m) when uniform, flat
+    when ragged), row_offsets (n+1,) from 0, coeffs ((n, 8m, 3) | (S_range, 8, 3)), first_yaw (n,), with `rows` rows (N, 11) (into
+    `out_rows` when given: a float64 array of at least N rows), with `derivs` jerk and snap (N, 3), with `cuboid` hit (segments,)
+    int32 = a row of the spline lies in the cuboid (inclusive bounds)."""
+    wps = np.ascontiguousarray(wps, dtype=np.float64)
+    if seg_offsets is None:
+        so = None
+        B, m = wps.shape[0], wps.shape[1] - 1
+    else:
+        so = np.ascontiguousarray(seg_offsets, dtype=np.int64)
+        B = len(so) - 1
+        m = int(np.diff(so).max()) if B > 0 else 1
+        if wps.shape != (int(so[-1]) + B, 3):
+            raise ValueError("a ragged batch's waypoints are (S + B, 3)")
+    b1 = B if b1 is None else int(b1)
+    b0, n = int(b0), b1 - int(b0)
+    if not 0 <= b0 <= b1 <= B:
+        raise ValueError(f"need 0 <= b0 <= b1 <= B, got [{b0}, {b1}) of {B}")
+    S = n * m if so is None else int(so[b1] - so[b0])
+    nt = int(n_threads or default_threads())
+    cub = None if cuboid is None else np.ascontiguousarray(cuboid, dtype=np.float64).reshape(6)
+    times, seg_rows, ro = np.empty(S), np.empty(S, np.int32), np.empty(n + 1, np.int64)
+    args = (_p(wps), _p(so), B, m, b0, b1, float(velocity), float(dt), _p(cub), nt)
+    rc = lib().oracle_plan_threads(*args, _p(times), _p(seg_rows), _p(ro), None, None, 0, None, None, None, None)
+    if rc != 0:
+        raise RuntimeError(f"oracle_plan_threads failed ({rc})")
+    N = int(ro[-1])
+    out = {"times": times, "seg_rows": seg_rows, "row_offsets": ro, "coeffs": np.empty((S, 8, 3)), "first_yaw": np.empty(n)}
+    if rows:
+        if out_rows is None:
+            out_rows = np.empty((N, 11))
+        elif out_rows.dtype != np.float64 or not out_rows.flags.c_contiguous or out_rows.shape[0] < N or out_rows.shape[1:] != (11,):
+            raise ValueError("out_rows must be a C-contiguous float64 (>= N, 11) array")
+        out["rows"] = out_rows[:N]
+    if derivs:
+        out["jerk"], out["snap"] = np.empty((N, 3)), np.empty((N, 3))
+    if cub is not None:
+        out["hit"] = np.empty(S, np.int32)
+    rc = lib().oracle_plan_threads(*args, None, None, None, _p(out["coeffs"]), _p(out.get("rows")), N, _p(out["first_yaw"]),
+                                   _p(out.get("jerk")), _p(out.get("snap")), _p(out.get("hit")))
+    if rc != 0:
+        raise RuntimeError(f"oracle_plan_threads failed ({rc})")
+    if so is None:
+        out["times"], out["seg_rows"] = times.reshape(n, m), seg_rows.reshape(n, m)
+        out["coeffs"] = out["coeffs"].reshape(n, 8 * m, 3)
+        if cub is not None:
+            out["hit"] = out["hit"].reshape(n, m)
+    return out
+
+
+def solve_ld(waypoints, velocity: float):
+    """oracle_solve's KKT system assembled and solved (pivoted LU) in long double -> (coeffs (8m, 3), times (m,)), rounded to
+    fp64 at the end.  Raises where long double is no wider than double: there is no silent fp64 fall-back."""
+    wp = np.ascontiguousarray(waypoints, dtype=np.float64)
+    m = wp.shape[0] - 1
+    coeffs, times = np.empty((8 * m, 3)), np.empty(m)
+    rc = lib().oracle_solve_ld(_p(wp), m, float(velocity), _p(coeffs), _p(times))
+    if rc == -5:
+        raise RuntimeError(f"long double has {lib().oracle_ldbl_mant_dig()} mantissa bits here; oracle_solve_ld needs >= 64")
+    if rc != 0:
+        raise RuntimeError(f"oracle_solve_ld failed ({rc})")
+    return coeffs, times
 
 
 # ---------------------------------------------------------------------------------------- RRT* (rrt_oracle.c)

@@ -537,3 +537,259 @@ out:
     free(tick_sel); free(lane_sel); free(th); free(args);
     return rc;
 }
+
+/* ------------------------------------------------------------------ whole-batch plan reference (tests only)
+ * Missions [b0, b1) of a batch, each planned by oracle_solve and sampled by oracle_sample (bit for bit those two, mission by
+ * mission), on n_threads POSIX threads (missions handed out 16 at a time).  Uniform batch: seg_offsets == NULL, wps [B][m+1][3].
+ * Ragged batch: seg_offsets [B+1], mission b has seg_offsets[b+1] - seg_offsets[b] segments (1 .. m) and its waypoints are rows
+ * seg_offsets[b] + b .. seg_offsets[b+1] + b of wps (S + B, 3) -- the layout of include/uavac.h.  Every output is relative to the
+ * range (segment 0 = the first segment of mission b0, row 0 = its first row) and may be NULL:
+ *   out_times / out_seg_rows   per segment, back to back;           out_row_offsets [n+1] (n = b1 - b0), out_row_offsets[0] = 0
+ *   out_coeffs [segments][8][3];                                    out_first_yaw [n] (yaw of each mission's first row, 0 if none)
+ *   out_rows [rows][11] (rows_capacity rows);                       out_jerk / out_snap [rows][3] (polynom orders 3 and 4)
+ *   out_hit [segments] = 1 where a row of the spline lies in `cuboid` (inclusive bounds, minimum_snap.py:81-87 + :327-357)
+ * With none of coeffs / rows / first_yaw / jerk / snap / hit asked for, only durations and row counts are computed (no solve):
+ * what a caller needs to size the row buffer.  Returns 0, -1 when a system is singular, -2 out of memory, -3 bad arguments,
+ * -4 when the rows do not fit rows_capacity (nothing solved then). */
+typedef struct {
+    const double *wps, *cuboid;
+    const int64_t *seg_offsets;
+    int m;
+    int64_t b0, b1;
+    double velocity, dt;
+    const int64_t *seg0, *row0;                /* [n+1]: range-relative first segment and first row of every mission */
+    int64_t *next;
+    double *out_coeffs, *out_first_yaw, *out_rows, *out_jerk, *out_snap;
+    int32_t *out_hit;
+    int rc;
+} plan_arg;
+
+static int mission_segments(const int64_t *seg_offsets, int m, int64_t b) {
+    return seg_offsets ? (int)(seg_offsets[b + 1] - seg_offsets[b]) : m;
+}
+
+static const double *mission_wps(const double *wps, const int64_t *seg_offsets, int m, int64_t b) {
+    return wps + (size_t)3 * (seg_offsets ? (size_t)(seg_offsets[b] + b) : (size_t)b * (size_t)(m + 1));
+}
+
+/* jerk / snap of one mission's rows: polynom(3 | 4, t) . coeffs, in oracle_sample's dot-product order */
+static void sample_derivs(const double *coeffs, const double *times, int m, double dt, double *jerk, double *snap) {
+    int64_t n = 0;
+    double row[NC];
+    for (int s = 0; s < m; ++s) {
+        const int64_t cnt = (int64_t)ceil(times[s] / dt);
+        for (int64_t k = 0; k < cnt; ++k, ++n) {
+            const double t = (double)k * dt;
+            for (int ord = 3; ord <= 4; ++ord) {
+                double *o = ord == 3 ? jerk : snap;
+                if (!o) continue;
+                polynom(ord, t, row);
+                for (int j = 0; j < 3; ++j) {
+                    double acc = 0.0;
+                    for (int i = 0; i < NC; ++i) acc += row[i] * coeffs[(size_t)(s * NC + i) * 3 + j];
+                    o[n * 3 + j] = acc;
+                }
+            }
+        }
+    }
+}
+
+static void *plan_worker(void *p) {
+    plan_arg *a = (plan_arg *)p;
+    const int m = a->m;
+    const int64_t n = a->b1 - a->b0;
+    double *coeffs = (double *)malloc(sizeof(double) * 24 * (size_t)m);
+    double *times = (double *)malloc(sizeof(double) * (size_t)m);
+    double *traj = NULL;
+    int64_t cap = 0;
+    if (!coeffs || !times) { a->rc = -2; goto done; }
+    for (;;) {
+        const int64_t i0 = __atomic_fetch_add(a->next, 16, __ATOMIC_RELAXED);
+        if (i0 >= n) break;
+        const int64_t i1 = i0 + 16 < n ? i0 + 16 : n;
+        for (int64_t i = i0; i < i1; ++i) {
+            const int64_t b = a->b0 + i;
+            const int mb = mission_segments(a->seg_offsets, m, b);
+            if (oracle_solve(mission_wps(a->wps, a->seg_offsets, m, b), mb, a->velocity, coeffs, times) != 0) { a->rc = -1; goto done; }
+            const int64_t rows = a->row0[i + 1] - a->row0[i];
+            if (rows > cap) {
+                free(traj);
+                cap = rows + rows / 4;
+                traj = (double *)malloc(sizeof(double) * 11 * (size_t)cap);
+                if (!traj) { a->rc = -2; goto done; }
+            }
+            if (oracle_sample(coeffs, times, mb, a->dt, traj) != rows) { a->rc = -3; goto done; }
+            const int64_t s0 = a->seg0[i], r0 = a->row0[i];
+            if (a->out_coeffs) memcpy(a->out_coeffs + (size_t)s0 * 24, coeffs, sizeof(double) * 24 * (size_t)mb);
+            if (a->out_first_yaw) a->out_first_yaw[i] = rows > 0 ? traj[9] : 0.0;
+            if (a->out_rows) memcpy(a->out_rows + (size_t)r0 * 11, traj, sizeof(double) * 11 * (size_t)rows);
+            if (a->out_jerk || a->out_snap)
+                sample_derivs(coeffs, times, mb, a->dt, a->out_jerk ? a->out_jerk + (size_t)r0 * 3 : NULL,
+                              a->out_snap ? a->out_snap + (size_t)r0 * 3 : NULL);
+            if (a->out_hit) {
+                const double *c = a->cuboid;
+                for (int s = 0; s < mb; ++s) a->out_hit[s0 + s] = 0;
+                for (int64_t r = 0; r < rows; ++r) {
+                    const double *o = traj + r * 11;
+                    if (o[0] >= c[0] && o[0] <= c[1] && o[1] >= c[2] && o[1] <= c[3] && o[2] >= c[4] && o[2] <= c[5])
+                        a->out_hit[s0 + (int)o[10]] = 1;
+                }
+            }
+        }
+    }
+done:
+    free(coeffs); free(times); free(traj);
+    return NULL;
+}
+
+int oracle_plan_threads(const double *wps, const int64_t *seg_offsets, int B, int m, int64_t b0, int64_t b1, double velocity,
+                        double dt, const double *cuboid, int n_threads, double *out_times, int32_t *out_seg_rows,
+                        int64_t *out_row_offsets, double *out_coeffs, double *out_rows, int64_t rows_capacity,
+                        double *out_first_yaw, double *out_jerk, double *out_snap, int32_t *out_hit) {
+    if (!wps || B < 0 || m < 1 || b0 < 0 || b1 < b0 || b1 > B || !(dt > 0.0) || !(velocity > 0.0) || (out_hit && !cuboid))
+        return -3;
+    if (seg_offsets)
+        for (int64_t b = b0; b < b1; ++b) {
+            const int64_t mb = seg_offsets[b + 1] - seg_offsets[b];
+            if (mb < 1 || mb > m) return -3;
+        }
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > 16) n_threads = 16;
+    const int64_t n = b1 - b0;
+    int64_t *seg0 = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n + 1));
+    int64_t *row0 = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n + 1));
+    double *times = (double *)malloc(sizeof(double) * (size_t)m);
+    pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)n_threads);
+    plan_arg *args = (plan_arg *)malloc(sizeof(plan_arg) * (size_t)n_threads);
+    int rc = 0;
+    int64_t next = 0;
+    if (!seg0 || !row0 || !times || !th || !args) { rc = -2; goto out; }
+    seg0[0] = row0[0] = 0;
+    for (int64_t i = 0; i < n; ++i) {                            /* durations and row counts: oracle_solve's own times */
+        const int64_t b = b0 + i;
+        const int mb = mission_segments(seg_offsets, m, b);
+        oracle_times(mission_wps(wps, seg_offsets, m, b), mb, velocity, times);
+        int64_t rows = 0;
+        for (int s = 0; s < mb; ++s) {
+            const int64_t cnt = (int64_t)ceil(times[s] / dt);
+            if (out_times) out_times[seg0[i] + s] = times[s];
+            if (out_seg_rows) out_seg_rows[seg0[i] + s] = (int32_t)cnt;
+            rows += cnt;
+        }
+        seg0[i + 1] = seg0[i] + mb;
+        row0[i + 1] = row0[i] + rows;
+    }
+    if (out_row_offsets) memcpy(out_row_offsets, row0, sizeof(int64_t) * (size_t)(n + 1));
+    if (!(out_coeffs || out_rows || out_first_yaw || out_jerk || out_snap || out_hit)) goto out;
+    if ((out_rows || out_jerk || out_snap) && row0[n] > rows_capacity) { rc = -4; goto out; }
+    int started = 0;
+    for (int t = 0; t < n_threads; ++t) {
+        plan_arg a = {wps, cuboid, seg_offsets, m, b0, b1, velocity, dt, seg0, row0, &next, out_coeffs, out_first_yaw, out_rows,
+                      out_jerk, out_snap, out_hit, 0};
+        args[t] = a;
+        if (pthread_create(&th[t], NULL, plan_worker, &args[t]) != 0) { rc = -2; break; }
+        ++started;
+    }
+    for (int t = 0; t < started; ++t) {
+        pthread_join(th[t], NULL);
+        if (args[t].rc != 0 && (rc == 0 || args[t].rc == -1)) rc = args[t].rc;
+    }
+out:
+    free(seg0); free(row0); free(times); free(th); free(args);
+    return rc;
+}
+
+/* ------------------------------------------------------------------ high-precision solve (tests only)
+ * oracle_solve's dense KKT assembly and pivoted LU carried out in long double (x87 extended on x86-64: 64-bit mantissa), from
+ * the same fp64 durations: a reference for the TRUE error of the kernels' solves and of the fp64 oracle.  Returns 0, -1 singular,
+ * -2 out of memory, -5 when this platform's long double is not wider than double (no silent fall-back to fp64). */
+#include <float.h>
+
+int oracle_ldbl_mant_dig(void) { return LDBL_MANT_DIG; }
+
+static void polynom_ld(int order, long double t, long double *row) {
+    for (int i = 0; i < NC; ++i) {
+        long double poly = 1.0L, der = (long double)i;
+        for (int k = 0; k < order; ++k) {
+            poly *= der;
+            if (der > 0) der -= 1.0L;
+        }
+        row[i] = poly * powl(t, der);
+    }
+}
+
+static int lu_solve_ld(long double *A, long double *b, int n, int nrhs) {
+    for (int k = 0; k < n; ++k) {
+        int p = k;
+        long double best = fabsl(A[k * n + k]);
+        for (int i = k + 1; i < n; ++i)
+            if (fabsl(A[i * n + k]) > best) { best = fabsl(A[i * n + k]); p = i; }
+        if (!(best > 0.0L)) return -1;
+        if (p != k) {
+            for (int j = 0; j < n; ++j) { long double t = A[k * n + j]; A[k * n + j] = A[p * n + j]; A[p * n + j] = t; }
+            for (int j = 0; j < nrhs; ++j) { long double t = b[k * nrhs + j]; b[k * nrhs + j] = b[p * nrhs + j]; b[p * nrhs + j] = t; }
+        }
+        for (int i = k + 1; i < n; ++i) {
+            long double l = A[i * n + k] / A[k * n + k];
+            if (l == 0.0L) continue;
+            for (int j = k + 1; j < n; ++j) A[i * n + j] -= l * A[k * n + j];
+            for (int j = 0; j < nrhs; ++j) b[i * nrhs + j] -= l * b[k * nrhs + j];
+        }
+    }
+    for (int i = n - 1; i >= 0; --i)
+        for (int j = 0; j < nrhs; ++j) {
+            long double s = b[i * nrhs + j];
+            for (int c = i + 1; c < n; ++c) s -= A[i * n + c] * b[c * nrhs + j];
+            b[i * nrhs + j] = s / A[i * n + i];
+        }
+    return 0;
+}
+
+int oracle_solve_ld(const double *wp, int m, double velocity, double *coeffs, double *times) {
+    if (LDBL_MANT_DIG < 64) return -5;
+    oracle_times(wp, m, velocity, times);
+    int nu = NC * m, ncon = 6 * m + 2, n = nu + ncon;
+    long double *K = (long double *)calloc((size_t)n * n, sizeof(long double));
+    long double *rhs = (long double *)calloc((size_t)n * 3, sizeof(long double));
+    if (!K || !rhs) { free(K); free(rhs); return -2; }
+    long double row[NC], row0[NC];
+    int r = 0;
+#define SETA_LD(rr, cc, v) do { K[(size_t)(nu + (rr)) * n + (cc)] = (v); K[(size_t)(cc) * n + nu + (rr)] = (v); } while (0)
+    polynom_ld(0, 0.0L, row0);
+    for (int s = 0; s < m; ++s, ++r) {
+        for (int i = 0; i < NC; ++i) SETA_LD(r, s * NC + i, row0[i]);
+        for (int j = 0; j < 3; ++j) rhs[(size_t)(nu + r) * 3 + j] = wp[3 * s + j];
+    }
+    for (int s = 0; s < m; ++s, ++r) {
+        polynom_ld(0, times[s], row);
+        for (int i = 0; i < NC; ++i) SETA_LD(r, s * NC + i, row[i]);
+        for (int j = 0; j < 3; ++j) rhs[(size_t)(nu + r) * 3 + j] = wp[3 * (s + 1) + j];
+    }
+    for (int k = 1; k <= 3; ++k, ++r) {
+        polynom_ld(k, 0.0L, row);
+        for (int i = 0; i < NC; ++i) SETA_LD(r, i, row[i]);
+    }
+    for (int k = 1; k <= 3; ++k, ++r) {
+        polynom_ld(k, times[m - 1], row);
+        for (int i = 0; i < NC; ++i) SETA_LD(r, (m - 1) * NC + i, row[i]);
+    }
+    for (int s = 1; s < m; ++s)
+        for (int k = 1; k <= 4; ++k, ++r) {
+            polynom_ld(k, times[s - 1], row);
+            polynom_ld(k, 0.0L, row0);
+            for (int i = 0; i < NC; ++i) { SETA_LD(r, (s - 1) * NC + i, row[i]); SETA_LD(r, s * NC + i, -row0[i]); }
+        }
+#undef SETA_LD
+    for (int s = 0; s < m; ++s)
+        for (int a = 4; a < NC; ++a)
+            for (int c = 4; c < NC; ++c) {
+                long double fa = a * (a - 1) * (a - 2) * (a - 3), fc = c * (c - 1) * (c - 2) * (c - 3);
+                int e = a + c - 7;
+                K[(size_t)(s * NC + a) * n + s * NC + c] = fa * fc * powl((long double)times[s], e) / e;
+            }
+    int rc = lu_solve_ld(K, rhs, n, 3);
+    if (rc == 0)
+        for (int i = 0; i < nu * 3; ++i) coeffs[i] = (double)rhs[i];
+    free(K); free(rhs);
+    return rc;
+}

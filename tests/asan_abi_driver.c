@@ -36,6 +36,9 @@ int main(void) {
     uavac_destroy(NULL);
     EXPECT(strcmp(uavac_last_error(NULL), "null context") == 0);
     EXPECT(strcmp(uavac_last_rollout_kernel(NULL), "") == 0);
+    EXPECT(strcmp(uavac_last_solve_kernel(NULL), "") == 0 && strcmp(uavac_last_sample_kernel(NULL), "") == 0);
+    int64_t sample_shape[5];
+    EXPECT(uavac_last_sample_launch(NULL, sample_shape) == UAVAC_EINVAL);
     EXPECT(uavac_device(NULL) == UAVAC_EINVAL);
     EXPECT(uavac_set_stream(NULL, NULL) == UAVAC_EINVAL && uavac_reset_stream(NULL) == UAVAC_EINVAL);
     EXPECT(uavac_synchronize(NULL) == UAVAC_EINVAL && uavac_set_option(NULL, "log_pitch", 0) == UAVAC_EINVAL);

@@ -304,10 +304,16 @@ int uavac_launch_sample(uavac_ctx *ctx, const double *coeffs, const int32_t *seg
     if (ctx->sampler_waves > 1)
         return uavac_launch_sample_stream(ctx, coeffs, seg_rows, row_offsets, B, m, dt, traj, x, ctx->sampler_waves, ctx->sampler_group);
 #define UAVAC_SAMPLE(H, D, Y)                                                                                          \
-    hipLaunchKernelGGL((minsnap_sample_kernel<H, D, Y>), dim3(B), dim3(SB), lds, ctx->stream, coeffs, seg_rows, row_offsets, \
-                       B, m, dt, traj, x.aabb, x.hit, x.yaw_dense, x.jerk, x.snap, x.capacity_rows, ctx->d_flags, x.first_yaw, \
-                       x.seg_offsets)
+    do {                                                                                                               \
+        hipLaunchKernelGGL((minsnap_sample_kernel<H, D, Y>), dim3(B), dim3(SB), lds, ctx->stream, coeffs, seg_rows, row_offsets, \
+                           B, m, dt, traj, x.aabb, x.hit, x.yaw_dense, x.jerk, x.snap, x.capacity_rows, ctx->d_flags, x.first_yaw, \
+                           x.seg_offsets);                                                                             \
+        ctx->last_sample = std::string("minsnap_sample_kernel<") + (H ? "true, " : "false, ") + (D ? "true, " : "false, ") + #Y ">"; \
+    } while (0)
+    const int64_t shape[5] = {B, SB, (int64_t)lds, 1, -1};          // (one mission per workgroup; no address phase)
+    for (int i = 0; i < 5; ++i) ctx->last_sample_launch[i] = shape[i];
     if (ragged) {
+        ctx->last_sample = hits ? "minsnap_sample_kernel<true, false, 8, true>" : "minsnap_sample_kernel<false, false, 8, true>";
         if (hits) hipLaunchKernelGGL((minsnap_sample_kernel<true, false, 8, true>), dim3(B), dim3(SB), lds, ctx->stream, coeffs,
                                      seg_rows, row_offsets, B, m, dt, traj, x.aabb, x.hit, x.yaw_dense, x.jerk, x.snap,
                                      x.capacity_rows, ctx->d_flags, x.first_yaw, x.seg_offsets);

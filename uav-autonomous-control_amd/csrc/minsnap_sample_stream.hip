@@ -343,6 +343,12 @@ int launch_stream(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows,
     const int groups = (B + G - 1) / G;
     hipLaunchKernelGGL(kern, dim3(groups), dim3(64 * W), lds, ctx->stream, coeffs, seg_rows, row_offsets, B, m, dt, traj, x.aabb,
                        x.hit, x.yaw_dense, x.jerk, x.snap, x.capacity_rows, ctx->d_flags, x.first_yaw, x.seg_offsets, G, phase);
+    auto tf = [](bool v) { return v ? "true" : "false"; };
+    char name[96];
+    snprintf(name, sizeof name, "minsnap_sample_stream_kernel<%d, %s, %s, %s>", W, tf(HITS), tf(DERIVS), tf(RAGGED));
+    ctx->last_sample = name;
+    const int64_t shape[5] = {groups, 64 * W, (int64_t)lds, G, phase};
+    for (int i = 0; i < 5; ++i) ctx->last_sample_launch[i] = shape[i];
     UAVAC_HIP(ctx, hipGetLastError());
     return UAVAC_OK;
 }

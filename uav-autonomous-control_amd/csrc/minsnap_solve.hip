@@ -466,6 +466,7 @@ int uavac_launch_solve(uavac_ctx *ctx, const double *wp, const double *times, in
     size_t lds = sizeof(double) * ((size_t)n * RS + (size_t)m * 12 + (size_t)(m + 1) * 3 + 64 + 8 + 8 + 32);
     hipLaunchKernelGGL(minsnap_solve_kernel, dim3(B), dim3(64), lds, ctx->stream, wp, times, B, m, coeffs, status,
                        ctx->d_flags);
+    ctx->last_solve = "minsnap_solve_kernel";
     UAVAC_HIP(ctx, hipGetLastError());
     return UAVAC_OK;
 }

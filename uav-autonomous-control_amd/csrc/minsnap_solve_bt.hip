@@ -483,6 +483,8 @@ int uavac_launch_solve_bt(uavac_ctx *ctx, const double *wp, const double *times,
         if (P && park > 48 * 1024) UAVAC_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)park)); \
         hipLaunchKernelGGL(kern, grid, dim3(TB), P ? park : 0, ctx->stream, wp, times, B, m, ctx->d_ws, coeffs, status, ctx->d_flags,   \
                            seg_offsets, guard_rows, guard_capacity, active);                                                        \
+        ctx->last_solve = std::string("minsnap_solve_bt_kernel<") + (R ? "true, " : "false, ") + (P ? "true, " : "false, ") +       \
+                          std::to_string(N) + ", " + std::to_string(K) + ">";                                                        \
     } while (0)
 #define UAVAC_SOLVE_LANES(R, P)                                                                                                     \
     do {                                                                                                                            \
@@ -492,6 +494,7 @@ int uavac_launch_solve_bt(uavac_ctx *ctx, const double *wp, const double *times,
         auto kern = minsnap_solve_bt_kernel<false, false, 64, 5>;
         hipLaunchKernelGGL(kern, grid, dim3(TB), 28 * TB * sizeof(double), ctx->stream, wp, times, B, m, ctx->d_ws, coeffs, status,
                            ctx->d_flags, seg_offsets, guard_rows, guard_capacity, active);
+        ctx->last_solve = "minsnap_solve_bt_kernel<false, false, 64, 5>";
     }
     else if (lds_park) { if (seg_offsets) UAVAC_SOLVE_LANES(true, true); else UAVAC_SOLVE_LANES(false, true); }
     else { if (seg_offsets) UAVAC_SOLVE_LANES(true, false); else UAVAC_SOLVE_LANES(false, false); }

@@ -358,6 +358,16 @@ int uavac_set_option(uavac_ctx *ctx, const char *name, int value) {
 
 const char *uavac_last_rollout_kernel(const uavac_ctx *ctx) { return ctx ? ctx->last_rollout.c_str() : ""; }
 
+const char *uavac_last_solve_kernel(const uavac_ctx *ctx) { return ctx ? ctx->last_solve.c_str() : ""; }
+
+const char *uavac_last_sample_kernel(const uavac_ctx *ctx) { return ctx ? ctx->last_sample.c_str() : ""; }
+
+int uavac_last_sample_launch(const uavac_ctx *ctx, int64_t out[5]) {
+    if (!ctx || !out) return UAVAC_EINVAL;
+    for (int i = 0; i < 5; ++i) out[i] = ctx->last_sample_launch[i];
+    return UAVAC_OK;
+}
+
 int uavac_last_rollout_vgprs(const uavac_ctx *ctx) { return ctx ? ctx->last_rollout_vgprs : UAVAC_EINVAL; }
 
 int uavac_last_rollout_launch(const uavac_ctx *ctx, int64_t out[6]) {

@@ -49,6 +49,9 @@ struct uavac_ctx {
     int last_rollout_vgprs = 0;      // ... and its vector registers per lane (hipFuncGetAttributes); 0 = unknown
     int64_t last_rollout_launch[6] = {0, 0, 0, 0, 0, 0};   // ... and its shape: grid, threads, dynamic LDS, log pitch, tiles, passes
     int launch_rc = UAVAC_OK;        // set by a rollout launcher that had to give up before the launch (text in err)
+    std::string last_solve;          // name and template arguments of the coefficient-solve kernel launched last (diagnostics)
+    std::string last_sample;         // ... and of the sampler kernel launched last
+    int64_t last_sample_launch[5] = {0, 0, 0, 0, 0};   // ... and its shape: grid, threads, dynamic LDS, missions per workgroup, address phase
 };
 
 // Every entry point that launches, allocates or copies runs with the ctx's device current and puts the caller's

@@ -66,6 +66,9 @@ _SIGNATURES = {
     "uavac_last_rollout_kernel": (C.c_char_p, [_P]),
     "uavac_last_rollout_vgprs": (C.c_int, [_P]),
     "uavac_last_rollout_launch": (C.c_int, [_P, _P]),
+    "uavac_last_solve_kernel": (C.c_char_p, [_P]),
+    "uavac_last_sample_kernel": (C.c_char_p, [_P]),
+    "uavac_last_sample_launch": (C.c_int, [_P, _P]),
     "uavac_device_identity": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "uavac_clock_probe_dev": (C.c_int, [_P, C.c_int, _P]),
     "uavac_build_info": (C.c_char_p, []),
@@ -276,6 +279,18 @@ class Context:
         out = (C.c_int64 * 6)()
         self.check(lib().uavac_last_rollout_launch(self._h, out))
         return dict(zip(("grid", "threads", "lds", "pitch", "n_tiles", "passes"), (int(v) for v in out)))
+
+    def last_solve_kernel(self) -> str:
+        return (lib().uavac_last_solve_kernel(self._h) or b"").decode()
+
+    def last_sample_kernel(self) -> str:
+        return (lib().uavac_last_sample_kernel(self._h) or b"").decode()
+
+    def last_sample_launch(self) -> dict:
+        """Shape of the sampler launched last: grid, threads, lds (dynamic bytes), group (missions per workgroup), phase."""
+        out = (C.c_int64 * 5)()
+        self.check(lib().uavac_last_sample_launch(self._h, out))
+        return dict(zip(("grid", "threads", "lds", "group", "phase"), (int(v) for v in out)))
 
     def device_identity(self) -> str:
         """"uuid=...;pci=...;name=..." of the GPU this ctx runs on."""
