@@ -48,6 +48,7 @@ extern "C" {
 #define UAVAC_STATE_ROWS 30     /* see uavac_control_* below                        */
 #define UAVAC_ISTATE_ROWS 4
 #define UAVAC_CMD_COLS 12
+#define UAVAC_SCORE_ROWS 11     /* tracking scores of the scored rollouts, see uavac_control_rollout_scored_dev */
 
 typedef struct uavac_ctx uavac_ctx;
 
@@ -419,6 +420,41 @@ int uavac_control_rollout_plan_ragged_dev(uavac_ctx *ctx, const uavac_vehicle *V
                                           const int64_t *row_offsets, const double *first_yaw, int max_m,
                                           double dt, double *state, int32_t *istate, int B, int K,
                                           double *state_log, double *cmd_log, const double *aabbs, int n_obs);
+
+/* Scored twins: the same flight (state, istate, state_log and the obstacle flag bit for bit what the unscored twin gives) while
+ * the kernel accumulates per-UAV tracking scores on the side, without a log.  The arguments are the twin's plus
+ * score [UAVAC_SCORE_ROWS][B] f64 (device memory) last.  score == NULL or cmd_log != NULL: UAVAC_EINVAL (scores are never
+ * accumulated together with a command log).
+ * A PERIOD is the inner_per_outer = F ticks that start with an outer update (a tick with istate[1] % F == 0 on a mission that
+ * has rows) and end after the dynamics step of its F-th tick; the outer update reads row r = the cursor.  At its end
+ * e = sqrt(dx*dx + dy*dy + dz*dz), d = position - row r's x y z (upstream's tracking_errors entry,
+ * tests/integration/test_mujoco_trajectory_tracking.py:26-36).  The period is SCORED only if r >= next_row; then, left to right
+ * one period after another: count += 1, next_row = r + 1, sum += e, sumsq += e*e, max = max(max, e), last = e.  From a fresh
+ * score (all zeros) rows 0 .. N-1 are scored once each and the repeated last-row periods after the cursor stops are not:
+ * sum / count is upstream's np.mean(tracking_errors), and once next_row == N, last is the distance to the final row at the end
+ * of its period (upstream's goal-distance check, the final row standing in for goal_position).
+ *   score rows: 0 count   1 next_row   2 sum of e   3 sum of e*e   4 max e   5 last e
+ *               6 pending row + 1 (0: none)   7 istate[1] when the scored launch that left it pending ended
+ *               8-10 the pending target x y z
+ * All zeros is a fresh start.  Callers read rows 0-5; rows 6-10 carry a period a launch ends inside of into the next scored
+ * launch, which resumes it only if row 7 == inner and inner % F != 0 (no tick, scored or not, ran in between), and drops it
+ * otherwise (an unscored launch or uavac_control_step_dev inside a period drops that period): a scored flight split into
+ * launches at any tick gives the same score bits as one launch. */
+int uavac_control_rollout_scored_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *traj,
+                                     const int64_t *row_offsets, double *state, int32_t *istate, int B,
+                                     int K, double *state_log, double *cmd_log, const double *aabbs,
+                                     int n_obs, double *score);
+int uavac_control_rollout_plan_scored_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs,
+                                          const int32_t *seg_rows, const int64_t *row_offsets,
+                                          const double *yaw, const double *first_yaw, int m, double dt,
+                                          double *state, int32_t *istate, int B, int K, double *state_log,
+                                          double *cmd_log, const double *aabbs, int n_obs, double *score);
+int uavac_control_rollout_plan_ragged_scored_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs,
+                                                 const int32_t *seg_rows, const int64_t *seg_offsets,
+                                                 const int64_t *row_offsets, const double *first_yaw, int max_m,
+                                                 double dt, double *state, int32_t *istate, int B, int K,
+                                                 double *state_log, double *cmd_log, const double *aabbs, int n_obs,
+                                                 double *score);
 /* One tick (K = 1, no logs): the literal drop-in of tc.step() + simulation.step(). */
 int uavac_control_step_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *traj,
                            const int64_t *row_offsets, double *state, int32_t *istate, int B);

@@ -934,9 +934,9 @@ int uavac_state_init_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *p
     return uavac_launch_state_init(ctx, uavac_make_vehk(*V), positions, B, hover, state, istate);
 }
 
-int uavac_control_rollout_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *traj, const int64_t *row_offsets,
-                              double *state, int32_t *istate, int B, int K, double *state_log, double *cmd_log,
-                              const double *aabbs, int n_obs) {
+static int rollout_rows(uavac_ctx *ctx, const uavac_vehicle *V, const double *traj, const int64_t *row_offsets, double *state,
+                        int32_t *istate, int B, int K, double *state_log, double *cmd_log, const double *aabbs, int n_obs,
+                        double *score) {
     UAVAC_ENTER(ctx);
     if (int rc = uavac_check_vehicle(ctx, V)) return rc;
     if (B < 1 || K < 0 || !traj || !row_offsets || !state || !istate || n_obs < 0)
@@ -945,13 +945,13 @@ int uavac_control_rollout_dev(uavac_ctx *ctx, const uavac_vehicle *V, const doub
     if ((state_log || cmd_log) && ctx->log_pitch > 0 && ctx->log_pitch < B)
         return uavac_fail(ctx, UAVAC_EINVAL, "option log_pitch is smaller than B");
     return uavac_launch_rollout(ctx, uavac_make_vehk(*V), traj, row_offsets, state, istate, B, K, state_log, cmd_log,
-                                aabbs, n_obs);
+                                aabbs, n_obs, nullptr, score);
 }
 
-int uavac_control_rollout_plan_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs, const int32_t *seg_rows,
-                                   const int64_t *row_offsets, const double *yaw, const double *first_yaw, int m, double dt,
-                                   double *state, int32_t *istate, int B, int K, double *state_log, double *cmd_log,
-                                   const double *aabbs, int n_obs) {
+static int rollout_plan(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs, const int32_t *seg_rows,
+                        const int64_t *row_offsets, const double *yaw, const double *first_yaw, int m, double dt, double *state,
+                        int32_t *istate, int B, int K, double *state_log, double *cmd_log, const double *aabbs, int n_obs,
+                        double *score) {
     UAVAC_ENTER(ctx);
     if (int rc = uavac_check_vehicle(ctx, V)) return rc;
     if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
@@ -965,13 +965,13 @@ int uavac_control_rollout_plan_dev(uavac_ctx *ctx, const uavac_vehicle *V, const
     PlanRef plan;
     plan.coeffs = coeffs; plan.seg_rows = seg_rows; plan.yaw = yaw; plan.first_yaw = first_yaw; plan.dt = dt; plan.m = m;
     return uavac_launch_rollout(ctx, uavac_make_vehk(*V), nullptr, row_offsets, state, istate, B, K, state_log, cmd_log,
-                                aabbs, n_obs, &plan);
+                                aabbs, n_obs, &plan, score);
 }
 
-int uavac_control_rollout_plan_ragged_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs, const int32_t *seg_rows,
-                                          const int64_t *seg_offsets, const int64_t *row_offsets, const double *first_yaw,
-                                          int max_m, double dt, double *state, int32_t *istate, int B, int K,
-                                          double *state_log, double *cmd_log, const double *aabbs, int n_obs) {
+static int rollout_plan_ragged(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs, const int32_t *seg_rows,
+                               const int64_t *seg_offsets, const int64_t *row_offsets, const double *first_yaw, int max_m,
+                               double dt, double *state, int32_t *istate, int B, int K, double *state_log, double *cmd_log,
+                               const double *aabbs, int n_obs, double *score) {
     UAVAC_ENTER(ctx);
     if (int rc = uavac_check_vehicle(ctx, V)) return rc;
     if (int rc = check_plan_args(ctx, coeffs, B, max_m)) return rc;
@@ -985,7 +985,65 @@ int uavac_control_rollout_plan_ragged_dev(uavac_ctx *ctx, const uavac_vehicle *V
     plan.coeffs = coeffs; plan.seg_rows = seg_rows; plan.first_yaw = first_yaw; plan.dt = dt; plan.m = max_m;
     plan.seg_offsets = seg_offsets;
     return uavac_launch_rollout(ctx, uavac_make_vehk(*V), nullptr, row_offsets, state, istate, B, K, state_log, cmd_log,
-                                aabbs, n_obs, &plan);
+                                aabbs, n_obs, &plan, score);
+}
+
+// scores are accumulated without a command log only (include/uavac.h): the kernel instances stay few
+static int check_score_args(uavac_ctx *ctx, const double *cmd_log, const double *score) {
+    if (!score) return uavac_fail(ctx, UAVAC_EINVAL, "null score");
+    if (cmd_log) return uavac_fail(ctx, UAVAC_EINVAL, "no scores together with a command log");
+    return UAVAC_OK;
+}
+
+int uavac_control_rollout_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *traj, const int64_t *row_offsets,
+                              double *state, int32_t *istate, int B, int K, double *state_log, double *cmd_log,
+                              const double *aabbs, int n_obs) {
+    return rollout_rows(ctx, V, traj, row_offsets, state, istate, B, K, state_log, cmd_log, aabbs, n_obs, nullptr);
+}
+
+int uavac_control_rollout_plan_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs, const int32_t *seg_rows,
+                                   const int64_t *row_offsets, const double *yaw, const double *first_yaw, int m, double dt,
+                                   double *state, int32_t *istate, int B, int K, double *state_log, double *cmd_log,
+                                   const double *aabbs, int n_obs) {
+    return rollout_plan(ctx, V, coeffs, seg_rows, row_offsets, yaw, first_yaw, m, dt, state, istate, B, K, state_log, cmd_log,
+                        aabbs, n_obs, nullptr);
+}
+
+int uavac_control_rollout_plan_ragged_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs, const int32_t *seg_rows,
+                                          const int64_t *seg_offsets, const int64_t *row_offsets, const double *first_yaw,
+                                          int max_m, double dt, double *state, int32_t *istate, int B, int K,
+                                          double *state_log, double *cmd_log, const double *aabbs, int n_obs) {
+    return rollout_plan_ragged(ctx, V, coeffs, seg_rows, seg_offsets, row_offsets, first_yaw, max_m, dt, state, istate, B, K,
+                               state_log, cmd_log, aabbs, n_obs, nullptr);
+}
+
+int uavac_control_rollout_scored_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *traj, const int64_t *row_offsets,
+                                     double *state, int32_t *istate, int B, int K, double *state_log, double *cmd_log,
+                                     const double *aabbs, int n_obs, double *score) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_score_args(ctx, cmd_log, score)) return rc;
+    return rollout_rows(ctx, V, traj, row_offsets, state, istate, B, K, state_log, cmd_log, aabbs, n_obs, score);
+}
+
+int uavac_control_rollout_plan_scored_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs, const int32_t *seg_rows,
+                                          const int64_t *row_offsets, const double *yaw, const double *first_yaw, int m, double dt,
+                                          double *state, int32_t *istate, int B, int K, double *state_log, double *cmd_log,
+                                          const double *aabbs, int n_obs, double *score) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_score_args(ctx, cmd_log, score)) return rc;
+    return rollout_plan(ctx, V, coeffs, seg_rows, row_offsets, yaw, first_yaw, m, dt, state, istate, B, K, state_log, cmd_log,
+                        aabbs, n_obs, score);
+}
+
+int uavac_control_rollout_plan_ragged_scored_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs,
+                                                 const int32_t *seg_rows, const int64_t *seg_offsets, const int64_t *row_offsets,
+                                                 const double *first_yaw, int max_m, double dt, double *state, int32_t *istate,
+                                                 int B, int K, double *state_log, double *cmd_log, const double *aabbs, int n_obs,
+                                                 double *score) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_score_args(ctx, cmd_log, score)) return rc;
+    return rollout_plan_ragged(ctx, V, coeffs, seg_rows, seg_offsets, row_offsets, first_yaw, max_m, dt, state, istate, B, K,
+                               state_log, cmd_log, aabbs, n_obs, score);
 }
 
 int uavac_control_step_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *traj, const int64_t *row_offsets,

@@ -219,4 +219,4 @@ struct PlanRef {
 };
 int uavac_launch_rollout(uavac_ctx *ctx, const VehK &V, const double *traj, const int64_t *row_offsets, double *state,
                          int32_t *istate, int B, int K, double *state_log, double *cmd_log, const double *aabbs,
-                         int n_obs, const PlanRef *plan = nullptr);
+                         int n_obs, const PlanRef *plan = nullptr, double *score = nullptr);

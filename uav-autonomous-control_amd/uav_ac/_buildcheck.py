@@ -167,7 +167,7 @@ def _vregs(text: str):
 _ROW_LOAD = re.compile(r"global_load_dwordx4 v\[(\d+):(\d+)\], (v\[\d+:\d+\]), off(?: offset:(\d+))?$")
 
 
-def check_row_prefetch(obj: str = None):
+def check_row_prefetch(obj: str = None, scored: bool = False):
     """The row-fed rollout kernels prefetch a trajectory row with loads the compiler does not know to be in flight (inline asm,
     control_rollout.hip row_issue / row_wait).  That is only right while the loads land in the very registers row_wait() hands
     on: for every row-fed variant, (1) every group of five row loads writes the same twenty registers, (2) no other instruction
@@ -175,13 +175,14 @@ def check_row_prefetch(obj: str = None):
     kernel's CONTROL-FLOW GRAPH (branch targets from the disassembly; a forward may-analysis "row loads possibly in flight"), not
     on the linear layout: a wait that sits in a block the executed path branches over proves nothing (round-5 advice).  Code
     that no row load reaches (ahead of the first one) is free to use the registers.  Raises RuntimeError otherwise; returns the
-    number of variants checked, None when the object file cannot be read."""
+    number of variants checked, None when the object file cannot be read.  `scored`: the same check on the scored twins
+    (scored_control_rollout_kernel, 8 row-fed variants) instead of the unscored kernels (16)."""
     kernels = _disassemble_cfg(obj or os.path.join(PKG, "build", "control_rollout.o"))
     if kernels is None:
         return None
     checked, bad = 0, []
     for name, ins in kernels.items():
-        if "control_rollout_kernel" not in name:
+        if "control_rollout_kernel" not in name or ("scored_control_rollout_kernel" in name) != scored:
             continue
         groups, i = [], 0
         while i + 4 < len(ins):
@@ -224,8 +225,8 @@ def check_row_prefetch(obj: str = None):
             if j not in inside and in_flight[j] and (_vregs(x) & dest):
                 bad.append((name[:90], f"'{x}' touches a row register while the row loads may be in flight"))
                 break
-    if bad or checked < 16:
-        raise RuntimeError(f"row prefetch of the row-fed rollout kernels: {checked} variants checked; {bad} (compiler: {compiler_version()})")
+    if bad or checked < (8 if scored else 16):
+        raise RuntimeError(f"row prefetch of the row-fed {'scored ' if scored else ''}rollout kernels: {checked} variants checked; {bad} (compiler: {compiler_version()})")
     return checked
 
 
@@ -300,6 +301,8 @@ def run_all(verbose: bool = False, write_stamp: bool = True) -> dict:
     result = {}
     steps = (("rollout_registers", check_rollout_registers, lambda r: f"{len(r)} rollout kernels, at most {max(v for _, v, _ in r)} VGPRs, no spills"),
              ("row_prefetch", check_row_prefetch, lambda r: f"row prefetch of {r} row-fed rollout kernels verified on the control-flow graph of the disassembly"),
+             ("scored_row_prefetch", lambda: check_row_prefetch(scored=True),
+              lambda r: f"row prefetch of {r} row-fed scored rollout kernels verified the same way"),
              ("heading_prefetch", check_heading_prefetch, lambda r: f"{r} coefficient prefetches of the streaming sampler verified in the disassembly"),
              ("no_diagnostics", check_no_diagnostics, lambda r: "no diagnostic symbol exported"),
              ("planning_registers", check_planning_registers, lambda r: f"{len(r)} sampler / solve kernels inside their register budgets, no spills"))

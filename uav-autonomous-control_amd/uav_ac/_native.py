@@ -20,6 +20,7 @@ OK, EINVAL, ENONFINITE, EHIP, ESINGULAR, ENOMEM, ECOMM, ETOOLCHAIN = 0, -1, -2, 
 COMM_ID_BYTES = 128
 MAX_SEGMENTS = 64
 TRAJ_COLS, STATE_ROWS, ISTATE_ROWS, CMD_COLS = 11, 30, 4, 12
+SCORE_ROWS = 11                  # tracking scores of the scored rollouts (include/uavac.h UAVAC_SCORE_ROWS)
 VERSION = 310
 GROUND_IN_CONTACT, GROUND_TAKEN_OFF, GROUND_HIT_AFTER_TAKEOFF = 1, 2, 4       # istate row 3 (include/uavac.h)
 
@@ -107,6 +108,12 @@ _SIGNATURES = {
                                                   C.c_int, C.c_int, _P, _P, _P, C.c_int]),
     "uavac_control_rollout_plan_ragged_dev": (C.c_int, [_P, C.POINTER(Vehicle), _P, _P, _P, _P, _P, C.c_int, C.c_double, _P, _P,
                                                          C.c_int, C.c_int, _P, _P, _P, C.c_int]),
+    "uavac_control_rollout_scored_dev": (C.c_int, [_P, C.POINTER(Vehicle), _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int,
+                                                    _P]),
+    "uavac_control_rollout_plan_scored_dev": (C.c_int, [_P, C.POINTER(Vehicle), _P, _P, _P, _P, _P, C.c_int, C.c_double, _P, _P,
+                                                         C.c_int, C.c_int, _P, _P, _P, C.c_int, _P]),
+    "uavac_control_rollout_plan_ragged_scored_dev": (C.c_int, [_P, C.POINTER(Vehicle), _P, _P, _P, _P, _P, C.c_int, C.c_double,
+                                                                _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P]),
     "uavac_control_step_dev": (C.c_int, [_P, C.POINTER(Vehicle), _P, _P, _P, _P, C.c_int]),
     "uavac_state_init": (C.c_int, [_P, C.POINTER(Vehicle), _P, C.c_int, C.c_int, _P, _P]),
     "uavac_control_rollout": (C.c_int, [_P, C.POINTER(Vehicle), _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int]),

@@ -77,6 +77,7 @@ class Fleet:
         else:                                    # a plan assembled from gathered parts: c0 of the first spline IS the first waypoint
             self._positions = plan.coeffs[:, 0, :].contiguous()
         self._plan_epoch = getattr(plan, "epoch", 0)
+        self.score = None                        # [SCORE_ROWS][B] tracking scores, allocated by the first scored rollout
         self.reset()
 
     def reset(self):
@@ -86,9 +87,28 @@ class Fleet:
         e.ctx.call("uavac_state_init_dev", C.byref(self.vehicle), _ptr(self._positions), self.B,
                    int(self._hover), _ptr(self.state), _ptr(self.istate))
         self._plan_epoch = getattr(self.plan, "epoch", 0)        # the carried yaw scan starts afresh
+        if self.score is not None:
+            self.reset_score()
 
-    def rollout(self, K: int, state_log=None, cmd_log=None, aabbs=None, log_pitch: int = None):
+    def reset_score(self):
+        """Tracking scores back to a fresh start (all zeros): the next scored rollout scores the missions from their cursor on."""
+        if self.score is not None:
+            self.score.zero_()
+
+    def tracking(self) -> dict:
+        """The scores so far, per UAV, in upstream's terms (uav_ac.scoring.summarize with the plan's row counts)."""
+        from .scoring import summarize
+        if self.score is None:
+            raise ValueError("no scored rollout has run: fleet.rollout(K, score=True)")
+        ro = self.plan.row_offsets
+        return summarize(self.score, self.istate, ro[1:] - ro[:-1])
+
+    def rollout(self, K: int, state_log=None, cmd_log=None, aabbs=None, log_pitch: int = None, score: bool = False):
         """K fused ticks.  state_log / cmd_log: None, True (allocate) or a preallocated tensor.
+
+        score=True: the scored twin of the same kernel form also accumulates per-UAV tracking scores into `self.score`
+        ([SCORE_ROWS][B], zeros on first use; see uav_ac.scoring and include/uavac.h) -- state, logs and flags bit for bit what
+        the unscored launch gives.  Not together with a command log (ValueError).
 
         Layout of the logs: rows are `pitch` doubles apart, [K][13 | 12][pitch], columns B .. pitch-1 never touched.
         * A caller's tensor is written DENSELY ([K][rows][B] in its first K*rows*B elements) unless `log_pitch` says
@@ -102,6 +122,10 @@ class Fleet:
         """
         e, torch = self.engine, self.engine._torch
         B = self.B
+        if score and cmd_log is not None:
+            raise ValueError("tracking scores are not accumulated together with a command log")
+        if score and self.score is None:
+            self.score = torch.zeros((nat.SCORE_ROWS, B), dtype=torch.float64, device=e.device)
         callers = any(t is not None and t is not True for t in (state_log, cmd_log))
         if log_pitch is not None:
             pitch = int(log_pitch)
@@ -127,13 +151,13 @@ class Fleet:
         if pitched:
             e.ctx.set_option("log_pitch", pitch)
         try:
-            self._launch_rollout(K, bufs.get("state_log"), bufs.get("cmd_log"), aabbs)
+            self._launch_rollout(K, bufs.get("state_log"), bufs.get("cmd_log"), aabbs, self.score if score else None)
         finally:
             if pitched:                       # the option belongs to this call: other users of the ctx get pitch = B
                 e.ctx.set_option("log_pitch", 0)
         return views.get("state_log"), views.get("cmd_log")
 
-    def _launch_rollout(self, K, state_log, cmd_log, aabbs):
+    def _launch_rollout(self, K, state_log, cmd_log, aabbs, score=None):
         e, torch = self.engine, self.engine._torch
         ab, n_obs = None, 0
         if aabbs is not None:
@@ -141,6 +165,7 @@ class Fleet:
             n_obs = int(ab.shape[0])
         e._bind_stream()
         p = self.plan
+        sfx, extra = ("_scored_dev", (_ptr(score),)) if score is not None else ("_dev", ())      # the scored twin of the same form
         if self.from_plan and getattr(p, "epoch", 0) != self._plan_epoch:
             # the plan was re-solved under a flying fleet (Engine.replan / solve without reset()): the yaw scan the vehicles
             # carry (state rows 26-29) belongs to the old coefficients.  Row -1 matches no cursor, so the kernel rebuilds
@@ -150,9 +175,9 @@ class Fleet:
         if self.from_plan and hasattr(p, "seg_offsets"):
             if self.yaw_from == "column":
                 raise ValueError("a ragged batch has no dense yaw column: yaw_from='scan'")
-            e.ctx.call("uavac_control_rollout_plan_ragged_dev", C.byref(self.vehicle), _ptr(p.coeffs), _ptr(p.seg_rows),
+            e.ctx.call("uavac_control_rollout_plan_ragged" + sfx, C.byref(self.vehicle), _ptr(p.coeffs), _ptr(p.seg_rows),
                        _ptr(p.seg_offsets), _ptr(p.row_offsets), _ptr(p.first_yaw), p.max_m, float(p.dt), _ptr(self.state),
-                       _ptr(self.istate), self.B, int(K), _ptr(state_log), _ptr(cmd_log), _ptr(ab), n_obs)
+                       _ptr(self.istate), self.B, int(K), _ptr(state_log), _ptr(cmd_log), _ptr(ab), n_obs, *extra)
         elif self.from_plan:
             # target rows are evaluated inside the kernel from the plan's coefficients; the yaw is scanned by the kernel
             # (plan.first_yaw) unless only the dense column exists or `yaw_from="column"` was asked for
@@ -162,15 +187,16 @@ class Fleet:
                 raise ValueError("this plan has neither first headings nor a dense yaw column")
             if self.yaw_from == "column" and yaw_col is None:
                 raise ValueError("yaw_from='column' needs a plan made with dense_yaw=True")
-            e.ctx.call("uavac_control_rollout_plan_dev", C.byref(self.vehicle), _ptr(p.coeffs), _ptr(p.seg_rows),
+            e.ctx.call("uavac_control_rollout_plan" + sfx, C.byref(self.vehicle), _ptr(p.coeffs), _ptr(p.seg_rows),
                        _ptr(p.row_offsets), _ptr(yaw_col), _ptr(first), p.m, float(p.dt), _ptr(self.state), _ptr(self.istate), self.B,
-                       int(K), _ptr(state_log), _ptr(cmd_log), _ptr(ab), n_obs)
+                       int(K), _ptr(state_log), _ptr(cmd_log), _ptr(ab), n_obs, *extra)
         else:
-            e.ctx.call("uavac_control_rollout_dev", C.byref(self.vehicle), _ptr(p.traj), _ptr(p.row_offsets),
-                       _ptr(self.state), _ptr(self.istate), self.B, int(K), _ptr(state_log), _ptr(cmd_log), _ptr(ab), n_obs)
+            e.ctx.call("uavac_control_rollout" + sfx, C.byref(self.vehicle), _ptr(p.traj), _ptr(p.row_offsets),
+                       _ptr(self.state), _ptr(self.istate), self.B, int(K), _ptr(state_log), _ptr(cmd_log), _ptr(ab), n_obs, *extra)
 
     def step(self):
-        """One tick: `tc.step()` + `simulation.step()` for every UAV (main.py:37-45, mujoco_sim.py:144-151)."""
+        """One tick: `tc.step()` + `simulation.step()` for every UAV (main.py:37-45, mujoco_sim.py:144-151).  Unscored: a
+        scoring period this tick belongs to is dropped by the next scored rollout (not scored)."""
         e = self.engine
         if getattr(self.plan, "traj", None) is None:
             raise ValueError("single ticks read the sampled rows: a rows-free plan flies through rollout()")
