@@ -79,7 +79,7 @@ def _tf(v):
 
 
 def _expect_solve(B, m, order=1, lanes=-1, park=-1, keep=-1, ragged=False):
-    """The kernel uavac_launch_solve_bt / uavac_launch_solve_tw pick for these options (their dispatch, restated)."""
+    """The kernel uavac_launch_coeff_solve and the two launchers behind it pick for these options (their dispatch, restated)."""
     S = _simds()
     cus = S // 4
     if order == 1 or (order < 0 and not (m <= 8 and not ragged and B >= 48 * S)):

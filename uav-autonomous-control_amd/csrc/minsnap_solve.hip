@@ -1,7 +1,7 @@
-// Minimum-snap time allocation, row counting and the PIVOTED (banded LU) form of the coefficient solve
-// (gfx950).  The solver the API uses by default is the lane-per-mission block-Thomas recurrence of
-// minsnap_solve_bt.hip; the wave-per-mission kernel below is kept as an independent cross-check
-// (uavac_minsnap_solve_banded_dev) and documents the formulation both share.
+// Minimum-snap planning ahead of the sampler (gfx950): time allocation and row counting (K0), and the coefficient solve (K1) as a
+// whole -- the dispatcher that picks its form (uavac_launch_coeff_solve) and the PIVOTED (banded LU) form.  The solver every plan
+// uses is the two-ended block-Thomas recurrence of minsnap_solve_tw.hip; the one-ended one of minsnap_solve_bt.hip and the
+// wave-per-mission kernel below (uavac_minsnap_solve_banded_dev) are kept as independent cross-checks.
 //
 // Replaces uav_ac/planning/minimum_snap.py (upstream paths):
 //   _generate_time_per_spline            :311-321   -> row_counts_kernel
@@ -9,23 +9,18 @@
 //   _create_polynom_matrices / _create_snap_cost_matrix / _compute_spline_parameters
 //                                        :138-255   -> minsnap_solve_kernel
 //
-// The reference solves one dense (14m+2)^2 KKT system per mission in the monomial
-// basis (cond ~1e10).  Here the same QP is restated in knot-derivative coordinates:
-// unknowns are (v, a, j) at the m-1 interior knots, C1..C3 continuity and the
-// position / rest constraints hold by construction, and the only equality left is
-// continuity of the 4th derivative at each interior knot.  Per segment everything
-// is a fixed 8x8 map scaled by powers of T (tau = t/T):
-//     cost_s   = T^-7 * e^T Q1 e ,  e = diag(1,T,T^2,T^3,1,T,T^2,T^3) d
-//     snap(0)  = T^-4 * S0 . e ,    snap(T) = T^-4 * S1 . e
-//     c_tau    = W e ,              c_t[i]  = c_tau[i] T^-i
-// with d = [p,v,a,j]@start (+) [p,v,a,j]@end and Q1, S0, S1, W exact small rationals
-// (W = inverse of the README's 8x8 boundary matrix at T=1, Q1 = W^T H1 W).
-// The KKT system has order 4(m-1), is block-tridiagonal in knot order (half
-// bandwidth 7) and has cond ~4e4; it is factorised by banded LU with partial
-// pivoting, one wavefront per mission, entirely in LDS, 3 right-hand sides (x,y,z).
-// Unique optimum => identical coefficients to the reference's KKT solve.
+// The formulation all three forms share -- the QP in knot-derivative coordinates, its tables Q1, S0, S1, W -- is derived in
+// minsnap_kkt.h.  Here the KKT system of order 4(m-1), block-tridiagonal in knot order (half
+// bandwidth 7, cond ~4e4), is factorised by banded LU with partial
+// pivoting, one wavefront per mission, entirely in LDS, 3 right-hand sides (x,y,z): ~16 k wave instructions per mission (pivot
+// search, row swaps and workgroup syncs on a matrix that is 85 % structural zeros) against ~6 k scalar fp64 operations of the
+// block-Thomas forms.
 
-#include "uavac_internal.h"
+#include "minsnap_kkt.h"
+
+// (the header's `fp contract(off)` is file-scope and would reach the kernels below.  hipcc compiles HIP with -ffp-contract=fast-honor-pragmas
+// unless told otherwise, and the Makefile does not tell it: `fast` is what these kernels had before the include)
+#pragma clang fp contract(fast)
 
 namespace {
 
@@ -33,25 +28,22 @@ constexpr int KL = 7;             // sub-diagonals of the knot-ordered KKT matri
 constexpr int BW = 22;            // stored band per row: columns [i-7, i+14] (fill-in of partial pivoting)
 constexpr int RS = 25;            // row stride in doubles: band + 3 right-hand sides (odd: spreads LDS banks)
 
-// Q1 = W^T H1 W: snap cost of a unit-duration septic in endpoint-derivative coordinates.
-__constant__ double kQ1[64] = {
-    100800, 50400, 10080, 840, -100800, 50400, -10080, 840,
-    50400, 25920, 5400, 480, -50400, 24480, -4680, 360,
-    10080, 5400, 1200, 120, -10080, 4680, -840, 60,
-    840, 480, 120, 16, -840, 360, -60, 4,
-    -100800, -50400, -10080, -840, 100800, -50400, 10080, -840,
-    50400, 24480, 4680, 360, -50400, 25920, -5400, 480,
-    -10080, -4680, -840, -60, 10080, -5400, 1200, -120,
-    840, 360, 60, 4, -840, 480, -120, 16};
-// 4th derivative at tau=0 / tau=1 as a function of the endpoint derivatives.
-__constant__ double kS0[8] = {-840, -480, -120, -16, 840, -360, 60, -4};
-__constant__ double kS1[8] = {840, 360, 60, 4, -840, 480, -120, 16};
-// W = M1^-1: endpoint derivatives -> ascending monomial coefficients (rows 4..7; rows 0..3 are 1,1,1/2,1/6 diag).
-__constant__ double kW[32] = {
-    -35, -20, -5, -2.0 / 3.0, 35, -15, 2.5, -1.0 / 6.0,
-    84, 45, 10, 1, -84, 39, -7, 0.5,
-    -70, -36, -7.5, -2.0 / 3.0, 70, -34, 6.5, -0.5,
-    20, 10, 2, 1.0 / 6.0, -20, 10, -2, 1.0 / 6.0};
+// The tables of minsnap_kkt.h, row-major in constant memory (the kernel below copies them to LDS).  flat() is constexpr so that these
+// stay constant-initialised: a __constant__ object cannot have a dynamic initialiser.
+template <int N> struct Flat { double v[N]; };
+template <int R, int C> constexpr Flat<R * C> flat(const double (&t)[R][C]) {
+    Flat<R * C> f{};
+    for (int i = 0; i < R * C; ++i) f.v[i] = t[i / C][i % C];
+    return f;
+}
+template <int N> constexpr Flat<N> flat(const double (&t)[N]) {
+    Flat<N> f{};
+    for (int i = 0; i < N; ++i) f.v[i] = t[i];
+    return f;
+}
+__constant__ Flat<64> kQ1 = flat(Q1c);
+__constant__ Flat<8> kS0 = flat(S0c), kS1 = flat(S1c);
+__constant__ Flat<32> kW = flat(Wc);
 
 // ------------------------------------------------------------------------------------------
 // Times and row counts: one thread per mission, 256 missions per workgroup, which also leaves the tile's row total.
@@ -240,9 +232,9 @@ __global__ void __launch_bounds__(64) minsnap_solve_kernel(const double *__restr
     double *S1 = S0 + 8;                      // [8]
     double *Wl = S1 + 8;                      // [32]
 
-    for (int i = lane; i < 64; i += 64) Q1[i] = kQ1[i];
-    if (lane < 8) { S0[lane] = kS0[lane]; S1[lane] = kS1[lane]; }
-    if (lane < 32) Wl[lane] = kW[lane];
+    for (int i = lane; i < 64; i += 64) Q1[i] = kQ1.v[i];
+    if (lane < 8) { S0[lane] = kS0.v[lane]; S1[lane] = kS1.v[lane]; }
+    if (lane < 32) Wl[lane] = kW.v[lane];
     for (int i = lane; i < (m + 1) * 3; i += 64) wpl[i] = wp[(size_t)b * (m + 1) * 3 + i];
     for (int s = lane; s < m; s += 64) {
         double T = times[(size_t)b * m + s];
@@ -460,8 +452,23 @@ int uavac_launch_plan_commit(uavac_ctx *ctx, const double *times_s, const int32_
     return UAVAC_OK;
 }
 
-int uavac_launch_solve(uavac_ctx *ctx, const double *wp, const double *times, int B, int m, double *coeffs,
-                       int32_t *status) {
+int uavac_launch_coeff_solve(uavac_ctx *ctx, const double *wp, const double *times, int B, int m, double *coeffs, int32_t *status,
+                             const int64_t *seg_offsets, const int64_t *guard_rows, int64_t guard_capacity, const int32_t *active) {
+    // WHICH ELIMINATION ORDER.  1 (default): two-ended, whatever the launch -- a mission's coefficients must not depend on how many
+    // other missions share its batch (a rank's shard of a job equals the job's own bits; ragged == uniform; a mission alone == in a
+    // batch: all tested bit for bit), and the two orders round differently (5e-14 relative).  0: one-ended.  -1 (opt-in, round 6):
+    // by the launch -- one-ended where it is the faster kernel, uniform batches of short missions from three quarters of a chip's
+    // worth of lanes on (m <= 8, B >= 48 * SIMDs: 52 against 56-59 us at 65 536 missions of 8 segments, 195 against 213 at 262 144;
+    // below that, and for longer missions at any size, the two-ended form wins: profiles/r05_solve_order_time.jsonl) -- for callers
+    // who take the last-bits dependence on the batch size for those 4-18 us.  Both orders sit equally close to the dense pivoted
+    // solve of the reference (<= 1e-9 on the coefficients against the `solve` goldens, tests/test_gpu_round6.py).
+    const bool two_ended = ctx->solve_order == 1 || (ctx->solve_order < 0 && !(m <= 8 && !seg_offsets && (int64_t)B >= (int64_t)48 * ctx->n_simds));
+    if (two_ended) return uavac_launch_solve_tw(ctx, wp, times, B, m, coeffs, status, seg_offsets, guard_rows, guard_capacity, active);
+    return uavac_launch_solve_bt(ctx, wp, times, B, m, coeffs, status, seg_offsets, guard_rows, guard_capacity, active);
+}
+
+int uavac_launch_solve_banded(uavac_ctx *ctx, const double *wp, const double *times, int B, int m, double *coeffs,
+                              int32_t *status) {
     int n = 4 * (m - 1);
     size_t lds = sizeof(double) * ((size_t)n * RS + (size_t)m * 12 + (size_t)(m + 1) * 3 + 64 + 8 + 8 + 32);
     hipLaunchKernelGGL(minsnap_solve_kernel, dim3(B), dim3(64), lds, ctx->stream, wp, times, B, m, coeffs, status,

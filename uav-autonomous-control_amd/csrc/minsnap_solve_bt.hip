@@ -2,21 +2,10 @@
 // the cross-check of the two-ended form in minsnap_solve_tw.hip (ctx option "solve_order" = 0 selects this file; same system, other
 // elimination order, other rounding).
 //
-// Same QP and same knot-derivative coordinates as minsnap_solve.hip (see its header for the derivation
-// and for the reference lines it replaces: uav_ac/planning/minimum_snap.py:138-255).  Ordered by knot,
-// the KKT matrix of order 4(m-1) is block tridiagonal with 4x4 blocks, unknowns (v, a, j, lambda) per
-// interior knot:
-//     D_k = C_{k-1} + A_k ,  U_k = B_k ,  L_k = B_{k-1}^T
-// where segment s contributes the symmetric 8x8 local block [[A_s, B_s], [B_s^T, C_s]] (start knot /
-// end knot), every entry a fixed small integer times a power of T_s.  The wave-per-mission banded LU of
-// minsnap_solve.hip spends ~16 k wave instructions per mission on it (pivot search, row swaps and
-// workgroup syncs on a matrix that is 85 % structural zeros).  Here one LANE owns a mission and runs the
-// block-Thomas recurrence entirely in registers:
-//     S_k = D_k - B_{k-1}^T Ut_{k-1} ;  [Ut_k | rt_k] = S_k^{-1} [B_k | r_k - B_{k-1}^T rt_{k-1}]
-//     x_k = rt_k - Ut_k x_{k+1}
-// about 6 k scalar fp64 operations per mission and no LDS traffic, no syncs.  Each S_k is a saddle block
-// [[G, c], [c^T, -e]] with G positive definite (the Hessian of the cost-to-go in the knot's derivatives)
-// and e >= 0, so natural-order elimination needs no pivoting; measured against the dense pivoted solve of
+// The QP in knot-derivative coordinates, its block-tridiagonal KKT system and the block-Thomas recurrence are derived in
+// minsnap_kkt.h, which also holds the pieces this kernel shares with the two-ended one.  Here one LANE owns a mission and runs
+// the recurrence entirely in registers, first knot to last and back: about 6 k scalar fp64 operations per mission and no LDS
+// traffic, no syncs.  Measured against the dense pivoted solve of
 // the reference formulation the sampled trajectories agree to 3e-12 on the SURVEY 8(d) distribution and
 // 3e-11 on segment lengths U(1,6) m (tests/test_gpu_planner.py).  A zero or non-finite pivot (repeated
 // waypoints) flags the mission exactly like the banded kernel.
@@ -26,143 +15,12 @@
 // reference's per-mission (8m, 3) layout is written in 192-byte runs.  Loads are issued a knot / segment ahead of
 // their use and ahead of that step's stores (see the kernel).
 
-#include "uavac_internal.h"
+#include "minsnap_kkt.h"
+#include "minsnap_solve_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-// Q1 = W^T H1 W, S0/S1 = end snaps, W rows 4..7: see minsnap_solve.hip
-constexpr double Q1c[8][8] = {
-    {100800, 50400, 10080, 840, -100800, 50400, -10080, 840},
-    {50400, 25920, 5400, 480, -50400, 24480, -4680, 360},
-    {10080, 5400, 1200, 120, -10080, 4680, -840, 60},
-    {840, 480, 120, 16, -840, 360, -60, 4},
-    {-100800, -50400, -10080, -840, 100800, -50400, 10080, -840},
-    {50400, 24480, 4680, 360, -50400, 25920, -5400, 480},
-    {-10080, -4680, -840, -60, 10080, -5400, 1200, -120},
-    {840, 360, 60, 4, -840, 480, -120, 16}};
-constexpr double S0c[8] = {-840, -480, -120, -16, 840, -360, 60, -4};
-constexpr double S1c[8] = {840, 360, 60, 4, -840, 480, -120, 16};
-constexpr double Wc[4][8] = {
-    {-35, -20, -5, -2.0 / 3.0, 35, -15, 2.5, -1.0 / 6.0},
-    {84, 45, 10, 1, -84, 39, -7, 0.5},
-    {-70, -36, -7.5, -2.0 / 3.0, 70, -34, 6.5, -0.5},
-    {20, 10, 2, 1.0 / 6.0, -20, 10, -2, 1.0 / 6.0}};
-
-// Local 8x8 KKT entry (la, lb) of a segment as coefficient * T^-e.  Local index: 0..3 = (v, a, j, lambda)
-// at the start knot, 4..7 at the end knot.  Both functions fold to literals once la, lb are unrolled.
-__device__ __forceinline__ constexpr double loc_coef(int la, int lb) {
-    const int ca = la & 3, cb = lb & 3;
-    if (ca == 3 && cb == 3) return 0.0;
-    if (ca == 3 || cb == 3) {
-        const int ll = (ca == 3) ? la : lb, ld = (ca == 3) ? lb : la;
-        const int d = (ld & 4) + (ld & 3) + 1;
-        return (ll & 4) ? S1c[d] : -S0c[d];        // knot constraint: snap_end(prev) - snap_start(next) = 0
-    }
-    return Q1c[(la & 4) + ca + 1][(lb & 4) + cb + 1];
-}
-__device__ __forceinline__ constexpr int loc_exp(int la, int lb) {
-    const int ca = la & 3, cb = lb & 3;
-    if (ca == 3 && cb == 3) return 0;
-    if (ca == 3) return 4 - (cb + 1);
-    if (cb == 3) return 4 - (ca + 1);
-    return 7 - (ca + 1) - (cb + 1);
-}
-// right-hand side of local row la: coefficient of p_start / p_end, times T^-e
-__device__ __forceinline__ constexpr double rhs_c0(int la) {
-    const int ca = la & 3;
-    if (ca == 3) return (la & 4) ? -S1c[0] : S0c[0];
-    return -Q1c[(la & 4) + ca + 1][0];
-}
-__device__ __forceinline__ constexpr double rhs_c1(int la) {
-    const int ca = la & 3;
-    if (ca == 3) return (la & 4) ? -S1c[4] : S0c[4];
-    return -Q1c[(la & 4) + ca + 1][4];
-}
-__device__ __forceinline__ constexpr int rhs_exp(int la) { return ((la & 3) == 3) ? 4 : 7 - ((la & 3) + 1); }
-
-struct Seg {
-    double A[4][4], B[4][4], C[4][4];     // start-start, start-end, end-end blocks
-    double rs[4][3], re[4][3];            // right-hand side rows of the start / end knot, per axis
-    double ip[8];                         // T^-e
-};
-
-__device__ __forceinline__ void build_segment(Seg &g, double T, const double p0[3], const double p1[3]) {
-    const double r = 1.0 / T;
-    g.ip[0] = 1.0;
-#pragma unroll
-    for (int e = 1; e < 8; ++e) g.ip[e] = g.ip[e - 1] * r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            g.A[i][j] = loc_coef(i, j) * g.ip[loc_exp(i, j)];
-            g.B[i][j] = loc_coef(i, 4 + j) * g.ip[loc_exp(i, 4 + j)];
-            g.C[i][j] = loc_coef(4 + i, 4 + j) * g.ip[loc_exp(4 + i, 4 + j)];
-        }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            g.rs[i][a] = (rhs_c0(i) * p0[a] + rhs_c1(i) * p1[a]) * g.ip[rhs_exp(i)];
-            g.re[i][a] = (rhs_c0(4 + i) * p0[a] + rhs_c1(4 + i) * p1[a]) * g.ip[rhs_exp(4 + i)];
-        }
-}
-
-// Solve S X = R (4x4, 7 right-hand sides) in natural order; returns false on a zero / non-finite pivot.
-__device__ __forceinline__ bool solve4(double S[4][4], double R[4][7]) {
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const double piv = S[j][j];
-        ok = ok && (fabs(piv) > 0.0) && isfinite(piv);
-        const double inv = 1.0 / piv;
-#pragma unroll
-        for (int i = j + 1; i < 4; ++i) {
-            const double l = S[i][j] * inv;
-#pragma unroll
-            for (int c = j + 1; c < 4; ++c) S[i][c] = fma(-l, S[j][c], S[i][c]);
-#pragma unroll
-            for (int c = 0; c < 7; ++c) R[i][c] = fma(-l, R[j][c], R[i][c]);
-        }
-    }
-#pragma unroll
-    for (int i = 3; i >= 0; --i) {
-        const double inv = 1.0 / S[i][i];
-#pragma unroll
-        for (int c = 0; c < 7; ++c) {
-            double s = R[i][c];
-#pragma unroll
-            for (int q = i + 1; q < 4; ++q) s = fma(-S[i][q], R[q][c], s);
-            R[i][c] = s * inv;
-        }
-    }
-    return ok;
-}
-
-// 24 monomial coefficients (ascending powers, [8][3]) of one segment from its knot data
-__device__ __forceinline__ void segment_coeffs(const double ip[8], double T, const double p0[3], const double p1[3],
-                                               const double x0[3][3], const double x1[3][3], double out[8][3]) {
-    const double T2 = T * T, T3 = T2 * T;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        // e = diag(1, T, T^2, T^3, 1, T, T^2, T^3) [p v a j]_start (+) [p v a j]_end
-        const double e[8] = {p0[a], T * x0[0][a], T2 * x0[1][a], T3 * x0[2][a],
-                             p1[a], T * x1[0][a], T2 * x1[1][a], T3 * x1[2][a]};
-        out[0][a] = p0[a];
-        out[1][a] = x0[0][a];
-        out[2][a] = 0.5 * x0[1][a];
-        out[3][a] = x0[2][a] * (1.0 / 6.0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            double s = 0.0;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) s = fma(Wc[i][q], e[q], s);
-            out[4 + i][a] = s * ip[4 + i];
-        }
-    }
-}
 
 constexpr int TB = 64;          // lanes (missions) per workgroup = one wave
 
@@ -264,6 +122,7 @@ __global__ void __launch_bounds__(TB) minsnap_solve_bt_kernel(const double *__re
                 nt = tm[tn];
             }
             build_segment(cur, T, p0, p1);
+            // (from here to the park store the same lines as in minsnap_solve_tw.hip: as functions of minsnap_kkt.h they move the schedule, see there)
             double S[4][4], R[4][7];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -309,15 +168,7 @@ __global__ void __launch_bounds__(TB) minsnap_solve_bt_kernel(const double *__re
             if (NREG > 0 && kk < NREG) {
 #pragma unroll
                 for (int q = 0; q < NREG; ++q)
-                    if (kk == q) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) kept[q][i * 4 + j] = R[i][j];
-#pragma unroll
-                            for (int a = 0; a < 3; ++a) kept[q][16 + i * 3 + a] = R[i][4 + a];
-                        }
-                    }
+                    if (kk == q) store_block(R, kept[q], 1);
             }
             prev = cur;
         }
@@ -347,15 +198,7 @@ __global__ void __launch_bounds__(TB) minsnap_solve_bt_kernel(const double *__re
     // on their way while the segment before is computed: [Ut | rt] of knot s - 1, start waypoint and duration of segment s
     double nxt[28], nw[3], nt;
     {
-        if (nk >= 1) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) nxt[i * 4 + j] = Ut[i][j];
-#pragma unroll
-                for (int a = 0; a < 3; ++a) nxt[16 + i * 3 + a] = rt[i][a];
-            }
-        }
+        if (nk >= 1) pack_block(Ut, rt, nxt);
 #pragma unroll
         for (int a = 0; a < 3; ++a) nw[a] = w[3 * (m - 1) + a];
         nt = tm[m - 1];
@@ -373,15 +216,9 @@ __global__ void __launch_bounds__(TB) minsnap_solve_bt_kernel(const double *__re
             if (NREG > 0 && s - 2 < NREG) {
 #pragma unroll
                 for (int q = 0; q < NREG; ++q)
-                    if (s - 2 == q) {
-#pragma unroll
-                        for (int i = 0; i < 28; ++i) nxt[i] = kept[q][i];
-                    }
+                    if (s - 2 == q) load_block(nxt, kept[q], 1);
             } else {
-                const double *o = park_at(s - 2);
-                const size_t ost = park_stride(s - 2);
-#pragma unroll
-                for (int i = 0; i < 28; ++i) nxt[i] = o[(size_t)i * ost];
+                load_block(nxt, park_at(s - 2), park_stride(s - 2));
             }
         }
         if (s >= 1) {
@@ -392,17 +229,7 @@ __global__ void __launch_bounds__(TB) minsnap_solve_bt_kernel(const double *__re
         if (!RAGGED || s >= 0) {
             double xs[4][3];                            // unknowns of knot s (zero at the start)
             if (s >= 1) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) {
-                        double v = cur[16 + i * 3 + a];
-                        if (s <= nk - 1) {              // knot s has a successor among the unknowns
-#pragma unroll
-                            for (int l = 0; l < 4; ++l) v = fma(-cur[i * 4 + l], xn[l][a], v);
-                        }
-                        xs[i][a] = v;
-                    }
+                substitute_knot(cur, s <= nk - 1, xn, xs);      // (s <= nk - 1: knot s has a successor among the unknowns)
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -439,24 +266,7 @@ __global__ void __launch_bounds__(TB) minsnap_solve_bt_kernel(const double *__re
 int uavac_launch_solve_bt(uavac_ctx *ctx, const double *wp, const double *times, int B, int m, double *coeffs,
                           int32_t *status, const int64_t *seg_offsets, const int64_t *guard_rows, int64_t guard_capacity,
                           const int32_t *active) {
-    // WHICH ELIMINATION ORDER.  1 (default): two-ended, whatever the launch -- a mission's coefficients must not depend on how many
-    // other missions share its batch (a rank's shard of a job equals the job's own bits; ragged == uniform; a mission alone == in a
-    // batch: all tested bit for bit), and the two orders round differently (5e-14 relative).  0: one-ended.  -1 (opt-in, round 6):
-    // by the launch -- one-ended where it is the faster kernel, uniform batches of short missions from three quarters of a chip's
-    // worth of lanes on (m <= 8, B >= 48 * SIMDs: 52 against 56-59 us at 65 536 missions of 8 segments, 195 against 213 at 262 144;
-    // below that, and for longer missions at any size, the two-ended form wins: profiles/r05_solve_order_time.jsonl) -- for callers
-    // who take the last-bits dependence on the batch size for those 4-18 us.  Both orders sit equally close to the dense pivoted
-    // solve of the reference (<= 1e-9 on the coefficients against the `solve` goldens, tests/test_gpu_round6.py).
-    const bool two_ended = ctx->solve_order == 1 || (ctx->solve_order < 0 && !(m <= 8 && !seg_offsets && (int64_t)B >= (int64_t)48 * ctx->n_simds));
-    if (two_ended) return uavac_launch_solve_tw(ctx, wp, times, B, m, coeffs, status, seg_offsets, guard_rows, guard_capacity, active);
-    const size_t need = (size_t)(m > 1 ? m - 1 : 1) * 28 * (size_t)B;
-    if (need > ctx->ws_cap) {
-        if (ctx->d_ws) UAVAC_HIP(ctx, hipFree(ctx->d_ws));
-        ctx->d_ws = nullptr;
-        ctx->ws_cap = 0;
-        UAVAC_HIP(ctx, hipMalloc(&ctx->d_ws, sizeof(double) * need));
-        ctx->ws_cap = need;
-    }
+    if (int rc = ensure_solve_workspace(ctx, B, m)) return rc;
     // How the solve is launched (never what it computes: tests/test_gpu_planner.py compares the coefficients bit for bit).
     //  * lanes: 64, 32 or 16 lanes of a wave carry a mission.  Below a chip's worth of full waves the kernel is bound by the
     //    latency of its dependent chains at one wave per SIMD, and two half-full waves hide each other's (B = 32 768, m = 8:
@@ -477,29 +287,24 @@ int uavac_launch_solve_bt(uavac_ctx *ctx, const double *wp, const double *times,
     const bool lds_park = fits && (ctx->solve_park >= 0 ? ctx->solve_park != 0 : waves <= cus * (per_cu < 8 ? per_cu : 8));
     const bool keep = !seg_offsets && !lds_park && (ctx->solve_keep >= 0 ? ctx->solve_keep != 0 : (ctx->solve_lanes < 0 && waves64 >= ctx->n_simds));
     const dim3 grid(keep ? waves64 : waves);
-#define UAVAC_SOLVE_LAUNCH(R, P, N, K)                                                                                             \
-    do {                                                                                                                            \
-        auto kern = minsnap_solve_bt_kernel<R, P, N, K>;                                                                            \
-        if (P && park > 48 * 1024) UAVAC_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)park)); \
-        hipLaunchKernelGGL(kern, grid, dim3(TB), P ? park : 0, ctx->stream, wp, times, B, m, ctx->d_ws, coeffs, status, ctx->d_flags,   \
-                           seg_offsets, guard_rows, guard_capacity, active);                                                        \
-        ctx->last_solve = std::string("minsnap_solve_bt_kernel<") + (R ? "true, " : "false, ") + (P ? "true, " : "false, ") +       \
-                          std::to_string(N) + ", " + std::to_string(K) + ">";                                                        \
-    } while (0)
-#define UAVAC_SOLVE_LANES(R, P)                                                                                                     \
-    do {                                                                                                                            \
-        if (lanes == 64) UAVAC_SOLVE_LAUNCH(R, P, 64, 0); else if (lanes == 32) UAVAC_SOLVE_LAUNCH(R, P, 32, 0); else UAVAC_SOLVE_LAUNCH(R, P, 16, 0); \
-    } while (0)
-    if (keep) {                                           // (the sixth knot's slab in LDS: 28 x 64 doubles of dynamic shared memory)
-        auto kern = minsnap_solve_bt_kernel<false, false, 64, 5>;
-        hipLaunchKernelGGL(kern, grid, dim3(TB), 28 * TB * sizeof(double), ctx->stream, wp, times, B, m, ctx->d_ws, coeffs, status,
-                           ctx->d_flags, seg_offsets, guard_rows, guard_capacity, active);
-        ctx->last_solve = "minsnap_solve_bt_kernel<false, false, 64, 5>";
-    }
-    else if (lds_park) { if (seg_offsets) UAVAC_SOLVE_LANES(true, true); else UAVAC_SOLVE_LANES(false, true); }
-    else { if (seg_offsets) UAVAC_SOLVE_LANES(true, false); else UAVAC_SOLVE_LANES(false, false); }
-#undef UAVAC_SOLVE_LANES
-#undef UAVAC_SOLVE_LAUNCH
-    UAVAC_HIP(ctx, hipGetLastError());
-    return UAVAC_OK;
+    const bool R = seg_offsets != nullptr;
+    // The thirteen instantiations, named in the order the code object has held them since they were first written (a kernel is emitted
+    // where it is first named): the comparison of the whole disassembly with an earlier build depends on it, nothing at run time does.
+    auto pick = [&](auto k64, auto k32, auto k16) { return lanes == 64 ? k64 : (lanes == 32 ? k32 : k16); };
+    auto kern = minsnap_solve_bt_kernel<false, false, 64, 5>;       // keep (the sixth knot's slab in LDS, 28 x 64 doubles of dynamic shared memory)
+    if (!keep && lds_park && R) kern = pick(minsnap_solve_bt_kernel<true, true, 64, 0>,
+                                            minsnap_solve_bt_kernel<true, true, 32, 0>,
+                                            minsnap_solve_bt_kernel<true, true, 16, 0>);
+    if (!keep && lds_park && !R) kern = pick(minsnap_solve_bt_kernel<false, true, 64, 0>,
+                                             minsnap_solve_bt_kernel<false, true, 32, 0>,
+                                             minsnap_solve_bt_kernel<false, true, 16, 0>);
+    if (!keep && !lds_park && R) kern = pick(minsnap_solve_bt_kernel<true, false, 64, 0>,
+                                             minsnap_solve_bt_kernel<true, false, 32, 0>,
+                                             minsnap_solve_bt_kernel<true, false, 16, 0>);
+    if (!keep && !lds_park && !R) kern = pick(minsnap_solve_bt_kernel<false, false, 64, 0>,
+                                              minsnap_solve_bt_kernel<false, false, 32, 0>,
+                                              minsnap_solve_bt_kernel<false, false, 16, 0>);
+    return launch_solve_kernel(ctx, kern, "minsnap_solve_bt_kernel", R, lds_park, keep ? 64 : lanes, keep ? 5 : 0, grid,
+                               keep ? 28 * TB * sizeof(double) : (lds_park ? park : 0), wp, times, B, m, coeffs, status, seg_offsets, guard_rows,
+                               guard_capacity, active);
 }

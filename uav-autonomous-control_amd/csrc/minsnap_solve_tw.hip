@@ -1,8 +1,8 @@
 // Minimum-snap coefficient solve, TWO-ENDED block-Thomas form: two lanes per mission (gfx950).
 //
-// Same QP, same knot-derivative coordinates and the same 4x4 block-tridiagonal KKT system as minsnap_solve_bt.hip (see there and
-// minsnap_solve.hip for the derivation and the reference lines it replaces: uav_ac/planning/minimum_snap.py:138-255).  That kernel
-// eliminates the interior knots from the first to the last in ONE lane and substitutes back; what bounds it from a chip's worth of
+// Same QP, same knot-derivative coordinates and the same 4x4 block-tridiagonal KKT system as minsnap_solve_bt.hip (minsnap_kkt.h
+// has the derivation, the reference lines it replaces -- uav_ac/planning/minimum_snap.py:138-255 -- and the pieces both kernels
+// share).  That kernel eliminates the interior knots from the first to the last in ONE lane and substitutes back; what bounds it from a chip's worth of
 // waves on is where the forward sweep's [Ut | rt] blocks wait for the backward sweep: a lane holds seven of them on chip (five in
 // registers, one in LDS, the last where it was computed), the rest is parked in HBM -- four of eleven at m = 12, twelve of nineteen
 // at m = 20 (counter bytes 2.5 x the algorithmic ones).
@@ -23,172 +23,14 @@
 // formulation to ~1e-11 on the sampled trajectories).  Every launch shape of THIS file computes the same bits (lanes per wave, where
 // the blocks are parked); which of the two files solves is the ctx option "solve_order" (1 = this one, the default; 0 = one-ended).
 
-#include "uavac_internal.h"
+#include "minsnap_kkt.h"
+#include "minsnap_solve_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-// Q1 = W^T H1 W, S0/S1 = end snaps, W rows 4..7: see minsnap_solve.hip
-constexpr double Q1c[8][8] = {
-    {100800, 50400, 10080, 840, -100800, 50400, -10080, 840},
-    {50400, 25920, 5400, 480, -50400, 24480, -4680, 360},
-    {10080, 5400, 1200, 120, -10080, 4680, -840, 60},
-    {840, 480, 120, 16, -840, 360, -60, 4},
-    {-100800, -50400, -10080, -840, 100800, -50400, 10080, -840},
-    {50400, 24480, 4680, 360, -50400, 25920, -5400, 480},
-    {-10080, -4680, -840, -60, 10080, -5400, 1200, -120},
-    {840, 360, 60, 4, -840, 480, -120, 16}};
-constexpr double S0c[8] = {-840, -480, -120, -16, 840, -360, 60, -4};
-constexpr double S1c[8] = {840, 360, 60, 4, -840, 480, -120, 16};
-constexpr double Wc[4][8] = {
-    {-35, -20, -5, -2.0 / 3.0, 35, -15, 2.5, -1.0 / 6.0},
-    {84, 45, 10, 1, -84, 39, -7, 0.5},
-    {-70, -36, -7.5, -2.0 / 3.0, 70, -34, 6.5, -0.5},
-    {20, 10, 2, 1.0 / 6.0, -20, 10, -2, 1.0 / 6.0}};
-
-// Local 8x8 KKT entry (la, lb) of a segment as coefficient * T^-e.  Local index: 0..3 = (v, a, j, lambda)
-// at the start knot, 4..7 at the end knot.  Both functions fold to literals once la, lb are unrolled.
-__device__ __forceinline__ constexpr double loc_coef(int la, int lb) {
-    const int ca = la & 3, cb = lb & 3;
-    if (ca == 3 && cb == 3) return 0.0;
-    if (ca == 3 || cb == 3) {
-        const int ll = (ca == 3) ? la : lb, ld = (ca == 3) ? lb : la;
-        const int d = (ld & 4) + (ld & 3) + 1;
-        return (ll & 4) ? S1c[d] : -S0c[d];        // knot constraint: snap_end(prev) - snap_start(next) = 0
-    }
-    return Q1c[(la & 4) + ca + 1][(lb & 4) + cb + 1];
-}
-__device__ __forceinline__ constexpr int loc_exp(int la, int lb) {
-    const int ca = la & 3, cb = lb & 3;
-    if (ca == 3 && cb == 3) return 0;
-    if (ca == 3) return 4 - (cb + 1);
-    if (cb == 3) return 4 - (ca + 1);
-    return 7 - (ca + 1) - (cb + 1);
-}
-// right-hand side of local row la: coefficient of p_start / p_end, times T^-e
-__device__ __forceinline__ constexpr double rhs_c0(int la) {
-    const int ca = la & 3;
-    if (ca == 3) return (la & 4) ? -S1c[0] : S0c[0];
-    return -Q1c[(la & 4) + ca + 1][0];
-}
-__device__ __forceinline__ constexpr double rhs_c1(int la) {
-    const int ca = la & 3;
-    if (ca == 3) return (la & 4) ? -S1c[4] : S0c[4];
-    return -Q1c[(la & 4) + ca + 1][4];
-}
-__device__ __forceinline__ constexpr int rhs_exp(int la) { return ((la & 3) == 3) ? 4 : 7 - ((la & 3) + 1); }
-
-struct Seg {
-    double A[4][4], B[4][4], C[4][4];     // start-start, start-end, end-end blocks
-    double rs[4][3], re[4][3];            // right-hand side rows of the start / end knot, per axis
-    double ip[8];                         // T^-e
-};
-
-__device__ __forceinline__ void build_segment(Seg &g, double T, const double p0[3], const double p1[3]) {
-    const double r = 1.0 / T;
-    g.ip[0] = 1.0;
-#pragma unroll
-    for (int e = 1; e < 8; ++e) g.ip[e] = g.ip[e - 1] * r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            g.A[i][j] = loc_coef(i, j) * g.ip[loc_exp(i, j)];
-            g.B[i][j] = loc_coef(i, 4 + j) * g.ip[loc_exp(i, 4 + j)];
-            g.C[i][j] = loc_coef(4 + i, 4 + j) * g.ip[loc_exp(4 + i, 4 + j)];
-        }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            g.rs[i][a] = (rhs_c0(i) * p0[a] + rhs_c1(i) * p1[a]) * g.ip[rhs_exp(i)];
-            g.re[i][a] = (rhs_c0(4 + i) * p0[a] + rhs_c1(4 + i) * p1[a]) * g.ip[rhs_exp(4 + i)];
-        }
-}
-
-// Solve S X = R (4x4, 7 right-hand sides) in natural order; returns false on a zero / non-finite pivot.
-__device__ __forceinline__ bool solve4(double S[4][4], double R[4][7]) {
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const double piv = S[j][j];
-        ok = ok && (fabs(piv) > 0.0) && isfinite(piv);
-        const double inv = 1.0 / piv;
-#pragma unroll
-        for (int i = j + 1; i < 4; ++i) {
-            const double l = S[i][j] * inv;
-#pragma unroll
-            for (int c = j + 1; c < 4; ++c) S[i][c] = fma(-l, S[j][c], S[i][c]);
-#pragma unroll
-            for (int c = 0; c < 7; ++c) R[i][c] = fma(-l, R[j][c], R[i][c]);
-        }
-    }
-#pragma unroll
-    for (int i = 3; i >= 0; --i) {
-        const double inv = 1.0 / S[i][i];
-#pragma unroll
-        for (int c = 0; c < 7; ++c) {
-            double s = R[i][c];
-#pragma unroll
-            for (int q = i + 1; q < 4; ++q) s = fma(-S[i][q], R[q][c], s);
-            R[i][c] = s * inv;
-        }
-    }
-    return ok;
-}
-
-// 24 monomial coefficients (ascending powers, [8][3]) of one segment from its knot data
-__device__ __forceinline__ void segment_coeffs(const double ip[8], double T, const double p0[3], const double p1[3],
-                                               const double x0[3][3], const double x1[3][3], double out[8][3]) {
-    const double T2 = T * T, T3 = T2 * T;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        // e = diag(1, T, T^2, T^3, 1, T, T^2, T^3) [p v a j]_start (+) [p v a j]_end
-        const double e[8] = {p0[a], T * x0[0][a], T2 * x0[1][a], T3 * x0[2][a],
-                             p1[a], T * x1[0][a], T2 * x1[1][a], T3 * x1[2][a]};
-        out[0][a] = p0[a];
-        out[1][a] = x0[0][a];
-        out[2][a] = 0.5 * x0[1][a];
-        out[3][a] = x0[2][a] * (1.0 / 6.0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            double s = 0.0;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) s = fma(Wc[i][q], e[q], s);
-            out[4 + i][a] = s * ip[4 + i];
-        }
-    }
-}
-
 constexpr int TB = 64;          // one wave: 32 mission slots, lane q the head and lane q + 32 the tail of slot q
-
-// H = C_prev - B_prev^T Ut, h = re_prev - B_prev^T rt: what the segments BEHIND a knot contribute to its 4x4 system (the Schur
-// complement of everything eliminated so far).  With `any` false nothing has been eliminated yet: H = C_prev, h = re_prev.
-__device__ __forceinline__ void schur_behind(const Seg &prev, bool any, const double Ut[4][4], const double rt[4][3], double H[4][4],
-                                             double h[4][3]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            double s = prev.C[i][j];
-            if (any) {
-#pragma unroll
-                for (int l = 0; l < 4; ++l) s = fma(-prev.B[l][i], Ut[l][j], s);
-            }
-            H[i][j] = s;
-        }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            double s = prev.re[i][a];
-            if (any) {
-#pragma unroll
-                for (int l = 0; l < 4; ++l) s = fma(-prev.B[l][i], rt[l][a], s);
-            }
-            h[i][a] = s;
-        }
-    }
-}
 
 // sign of unknown i (v, a, j, lambda) under time reversal
 __device__ __forceinline__ constexpr double jsign(int i) { return i == 1 ? 1.0 : -1.0; }
@@ -282,6 +124,7 @@ __global__ void __launch_bounds__(TB) minsnap_solve_tw_kernel(const double *__re
                 nt = tv((k + 1 <= m - 1) ? k + 1 : m - 1);
             }
             build_segment(cur, T, p0, p1);
+            // (from here to the park store the same lines as in minsnap_solve_bt.hip: as functions of minsnap_kkt.h they move the schedule, see there)
             double S[4][4], R[4][7];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -327,15 +170,7 @@ __global__ void __launch_bounds__(TB) minsnap_solve_tw_kernel(const double *__re
             if (NREG > 0 && kk < NREG) {
 #pragma unroll
                 for (int qq = 0; qq < NREG; ++qq)
-                    if (kk == qq) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) kept[qq][i * 4 + j] = R[i][j];
-#pragma unroll
-                            for (int a = 0; a < 3; ++a) kept[qq][16 + i * 3 + a] = R[i][4 + a];
-                        }
-                    }
+                    if (kk == qq) store_block(R, kept[qq], 1);
             }
             prev = cur;
         }
@@ -407,13 +242,7 @@ __global__ void __launch_bounds__(TB) minsnap_solve_tw_kernel(const double *__re
     // on their way while the segment before is computed: the block of view knot s - 2, start waypoint and duration of view segment s - 1
     double nxt[28], nw[3], nt;
     {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) nxt[i * 4 + j] = Ut[i][j];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) nxt[16 + i * 3 + a] = rt[i][a];
-        }
+        pack_block(Ut, rt, nxt);
         const double *s0 = wv(nel);
 #pragma unroll
         for (int a = 0; a < 3; ++a) nw[a] = s0[a];
@@ -432,15 +261,9 @@ __global__ void __launch_bounds__(TB) minsnap_solve_tw_kernel(const double *__re
             if (NREG > 0 && s - 2 < NREG) {
 #pragma unroll
                 for (int qq = 0; qq < NREG; ++qq)
-                    if (s - 2 == qq) {
-#pragma unroll
-                        for (int i = 0; i < 28; ++i) nxt[i] = kept[qq][i];
-                    }
+                    if (s - 2 == qq) load_block(nxt, kept[qq], 1);
             } else {
-                const double *o = park_at(s - 2);
-                const size_t ost = park_stride(s - 2);
-#pragma unroll
-                for (int i = 0; i < 28; ++i) nxt[i] = o[(size_t)i * ost];
+                load_block(nxt, park_at(s - 2), park_stride(s - 2));
             }
         }
         if (s >= 1) {
@@ -452,15 +275,7 @@ __global__ void __launch_bounds__(TB) minsnap_solve_tw_kernel(const double *__re
         if (s >= 0 && step < nseg) {
             double xs[4][3];                            // unknowns of view knot s - 1 (the near end of view segment s); zero at the mission's end point
             if (s >= 1) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) {
-                        double v = cur[16 + i * 3 + a];
-#pragma unroll
-                        for (int l = 0; l < 4; ++l) v = fma(-cur[i * 4 + l], xn[l][a], v);
-                        xs[i][a] = v;
-                    }
+                substitute_knot(cur, true, xn, xs);
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -530,38 +345,26 @@ int uavac_launch_solve_tw(uavac_ctx *ctx, const double *wp, const double *times,
     // The HBM workspace [m - 1][28][B] (rows = a knot's index in its mission) is only needed by the forms that park there: a launch
     // that parks in LDS never touches it (round-5 advice: 411 MB at B = 262 144, m = 8 were allocated for nothing).
     if (!lds_park) {
-        const size_t need = (size_t)(m > 1 ? m - 1 : 1) * 28 * (size_t)B;
-        if (need > ctx->ws_cap) {
-            if (ctx->d_ws) UAVAC_HIP(ctx, hipFree(ctx->d_ws));
-            ctx->d_ws = nullptr;
-            ctx->ws_cap = 0;
-            UAVAC_HIP(ctx, hipMalloc(&ctx->d_ws, sizeof(double) * need));
-            ctx->ws_cap = need;
-        }
+        if (int rc = ensure_solve_workspace(ctx, B, m)) return rc;
     }
-#define UAVAC_SOLVE_LAUNCH(R, P, N, K)                                                                                             \
-    do {                                                                                                                            \
-        auto kern = minsnap_solve_tw_kernel<R, P, N, K>;                                                                            \
-        if (P && park > 48 * 1024) UAVAC_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)park)); \
-        hipLaunchKernelGGL(kern, grid, dim3(TB), P ? park : 0, ctx->stream, wp, times, B, m, ctx->d_ws, coeffs, status, ctx->d_flags,   \
-                           seg_offsets, guard_rows, guard_capacity, active);                                                        \
-        ctx->last_solve = std::string("minsnap_solve_tw_kernel<") + (R ? "true, " : "false, ") + (P ? "true, " : "false, ") +       \
-                          std::to_string(N) + ", " + std::to_string(K) + ">";                                                        \
-    } while (0)
-#define UAVAC_SOLVE_LANES(R, P)                                                                                                     \
-    do {                                                                                                                            \
-        if (nm == 32) UAVAC_SOLVE_LAUNCH(R, P, 32, 0); else if (nm == 16) UAVAC_SOLVE_LAUNCH(R, P, 16, 0); else UAVAC_SOLVE_LAUNCH(R, P, 8, 0); \
-    } while (0)
-    if (keep) {                                           // (the sixth block's slab in LDS: 28 x 64 doubles of dynamic shared memory)
-        auto kern = minsnap_solve_tw_kernel<false, false, 32, 5>;
-        hipLaunchKernelGGL(kern, grid, dim3(TB), 28 * TB * sizeof(double), ctx->stream, wp, times, B, m, ctx->d_ws, coeffs, status,
-                           ctx->d_flags, seg_offsets, guard_rows, guard_capacity, active);
-        ctx->last_solve = "minsnap_solve_tw_kernel<false, false, 32, 5>";
-    }
-    else if (lds_park) { if (seg_offsets) UAVAC_SOLVE_LANES(true, true); else UAVAC_SOLVE_LANES(false, true); }
-    else { if (seg_offsets) UAVAC_SOLVE_LANES(true, false); else UAVAC_SOLVE_LANES(false, false); }
-#undef UAVAC_SOLVE_LANES
-#undef UAVAC_SOLVE_LAUNCH
-    UAVAC_HIP(ctx, hipGetLastError());
-    return UAVAC_OK;
+    const bool R = seg_offsets != nullptr;
+    // The thirteen instantiations, named in the order the code object has held them since they were first written (a kernel is emitted
+    // where it is first named): the comparison of the whole disassembly with an earlier build depends on it, nothing at run time does.
+    auto pick = [&](auto k32, auto k16, auto k8) { return nm == 32 ? k32 : (nm == 16 ? k16 : k8); };
+    auto kern = minsnap_solve_tw_kernel<false, false, 32, 5>;       // keep (the sixth block's slab in LDS, 28 x 64 doubles of dynamic shared memory)
+    if (!keep && lds_park && R) kern = pick(minsnap_solve_tw_kernel<true, true, 32, 0>,
+                                            minsnap_solve_tw_kernel<true, true, 16, 0>,
+                                            minsnap_solve_tw_kernel<true, true, 8, 0>);
+    if (!keep && lds_park && !R) kern = pick(minsnap_solve_tw_kernel<false, true, 32, 0>,
+                                             minsnap_solve_tw_kernel<false, true, 16, 0>,
+                                             minsnap_solve_tw_kernel<false, true, 8, 0>);
+    if (!keep && !lds_park && R) kern = pick(minsnap_solve_tw_kernel<true, false, 32, 0>,
+                                             minsnap_solve_tw_kernel<true, false, 16, 0>,
+                                             minsnap_solve_tw_kernel<true, false, 8, 0>);
+    if (!keep && !lds_park && !R) kern = pick(minsnap_solve_tw_kernel<false, false, 32, 0>,
+                                              minsnap_solve_tw_kernel<false, false, 16, 0>,
+                                              minsnap_solve_tw_kernel<false, false, 8, 0>);
+    return launch_solve_kernel(ctx, kern, "minsnap_solve_tw_kernel", R, lds_park, keep ? 32 : nm, keep ? 5 : 0, grid,
+                               keep ? 28 * TB * sizeof(double) : (lds_park ? park : 0), wp, times, B, m, coeffs, status, seg_offsets, guard_rows,
+                               guard_capacity, active);
 }

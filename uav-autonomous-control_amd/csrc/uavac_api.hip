@@ -435,7 +435,7 @@ int uavac_minsnap_solve_dev(uavac_ctx *ctx, const double *wp, const double *time
     UAVAC_ENTER(ctx);
     if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
     if (!times || !coeffs) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    return uavac_launch_solve_bt(ctx, wp, times, B, m, coeffs, status);
+    return uavac_launch_coeff_solve(ctx, wp, times, B, m, coeffs, status);
 }
 
 int uavac_minsnap_solve_banded_dev(uavac_ctx *ctx, const double *wp, const double *times, int B, int m,
@@ -443,7 +443,7 @@ int uavac_minsnap_solve_banded_dev(uavac_ctx *ctx, const double *wp, const doubl
     UAVAC_ENTER(ctx);
     if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
     if (!times || !coeffs) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    return uavac_launch_solve(ctx, wp, times, B, m, coeffs, status);
+    return uavac_launch_solve_banded(ctx, wp, times, B, m, coeffs, status);
 }
 
 static int check_sample_args(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *row_offsets,
@@ -528,7 +528,7 @@ int uavac_minsnap_solve_ragged_dev(uavac_ctx *ctx, const double *wp, const doubl
     UAVAC_ENTER(ctx);
     if (int rc = check_plan_args(ctx, wp, B, max_m)) return rc;
     if (!seg_offsets || !times || !coeffs) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    return uavac_launch_solve_bt(ctx, wp, times, B, max_m, coeffs, status, seg_offsets);
+    return uavac_launch_coeff_solve(ctx, wp, times, B, max_m, coeffs, status, seg_offsets);
 }
 
 int uavac_minsnap_sample_ragged_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets,
@@ -564,7 +564,7 @@ int uavac_minsnap_plan_dev(uavac_ctx *ctx, const double *wp, int B, int m, doubl
         // arrays; the one value of the sampler a plan-fed rollout needs comes from the first-heading kernel.
         if (yaw) return uavac_fail(ctx, UAVAC_EINVAL, "a dense yaw column needs the rows: traj is NULL");
         if (int rc = uavac_launch_row_counts(ctx, wp, B, m, velocity, dt, times, seg_rows, row_offsets)) return rc;
-        if (int rc = uavac_launch_solve_bt(ctx, wp, times, B, m, coeffs, status)) return rc;
+        if (int rc = uavac_launch_coeff_solve(ctx, wp, times, B, m, coeffs, status)) return rc;
         return first_yaw ? uavac_launch_first_yaw(ctx, coeffs, seg_rows, nullptr, B, m, dt, first_yaw) : UAVAC_OK;
     }
     if (traj_capacity_rows < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative capacity");
@@ -595,7 +595,7 @@ int uavac_minsnap_plan_dev(uavac_ctx *ctx, const double *wp, int B, int m, doubl
     // (Round 6 tried to hide this solve behind the sampler: the batch cut into 2 / 4 / 8 mission blocks, block i sampled on an
     // auxiliary stream while block i + 1 was being solved.  Bit-identical and SLOWER -- +1.3 % / +13 % / +23 % at 65 536 x 12 --
     // because a solve wave cannot get onto a SIMD the sampler's grid keeps full: commit 53921dc, profiles/r06_plan_blocks_ab*.jsonl.)
-    if (int rc = uavac_launch_solve_bt(ctx, wp, times_s, B, m, coeffs, status, nullptr, row_offsets_s + B, traj_capacity_rows))
+    if (int rc = uavac_launch_coeff_solve(ctx, wp, times_s, B, m, coeffs, status, nullptr, row_offsets_s + B, traj_capacity_rows))
         return rc;
     SampleExtras x;
     x.yaw_dense = yaw;
@@ -641,7 +641,7 @@ int uavac_minsnap_obstacle_round_dev(uavac_ctx *ctx, const double *wp, const int
     if (!(velocity > 0.0) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "velocity and dt must be > 0");
     UAVAC_HIP(ctx, hipMemsetAsync(counters, 0, 4 * sizeof(int32_t), ctx->stream));
     if (int rc = uavac_launch_row_counts(ctx, wp, B, max_m, velocity, dt, times, seg_rows, row_offsets, seg_offsets)) return rc;
-    if (int rc = uavac_launch_solve_bt(ctx, wp, times, B, max_m, coeffs, nullptr, seg_offsets, nullptr, 0, active)) return rc;
+    if (int rc = uavac_launch_coeff_solve(ctx, wp, times, B, max_m, coeffs, nullptr, seg_offsets, nullptr, 0, active)) return rc;
     return uavac_launch_obstacle_scan_and_insert(ctx, wp, seg_offsets, coeffs, seg_rows, B, max_m, dt, aabb, active, overflow,
                                                  touched, hit, wp_out, seg_offsets_out, counters);
 }
@@ -699,7 +699,7 @@ int uavac_minsnap_solve(uavac_ctx *ctx, const double *wp, int B, int m, double v
     if (int rc = h2d_staged(ctx, dwp, wp, nwp * 8)) return rc;
     // dt only shapes the row counts, which this entry point does not return
     if (int rc = uavac_launch_row_counts(ctx, dwp, B, m, velocity, 1.0, dt_, dsr, dro)) return rc;
-    if (int rc = uavac_launch_solve_bt(ctx, dwp, dt_, B, m, dco, nullptr)) return rc;
+    if (int rc = uavac_launch_coeff_solve(ctx, dwp, dt_, B, m, dco, nullptr)) return rc;
     if (int rc = d2h_staged(ctx, coeffs, dco, nco * 8)) return rc;
     if (times) if (int rc = d2h_staged(ctx, times, dt_, nseg * 8)) return rc;
     int32_t fl[4];
@@ -794,7 +794,7 @@ int uavac_minsnap_plan_ragged(uavac_ctx *ctx, const double *wp, const int64_t *s
         if (int rc = stage_inputs((size_t)total * UAVAC_TRAJ_COLS * 8, dwp, dso, dtm, dsr, dro, dco, dtr)) return rc;
         if (int rc = uavac_launch_row_counts(ctx, dwp, B, max_m, velocity, dt, dtm, dsr, dro, dso)) return rc;
     }
-    if (int rc = uavac_launch_solve_bt(ctx, dwp, dtm, B, max_m, dco, nullptr, dso)) return rc;
+    if (int rc = uavac_launch_coeff_solve(ctx, dwp, dtm, B, max_m, dco, nullptr, dso)) return rc;
     if (rows) {
         SampleExtras x;
         x.seg_offsets = dso;

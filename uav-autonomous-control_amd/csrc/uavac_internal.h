@@ -153,17 +153,22 @@ struct VehK {
 VehK uavac_make_vehk(const uavac_vehicle &V);
 int uavac_check_vehicle(uavac_ctx *ctx, const uavac_vehicle *V);
 
-// launchers (one per .hip file)
+// launchers
 // seg_offsets (device, [B+1]) != NULL: ragged batch -- mission b has seg_offsets[b+1] - seg_offsets[b] segments (1 .. m,
 // m = the batch's maximum); waypoints, times, row counts, coefficients and hit flags lie back to back
 int uavac_launch_row_counts(uavac_ctx *ctx, const double *wp, int B, int m, double velocity, double dt,
                             double *times, int32_t *seg_rows, int64_t *row_offsets, const int64_t *seg_offsets = nullptr);
+// The coefficient solve (minsnap_solve.hip): hands over to the two-ended or the one-ended block-Thomas launcher by ctx->solve_order.
 // guard_rows (device, may be NULL): the launch does nothing when *guard_rows > guard_capacity (a refused planning chain)
-int uavac_launch_solve_bt(uavac_ctx *ctx, const double *wp, const double *times, int B, int m, double *coeffs,
-                          int32_t *status, const int64_t *seg_offsets = nullptr, const int64_t *guard_rows = nullptr,
-                          int64_t guard_capacity = 0, const int32_t *active = nullptr);
-// the two-ended form (minsnap_solve_tw.hip): two lanes per mission; uavac_launch_solve_bt hands over to it unless ctx->solve_order == 0
+int uavac_launch_coeff_solve(uavac_ctx *ctx, const double *wp, const double *times, int B, int m, double *coeffs,
+                             int32_t *status, const int64_t *seg_offsets = nullptr, const int64_t *guard_rows = nullptr,
+                             int64_t guard_capacity = 0, const int32_t *active = nullptr);
+// its two forms: two lanes per mission (minsnap_solve_tw.hip), one lane per mission (minsnap_solve_bt.hip); what the two launchers
+// share on the host side is in minsnap_solve_launch.h, the device pieces of both kernels in minsnap_kkt.h
 int uavac_launch_solve_tw(uavac_ctx *ctx, const double *wp, const double *times, int B, int m, double *coeffs,
+                          int32_t *status, const int64_t *seg_offsets, const int64_t *guard_rows, int64_t guard_capacity,
+                          const int32_t *active);
+int uavac_launch_solve_bt(uavac_ctx *ctx, const double *wp, const double *times, int B, int m, double *coeffs,
                           int32_t *status, const int64_t *seg_offsets, const int64_t *guard_rows, int64_t guard_capacity,
                           const int32_t *active);
 // One round of the obstacle loop on the device (minsnap_obstacles.hip): collision scan of the active missions' splines
@@ -181,8 +186,9 @@ int uavac_ensure_totals(uavac_ctx *ctx, int B, int32_t **totals, int64_t **tile_
 // times / seg_rows / row_offsets from scratch into the caller's arrays unless row_offsets_s[B] > capacity_rows
 int uavac_launch_plan_commit(uavac_ctx *ctx, const double *times_s, const int32_t *seg_rows_s, const int64_t *row_offsets_s,
                              int B, int m, int64_t capacity_rows, double *times, int32_t *seg_rows, int64_t *row_offsets);
-int uavac_launch_solve(uavac_ctx *ctx, const double *wp, const double *times, int B, int m, double *coeffs,
-                       int32_t *status);
+// the pivoted banded-LU form of the coefficient solve: the cross-check behind uavac_minsnap_solve_banded_dev
+int uavac_launch_solve_banded(uavac_ctx *ctx, const double *wp, const double *times, int B, int m, double *coeffs,
+                              int32_t *status);
 // Optional outputs / inputs of the sampler (minsnap_sample.hip)
 struct SampleExtras {
     const double *aabb = nullptr;    // [6] cuboid of the collision scan, with
