@@ -56,6 +56,10 @@ def lib():
         _lib.oracle_sample.argtypes = [_P, _P, C.c_int, C.c_double, _P]
         _lib.oracle_rollout.restype = None
         _lib.oracle_rollout.argtypes = [C.POINTER(Vehicle), _P, C.c_int64, _P, _P, C.c_int, _P, _P, _P, C.c_int]
+        _lib.oracle_rollout_ld.restype = None
+        _lib.oracle_rollout_ld.argtypes = _lib.oracle_rollout.argtypes
+        _lib.oracle_tick_margins_ld.restype = None
+        _lib.oracle_tick_margins_ld.argtypes = [C.POINTER(Vehicle), _P, C.c_int64, _P, _P, _P]
         _lib.oracle_bench_threads.restype = C.c_int64
         _lib.oracle_bench_threads.argtypes = [C.POINTER(Vehicle), _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                               C.c_int, C.c_double, _P]
@@ -123,6 +127,30 @@ def rollout(traj, state, istate, K: int, V: Vehicle | None = None, log_state=Tru
     lib().oracle_rollout(C.byref(V), _p(traj), len(traj), _p(state), _p(istate), K, _p(slog), _p(clog), _p(ab),
                          0 if ab is None else len(ab))
     return slog, clog
+
+
+def rollout_ld(traj, state, istate, K: int, V: Vehicle | None = None, log_state=True, log_cmd=True, aabbs=None):
+    """`rollout` with every operation in long double (`oracle_rollout_ld`): same arguments, same outputs, rounded to fp64 where they
+    leave.  Raises where long double is no wider than double: there is no silent fp64 fall-back."""
+    if lib().oracle_ldbl_mant_dig() < 64:
+        raise RuntimeError(f"long double has {lib().oracle_ldbl_mant_dig()} mantissa bits here; oracle_rollout_ld needs >= 64")
+    V = V or Vehicle.default()
+    traj = np.ascontiguousarray(traj, dtype=np.float64)
+    slog = np.empty((K, 13)) if log_state else None
+    clog = np.empty((K, 12)) if log_cmd else None
+    ab = None if aabbs is None else np.ascontiguousarray(aabbs, dtype=np.float64)
+    lib().oracle_rollout_ld(C.byref(V), _p(traj), len(traj), _p(state), _p(istate), K, _p(slog), _p(clog), _p(ab),
+                            0 if ab is None else len(ab))
+    return slog, clog
+
+
+def tick_margins_ld(traj, state, istate, V: Vehicle) -> np.ndarray:
+    """How far the long-double tick from (state[26], istate[4]) is from each of its discontinuous decisions
+    (`oracle_tick_margins_ld`): yaw wrap, |R22|, ground |r| before and after the step, take-off height.  1 where none applies."""
+    traj = np.ascontiguousarray(traj, dtype=np.float64)
+    out = np.empty(5)
+    lib().oracle_tick_margins_ld(C.byref(V), _p(traj), len(traj), _p(state), _p(istate), _p(out))
+    return out
 
 
 def bench_threads(wps, velocity: float, dt: float, ticks: int, n_threads: int, budget_s: float, V: Vehicle | None = None):

@@ -793,3 +793,218 @@ int oracle_solve_ld(const double *wp, int m, double velocity, double *coeffs, do
     free(K); free(rhs);
     return rc;
 }
+
+/* ------------------------------------------------------------------ high-precision tick (tests only)
+ * oracle_rollout's tick -- controller (main.py:37-61, controller.py:26-168, quad.py:88-122) then vehicle (mujoco_sim.py:232-251 +
+ * the Euler free-joint step and the build-defined ground contact) -- with every operation in long double, from the same fp64
+ * state, rows and vehicle, rounded to fp64 where a value leaves: the end state and the two logs.  Between ticks of one call the
+ * state stays in long double.  Written from the upstream formulas, not from the fp64 functions above: the rotation matrix in
+ * closed form, the quaternion product as the Hamilton product.  Integer outputs follow oracle_rollout's rules.  Does nothing
+ * where long double is no wider than double (callers ask oracle_ldbl_mant_dig first). */
+typedef long double ld;
+#define PI_LD 3.141592653589793238462643383279502884L
+
+static ld clip_ld(ld x, ld lo, ld hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+static ld pymod_ld(ld a, ld b) { /* Python's float % for b > 0 */
+    ld r = fmodl(a, b);
+    if (r < 0.0L) r += b;
+    return r;
+}
+
+typedef struct {
+    ld p[3], q[4], v[3], w[3], om[4], omc[4], integ, thrust, pqr[3];
+    int32_t idx, inner, collided, gbits;
+} uav_ld;
+
+/* body -> world rotation of the normalised quaternion (quad.py:133-155, written out) */
+static void rot_ld(const ld *q, ld R[3][3]) {
+    const ld n = sqrtl(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const ld a = q[0] / n, b = q[1] / n, c = q[2] / n, d = q[3] / n;
+    R[0][0] = 1.0L - 2.0L * (c * c + d * d); R[0][1] = 2.0L * (b * c - a * d);        R[0][2] = 2.0L * (b * d + a * c);
+    R[1][0] = 2.0L * (b * c + a * d);        R[1][1] = 1.0L - 2.0L * (b * b + d * d); R[1][2] = 2.0L * (c * d - a * b);
+    R[2][0] = 2.0L * (b * d - a * c);        R[2][1] = 2.0L * (c * d + a * b);        R[2][2] = 1.0L - 2.0L * (b * b + c * c);
+}
+
+static void controller_tick_ld(const oracle_vehicle *V, uav_ld *u, const double *traj, int64_t nrows) {
+    const ld mass = V->mass, fmin_ = V->min_thrust, fmax_ = V->max_thrust;
+    if (u->inner % V->F == 0 && nrows > 0) {
+        const double *tg = traj + (int64_t)u->idx * 11;
+        ld R[3][3];
+        rot_ld(u->q, R);
+        /* altitude */
+        const ld zd = clip_ld((ld)tg[5], -(ld)V->max_ascent, (ld)V->max_descent);
+        const ld ez = (ld)tg[2] - u->p[2], ezd = zd - u->v[2];
+        u->integ = clip_ld(u->integ + ez * (ld)V->dt_outer, -10.0L, 10.0L);
+        const ld acc = ((ld)V->kp_z * ez + (ld)V->ki_z * u->integ + (ld)V->kd_z * ezd + (ld)tg[8] - (ld)V->g) / R[2][2];
+        const ld c = clip_ld(-mass * acc, 4.0L * fmin_, 4.0L * fmax_);
+        u->thrust = c;
+        /* lateral */
+        ld vdx = tg[3], vdy = tg[4];
+        const ld vm = sqrtl(vdx * vdx + vdy * vdy);
+        if (vm > (ld)V->max_speed_xy) { vdx = vdx / vm * (ld)V->max_speed_xy; vdy = vdy / vm * (ld)V->max_speed_xy; }
+        ld ax = (ld)V->kp_xy * ((ld)tg[0] - u->p[0]) + (ld)V->kd_xy * (vdx - u->v[0]) + (ld)tg[6];
+        ld ay = (ld)V->kp_xy * ((ld)tg[1] - u->p[1]) + (ld)V->kd_xy * (vdy - u->v[1]) + (ld)tg[7];
+        const ld am = sqrtl(ax * ax + ay * ay);
+        if (am > (ld)V->max_horiz_accel) { ax = ax / am * (ld)V->max_horiz_accel; ay = ay / am * (ld)V->max_horiz_accel; }
+        const ld az = -c / mass;
+        const ld bx = clip_ld(ax / az, -(ld)V->max_tilt, (ld)V->max_tilt), by = clip_ld(ay / az, -(ld)V->max_tilt, (ld)V->max_tilt);
+        /* roll / pitch */
+        const ld bdx = (ld)V->kp_roll * (bx - R[0][2]), bdy = (ld)V->kp_pitch * (by - R[1][2]);
+        const ld pc = (R[1][0] * bdx - R[0][0] * bdy) / R[2][2];
+        const ld qc = (R[1][1] * bdx - R[0][1] * bdy) / R[2][2];
+        /* yaw, on the Euler angles of the stored quaternion (quad.py:189-213) */
+        const ld *q = u->q;
+        const ld phi = atan2l(2.0L * (q[0] * q[1] + q[2] * q[3]), 1.0L - 2.0L * (q[1] * q[1] + q[2] * q[2]));
+        const ld theta = asinl(clip_ld(2.0L * (q[0] * q[2] - q[3] * q[1]), -1.0L, 1.0L));
+        const ld psi = atan2l(2.0L * (q[0] * q[3] + q[1] * q[2]), 1.0L - 2.0L * (q[2] * q[2] + q[3] * q[3]));
+        const ld pd = pymod_ld((ld)tg[9], 2.0L * PI_LD);
+        const ld ye = pymod_ld(pd - psi + PI_LD, 2.0L * PI_LD) - PI_LD;
+        u->pqr[0] = pc; u->pqr[1] = qc;
+        u->pqr[2] = ((ld)V->kp_yaw * ye * cosl(theta) - qc * sinl(phi)) / cosl(phi);
+        u->idx = (u->idx + 1 < nrows - 1) ? u->idx + 1 : (int32_t)(nrows - 1);
+    }
+    /* body rates: I kp (cmd - w) + w x (I w) */
+    const ld *w = u->w;
+    const ld I0 = V->I[0], I1 = V->I[1], I2 = V->I[2];
+    const ld Mx = I0 * (ld)V->kp_p * (u->pqr[0] - w[0]) + (w[1] * (I2 * w[2]) - w[2] * (I1 * w[1]));
+    const ld My = I1 * (ld)V->kp_q * (u->pqr[1] - w[1]) + (w[2] * (I0 * w[0]) - w[0] * (I2 * w[2]));
+    const ld Mz = I2 * (ld)V->kp_r * (u->pqr[2] - w[2]) + (w[0] * (I1 * w[1]) - w[1] * (I0 * w[0]));
+    /* allocation */
+    const ld col = clip_ld(u->thrust, 4.0L * fmin_, 4.0L * fmax_) / 4.0L;
+    const ld pb = Mx / (ld)V->arm, qb = My / (ld)V->arm, rb = -Mz / (ld)V->kappa;
+    const ld mf[4] = {(pb + qb + rb) / 4.0L, (-pb + qb - rb) / 4.0L, (-pb - qb + rb) / 4.0L, (pb - qb - rb) / 4.0L};
+    ld lim = 1.0L;                                                  /* min over rotors of the limit, clipped to [0, 1] below */
+    int any = 0;
+    for (int i = 0; i < 4; ++i) {
+        ld l = 1.0L;
+        if (mf[i] > 0.0L) l = (fmax_ - col) / mf[i];
+        else if (mf[i] < 0.0L) l = (fmin_ - col) / mf[i];
+        if (!any || l < lim) lim = l;
+        any = 1;
+    }
+    const ld sc = clip_ld(lim, 0.0L, 1.0L);
+    for (int i = 0; i < 4; ++i) {
+        const ld f = clip_ld(col + sc * mf[i], fmin_, fmax_);
+        u->omc[i] = sqrtl(f / (ld)V->kf);
+        const ld tau = u->omc[i] > u->om[i] ? (ld)V->tau_rise : (ld)V->tau_fall;
+        u->om[i] += (1.0L - expl(-(ld)V->dt / tau)) * (u->omc[i] - u->om[i]);
+    }
+    u->inner += 1;
+}
+
+static void dynamics_step_ld(const oracle_vehicle *V, uav_ld *u) {
+    const ld dt = V->dt, kf = V->kf, arm = V->arm, mass = V->mass;
+    ld f[4];
+    for (int i = 0; i < 4; ++i) f[i] = kf * u->om[i] * u->om[i];
+    const ld T = f[0] + f[1] + f[2] + f[3];
+    const ld tau[3] = {arm * (f[0] + f[3] - f[1] - f[2]), arm * (f[0] + f[1] - f[2] - f[3]), (ld)V->kappa * (-f[0] + f[1] - f[2] + f[3])};
+    ld R[3][3];
+    rot_ld(u->q, R);
+    ld *w = u->w;
+    const ld I[3] = {V->I[0], V->I[1], V->I[2]};
+    const ld gyro[3] = {w[1] * (I[2] * w[2]) - w[2] * (I[1] * w[1]), w[2] * (I[0] * w[0]) - w[0] * (I[2] * w[2]),
+                        w[0] * (I[1] * w[1]) - w[1] * (I[0] * w[0])};
+    const ld acc[3] = {-(T / mass) * R[0][2], -(T / mass) * R[1][2], (ld)V->g - (T / mass) * R[2][2]};
+    ld vz_ref = 0.0L;
+    int touching = 0;
+    if (V->ground) {
+        const ld r = u->p[2] - ((ld)V->ground_z - (ld)V->ground_clearance), tc = V->ground_timeconst;
+        if (r > 0.0L) { touching = 1; vz_ref = u->v[2] + dt * -(2.0L / tc * u->v[2] + r / (tc * tc)); }
+    }
+    for (int i = 0; i < 3; ++i) u->v[i] += dt * acc[i];
+    if (touching && vz_ref < u->v[2]) u->v[2] = vz_ref;
+    ld wn2 = 0.0L;
+    for (int i = 0; i < 3; ++i) {
+        w[i] += dt * ((tau[i] - gyro[i]) / I[i]);
+        u->p[i] += dt * u->v[i];
+        wn2 += w[i] * w[i];
+    }
+    /* q <- normalise(q (x) [cos h, sin(h) w / |w|]), h = |w| dt / 2 */
+    const ld *q = u->q;
+    ld nq[4] = {q[0], q[1], q[2], q[3]};
+    const ld wn = sqrtl(wn2);
+    if (wn > 0.0L) {
+        const ld h = 0.5L * wn * dt, s = sinl(h) / wn, d0 = cosl(h), d1 = s * w[0], d2 = s * w[1], d3 = s * w[2];
+        nq[0] = q[0] * d0 - q[1] * d1 - q[2] * d2 - q[3] * d3;
+        nq[1] = q[0] * d1 + q[1] * d0 + q[2] * d3 - q[3] * d2;
+        nq[2] = q[0] * d2 - q[1] * d3 + q[2] * d0 + q[3] * d1;
+        nq[3] = q[0] * d3 + q[1] * d2 - q[2] * d1 + q[3] * d0;
+    }
+    const ld nn = sqrtl(nq[0] * nq[0] + nq[1] * nq[1] + nq[2] * nq[2] + nq[3] * nq[3]);
+    for (int i = 0; i < 4; ++i) u->q[i] = nq[i] / nn;
+    if (V->ground) {
+        const ld zc = (ld)V->ground_z - (ld)V->ground_clearance;
+        if ((ld)V->ground_z - u->p[2] >= 0.1L) u->gbits |= 2;
+        const int now = u->p[2] - zc > 0.0L;
+        u->gbits = now ? (u->gbits | 1) : (u->gbits & ~1);
+        if (now && (u->gbits & 2)) u->gbits |= 4;
+    }
+}
+
+static void x_of_ld(const uav_ld *u, double *X) {
+    for (int i = 0; i < 3; ++i) { X[i] = (double)u->p[i]; X[7 + i] = (double)u->v[i]; X[10 + i] = (double)u->w[i]; }
+    for (int i = 0; i < 4; ++i) X[3 + i] = (double)u->q[i];
+}
+
+void oracle_rollout_ld(const oracle_vehicle *V, const double *traj, int64_t nrows, double *state, int32_t *istate,
+                       int K, double *state_log, double *cmd_log, const double *aabbs, int n_obs) {
+    if (LDBL_MANT_DIG < 64) return;
+    uav_ld u;
+    for (int i = 0; i < 3; ++i) { u.p[i] = state[i]; u.v[i] = state[7 + i]; u.w[i] = state[10 + i]; u.pqr[i] = state[23 + i]; }
+    for (int i = 0; i < 4; ++i) { u.q[i] = state[3 + i]; u.om[i] = state[13 + i]; u.omc[i] = state[17 + i]; }
+    u.integ = state[21]; u.thrust = state[22];
+    u.idx = istate[0]; u.inner = istate[1]; u.collided = istate[2]; u.gbits = istate[3];
+    for (int k = 0; k < K; ++k) {
+        controller_tick_ld(V, &u, traj, nrows);
+        if (cmd_log) {
+            double *c = cmd_log + (size_t)k * 12;
+            c[0] = (double)u.thrust;
+            for (int i = 0; i < 3; ++i) c[1 + i] = (double)u.pqr[i];
+            for (int i = 0; i < 4; ++i) { c[4 + i] = (double)u.omc[i]; c[8 + i] = (double)u.om[i]; }
+        }
+        dynamics_step_ld(V, &u);
+        for (int o = 0; o < n_obs; ++o) {
+            const double *c = aabbs + 6 * o;
+            if (u.p[0] >= c[0] && u.p[0] <= c[1] && u.p[1] >= c[2] && u.p[1] <= c[3] && u.p[2] >= c[4] && u.p[2] <= c[5])
+                u.collided = 1;
+        }
+        if (state_log) x_of_ld(&u, state_log + (size_t)k * 13);
+    }
+    x_of_ld(&u, state);
+    for (int i = 0; i < 4; ++i) { state[13 + i] = (double)u.om[i]; state[17 + i] = (double)u.omc[i]; }
+    state[21] = (double)u.integ; state[22] = (double)u.thrust;
+    for (int i = 0; i < 3; ++i) state[23 + i] = (double)u.pqr[i];
+    istate[0] = u.idx; istate[1] = u.inner; istate[2] = u.collided; istate[3] = u.gbits;
+}
+
+/* Margins of the discontinuous decisions one OUTER + vehicle tick takes from (state, istate), in long double, for tests that must
+ * not compare values across a decision the reference itself takes by a hair: out[0] = distance of the yaw error's argument
+ * (pd - psi + pi) mod 2 pi from the wrap (0 or 2 pi), out[1] = |R22|, out[2] = |r| of the ground test before the step,
+ * out[3] = |r| after it, out[4] = |ground_z - z - take-off height| after it.  Entries that do not apply (no outer tick, no
+ * ground) are 1. */
+void oracle_tick_margins_ld(const oracle_vehicle *V, const double *traj, int64_t nrows, const double *state, const int32_t *istate,
+                            double *out) {
+    for (int i = 0; i < 5; ++i) out[i] = 1.0;
+    if (LDBL_MANT_DIG < 64) return;
+    ld q[4] = {state[3], state[4], state[5], state[6]};
+    if (istate[1] % V->F == 0 && nrows > 0) {
+        ld R[3][3];
+        rot_ld(q, R);
+        out[1] = (double)fabsl(R[2][2]);
+        const double *tg = traj + (int64_t)istate[0] * 11;
+        const ld psi = atan2l(2.0L * (q[0] * q[3] + q[1] * q[2]), 1.0L - 2.0L * (q[2] * q[2] + q[3] * q[3]));
+        const ld a = pymod_ld(pymod_ld((ld)tg[9], 2.0L * PI_LD) - psi + PI_LD, 2.0L * PI_LD);
+        out[0] = (double)(a < 2.0L * PI_LD - a ? a : 2.0L * PI_LD - a);
+    }
+    if (V->ground) {
+        double s[26];
+        int32_t is[4];
+        memcpy(s, state, sizeof s); memcpy(is, istate, sizeof is);
+        const ld zc = (ld)V->ground_z - (ld)V->ground_clearance;
+        out[2] = (double)fabsl((ld)state[2] - zc);
+        oracle_rollout_ld(V, traj, nrows, s, is, 1, NULL, NULL, NULL, 0);
+        out[3] = (double)fabsl((ld)s[2] - zc);
+        out[4] = (double)fabsl((ld)V->ground_z - (ld)s[2] - 0.1L);
+    }
+}

@@ -324,3 +324,67 @@ def test_solve_ld_is_the_more_precise_solve(m):
         assert e_ld <= e_64 and e_ld <= 1e-15, (e_ld, e_64)
         e_ld_all, e_64_all = max(e_ld_all, e_ld), max(e_64_all, e_64)
     assert e_64_all > 0.0                                         # (the fp64 solve does carry an error to measure)
+
+
+# ------------------------------------------------------------------------------------------ one tick from arbitrary states
+# (the state families, the bound and the exclusion rule of tests/test_gpu_one_tick_parity.py, on the reference side alone)
+def _one_tick():
+    if cc.lib().oracle_ldbl_mant_dig() < 64:
+        pytest.skip("long double is no wider than double here")
+    import test_gpu_one_tick_parity as otp
+    return otp
+
+
+def test_one_tick_families_census():
+    """Every branch the one-tick families are meant to take is taken by at least 16 lanes (predicates of control_law.h restated in
+    NumPy), the tie lanes are exact ties in fp64, about 4 000 lanes in all and no launch a whole number of 64-lane tiles."""
+    otp = _one_tick()
+    fams = [otp.build(n) for n in otp.NAMES]
+    counts = otp.census(fams)
+    short = {k: n for k, n in counts.items() if n < 16}
+    assert not short, short
+    assert len(counts) >= 70
+    total = sum(f["B"] for f in fams)
+    assert 3500 <= total <= 4500 and all(f["B"] % 64 for f in fams), [f["B"] for f in fams]
+    for f in fams:
+        assert np.isfinite(f["state"]).all() and np.isfinite(f["traj"]).all()
+        nrows = np.diff(f["row_offsets"])
+        assert (f["istate"][0] >= 0).all() and (f["istate"][0] < nrows).all()          # the oracle does not clamp a cursor
+
+
+def test_one_tick_oracles_agree_within_the_bound():
+    """oracle_rollout against oracle_rollout_ld, one tick from every lane: with the fp64 oracle in the kernel's place the bound holds
+    at margin 1 (it is attainable by a correct fp64 implementation), every output of both is finite, integer outputs are equal,
+    and the long-double twin is not the fp64 oracle in disguise."""
+    otp = _one_tick()
+    differ = 0
+    for name in otp.NAMES:
+        fam, ref = otp.build(name), otp.reference(name)
+        keep = ~otp.excluded(name)
+        for what in ("state", "slog", "clog"):
+            t, r = ref[f"t_{what}"], ref[f"r_{what}"]
+            assert np.isfinite(t).all() and np.isfinite(r).all(), (name, what)
+            otp.assert_within_bound(what, fam, r, t, r, keep, margin=1.0)
+            differ += int((t != r).any(axis=tuple(range(t.ndim - 1))).sum())
+        assert np.array_equal(ref["t_istate"][:, keep], ref["r_istate"][:, keep])
+        assert np.array_equal(ref["t_slog"][0], ref["t_state"][:13]) and np.array_equal(ref["t_clog"][0, 0], ref["t_state"][22])
+    assert differ > 1000
+
+
+def test_one_tick_exclusions_stay_under_half_a_percent():
+    otp = _one_tick()
+    for name in otp.NAMES:
+        ex = otp.excluded(name)
+        assert ex.mean() <= 0.005, (name, int(ex.sum()), [otp.build(name)["labels"][i] for i in np.flatnonzero(ex)[:8]])
+
+
+def test_one_tick_numpy_restatement_tracks_the_oracle():
+    """The NumPy restatement of control_law.h that computes the census (numpy_tick) is itself within 64x the bound of the long-double
+    oracle on 99 % of the lanes: its branch predicates describe the tick the oracles compute."""
+    otp = _one_tick()
+    for name in otp.NAMES:
+        fam, ref = otp.build(name), otp.reference(name)
+        new, cmd, ist, _ = otp.numpy_tick(fam)
+        ok = (np.abs(new - ref["t_state"]) <= otp.bound(ref["t_state"], ref["r_state"], 64 * otp.M_BOUND)).all(axis=0)
+        assert ok.mean() >= 0.99, (name, ok.mean(), [fam["labels"][i] for i in np.flatnonzero(~ok)[:10]])
+        assert (ist == ref["t_istate"]).all(axis=0).mean() >= 0.99
