@@ -167,7 +167,7 @@ int uavac_clock_probe_dev(uavac_ctx *ctx, int window_us, int64_t *stamps);
  * registers instead of the workspace (same bits).  "sampler_waves": 4 (default), 2, 8, 16 = wavefronts per workgroup of the
  * chunk-streaming sampler, "sampler_group": 1 (default) .. 64 = consecutive missions per workgroup;
  * "sampler_waves" 1 = the one-wave-per-mission sampler (same rows bit for bit; faster into some row
- * buffers, slower into most: DESIGN K2).
+ * buffers, slower into most: DESIGN K2).  "audit_lanes": 16 (default) or 64 = lanes per mission of uavac_minsnap_audit_dev.
  * Defaults from the environment (UAVAC_ROLLOUT_ALIGN, UAVAC_YAW_GROUP, UAVAC_SAMPLER_WAVES, UAVAC_SAMPLER_GROUP) at uavac_create.
  * ONE option is not a tuning knob but part of the log layout: "log_pitch" = P doubles per log row,
  * 0 (default) = B.  With P >= B the rollouts write state_log [K][13][P] and cmd_log [K][12][P]
@@ -263,11 +263,43 @@ int uavac_minsnap_plan_dev(uavac_ctx *ctx, const double *wp, int B, int m, doubl
 
 /* first_yaw [B] of a solved plan WITHOUT sampling its rows: the heading of each mission's first sample with |v_xy| >= 1e-3
  * (MinimumSnap._calculate_yaws, minimum_snap.py:126-136: the rows before it take that heading; 0 when no sample has one) --
- * bit for bit what the sampler writes into first_yaw, from coeffs [B][8m][3] and seg_rows [B][m] alone.  One wavefront per
- * mission walks the rows 64 at a time from row 0 and stops at the first valid one.  seg_offsets [B+1] (device) != NULL: a
- * ragged batch (coeffs [S][8][3], seg_rows [S] back to back, m = the largest segment count); NULL: uniform. */
+ * bit for bit what the sampler writes into first_yaw, from coeffs [B][8m][3] and seg_rows [B][m] alone.  Sixteen lanes per
+ * mission (four missions per wavefront) walk the rows sixteen at a time from row 0 and stop at the first step that holds a valid
+ * one.  seg_offsets [B+1] (device) != NULL: a ragged batch (coeffs [S][8][3], seg_rows [S] back to back, m = the largest
+ * segment count); NULL: uniform. */
 int uavac_minsnap_first_yaw_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets,
                                 int B, int m, double dt, double *first_yaw);
+
+/* PLAN AUDIT: what the sampled rows of a solved plan would show, per mission, WITHOUT sampling them -- whether a plan (a rows-free
+ * one in particular) is flyable before it is flown.  The control law clips the target climb rate, the target horizontal velocity
+ * and the horizontal acceleration command (max_ascent / max_descent, max_speed_xy, max_horiz_accel of uavac_vehicle); the planner
+ * knows none of these limits, and the obstacle loop does not re-check earlier cuboids (uavac_minsnap_obstacle_waypoints).  One
+ * kernel walks every mission's rows with the sampler's own arithmetic -- exactly the rows the sampler would write, row r of
+ * segment s at t = (r - first row of s) * dt -- and stores none of them.  seg_offsets as in uavac_minsnap_first_yaw_dev: NULL =
+ * uniform batch (coeffs [B][8m][3], seg_rows [B][m]); otherwise ragged (arrays back to back, m = the largest segment count,
+ * segment counts clamped to 1 .. m as the sampler clamps them).
+ *   audit [UAVAC_AUDIT_ROWS][B] f64 (SoA like the score block), maxima over the mission's rows:
+ *     0 the mission's row total (exact as a double)      4 peak horizontal acceleration sqrt(ax^2 + ay^2)
+ *     1 peak horizontal speed sqrt(vx^2 + vy^2)           5 peak upward acceleration   max(-az)   (NED)
+ *     2 peak climb rate   max(-vz)   (NED)                6 peak downward acceleration max(az)
+ *     3 peak descent rate max(vz)                         7 peak speed sqrt(vx^2 + vy^2 + vz^2)
+ *   cuboids  [n_cuboids][6]  xmin xmax ymin ymax zmin zmax, 0 <= n_cuboids <= UAVAC_AUDIT_MAX_CUBOIDS
+ *   hit_rows  [n_cuboids][B] i32: how many of the mission's samples lie inside cuboid c (inclusive test of is_collision_cuboid,
+ *             minimum_snap.py:327-357, on the very positions the sampler stores)
+ *   first_hit [n_cuboids][B] i32: mission-local index of the first such row, -1 when there is none
+ * n_cuboids == 0: cuboids, hit_rows and first_hit must all be NULL.
+ * ROUNDING is part of the contract: the squares are separately rounded products and sums (no fused multiply-add), the maximum
+ * is taken of the squares, one correctly rounded sqrt comes last -- a peak equals np.sqrt(vx * vx + vy * vy).max() (row 7:
+ * vx * vx + vy * vy + vz * vz, left to right) over the sampler's rows bit for bit, whatever the launch shape or the batch split
+ * (option "audit_lanes": 16 (default) or 64 lanes of a wavefront per mission; a tuning knob, same results).
+ * A mission with ANY non-finite sample -- a singular knot system writes NaN coefficients -- reports NaN in rows 1-7, no hits and
+ * first_hit -1 (so does a mission without rows): a singular plan never looks feasible.
+ * UAVAC_EINVAL before anything is enqueued: n_cuboids outside 0 .. UAVAC_AUDIT_MAX_CUBOIDS, a NULL where a pointer is required
+ * (or a pointer where n_cuboids == 0 requires NULL), B < 1, m outside 1 .. UAVAC_MAX_SEGMENTS, dt not positive and finite. */
+#define UAVAC_AUDIT_ROWS 8
+#define UAVAC_AUDIT_MAX_CUBOIDS 16
+int uavac_minsnap_audit_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                            double dt, const double *cuboids, int n_cuboids, double *audit, int32_t *hit_rows, int32_t *first_hit);
 
 /* row_offsets [B+1] from per-segment row counts that exist already -- the second half of
  * uavac_minsnap_row_counts_dev on its own, for a plan whose seg_rows [B][m] came from elsewhere (the

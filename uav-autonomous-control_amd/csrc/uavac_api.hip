@@ -318,6 +318,9 @@ int uavac_set_option(uavac_ctx *ctx, const char *name, int value) {
     if (n == "yaw_group") {
         if (value != 1 && value != 4 && value != 8 && value != 16) return uavac_fail(ctx, UAVAC_EINVAL, "yaw_group is 1, 4, 8 or 16");
         ctx->yaw_group = value;
+    } else if (n == "audit_lanes") {
+        if (value != 16 && value != 64) return uavac_fail(ctx, UAVAC_EINVAL, "audit_lanes is 16 or 64");
+        ctx->audit_lanes = value;
     } else if (n == "sampler_waves") {
         if (value != 1 && value != 2 && value != 4 && value != 8 && value != 16) return uavac_fail(ctx, UAVAC_EINVAL, "sampler_waves is 1, 2, 4, 8 or 16");
         ctx->sampler_waves = value;
@@ -611,6 +614,19 @@ int uavac_minsnap_first_yaw_dev(uavac_ctx *ctx, const double *coeffs, const int3
     if (!seg_rows || !first_yaw) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
     if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
     return uavac_launch_first_yaw(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, first_yaw);
+}
+
+int uavac_minsnap_audit_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                            double dt, const double *cuboids, int n_cuboids, double *audit, int32_t *hit_rows, int32_t *first_hit) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
+    if (!seg_rows || !audit) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
+    if (n_cuboids < 0 || n_cuboids > UAVAC_AUDIT_MAX_CUBOIDS)
+        return uavac_fail(ctx, UAVAC_EINVAL, "n_cuboids must be in [0, UAVAC_AUDIT_MAX_CUBOIDS]");
+    if (n_cuboids == 0 ? (cuboids || hit_rows || first_hit) : (!cuboids || !hit_rows || !first_hit))
+        return uavac_fail(ctx, UAVAC_EINVAL, "cuboids, hit_rows and first_hit go with n_cuboids > 0: all three or none");
+    return uavac_launch_audit(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, cuboids, n_cuboids, audit, hit_rows, first_hit);
 }
 
 int uavac_minsnap_row_offsets_dev(uavac_ctx *ctx, const int32_t *seg_rows, int B, int m, int64_t *row_offsets) {

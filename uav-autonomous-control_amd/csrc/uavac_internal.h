@@ -33,6 +33,7 @@ struct uavac_ctx {
     int sampler_waves = 4;           // tuning: wavefronts per workgroup of the sampler: 2, 4, 8, 16 (minsnap_sample_stream.hip); 1 = one wave per mission (minsnap_sample.hip)
     int sampler_group = 1;           // tuning: consecutive missions per workgroup of the streaming sampler
     int yaw_group = 8;               // tuning: chunks of the sampler's dense yaw column that leave together (1, 4, 8, 16)
+    int audit_lanes = 16;            // tuning: lanes of a wavefront that walk one mission in the plan audit: 16 or 64 (minsnap_audit.hip; same results)
     int rollout_align = 1;           // tuning: launch the 2-wave aligner kernel before a logged launch of shape 1
     int late_handover = -1;          // tuning: -1 = the launcher picks per launch; 0 / 1 = slab handed over at the end of the tick / a third of a tick later
     int coeff_dma = -1;              // tuning: -1 = the launcher picks per launch; 0 / 1 / 2 = the plan-fed rollout's PMODE (control_rollout.hip)
@@ -211,6 +212,10 @@ int uavac_launch_yaw_scan(uavac_ctx *ctx, const double *velocities, const int64_
 // first_yaw [B] without the rows (minsnap_first_yaw.hip): what the sampler writes there, from the coefficients and row counts alone
 int uavac_launch_first_yaw(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                            double dt, double *first_yaw);
+// what a plan's rows would show, per mission, without the rows (minsnap_audit.hip): audit [UAVAC_AUDIT_ROWS][B], and per cuboid
+// hit_rows / first_hit [n_cuboids][B]
+int uavac_launch_audit(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                       double dt, const double *cuboids, int n_cuboids, double *audit, int32_t *hit_rows, int32_t *first_hit);
 int uavac_launch_state_init(uavac_ctx *ctx, const VehK &V, const double *positions, int B, int hover, double *state,
                             int32_t *istate);
 // What the rollout needs to evaluate target rows itself instead of reading them (control_rollout.hip, POLY)

@@ -41,12 +41,13 @@ def rollout_register_counts(obj: str = None):
 def check_planning_registers():
     """The planning kernels' budgets: the chunk-streaming sampler without jerk / snap runs six waves per SIMD (<= 80 vector
     registers; with jerk / snap four: <= 128), the solve one or two (the variant that keeps five knots in registers: <= 512, the
-    others <= 256); none may spill (a spill in the sampler showed as 3 % more HBM writes and no other symptom, NOTES R4-2).
+    others <= 256), the plan audit three (<= 168); none may spill (a spill in the sampler showed as 3 % more HBM writes and no other symptom, NOTES R4-2).
     Returns the counts, None when they cannot be read."""
     s = kernel_register_counts(os.path.join(PKG, "build", "minsnap_sample_stream.o"), "minsnap_sample_stream_kernel")
     k = kernel_register_counts(os.path.join(PKG, "build", "minsnap_solve_bt.o"), "minsnap_solve_bt_kernel")
     k2 = kernel_register_counts(os.path.join(PKG, "build", "minsnap_solve_tw.o"), "minsnap_solve_tw_kernel")
-    if s is None or k is None or k2 is None:
+    a = kernel_register_counts(os.path.join(PKG, "build", "minsnap_audit.o"), "minsnap_audit_kernel")
+    if s is None or k is None or k2 is None or a is None:
         return None
     k = k + k2                                        # (the two-ended solve: same budgets, same naming of the last template argument)
     bad = []
@@ -60,10 +61,13 @@ def check_planning_registers():
         limit = 512 if n.rstrip("E").endswith("Li5") or "Li5EE" in n else 256
         if v > limit or sp:
             bad.append((n[:70], v, sp, limit))
-    if len(s) < 20 or len(k) < 20 or bad:
-        raise RuntimeError(f"planning kernels outside their register budgets (name, VGPRs, spills, limit): {bad}; {len(s)} sampler and "
-                           f"{len(k)} solve variants found (compiler: {compiler_version()})")
-    return s + k
+    for n, v, sp in a:                                # the plan audit: three waves per SIMD (built: 100 .. 146 registers)
+        if v > 168 or sp:
+            bad.append((n[:70], v, sp, 168))
+    if len(s) < 20 or len(k) < 20 or len(a) < 4 or bad:
+        raise RuntimeError(f"planning kernels outside their register budgets (name, VGPRs, spills, limit): {bad}; {len(s)} sampler, "
+                           f"{len(k)} solve and {len(a)} audit variants found (compiler: {compiler_version()})")
+    return s + k + a
 
 
 def check_rollout_registers(obj: str = None):

@@ -21,6 +21,7 @@ COMM_ID_BYTES = 128
 MAX_SEGMENTS = 64
 TRAJ_COLS, STATE_ROWS, ISTATE_ROWS, CMD_COLS = 11, 30, 4, 12
 SCORE_ROWS = 11                  # tracking scores of the scored rollouts (include/uavac.h UAVAC_SCORE_ROWS)
+AUDIT_ROWS, AUDIT_MAX_CUBOIDS = 8, 16       # plan audit (include/uavac.h uavac_minsnap_audit_dev)
 VERSION = 310
 GROUND_IN_CONTACT, GROUND_TAKEN_OFF, GROUND_HIT_AFTER_TAKEOFF = 1, 2, 4       # istate row 3 (include/uavac.h)
 
@@ -87,6 +88,7 @@ _SIGNATURES = {
     "uavac_minsnap_plan_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,
                                           C.c_int64, _P, _P]),
     "uavac_minsnap_first_yaw_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P]),
+    "uavac_minsnap_audit_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, _P, _P]),
     "uavac_minsnap_row_offsets_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "uavac_minsnap_row_offsets_ragged_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     "uavac_minsnap_plan_ragged": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_double, _P, _P, _P, _P, C.c_int64]),

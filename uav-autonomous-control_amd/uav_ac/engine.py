@@ -151,6 +151,25 @@ class RaggedBatch:
 
 
 @dataclass
+class PlanAudit:
+    """What the sampled rows of a plan would show, per mission (`Engine.audit`, include/uavac.h uavac_minsnap_audit_dev): device
+    tensors, the peaks (B,) f64 -- maxima over exactly the rows the sampler writes, NaN for a mission with a non-finite sample --
+    and per cuboid (n, B) i32 how many samples lie inside it and the mission-local index of the first one (-1: none).
+    `uav_ac.scoring.plan_feasibility` judges it against a vehicle's flight limits."""
+    rows: "object"           # (B,) f64: the mission's row total
+    speed_xy: "object"       # peak sqrt(vx^2 + vy^2)
+    ascent: "object"         # peak climb rate max(-vz) (NED)
+    descent: "object"        # peak descent rate max(vz)
+    accel_xy: "object"       # peak sqrt(ax^2 + ay^2)
+    accel_up: "object"       # peak max(-az)
+    accel_down: "object"     # peak max(az)
+    speed: "object"          # peak sqrt(vx^2 + vy^2 + vz^2)
+    hit_rows: "object"       # (n, B) i32
+    first_hit: "object"      # (n, B) i32
+    block: "object" = None   # the [AUDIT_ROWS][B] block the eight rows above are views of
+
+
+@dataclass
 class RRTDeviceBatch:
     """Device-resident results of `Engine.rrt_star` (torch tensors; layouts of include/uavac.h).
     counts[:, k]: 0 n_nodes, 1 iterations begun, 2 status, 3 entries when best_tree was stored, 4 best_path rows,
@@ -400,6 +419,39 @@ class Engine:
         self.ctx.call("uavac_minsnap_first_yaw_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
                       plan.B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(out))
         return out
+
+    def audit(self, plan, obstacles=None) -> PlanAudit:
+        """What the plan's sampled rows would show, per mission, without sampling them (`uavac_minsnap_audit_dev`): the row total,
+        the peaks of horizontal speed, climb and descent rate, horizontal / upward / downward acceleration and speed, and for each
+        cuboid of `obstacles` ((n, 6) array or tensor, xmin xmax ymin ymax zmin zmax; n <= 16) how many samples lie inside it and
+        which does first.  `plan`: a Plan (with rows or rows-free), a RaggedBatch, or a RaggedPlan (audited from the batch it was
+        sampled from; one without a batch -- `plan_collision_free(device_loop=False)` -- is re-planned rows-free from its final
+        waypoints, which gives the same coefficients bit for bit).  Reads coefficients and row counts only, never `plan.traj`;
+        stream-ordered like the other _dev calls, no sync.  `uav_ac.scoring.plan_feasibility` turns the result into verdicts."""
+        torch = self._torch
+        if isinstance(plan, RaggedPlan):
+            batch = plan.batch
+            if batch is None:
+                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
+            plan = batch
+        ragged = hasattr(plan, "seg_offsets")
+        B = int(plan.B)
+        kw = dict(device=self.device)
+        cub = None
+        n = 0
+        if obstacles is not None:
+            cub = self._dev(obstacles, torch.float64).reshape(-1, 6)
+            n = int(cub.shape[0])
+            if n > nat.AUDIT_MAX_CUBOIDS:
+                raise ValueError(f"{n} cuboids; at most {nat.AUDIT_MAX_CUBOIDS} per audit")
+        block = torch.empty((nat.AUDIT_ROWS, B), dtype=torch.float64, **kw)
+        hit_rows = torch.empty((n, B), dtype=torch.int32, **kw)
+        first_hit = torch.empty((n, B), dtype=torch.int32, **kw)
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_audit_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
+                      B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(cub) if n else None, n, _ptr(block),
+                      _ptr(hit_rows) if n else None, _ptr(first_hit) if n else None)
+        return PlanAudit(*block.unbind(0), hit_rows, first_hit, block)
 
     def sample_range(self, plan: Plan, b0: int, b1: int):
         """The rows (and first headings) of missions [b0, b1) of a uniform plan, written where `sample(plan)` writes them: the

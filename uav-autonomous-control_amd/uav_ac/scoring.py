@@ -6,6 +6,9 @@ row to score, the sum, sum of squares, maximum and last of e = |position - targe
 checks one UAV from a full log (tests/integration/test_mujoco_trajectory_tracking.py:26-36): mean tracking error < 0.5 m, final
 distance to the goal < 0.5 m, no collision.  `summarize` turns a score block into those quantities for every UAV at once and
 `acceptance` applies upstream's three assertions.  Pure torch: works on device and on CPU tensors alike.
+
+`plan_feasibility` is the judge BEFORE the flight: it compares a plan audit (`Engine.audit`, include/uavac.h
+uavac_minsnap_audit_dev) with the flight limits the control law clips its targets to.
 """
 from __future__ import annotations
 
@@ -56,3 +59,27 @@ def acceptance(summary: dict, mean_tol: float = 0.5, final_tol: float = 0.5) -> 
     final_ok = summary["complete"] & (summary["final_error"] < final_tol)
     no_collision = ~summary["collided"]
     return {"mean_ok": mean_ok, "final_ok": final_ok, "no_collision": no_collision, "passed": mean_ok & final_ok & no_collision}
+
+
+def plan_feasibility(audit, vehicle=None, slack: float = 0.0) -> dict:
+    """A plan audit (`Engine.audit` -> PlanAudit, or anything with its fields; device or CPU tensors) against the limits the control
+    law silently clips what the planner asks for to (csrc/control_law.h: target climb rate, target horizontal velocity, horizontal
+    acceleration command) -> dict of (B,) bool tensors:
+    speed_ok (speed_xy <= max_speed_xy + slack), ascent_ok (ascent <= max_ascent + slack), descent_ok (descent <= max_descent +
+    slack), accel_ok (accel_xy <= max_horiz_accel + slack), clear (no sample inside any cuboid; all true when none was given),
+    feasible (all five).  A NaN peak -- a mission with a non-finite sample, i.e. a singular plan -- fails every test, `clear`
+    included.  `vehicle`: a `Vehicle` (or anything with the four limits); None = `uavac_vehicle_default`."""
+    import torch
+    V = nat.Vehicle.default() if vehicle is None else vehicle
+    slack = float(slack)
+    speed_ok = audit.speed_xy <= float(V.max_speed_xy) + slack
+    ascent_ok = audit.ascent <= float(V.max_ascent) + slack
+    descent_ok = audit.descent <= float(V.max_descent) + slack
+    accel_ok = audit.accel_xy <= float(V.max_horiz_accel) + slack
+    finite = ~(torch.isnan(audit.speed_xy) | torch.isnan(audit.ascent) | torch.isnan(audit.descent) | torch.isnan(audit.accel_xy))
+    hits = getattr(audit, "hit_rows", None)
+    clear = finite.clone()
+    if hits is not None and hits.numel() > 0:
+        clear = clear & (hits.reshape(-1, finite.shape[0]) == 0).all(dim=0).to(finite.device)
+    return {"speed_ok": speed_ok, "ascent_ok": ascent_ok, "descent_ok": descent_ok, "accel_ok": accel_ok, "clear": clear,
+            "feasible": speed_ok & ascent_ok & descent_ok & accel_ok & clear}
