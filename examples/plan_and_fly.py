@@ -7,8 +7,11 @@
   4. the cascaded controller flies them, with the per-tick obstacle test fused into the rollout
                                                                 (Fleet.rollout with aabbs)
 Both planners see the obstacles inflated by `clearance`; the flight is tested against the true ones.
+`--retime` (opt-in) puts a step between 3 and 4: the missions whose plan asks for more than the control law gives (the vehicle's
+speed, climb, descent and horizontal-acceleration limits) are slowed down by exactly the factor they need (Engine.retime); the
+curves stay where the obstacle loop put them.
 
-    python examples/plan_and_fly.py [B]
+    python examples/plan_and_fly.py [B] [--retime]
 """
 import os
 import sys
@@ -23,7 +26,7 @@ from uav_ac.fleet import Engine                                   # noqa: E402
 from uav_ac.simulation.mujoco_sim import MujocoSimulation         # noqa: E402
 
 
-def main(B: int = 256, velocity: float = 2.0, seed: int = 0, clearance: float = 0.3):
+def main(B: int = 256, velocity: float = 2.0, seed: int = 0, clearance: float = 0.3, retime: bool = False):
     import torch
     sim = MujocoSimulation()                                       # packaged lab course: obstacles, bounds, start, goal
     keep_out = sim.obstacles + np.array([-1, 1, -1, 1, -1, 1]) * clearance     # planners see inflated cuboids
@@ -44,6 +47,13 @@ def main(B: int = 256, velocity: float = 2.0, seed: int = 0, clearance: float = 
     waypoints = [thin[b, :thin_len[b]] for b in ok]
     t2 = time.perf_counter()
     plan = eng.plan_collision_free(waypoints, keep_out, velocity, 0.01, strict=False, recheck_passes=4)
+    retimed = ""
+    if retime:
+        result = eng.retime(plan)
+        plan = result.plan
+        slowed = result.factors > 1.0
+        retimed = (f"; retimed {int(slowed.sum())} missions in {result.passes} passes (largest factor "
+                   f"{float(result.factors[slowed].max()) if bool(slowed.any()) else 1.0:.3f}, {int((~result.converged).sum())} still over a limit)")
     t3 = time.perf_counter()
     fleet = eng.fleet(plan)
     rows = (plan.row_offsets[1:] - plan.row_offsets[:-1]).max().item()
@@ -57,10 +67,11 @@ def main(B: int = 256, velocity: float = 2.0, seed: int = 0, clearance: float = 
     arrived = (miss < 0.5) & ~collided & plan.converged
     print(f"{B} vehicles: RRT* found {len(ok)} paths in {1e3 * (t1 - t0):.0f} ms (mean {res.best_len[ok].mean():.1f} nodes, "
           f"{np.mean([len(w) for w in waypoints]):.1f} after thinning, {1e3 * (t2 - t1):.0f} ms); "
-          f"min-snap around obstacles {1e3 * (t3 - t2):.0f} ms ({plan.total_rows} rows, {int((~plan.converged).sum())} not converged); "
+          f"min-snap around obstacles {1e3 * (t3 - t2):.0f} ms ({plan.total_rows} rows, {int((~plan.converged).sum())} not converged){retimed}; "
           f"flight {1e3 * (t4 - t3):.0f} ms: {int(arrived.sum())} arrived within 0.5 m, {int(collided.sum())} touched an obstacle")
     return {"found": len(ok), "arrived": int(arrived.sum()), "collided": int(collided.sum()), "flown": len(ok)}
 
 
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 256)
+    args = [a for a in sys.argv[1:] if a != "--retime"]
+    main(int(args[0]) if args else 256, retime="--retime" in sys.argv[1:])

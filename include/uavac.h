@@ -301,6 +301,61 @@ int uavac_minsnap_first_yaw_dev(uavac_ctx *ctx, const double *coeffs, const int3
 int uavac_minsnap_audit_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                             double dt, const double *cuboids, int n_cuboids, double *audit, int32_t *hit_rows, int32_t *first_hit);
 
+/* ONE CRUISE SPEED PER MISSION: the _v twins of uavac_minsnap_row_counts_dev, uavac_minsnap_row_counts_ragged_dev and
+ * uavac_minsnap_plan_dev (both of its forms: rows with a capacity and flag 2 and the same all-or-nothing commit, and rows-free with
+ * traj == NULL) take velocities [B] (device) where those take `velocity` -- what a fleet of MinimumSnap(path, obstacles, velocity,
+ * dt) objects with different speeds is (minimum_snap.py:13-57: every object carries its own).  Everything downstream works from
+ * times / seg_rows / coeffs alone and has no such twin: solve, samplers, first headings, audit, plan-fed rollouts, plan gathers.
+ * CONTRACT: mission b's durations, row counts, coefficients, rows and first heading are bit for bit what the scalar entry point
+ * gives that mission at velocity = velocities[b]: the same kernel with the same arithmetic (norm nested in fused multiply-adds, one
+ * IEEE division, the factor 1.5 on the first and last segment, ceil(T / dt)).  A velocities[b] that is not positive and finite
+ * cannot be refused by the host: it raises sticky flag 0 like a non-finite duration, its mission gets 0 rows (its durations are
+ * whatever the division gives, its coefficients accordingly: do not fly it), and the other missions are unaffected. */
+int uavac_minsnap_row_counts_v_dev(uavac_ctx *ctx, const double *wp, int B, int m, const double *velocities,
+                                   double dt, double *times, int32_t *seg_rows, int64_t *row_offsets);
+int uavac_minsnap_row_counts_ragged_v_dev(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B,
+                                          int max_m, const double *velocities, double dt, double *times,
+                                          int32_t *seg_rows, int64_t *row_offsets);
+int uavac_minsnap_plan_v_dev(uavac_ctx *ctx, const double *wp, int B, int m, const double *velocities, double dt,
+                             double *times, int32_t *seg_rows, int64_t *row_offsets, double *coeffs,
+                             int32_t *status, double *traj, int64_t traj_capacity_rows, double *yaw,
+                             double *first_yaw);
+
+/* RETIMING FACTORS: by how much each mission of an audited plan must be slowed down to stay inside the limits the control law
+ * clips its targets to.  Scaling every segment duration of a mission by k > 1 -- planning it at velocity / k -- leaves the
+ * minimum-snap curve where it is (p'(t) = p(t / k)): velocity peaks scale by 1 / k, acceleration peaks by 1 / k^2.
+ *   audit      [UAVAC_AUDIT_ROWS][B]  of uavac_minsnap_audit_dev (rows 1-4 are read)
+ *   limits     [4] HOST: max_speed_xy, max_ascent, max_descent, max_horiz_accel (uavac_vehicle)
+ *   velocities [B] in/out, factors [B] out, counters [2] i32 (device; ADDED to, not cleared: zero them first)
+ * Per mission, every step ONE rounded IEEE operation, nothing contracted (part of the contract: uav_ac.scoring.retime_factors, a
+ * NumPy restatement, gives the same bits):
+ *   r = max(speed_xy / limits[0], ascent / limits[1], descent / limits[2], sqrt(accel_xy / limits[3]))
+ *   any of the four peaks NaN (a singular plan, a mission without rows): factors[b] = NaN, velocity untouched, counters[1] += 1;
+ *   r <= 1: factors[b] = 1.0, velocity untouched bit for bit;
+ *   else    k = r / (1 - margin), factors[b] = k, velocities[b] = velocities[b] / k, counters[0] += 1.
+ * The audit's peaks are maxima over SAMPLES, and the slower plan is sampled elsewhere on the curve: `margin` must exceed the
+ * relative gap between sampled and continuous peaks (about 1e-4 for 3 m legs at 3 m/s and dt = 0.01; more for a coarser dt) for
+ * one pass to suffice.  UAVAC_EINVAL before anything is enqueued: a limit that is not positive and finite, margin outside [0, 1),
+ * B < 1, a NULL pointer. */
+int uavac_minsnap_retime_factors_dev(uavac_ctx *ctx, const double *audit, int B, const double limits[4], double margin,
+                                     double *velocities, double *factors, int32_t *counters);
+/* THE LOOP that slows down exactly the missions that need it, by exactly the factor they need.  Pointers are DEVICE pointers
+ * except limits and passes; unlike the other _dev calls this one SYNCHRONISES: once per pass the host reads the two counters
+ * (like the obstacle loop reads its four).  seg_offsets == NULL: uniform batch, wp [B][m+1][3]; otherwise ragged (arrays back to
+ * back, m = the largest segment count).  Each pass: the rows-free chain at the current velocities (times + row counts, offsets,
+ * coefficient solve, first headings when first_yaw != NULL), uavac_minsnap_audit_dev without cuboids, the factors above.  It
+ * stops when no mission was slowed down, or after max_passes retimings -- the pass after the last retiming only judges:
+ * max_passes = 0 audits the plan at the given velocities and changes none.  No row is sampled anywhere; sample once afterwards
+ * with the samplers.  On return times, seg_rows, row_offsets, coeffs, status (may be NULL), first_yaw (may be NULL) and audit
+ * [UAVAC_AUDIT_ROWS][B] describe the plan AT THE RETURNED velocities [B] (in/out); factors_total [B] = the product of the
+ * mission's factors in pass order (1.0 when it was never touched, NaN when a peak was NaN), one rounded multiplication per pass;
+ * converged [B] i32 = 1 iff the mission's last audit asked for no retiming (a NaN mission: 0); *passes = retimings done.
+ * The sticky flags are left to the caller (uavac_take_flags).  UAVAC_EINVAL as for the factors, and for max_passes < 0. */
+int uavac_minsnap_retime_dev(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B, int m, double *velocities,
+                             double dt, const double limits[4], double margin, int max_passes, double *times,
+                             int32_t *seg_rows, int64_t *row_offsets, double *coeffs, int32_t *status, double *first_yaw,
+                             double *audit, double *factors_total, int32_t *converged, int *passes);
+
 /* row_offsets [B+1] from per-segment row counts that exist already -- the second half of
  * uavac_minsnap_row_counts_dev on its own, for a plan whose seg_rows [B][m] came from elsewhere (the
  * peers' plans after uavac_gather_plan_dev): exclusive prefix sum of the per-mission totals

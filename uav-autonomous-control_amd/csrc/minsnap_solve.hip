@@ -18,6 +18,8 @@
 
 #include "minsnap_kkt.h"
 
+#include <type_traits>
+
 // (the header's `fp contract(off)` is file-scope and would reach the kernels below.  hipcc compiles HIP with -ffp-contract=fast-honor-pragmas
 // unless told otherwise, and the Makefile does not tell it: `fast` is what these kernels had before the include)
 #pragma clang fp contract(fast)
@@ -66,11 +68,19 @@ __device__ __forceinline__ int64_t block_inclusive_scan_256(int64_t v, int64_t *
     return v + base;
 }
 
+// The cruise speed of mission b: the batch's one value, or the mission's own out of velocities [B].
+__device__ __forceinline__ double velocity_of(double v, int) { return v; }
+__device__ __forceinline__ double velocity_of(const double *v, int b) { return v[b]; }
+
 // RAGGED: mission b has m_b = seg_offsets[b + 1] - seg_offsets[b] segments (1 .. m, m = the batch's maximum) and m_b + 1
 // waypoints; waypoints, times and row counts of the batch lie back to back (mission b's first waypoint is waypoint
 // seg_offsets[b] + b, its first segment is segment seg_offsets[b]).  A count outside 1 .. m raises flag 0 and is clamped.
-template <bool RAGGED>
-__global__ void __launch_bounds__(256) row_counts_kernel(const double *__restrict__ wp, int B, int m_uniform, double velocity,
+// Vel: double = one cruise speed for the batch, validated on the host (every instruction as before the per-mission form
+// existed); const double * = velocities [B], one per mission (uavac_minsnap_*_v_dev) -- the same arithmetic on the mission's own
+// value, which only the device can validate: one that is not positive and finite raises flag 0 and leaves its mission without
+// rows, whatever its durations come to (a negative speed gives finite, negative ones).
+template <bool RAGGED, class Vel>
+__global__ void __launch_bounds__(256) row_counts_kernel(const double *__restrict__ wp, int B, int m_uniform, Vel velocity_arg,
                                                          double dt, double *__restrict__ times,
                                                          int32_t *__restrict__ seg_rows, int32_t *__restrict__ totals,
                                                          int64_t *__restrict__ tile_sum, int32_t *__restrict__ flags,
@@ -84,10 +94,14 @@ __global__ void __launch_bounds__(256) row_counts_kernel(const double *__restric
         size_t seg0 = (size_t)b * m_uniform;
         const double *w = wp + (size_t)b * (m_uniform + 1) * 3;
         bool bad = false;
+        constexpr bool PER_MISSION = !std::is_same<Vel, double>::value;
+        const double velocity = velocity_of(velocity_arg, b);
+        const bool bad_speed = PER_MISSION && !(velocity > 0.0 && isfinite(velocity));
+        bad = bad_speed;
         if (RAGGED) {
             seg0 = (size_t)seg_offsets[b];
             const int64_t mb = seg_offsets[b + 1] - seg_offsets[b];
-            bad = mb < 1 || mb > m_uniform;
+            bad = bad || mb < 1 || mb > m_uniform;
             m = (int)(mb < 1 ? 1 : (mb > m_uniform ? m_uniform : mb));
             w = wp + (seg0 + (size_t)b) * 3;
         }
@@ -106,6 +120,7 @@ __global__ void __launch_bounds__(256) row_counts_kernel(const double *__restric
             bad = bad || !isfinite(T);
             double q = ceil(T / dt);
             int rows = (isfinite(q) && q > 0.0 && q < 2.0e9) ? (int)q : 0;
+            if (PER_MISSION && bad_speed) rows = 0;
             times[s] = T;
             seg_rows[s] = rows;
             total += rows;
@@ -404,21 +419,32 @@ int uavac_launch_totals_scan(uavac_ctx *ctx, int B, int64_t *out) {
     return UAVAC_OK;
 }
 
-int uavac_launch_row_counts(uavac_ctx *ctx, const double *wp, int B, int m, double velocity, double dt,
-                            double *times, int32_t *seg_rows, int64_t *row_offsets, const int64_t *seg_offsets) {
+template <class Vel>
+static int launch_row_counts(uavac_ctx *ctx, const double *wp, int B, int m, Vel velocity, double dt, double *times,
+                             int32_t *seg_rows, int64_t *row_offsets, const int64_t *seg_offsets) {
     const int n_tiles = (B + 255) / 256;
     int64_t *tiles = nullptr;
     if (int rc = ensure_totals(ctx, B, &tiles)) return rc;
     if (seg_offsets)
-        hipLaunchKernelGGL(row_counts_kernel<true>, dim3(n_tiles), dim3(256), 0, ctx->stream, wp, B, m, velocity, dt,
+        hipLaunchKernelGGL((row_counts_kernel<true, Vel>), dim3(n_tiles), dim3(256), 0, ctx->stream, wp, B, m, velocity, dt,
                            times, seg_rows, ctx->d_totals, tiles, ctx->d_flags, seg_offsets);
     else
-        hipLaunchKernelGGL(row_counts_kernel<false>, dim3(n_tiles), dim3(256), 0, ctx->stream, wp, B, m, velocity, dt,
+        hipLaunchKernelGGL((row_counts_kernel<false, Vel>), dim3(n_tiles), dim3(256), 0, ctx->stream, wp, B, m, velocity, dt,
                            times, seg_rows, ctx->d_totals, tiles, ctx->d_flags, seg_offsets);
     hipLaunchKernelGGL(row_offsets_kernel, dim3(n_tiles), dim3(256), 0, ctx->stream, ctx->d_totals, B, tiles,
                        row_offsets);
     UAVAC_HIP(ctx, hipGetLastError());
     return UAVAC_OK;
+}
+
+int uavac_launch_row_counts(uavac_ctx *ctx, const double *wp, int B, int m, double velocity, double dt,
+                            double *times, int32_t *seg_rows, int64_t *row_offsets, const int64_t *seg_offsets) {
+    return launch_row_counts<double>(ctx, wp, B, m, velocity, dt, times, seg_rows, row_offsets, seg_offsets);
+}
+
+int uavac_launch_row_counts_v(uavac_ctx *ctx, const double *wp, int B, int m, const double *velocities, double dt,
+                              double *times, int32_t *seg_rows, int64_t *row_offsets, const int64_t *seg_offsets) {
+    return launch_row_counts<const double *>(ctx, wp, B, m, velocities, dt, times, seg_rows, row_offsets, seg_offsets);
 }
 
 // row_offsets of a plan whose per-segment row counts exist already (they arrived from another rank,

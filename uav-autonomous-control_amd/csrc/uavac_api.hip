@@ -212,6 +212,71 @@ int uavac_check_vehicle(uavac_ctx *ctx, const uavac_vehicle *V) {
     return UAVAC_OK;
 }
 
+namespace {
+
+// times + row counts + offsets at one cruise speed for the batch, or at one per mission (velocities [B], device)
+int launch_counts(uavac_ctx *ctx, const double *wp, int B, int m, double velocity, double dt, double *times, int32_t *seg_rows,
+                         int64_t *row_offsets, const int64_t *seg_offsets = nullptr) {
+    return uavac_launch_row_counts(ctx, wp, B, m, velocity, dt, times, seg_rows, row_offsets, seg_offsets);
+}
+int launch_counts(uavac_ctx *ctx, const double *wp, int B, int m, const double *velocities, double dt, double *times,
+                         int32_t *seg_rows, int64_t *row_offsets, const int64_t *seg_offsets = nullptr) {
+    return uavac_launch_row_counts_v(ctx, wp, B, m, velocities, dt, times, seg_rows, row_offsets, seg_offsets);
+}
+
+// The planning chain behind uavac_minsnap_plan_dev (Vel = double) and uavac_minsnap_plan_v_dev (Vel = const double *); the
+// arguments have been validated.
+template <class Vel>
+int plan_chain(uavac_ctx *ctx, const double *wp, int B, int m, Vel velocity, double dt, double *times, int32_t *seg_rows,
+                      int64_t *row_offsets, double *coeffs, int32_t *status, double *traj, int64_t traj_capacity_rows, double *yaw,
+                      double *first_yaw) {
+    if (!traj) {
+        // Rows-free chain: no row buffer, hence nothing to refuse -- times, row counts and offsets go straight into the caller's
+        // arrays; the one value of the sampler a plan-fed rollout needs comes from the first-heading kernel.
+        if (yaw) return uavac_fail(ctx, UAVAC_EINVAL, "a dense yaw column needs the rows: traj is NULL");
+        if (int rc = launch_counts(ctx, wp, B, m, velocity, dt, times, seg_rows, row_offsets)) return rc;
+        if (int rc = uavac_launch_coeff_solve(ctx, wp, times, B, m, coeffs, status)) return rc;
+        return first_yaw ? uavac_launch_first_yaw(ctx, coeffs, seg_rows, nullptr, B, m, dt, first_yaw) : UAVAC_OK;
+    }
+    if (traj_capacity_rows < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative capacity");
+    // The whole chain enqueued from here: nothing returns to the caller (or to an interpreter) between the launches.
+    // Times, row counts and offsets go to ctx scratch first; whether the plan fits the caller's row buffer is only known on
+    // the device (row_offsets_s[B]), so every later stage reads that one word: the commit kernel copies the three arrays
+    // into the caller's only when it fits, the solver and the sampler do nothing when it does not (the sampler raises
+    // flag 2).  A refused plan leaves times, seg_rows, row_offsets, coeffs, rows and first_yaw exactly as they were.
+    const size_t nseg = (size_t)B * m;
+    const size_t o_rows = uavac_arena_size(nseg * 8), o_offs = o_rows + uavac_arena_size(nseg * 4);
+    const size_t need = o_offs + uavac_arena_size(((size_t)B + 1) * 8);
+    if (need > ctx->plan_cap) {
+        UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));          // nothing enqueued may still use the old block
+        if (ctx->d_plan) UAVAC_HIP(ctx, hipFree(ctx->d_plan));
+        ctx->d_plan = nullptr;
+        ctx->plan_cap = 0;
+        void *p = nullptr;
+        UAVAC_HIP(ctx, hipMalloc(&p, need));
+        ctx->d_plan = static_cast<char *>(p);
+        ctx->plan_cap = need;
+    }
+    double *times_s = reinterpret_cast<double *>(ctx->d_plan);
+    int32_t *seg_rows_s = reinterpret_cast<int32_t *>(ctx->d_plan + o_rows);
+    int64_t *row_offsets_s = reinterpret_cast<int64_t *>(ctx->d_plan + o_offs);
+    if (int rc = launch_counts(ctx, wp, B, m, velocity, dt, times_s, seg_rows_s, row_offsets_s)) return rc;
+    if (int rc = uavac_launch_plan_commit(ctx, times_s, seg_rows_s, row_offsets_s, B, m, traj_capacity_rows, times, seg_rows,
+                                          row_offsets)) return rc;
+    // (Round 6 tried to hide this solve behind the sampler: the batch cut into 2 / 4 / 8 mission blocks, block i sampled on an
+    // auxiliary stream while block i + 1 was being solved.  Bit-identical and SLOWER -- +1.3 % / +13 % / +23 % at 65 536 x 12 --
+    // because a solve wave cannot get onto a SIMD the sampler's grid keeps full: commit 53921dc, profiles/r06_plan_blocks_ab*.jsonl.)
+    if (int rc = uavac_launch_coeff_solve(ctx, wp, times_s, B, m, coeffs, status, nullptr, row_offsets_s + B, traj_capacity_rows))
+        return rc;
+    SampleExtras x;
+    x.yaw_dense = yaw;
+    x.first_yaw = first_yaw;
+    x.capacity_rows = traj_capacity_rows;         // the sampler refuses (flag 2) instead of overrunning the buffer
+    return uavac_launch_sample(ctx, coeffs, seg_rows_s, row_offsets_s, B, m, dt, traj, x);
+}
+
+}  // namespace
+
 extern "C" {
 
 int uavac_version(void) { return UAVAC_VERSION; }
@@ -562,49 +627,99 @@ int uavac_minsnap_plan_dev(uavac_ctx *ctx, const double *wp, int B, int m, doubl
     if (!times || !seg_rows || !row_offsets || !coeffs) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
     if (!std::isfinite(velocity) || !std::isfinite(dt)) return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite velocity or dt");
     if (!(velocity > 0.0) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "velocity and dt must be > 0");
-    if (!traj) {
-        // Rows-free chain: no row buffer, hence nothing to refuse -- times, row counts and offsets go straight into the caller's
-        // arrays; the one value of the sampler a plan-fed rollout needs comes from the first-heading kernel.
-        if (yaw) return uavac_fail(ctx, UAVAC_EINVAL, "a dense yaw column needs the rows: traj is NULL");
-        if (int rc = uavac_launch_row_counts(ctx, wp, B, m, velocity, dt, times, seg_rows, row_offsets)) return rc;
-        if (int rc = uavac_launch_coeff_solve(ctx, wp, times, B, m, coeffs, status)) return rc;
-        return first_yaw ? uavac_launch_first_yaw(ctx, coeffs, seg_rows, nullptr, B, m, dt, first_yaw) : UAVAC_OK;
+    return plan_chain(ctx, wp, B, m, velocity, dt, times, seg_rows, row_offsets, coeffs, status, traj, traj_capacity_rows, yaw, first_yaw);
+}
+
+// ---------------------------------------------------------------- planning, device, one cruise speed per mission
+static int check_dt(uavac_ctx *ctx, double dt) {
+    if (!std::isfinite(dt)) return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite dt");
+    if (!(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be > 0");
+    return UAVAC_OK;
+}
+
+int uavac_minsnap_row_counts_v_dev(uavac_ctx *ctx, const double *wp, int B, int m, const double *velocities, double dt,
+                                   double *times, int32_t *seg_rows, int64_t *row_offsets) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
+    if (!velocities || !times || !seg_rows || !row_offsets) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_dt(ctx, dt)) return rc;
+    return uavac_launch_row_counts_v(ctx, wp, B, m, velocities, dt, times, seg_rows, row_offsets);
+}
+
+int uavac_minsnap_row_counts_ragged_v_dev(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B, int max_m,
+                                          const double *velocities, double dt, double *times, int32_t *seg_rows,
+                                          int64_t *row_offsets) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, wp, B, max_m)) return rc;
+    if (!seg_offsets || !velocities || !times || !seg_rows || !row_offsets) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_dt(ctx, dt)) return rc;
+    return uavac_launch_row_counts_v(ctx, wp, B, max_m, velocities, dt, times, seg_rows, row_offsets, seg_offsets);
+}
+
+int uavac_minsnap_plan_v_dev(uavac_ctx *ctx, const double *wp, int B, int m, const double *velocities, double dt, double *times,
+                             int32_t *seg_rows, int64_t *row_offsets, double *coeffs, int32_t *status, double *traj,
+                             int64_t traj_capacity_rows, double *yaw, double *first_yaw) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
+    if (!velocities || !times || !seg_rows || !row_offsets || !coeffs) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_dt(ctx, dt)) return rc;
+    return plan_chain(ctx, wp, B, m, velocities, dt, times, seg_rows, row_offsets, coeffs, status, traj, traj_capacity_rows, yaw,
+                      first_yaw);
+}
+
+// ---------------------------------------------------------------- retiming to the flight limits
+static int check_retime_args(uavac_ctx *ctx, int B, const double *limits, double margin, RetimeLimits *L) {
+    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
+    if (!limits) return uavac_fail(ctx, UAVAC_EINVAL, "null limits");
+    for (int i = 0; i < 4; ++i)
+        if (!(limits[i] > 0.0) || !std::isfinite(limits[i])) return uavac_fail(ctx, UAVAC_EINVAL, "every limit must be finite and > 0");
+    if (!(margin >= 0.0 && margin < 1.0)) return uavac_fail(ctx, UAVAC_EINVAL, "margin must be in [0, 1)");
+    *L = RetimeLimits{limits[0], limits[1], limits[2], limits[3]};
+    return UAVAC_OK;
+}
+
+int uavac_minsnap_retime_factors_dev(uavac_ctx *ctx, const double *audit, int B, const double limits[4], double margin,
+                                     double *velocities, double *factors, int32_t *counters) {
+    UAVAC_ENTER(ctx);
+    RetimeLimits L;
+    if (int rc = check_retime_args(ctx, B, limits, margin, &L)) return rc;
+    if (!audit || !velocities || !factors || !counters) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    return uavac_launch_retime_factors(ctx, audit, B, L, margin, 1, velocities, factors, counters, nullptr, nullptr);
+}
+
+int uavac_minsnap_retime_dev(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B, int m, double *velocities,
+                             double dt, const double limits[4], double margin, int max_passes, double *times, int32_t *seg_rows,
+                             int64_t *row_offsets, double *coeffs, int32_t *status, double *first_yaw, double *audit,
+                             double *factors_total, int32_t *converged, int *passes) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
+    RetimeLimits L;
+    if (int rc = check_retime_args(ctx, B, limits, margin, &L)) return rc;
+    if (!velocities || !times || !seg_rows || !row_offsets || !coeffs || !audit || !factors_total || !converged || !passes)
+        return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_dt(ctx, dt)) return rc;
+    if (max_passes < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative max_passes");
+    *passes = 0;
+    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size((size_t)B * 8) + uavac_arena_size(2 * sizeof(int32_t)))) return rc;
+    double *d_factors = take<double>(ctx, (size_t)B);
+    int32_t *d_counters = take<int32_t>(ctx, 2);
+    if (int rc = uavac_launch_fill_f64(ctx, factors_total, (size_t)B, 1.0)) return rc;
+    for (int retimed = 0;; ++retimed) {
+        // the rows-free chain at the current speeds, its audit, and what the audit asks for -- no row is sampled anywhere
+        if (int rc = uavac_launch_row_counts_v(ctx, wp, B, m, velocities, dt, times, seg_rows, row_offsets, seg_offsets)) return rc;
+        if (int rc = uavac_launch_coeff_solve(ctx, wp, times, B, m, coeffs, status, seg_offsets)) return rc;
+        if (first_yaw) if (int rc = uavac_launch_first_yaw(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, first_yaw)) return rc;
+        if (int rc = uavac_launch_audit(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, nullptr, 0, audit, nullptr, nullptr)) return rc;
+        UAVAC_HIP(ctx, hipMemsetAsync(d_counters, 0, 2 * sizeof(int32_t), ctx->stream));
+        const int apply = retimed < max_passes;            // out of passes: the verdict only, the speeds stay what the plan was made at
+        if (int rc = uavac_launch_retime_factors(ctx, audit, B, L, margin, apply, velocities, d_factors, d_counters, factors_total,
+                                                 converged)) return rc;
+        int32_t cnt[2];
+        if (int rc = d2h_staged(ctx, cnt, d_counters, sizeof cnt)) return rc;           // the pass's one read-back (synchronises)
+        if (cnt[0] == 0 || !apply) break;
+        *passes = retimed + 1;
     }
-    if (traj_capacity_rows < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative capacity");
-    // The whole chain enqueued from here: nothing returns to the caller (or to an interpreter) between the launches.
-    // Times, row counts and offsets go to ctx scratch first; whether the plan fits the caller's row buffer is only known on
-    // the device (row_offsets_s[B]), so every later stage reads that one word: the commit kernel copies the three arrays
-    // into the caller's only when it fits, the solver and the sampler do nothing when it does not (the sampler raises
-    // flag 2).  A refused plan leaves times, seg_rows, row_offsets, coeffs, rows and first_yaw exactly as they were.
-    const size_t nseg = (size_t)B * m;
-    const size_t o_rows = uavac_arena_size(nseg * 8), o_offs = o_rows + uavac_arena_size(nseg * 4);
-    const size_t need = o_offs + uavac_arena_size(((size_t)B + 1) * 8);
-    if (need > ctx->plan_cap) {
-        UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));          // nothing enqueued may still use the old block
-        if (ctx->d_plan) UAVAC_HIP(ctx, hipFree(ctx->d_plan));
-        ctx->d_plan = nullptr;
-        ctx->plan_cap = 0;
-        void *p = nullptr;
-        UAVAC_HIP(ctx, hipMalloc(&p, need));
-        ctx->d_plan = static_cast<char *>(p);
-        ctx->plan_cap = need;
-    }
-    double *times_s = reinterpret_cast<double *>(ctx->d_plan);
-    int32_t *seg_rows_s = reinterpret_cast<int32_t *>(ctx->d_plan + o_rows);
-    int64_t *row_offsets_s = reinterpret_cast<int64_t *>(ctx->d_plan + o_offs);
-    if (int rc = uavac_launch_row_counts(ctx, wp, B, m, velocity, dt, times_s, seg_rows_s, row_offsets_s)) return rc;
-    if (int rc = uavac_launch_plan_commit(ctx, times_s, seg_rows_s, row_offsets_s, B, m, traj_capacity_rows, times, seg_rows,
-                                          row_offsets)) return rc;
-    // (Round 6 tried to hide this solve behind the sampler: the batch cut into 2 / 4 / 8 mission blocks, block i sampled on an
-    // auxiliary stream while block i + 1 was being solved.  Bit-identical and SLOWER -- +1.3 % / +13 % / +23 % at 65 536 x 12 --
-    // because a solve wave cannot get onto a SIMD the sampler's grid keeps full: commit 53921dc, profiles/r06_plan_blocks_ab*.jsonl.)
-    if (int rc = uavac_launch_coeff_solve(ctx, wp, times_s, B, m, coeffs, status, nullptr, row_offsets_s + B, traj_capacity_rows))
-        return rc;
-    SampleExtras x;
-    x.yaw_dense = yaw;
-    x.first_yaw = first_yaw;
-    x.capacity_rows = traj_capacity_rows;         // the sampler refuses (flag 2) instead of overrunning the buffer
-    return uavac_launch_sample(ctx, coeffs, seg_rows_s, row_offsets_s, B, m, dt, traj, x);
+    return UAVAC_OK;
 }
 
 int uavac_minsnap_first_yaw_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B,

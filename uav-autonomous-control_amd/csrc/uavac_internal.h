@@ -159,6 +159,10 @@ int uavac_check_vehicle(uavac_ctx *ctx, const uavac_vehicle *V);
 // m = the batch's maximum); waypoints, times, row counts, coefficients and hit flags lie back to back
 int uavac_launch_row_counts(uavac_ctx *ctx, const double *wp, int B, int m, double velocity, double dt,
                             double *times, int32_t *seg_rows, int64_t *row_offsets, const int64_t *seg_offsets = nullptr);
+// the same with a cruise speed per mission, velocities [B] (device): a value that is not positive and finite raises flag 0 and
+// leaves its mission without rows
+int uavac_launch_row_counts_v(uavac_ctx *ctx, const double *wp, int B, int m, const double *velocities, double dt,
+                              double *times, int32_t *seg_rows, int64_t *row_offsets, const int64_t *seg_offsets = nullptr);
 // The coefficient solve (minsnap_solve.hip): hands over to the two-ended or the one-ended block-Thomas launcher by ctx->solve_order.
 // guard_rows (device, may be NULL): the launch does nothing when *guard_rows > guard_capacity (a refused planning chain)
 int uavac_launch_coeff_solve(uavac_ctx *ctx, const double *wp, const double *times, int B, int m, double *coeffs,
@@ -216,6 +220,16 @@ int uavac_launch_first_yaw(uavac_ctx *ctx, const double *coeffs, const int32_t *
 // hit_rows / first_hit [n_cuboids][B]
 int uavac_launch_audit(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                        double dt, const double *cuboids, int n_cuboids, double *audit, int32_t *hit_rows, int32_t *first_hit);
+// Retiming factors from an audit block (minsnap_retime.hip): factors [B], counters [2] += {missions slowed down, missions with a
+// NaN peak}; apply != 0 divides the velocities of the missions over a limit by their factor.  The loop's extras (each may be NULL):
+// factors_total [B] *= the factor applied (NaN for a NaN mission), converged [B] = 1 where the factor is 1.0, else 0.
+struct RetimeLimits {
+    double speed_xy, ascent, descent, horiz_accel;
+};
+int uavac_launch_retime_factors(uavac_ctx *ctx, const double *audit, int B, const RetimeLimits &limits, double margin, int apply,
+                                double *velocities, double *factors, int32_t *counters, double *factors_total, int32_t *converged);
+// out [n] = value (minsnap_retime.hip)
+int uavac_launch_fill_f64(uavac_ctx *ctx, double *out, size_t n, double value);
 int uavac_launch_state_init(uavac_ctx *ctx, const VehK &V, const double *positions, int B, int hover, double *state,
                             int32_t *istate);
 // What the rollout needs to evaluate target rows itself instead of reading them (control_rollout.hip, POLY)

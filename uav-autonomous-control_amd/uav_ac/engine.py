@@ -48,6 +48,7 @@ class Plan:
     pooled: bool = False             # the rows live in the Engine's pooled buffer (shared with every other pooled plan of that Engine)
     epoch: int = 0                   # bumped whenever the plan is re-solved / re-sampled in place (Engine.replan / solve / sample):
                                      # an attached Fleet then rebuilds the yaw scan it carries instead of trusting a stale one
+    velocities: "object" = None      # (B,) f64, device: one cruise speed per mission (`velocity` is then NaN); None = the one `velocity`
 
     def mission(self, b: int) -> np.ndarray:
         """Rows of mission b as a fresh host array (N_b, 11) -- the reference's `full_trajectory`."""
@@ -129,6 +130,7 @@ class RaggedBatch:
     total_rows: int
     first_yaw: "object"              # (B,) f64
     hit: "object" = None             # (S,) i32 when a cuboid was given
+    velocities: "object" = None      # (B,) f64, device: one cruise speed per mission (`velocity` is then NaN); None = the one `velocity`
 
     def mission(self, b: int) -> np.ndarray:
         if self.traj is None:
@@ -167,6 +169,17 @@ class PlanAudit:
     hit_rows: "object"       # (n, B) i32
     first_hit: "object"      # (n, B) i32
     block: "object" = None   # the [AUDIT_ROWS][B] block the eight rows above are views of
+
+
+@dataclass
+class RetimeResult:
+    """What `Engine.retime` returns: the plan at speeds that keep every converged mission inside the flight limits."""
+    plan: "object"           # of the kind that was given (Plan / RaggedBatch / RaggedPlan), planned at `velocities`; with rows if it had rows
+    velocities: "object"     # (B,) f64, device: the cruise speed of every mission after retiming (== plan.velocities)
+    factors: "object"        # (B,) f64: product of the mission's slow-down factors (1.0: never touched; NaN: a NaN peak, e.g. singular)
+    passes: int              # retimings done (0: every mission was inside the limits, or max_passes = 0)
+    converged: "object"      # (B,) bool: the mission's last audit asked for no retiming
+    audit: PlanAudit         # the audit of `plan` (no cuboids)
 
 
 @dataclass
@@ -239,8 +252,19 @@ class Engine:
         c0, r0, c1, r1 = (int(v) for v in stamps.cpu().tolist())
         return (c1 - c0) / max(1, r1 - r0) * 0.1
 
+    def _speeds(self, velocity, B: int):
+        """`velocity` as the planning entry points take it -> (scalar, None) for one cruise speed, (NaN, (B,) f64 device tensor) for
+        one per mission (anything that is not a number: a tensor, an array, a sequence)."""
+        torch = self._torch
+        if isinstance(velocity, (int, float, np.floating, np.integer)) or (getattr(velocity, "ndim", 1) == 0):
+            return float(velocity), None
+        v = self._dev(velocity, torch.float64).reshape(-1)
+        if v.numel() != B:
+            raise ValueError(f"one cruise speed per mission: expected {B} velocities, got {v.numel()}")
+        return float("nan"), v
+
     # -- planning ---------------------------------------------------------------
-    def plan(self, waypoints, velocity: float = 1.0, dt: float = 0.01, strict: bool = True, dense_yaw: bool = False,
+    def plan(self, waypoints, velocity=1.0, dt: float = 0.01, strict: bool = True, dense_yaw: bool = False,
              placement_trials: int = 1, pool: bool = False, rows: bool = True) -> Plan:
         """Batched `MinimumSnap(path, None, velocity, dt).get_trajectory()` (minimum_snap.py:59-61,97-124).
         `strict`: raise UavacError(ESINGULAR) when a mission's knot system is singular (a repeated waypoint) instead of
@@ -259,6 +283,10 @@ class Engine:
         plan-fed `Fleet` and `RcclComm.gather_plan` need; for the ranks of a multi-GPU job whose trajectories are sampled where they
         are wanted (the gather's root re-samples them from the gathered plan, bit-identical).  `Engine.sample_rows(plan)` adds the
         rows later.
+        `velocity`: a number -- one cruise speed for the batch, the scalar entry points exactly as ever -- or a (B,) tensor / array:
+        one per mission (`uavac_minsnap_*_v_dev`; `plan.velocities`, and `plan.velocity` is NaN).  Mission b is then bit for bit what
+        a scalar call at velocity[b] gives it.  A speed that is not positive and finite cannot be refused without a sync: it raises
+        device flag 0 (`take_flags`) and leaves its mission without rows.
         """
         torch = self._torch
         wp = self._dev(waypoints, torch.float64)
@@ -267,6 +295,7 @@ class Engine:
         if not bool(torch.isfinite(wp).all()):
             raise ValueError("waypoints must be finite")
         B, m = int(wp.shape[0]), int(wp.shape[1]) - 1
+        velocity, speeds = self._speeds(velocity, B)
         kw = dict(device=self.device)
         times = torch.empty((B, m), dtype=torch.float64, **kw)
         seg_rows = torch.empty((B, m), dtype=torch.int32, **kw)
@@ -278,22 +307,28 @@ class Engine:
             if dense_yaw or pool or int(placement_trials) > 1:
                 raise ValueError("dense_yaw, pool and placement_trials are about the rows: not with rows=False")
             first_yaw = torch.empty((B,), dtype=torch.float64, **kw)
-            plan = Plan(B, m, float(velocity), float(dt), wp, times, seg_rows, row_offsets, coeffs, status, None, 0, None, first_yaw)
+            plan = Plan(B, m, float(velocity), float(dt), wp, times, seg_rows, row_offsets, coeffs, status, None, 0, None, first_yaw,
+                        velocities=speeds)
             self.replan(plan)
             plan.epoch = 0
             plan.total_rows = int(row_offsets[-1].item())       # (the one host sync; the rows would have needed it to be allocated)
             if strict:
                 self.check(plan)
             return plan
-        self.ctx.call("uavac_minsnap_row_counts_dev", _ptr(wp), B, m, float(velocity), float(dt), _ptr(times),
-                      _ptr(seg_rows), _ptr(row_offsets))
+        if speeds is None:
+            self.ctx.call("uavac_minsnap_row_counts_dev", _ptr(wp), B, m, float(velocity), float(dt), _ptr(times),
+                          _ptr(seg_rows), _ptr(row_offsets))
+        else:
+            self.ctx.call("uavac_minsnap_row_counts_v_dev", _ptr(wp), B, m, _ptr(speeds), float(dt), _ptr(times),
+                          _ptr(seg_rows), _ptr(row_offsets))
         self.ctx.call("uavac_minsnap_solve_dev", _ptr(wp), _ptr(times), B, m, _ptr(coeffs), _ptr(status))
         total = int(row_offsets[-1].item())                 # the one host sync: sizes the trajectory buffer
         pooled = pool and self._row_pool is not None and self._row_pool.shape[0] >= total
         traj = self._row_pool[:total] if pooled else torch.empty((total, nat.TRAJ_COLS), dtype=torch.float64, **kw)
         yaw = torch.empty((total,), dtype=torch.float64, **kw) if dense_yaw else None
         first_yaw = torch.empty((B,), dtype=torch.float64, **kw)
-        plan = Plan(B, m, float(velocity), float(dt), wp, times, seg_rows, row_offsets, coeffs, status, traj, total, yaw, first_yaw)
+        plan = Plan(B, m, float(velocity), float(dt), wp, times, seg_rows, row_offsets, coeffs, status, traj, total, yaw, first_yaw,
+                    velocities=speeds)
         del traj                                                 # (place_rows may release the first draw: no second reference to it)
         self.sample(plan)
         if int(placement_trials) > 1 and total > 0 and not pooled:
@@ -384,9 +419,14 @@ class Engine:
             return                                               # (`empty_plan`: nothing to plan)
         self._bind_stream()
         cap = 0 if plan.traj is None else int(plan.traj.shape[0])
-        self.ctx.call("uavac_minsnap_plan_dev", _ptr(plan.waypoints), plan.B, plan.m, plan.velocity, plan.dt,
-                      _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets), _ptr(plan.coeffs), _ptr(plan.status),
-                      _ptr(plan.traj), cap, _ptr(plan.yaw), _ptr(plan.first_yaw))
+        if getattr(plan, "velocities", None) is None:
+            self.ctx.call("uavac_minsnap_plan_dev", _ptr(plan.waypoints), plan.B, plan.m, plan.velocity, plan.dt,
+                          _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets), _ptr(plan.coeffs), _ptr(plan.status),
+                          _ptr(plan.traj), cap, _ptr(plan.yaw), _ptr(plan.first_yaw))
+        else:                                                    # one cruise speed per mission (read from the device at every replan)
+            self.ctx.call("uavac_minsnap_plan_v_dev", _ptr(plan.waypoints), plan.B, plan.m, _ptr(plan.velocities), plan.dt,
+                          _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets), _ptr(plan.coeffs), _ptr(plan.status),
+                          _ptr(plan.traj), cap, _ptr(plan.yaw), _ptr(plan.first_yaw))
         plan.__dict__["_rows_stale"] = True                      # (no sync here: Plan.total_rows reads it when asked)
         plan.epoch += 1
 
@@ -452,6 +492,67 @@ class Engine:
                       B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(cub) if n else None, n, _ptr(block),
                       _ptr(hit_rows) if n else None, _ptr(first_hit) if n else None)
         return PlanAudit(*block.unbind(0), hit_rows, first_hit, block)
+
+    DEFAULT_RETIME_MARGIN = 1e-3
+
+    def retime(self, plan, vehicle: Optional[nat.Vehicle] = None, margin: float = DEFAULT_RETIME_MARGIN, max_passes: int = 4) -> RetimeResult:
+        """Slow down exactly the missions of `plan` that ask for more than the control law gives (`vehicle`'s max_speed_xy,
+        max_ascent, max_descent, max_horiz_accel; None = `uavac_vehicle_default`), by exactly the factor they need
+        (`uavac_minsnap_retime_dev`): per pass the rows-free chain at the current per-mission speeds, the audit, and per mission
+        r = max(speed_xy / L0, ascent / L1, descent / L2, sqrt(accel_xy / L3)); a mission with r > 1 is planned again at
+        velocity / (r / (1 - margin)), which leaves its curve where it is and scales its velocity peaks by 1 / k, its acceleration
+        peaks by 1 / k^2.  Stops when no mission was slowed down or after `max_passes` retimings (0: audit only, no speed changes);
+        one host sync per pass, no row sampled inside the loop.
+        `margin`: the audit's peaks are maxima over SAMPLES, and the slower plan is sampled elsewhere on the curve, so its peaks may
+        lie above peak / k by the gap between sampled and continuous maxima -- about 1e-4 relative on the bench distribution (3 m
+        legs at 3 m/s) at dt = 0.01, and larger for a coarser dt.  The default of 1e-3 clears that with room and costs 0.1 % of
+        speed; a margin below the gap costs further passes, not correctness (`converged` tells).
+        `plan`: a Plan, a RaggedBatch, or a RaggedPlan that has its batch; it is left as it is.  -> RetimeResult whose `.plan` is of
+        the same kind, with fresh buffers: rows-free if the input was, else with rows sampled ONCE at the end.  Missions whose plan
+        is singular (or has no rows) keep their speed, report a NaN factor and converged = False; the device flags are left to the
+        caller (`take_flags`)."""
+        torch = self._torch
+        wrapper = plan if isinstance(plan, RaggedPlan) else None
+        if wrapper is not None:
+            if plan.batch is None:
+                raise ValueError("this RaggedPlan has no batch (plan_collision_free(device_loop=False)): retime eng.plan_ragged(plan.final_waypoints, ...)")
+            plan = plan.batch
+        if plan.waypoints is None:
+            raise ValueError("retiming plans again from the waypoints: a plan assembled from gathered parts has none")
+        ragged = hasattr(plan, "seg_offsets")
+        B = int(plan.B)
+        m = int(plan.max_m if ragged else plan.m)
+        V = nat.Vehicle.default() if vehicle is None else vehicle
+        limits = (C.c_double * 4)(float(V.max_speed_xy), float(V.max_ascent), float(V.max_descent), float(V.max_horiz_accel))
+        kw = dict(device=self.device)
+        old = getattr(plan, "velocities", None)
+        speeds = old.clone() if old is not None else torch.full((B,), float(plan.velocity), dtype=torch.float64, **kw)
+        times, seg_rows, coeffs = torch.empty_like(plan.times), torch.empty_like(plan.seg_rows), torch.empty_like(plan.coeffs)
+        row_offsets = torch.empty((B + 1,), dtype=torch.int64, **kw)
+        status = torch.zeros((B,), dtype=torch.int32, **kw)
+        first_yaw = torch.empty((B,), dtype=torch.float64, **kw)
+        block = torch.empty((nat.AUDIT_ROWS, B), dtype=torch.float64, **kw)
+        factors = torch.empty((B,), dtype=torch.float64, **kw)
+        converged = torch.empty((B,), dtype=torch.int32, **kw)
+        passes = C.c_int(0)
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_retime_dev", _ptr(plan.waypoints), _ptr(plan.seg_offsets) if ragged else None, B, m, _ptr(speeds),
+                      float(plan.dt), limits, float(margin), int(max_passes), _ptr(times), _ptr(seg_rows), _ptr(row_offsets),
+                      _ptr(coeffs), _ptr(status), _ptr(first_yaw), _ptr(block), _ptr(factors), _ptr(converged), C.byref(passes))
+        total = int(row_offsets[-1].item())
+        if ragged:
+            out = RaggedBatch(B, m, float("nan"), float(plan.dt), plan.seg_offsets, plan.seg_offsets_host, plan.waypoints, times,
+                              seg_rows, row_offsets, coeffs, status, None, total, first_yaw, None, speeds)
+        else:
+            out = Plan(B, m, float("nan"), float(plan.dt), plan.waypoints, times, seg_rows, row_offsets, coeffs, status, None, total,
+                       None, first_yaw, velocities=speeds)
+        if plan.traj is not None:
+            self.sample_rows(out)                                # the rows, once
+        if wrapper is not None:
+            out = RaggedPlan(B, float("nan"), float(plan.dt), wrapper.final_waypoints, out.row_offsets, out.traj, out.total_rows,
+                             wrapper.start_positions, wrapper.converged, out)
+        empty = torch.empty((0, B), dtype=torch.int32, **kw)
+        return RetimeResult(out, speeds, factors, int(passes.value), converged != 0, PlanAudit(*block.unbind(0), empty, empty, block))
 
     def sample_range(self, plan: Plan, b0: int, b1: int):
         """The rows (and first headings) of missions [b0, b1) of a uniform plan, written where `sample(plan)` writes them: the
@@ -761,13 +862,14 @@ class Engine:
         converged[sorted(failed)] = False
         return RaggedPlan(B, float(velocity), float(dt), wps, offsets, traj, total, starts, converged)
 
-    def plan_ragged(self, waypoints, velocity: float = 1.0, dt: float = 0.01, cuboid=None, strict: bool = True,
+    def plan_ragged(self, waypoints, velocity=1.0, dt: float = 0.01, cuboid=None, strict: bool = True,
                     rows: bool = True) -> RaggedBatch:
         """`MinimumSnap(path_b, None, velocity, dt).get_trajectory()` for B paths of DIFFERENT lengths in one batch
         (minimum_snap.py:13-57 takes any path; `Engine.plan` wants equal lengths).  `waypoints`: B arrays (m_b + 1, 3),
         1 <= m_b <= UAVAC_MAX_SEGMENTS.  Mission b's rows and coefficients equal those of `plan` on it alone, bit for
         bit.  `cuboid` (6,): also return per-spline hit flags (the collision scan of minimum_snap.py:81-87).
-        `rows=False`: no rows (`batch.traj` is None), the first headings from `uavac_minsnap_first_yaw_dev`; not with `cuboid`."""
+        `rows=False`: no rows (`batch.traj` is None), the first headings from `uavac_minsnap_first_yaw_dev`; not with `cuboid`.
+        `velocity`: a number, or a (B,) tensor / array of one cruise speed per mission (see `plan`)."""
         torch = self._torch
         wps = [np.ascontiguousarray(w, dtype=np.float64) for w in waypoints]
         B = len(wps)
@@ -787,10 +889,11 @@ class Engine:
             self.check(batch)
         return batch
 
-    def _plan_ragged_tensors(self, wp, so, so_host, max_m: int, velocity: float, dt: float, cuboid, rows: bool = True) -> RaggedBatch:
+    def _plan_ragged_tensors(self, wp, so, so_host, max_m: int, velocity, dt: float, cuboid, rows: bool = True) -> RaggedBatch:
         """`plan_ragged` on device-resident waypoints wp (S + B, 3) / seg_offsets so (B + 1,) (so_host: the same on the host)."""
         torch = self._torch
         B, S = len(so_host) - 1, int(so_host[-1])
+        velocity, speeds = self._speeds(velocity, B)
         kw = dict(device=self.device)
         times = torch.empty((S,), dtype=torch.float64, **kw)
         seg_rows = torch.empty((S,), dtype=torch.int32, **kw)
@@ -803,27 +906,35 @@ class Engine:
             hit = torch.empty((S,), dtype=torch.int32, **kw)
             aabb = self._dev(np.asarray(cuboid, dtype=np.float64).reshape(6), torch.float64)
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_row_counts_ragged_dev", _ptr(wp), _ptr(so), B, max_m, float(velocity), float(dt),
-                      _ptr(times), _ptr(seg_rows), _ptr(row_offsets))
+        if speeds is None:
+            self.ctx.call("uavac_minsnap_row_counts_ragged_dev", _ptr(wp), _ptr(so), B, max_m, float(velocity), float(dt),
+                          _ptr(times), _ptr(seg_rows), _ptr(row_offsets))
+        else:
+            self.ctx.call("uavac_minsnap_row_counts_ragged_v_dev", _ptr(wp), _ptr(so), B, max_m, _ptr(speeds), float(dt),
+                          _ptr(times), _ptr(seg_rows), _ptr(row_offsets))
         self.ctx.call("uavac_minsnap_solve_ragged_dev", _ptr(wp), _ptr(times), _ptr(so), B, max_m, _ptr(coeffs), _ptr(status))
         if not rows:
             if cuboid is not None:
                 raise ValueError("the collision scan walks the rows' positions: not with rows=False")
             self.ctx.call("uavac_minsnap_first_yaw_dev", _ptr(coeffs), _ptr(seg_rows), _ptr(so), B, max_m, float(dt), _ptr(first_yaw))
             return RaggedBatch(B, max_m, float(velocity), float(dt), so, so_host, wp, times, seg_rows, row_offsets, coeffs, status,
-                               None, int(row_offsets[-1].item()), first_yaw, None)
+                               None, int(row_offsets[-1].item()), first_yaw, None, speeds)
         total = int(row_offsets[-1].item())
         traj = torch.empty((total, nat.TRAJ_COLS), dtype=torch.float64, **kw)
         self.ctx.call("uavac_minsnap_sample_ragged_dev", _ptr(coeffs), _ptr(seg_rows), _ptr(so), _ptr(row_offsets), B, max_m,
                       S, float(dt), _ptr(traj), total, _ptr(aabb), _ptr(hit), _ptr(first_yaw))
         return RaggedBatch(B, max_m, float(velocity), float(dt), so, so_host, wp, times, seg_rows, row_offsets, coeffs, status,
-                           traj, total, first_yaw, hit)
+                           traj, total, first_yaw, hit, speeds)
 
     def solve(self, plan: Plan):
         """Re-run times/row counts + coefficient solve into plan's buffers (no allocation, no sync)."""
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_row_counts_dev", _ptr(plan.waypoints), plan.B, plan.m, plan.velocity, plan.dt,
-                      _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets))
+        if getattr(plan, "velocities", None) is None:
+            self.ctx.call("uavac_minsnap_row_counts_dev", _ptr(plan.waypoints), plan.B, plan.m, plan.velocity, plan.dt,
+                          _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets))
+        else:
+            self.ctx.call("uavac_minsnap_row_counts_v_dev", _ptr(plan.waypoints), plan.B, plan.m, _ptr(plan.velocities), plan.dt,
+                          _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets))
         self.ctx.call("uavac_minsnap_solve_dev", _ptr(plan.waypoints), _ptr(plan.times), plan.B, plan.m,
                       _ptr(plan.coeffs), _ptr(plan.status))
         plan.epoch += 1

@@ -8,9 +8,13 @@ distance to the goal < 0.5 m, no collision.  `summarize` turns a score block int
 `acceptance` applies upstream's three assertions.  Pure torch: works on device and on CPU tensors alike.
 
 `plan_feasibility` is the judge BEFORE the flight: it compares a plan audit (`Engine.audit`, include/uavac.h
-uavac_minsnap_audit_dev) with the flight limits the control law clips its targets to.
+uavac_minsnap_audit_dev) with the flight limits the control law clips its targets to.  `retime_factors` says by how much each
+mission has to be slowed down to pass it: the CPU statement of the rule the retiming kernel implements (include/uavac.h
+uavac_minsnap_retime_factors_dev), NumPy on the host, bit for bit.
 """
 from __future__ import annotations
+
+import numpy as np
 
 from . import _native as nat
 
@@ -83,3 +87,59 @@ def plan_feasibility(audit, vehicle=None, slack: float = 0.0) -> dict:
         clear = clear & (hits.reshape(-1, finite.shape[0]) == 0).all(dim=0).to(finite.device)
     return {"speed_ok": speed_ok, "ascent_ok": ascent_ok, "descent_ok": descent_ok, "accel_ok": accel_ok, "clear": clear,
             "feasible": speed_ok & ascent_ok & descent_ok & accel_ok & clear}
+
+
+DEFAULT_RETIME_MARGIN = 1e-3     # see `retime_factors`; the default of `Engine.retime`
+
+
+def _host(x) -> np.ndarray:
+    return np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, dtype=np.float64)
+
+
+def retime_factors(audit, vehicle=None, margin: float = DEFAULT_RETIME_MARGIN, velocities=None) -> dict:
+    """By how much each mission of an audited plan must be slowed down to stay inside the limits the control law clips its targets
+    to -- the SPECIFICATION of `uavac_minsnap_retime_factors_dev` (csrc/minsnap_retime.hip), which is tested against it bit for bit.
+    `audit`: a PlanAudit (or anything with speed_xy, ascent, descent, accel_xy), or the (AUDIT_ROWS, B) block itself; tensors (any
+    device) or arrays.  `vehicle`: anything with the four limits; None = `uavac_vehicle_default`.
+
+    Scaling every segment duration of a mission by k > 1 -- planning it at velocity / k -- leaves the minimum-snap curve where it is,
+    p'(t) = p(t / k): velocity peaks scale by 1 / k, acceleration peaks by 1 / k^2.  Per mission, every step ONE rounded IEEE
+    operation (NumPy's elementwise float64 division, sqrt and fmax are exactly that):
+        r = max(speed_xy / max_speed_xy, ascent / max_ascent, descent / max_descent, sqrt(accel_xy / max_horiz_accel))
+        a NaN among the four peaks (a singular plan, a mission without rows) -> factor NaN, velocity untouched
+        r <= 1                                                               -> factor 1.0, velocity untouched bit for bit
+        otherwise                                      k = r / (1 - margin)  -> factor k,   velocity / k
+    `margin` in [0, 1): the audit's peaks are maxima over SAMPLES and the slower plan is sampled elsewhere on the curve, so its
+    sampled peaks can exceed peak / k by the relative gap between sampled and continuous maxima -- about 1e-4 on the bench
+    distribution (3 m legs at 3 m/s) at dt = 0.01, growing with dt.  With a margin above the gap one pass suffices; the default 1e-3
+    costs 0.1 % of cruise speed.
+    -> dict of host arrays / ints: factors (B,) f64, retimed (B,) bool, nan (B,) bool, n_retimed, n_nan -- the kernel's two counters
+    -- and, when `velocities` (B,) was given, velocities (B,) f64: the new ones."""
+    V = nat.Vehicle.default() if vehicle is None else vehicle
+    limits = [float(V.max_speed_xy), float(V.max_ascent), float(V.max_descent), float(V.max_horiz_accel)]
+    margin = float(margin)
+    if not all(np.isfinite(x) and x > 0.0 for x in limits):
+        raise ValueError("every flight limit must be finite and > 0")
+    if not (0.0 <= margin < 1.0):
+        raise ValueError("margin must be in [0, 1)")
+    if hasattr(audit, "speed_xy"):
+        peaks = [_host(audit.speed_xy), _host(audit.ascent), _host(audit.descent), _host(audit.accel_xy)]
+    else:
+        block = _host(audit)
+        if block.ndim != 2 or block.shape[0] != nat.AUDIT_ROWS:
+            raise ValueError(f"an audit block is [{nat.AUDIT_ROWS}][B], got {block.shape}")
+        peaks = [block[1], block[2], block[3], block[4]]
+    speed_xy, ascent, descent, accel_xy = (p.reshape(-1) for p in peaks)
+    nan = np.isnan(speed_xy) | np.isnan(ascent) | np.isnan(descent) | np.isnan(accel_xy)
+    with np.errstate(invalid="ignore"):
+        r = np.fmax(np.fmax(speed_xy / limits[0], ascent / limits[1]),
+                    np.fmax(descent / limits[2], np.sqrt(accel_xy / limits[3])))
+        retimed = ~nan & (r > 1.0)
+        k = r / (1.0 - margin)
+    factors = np.where(nan, np.nan, np.where(retimed, k, 1.0))
+    out = {"factors": factors, "retimed": retimed, "nan": nan, "n_retimed": int(retimed.sum()), "n_nan": int(nan.sum())}
+    if velocities is not None:
+        v = _host(velocities).reshape(-1).copy()
+        v[retimed] = v[retimed] / factors[retimed]
+        out["velocities"] = v
+    return out
