@@ -321,6 +321,35 @@ int uavac_minsnap_plan_v_dev(uavac_ctx *ctx, const double *wp, int B, int m, con
                              int32_t *status, double *traj, int64_t traj_capacity_rows, double *yaw,
                              double *first_yaw);
 
+/* MISSIONS THAT START AND END IN MOTION.  uavac_minsnap_solve_dev pins velocity, acceleration and jerk to zero at the first and last
+ * waypoint (MinimumSnap._generate_start_and_goal_constraints, minimum_snap.py:200-223); these two take them per mission:
+ *   bc [B][6][3] f64 (device): rows 0-2 = velocity, acceleration, jerk at the FIRST waypoint, rows 3-5 = the same at the LAST one;
+ *                              columns x y z (NED, SI units: m/s, m/s^2, m/s^3).
+ * The same QP with those six right-hand sides: the optimum of the reference's dense KKT system with b[2m : 2m+3] = bc rows 0-2 and
+ * b[2m+3 : 2m+6] = bc rows 3-5.  One lane per mission, one-ended block-Thomas recurrence (csrc/minsnap_solve_bc.hip); the boundary
+ * values touch the right-hand side of the first and last interior knot and the coefficients of the first and last segment only.
+ * BIT-EXACT by construction: a mission's coeffs[1] == v0, coeffs[2] == 0.5 * a0, coeffs[3] == j0 * (1.0 / 6.0) (rows of its first
+ * segment, per column).  With bc all zero the result is the rest-to-rest optimum, rounded as the one-ended elimination rounds it
+ * (within 1e-12 of uavac_minsnap_solve_dev relative to the largest coefficient, not bit-equal to it).
+ * status [B] (may be NULL) and sticky flag 1 as for uavac_minsnap_solve_dev: a singular knot system gives status 1 and NaN
+ * coefficients.  A NON-FINITE value in mission b's bc cannot be refused without a sync: mission b's coefficients come out
+ * non-finite (its status stays 0: the pivots do not depend on bc -- the plan audit reports such a mission as NaN), the other
+ * missions are unaffected.
+ * uavac_minsnap_solve_bc_dev: seg_offsets == NULL: a uniform batch (wp [B][m+1][3], times [B][m], coeffs [B][8m][3]); otherwise the
+ * ragged layout of uavac_minsnap_solve_ragged_dev with m = the largest segment count.  Mission b of a ragged call equals a uniform
+ * call on it alone, and any split of a batch the whole, bit for bit.  UAVAC_EINVAL as for uavac_minsnap_solve_dev, and for bc == NULL.
+ * uavac_minsnap_plan_bc_dev: uavac_minsnap_plan_v_dev with this solve in the solve's place -- both forms, rows with a capacity,
+ * flag 2 and the all-or-nothing commit (a refused plan keeps its coefficients), and rows-free with traj == NULL; velocities [B] is
+ * always a device array.  Durations, row counts and offsets do not depend on bc: same kernels, same bits as the _v chain.
+ * CONTRACT: everything downstream reads only times / seg_rows / coeffs and is unchanged -- samplers, first headings, audit,
+ * plan-fed rollouts, plan gathers.  Row 0 of a mission then carries velocity v0, and its yaw is the heading of v0 where
+ * |v0_xy| >= 1e-3. */
+int uavac_minsnap_solve_bc_dev(uavac_ctx *ctx, const double *wp, const double *times, const int64_t *seg_offsets, int B, int m,
+                               const double *bc, double *coeffs, int32_t *status);
+int uavac_minsnap_plan_bc_dev(uavac_ctx *ctx, const double *wp, int B, int m, const double *velocities, double dt,
+                              const double *bc, double *times, int32_t *seg_rows, int64_t *row_offsets, double *coeffs,
+                              int32_t *status, double *traj, int64_t traj_capacity_rows, double *yaw, double *first_yaw);
+
 /* RETIMING FACTORS: by how much each mission of an audited plan must be slowed down to stay inside the limits the control law
  * clips its targets to.  Scaling every segment duration of a mission by k > 1 -- planning it at velocity / k -- leaves the
  * minimum-snap curve where it is (p'(t) = p(t / k)): velocity peaks scale by 1 / k, acceleration peaks by 1 / k^2.

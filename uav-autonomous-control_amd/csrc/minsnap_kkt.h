@@ -1,6 +1,6 @@
 // The minimum-snap KKT system in knot-derivative coordinates: the pieces every form of the coefficient solve shares (gfx950).
-// Included by minsnap_solve_tw.hip (two-ended block-Thomas, the default), minsnap_solve_bt.hip (one-ended, its cross-check) and
-// minsnap_solve.hip (pivoted banded LU: the tables only).  The C oracle of the tests keeps a copy of its own on purpose: it shares no code with the product.
+// Included by minsnap_solve_tw.hip (two-ended block-Thomas, the default), minsnap_solve_bt.hip (one-ended, its cross-check),
+// minsnap_solve_bc.hip (one-ended with boundary derivatives) and minsnap_solve.hip (pivoted banded LU: the tables only).  The C oracle of the tests keeps a copy of its own on purpose: it shares no code with the product.
 //
 // Replaces uav_ac/planning/minimum_snap.py:138-255 (_create_polynom_matrices / _create_snap_cost_matrix /
 // _compute_spline_parameters).  The reference solves one dense (14m+2)^2 KKT system per mission in the monomial
@@ -241,6 +241,34 @@ __device__ __forceinline__ void segment_coeffs(const double ip[8], double T, con
             out[4 + i][a] = s * ip[4 + i];
         }
     }
+}
+
+// ---- boundary derivatives (minsnap_solve_bc.hip): a mission that starts / ends in motion.  The known (v, a, j) of the first / last
+// waypoint act like a knot's unknowns without a multiplier; what the first / last segment couples from them into its other knot
+// moves to that knot's right-hand side, the snap-continuity row (i = 3) included.
+// first segment: re -= B^T x0
+__device__ __forceinline__ void start_boundary_rhs(Seg &g, const double x0[3][3]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            double s = g.re[i][a];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) s = fma(-g.B[j][i], x0[j][a], s);
+            g.re[i][a] = s;
+        }
+}
+// last segment: rs -= B xg
+__device__ __forceinline__ void goal_boundary_rhs(Seg &g, const double xg[3][3]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            double s = g.rs[i][a];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) s = fma(-g.B[i][j], xg[j][a], s);
+            g.rs[i][a] = s;
+        }
 }
 
 }  // namespace

@@ -224,18 +224,23 @@ int launch_counts(uavac_ctx *ctx, const double *wp, int B, int m, const double *
     return uavac_launch_row_counts_v(ctx, wp, B, m, velocities, dt, times, seg_rows, row_offsets, seg_offsets);
 }
 
-// The planning chain behind uavac_minsnap_plan_dev (Vel = double) and uavac_minsnap_plan_v_dev (Vel = const double *); the
+// The planning chain behind uavac_minsnap_plan_dev (Vel = double), uavac_minsnap_plan_v_dev (Vel = const double *) and
+// uavac_minsnap_plan_bc_dev (the latter with bc != NULL: the solve with boundary derivatives in the solve's place); the
 // arguments have been validated.
 template <class Vel>
 int plan_chain(uavac_ctx *ctx, const double *wp, int B, int m, Vel velocity, double dt, double *times, int32_t *seg_rows,
                       int64_t *row_offsets, double *coeffs, int32_t *status, double *traj, int64_t traj_capacity_rows, double *yaw,
-                      double *first_yaw) {
+                      double *first_yaw, const double *bc = nullptr) {
+    auto solve = [&](const double *tm, const int64_t *guard_rows, int64_t guard_capacity) {
+        return bc ? uavac_launch_solve_bc(ctx, wp, tm, B, m, bc, coeffs, status, nullptr, guard_rows, guard_capacity)
+                  : uavac_launch_coeff_solve(ctx, wp, tm, B, m, coeffs, status, nullptr, guard_rows, guard_capacity);
+    };
     if (!traj) {
         // Rows-free chain: no row buffer, hence nothing to refuse -- times, row counts and offsets go straight into the caller's
         // arrays; the one value of the sampler a plan-fed rollout needs comes from the first-heading kernel.
         if (yaw) return uavac_fail(ctx, UAVAC_EINVAL, "a dense yaw column needs the rows: traj is NULL");
         if (int rc = launch_counts(ctx, wp, B, m, velocity, dt, times, seg_rows, row_offsets)) return rc;
-        if (int rc = uavac_launch_coeff_solve(ctx, wp, times, B, m, coeffs, status)) return rc;
+        if (int rc = solve(times, nullptr, 0)) return rc;
         return first_yaw ? uavac_launch_first_yaw(ctx, coeffs, seg_rows, nullptr, B, m, dt, first_yaw) : UAVAC_OK;
     }
     if (traj_capacity_rows < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative capacity");
@@ -266,8 +271,7 @@ int plan_chain(uavac_ctx *ctx, const double *wp, int B, int m, Vel velocity, dou
     // (Round 6 tried to hide this solve behind the sampler: the batch cut into 2 / 4 / 8 mission blocks, block i sampled on an
     // auxiliary stream while block i + 1 was being solved.  Bit-identical and SLOWER -- +1.3 % / +13 % / +23 % at 65 536 x 12 --
     // because a solve wave cannot get onto a SIMD the sampler's grid keeps full: commit 53921dc, profiles/r06_plan_blocks_ab*.jsonl.)
-    if (int rc = uavac_launch_coeff_solve(ctx, wp, times_s, B, m, coeffs, status, nullptr, row_offsets_s + B, traj_capacity_rows))
-        return rc;
+    if (int rc = solve(times_s, row_offsets_s + B, traj_capacity_rows)) return rc;
     SampleExtras x;
     x.yaw_dense = yaw;
     x.first_yaw = first_yaw;
@@ -665,6 +669,26 @@ int uavac_minsnap_plan_v_dev(uavac_ctx *ctx, const double *wp, int B, int m, con
     if (int rc = check_dt(ctx, dt)) return rc;
     return plan_chain(ctx, wp, B, m, velocities, dt, times, seg_rows, row_offsets, coeffs, status, traj, traj_capacity_rows, yaw,
                       first_yaw);
+}
+
+// ---------------------------------------------------------------- missions that start and end in motion
+int uavac_minsnap_solve_bc_dev(uavac_ctx *ctx, const double *wp, const double *times, const int64_t *seg_offsets, int B, int m,
+                               const double *bc, double *coeffs, int32_t *status) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
+    if (!times || !bc || !coeffs) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    return uavac_launch_solve_bc(ctx, wp, times, B, m, bc, coeffs, status, seg_offsets, nullptr, 0);
+}
+
+int uavac_minsnap_plan_bc_dev(uavac_ctx *ctx, const double *wp, int B, int m, const double *velocities, double dt, const double *bc,
+                              double *times, int32_t *seg_rows, int64_t *row_offsets, double *coeffs, int32_t *status, double *traj,
+                              int64_t traj_capacity_rows, double *yaw, double *first_yaw) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
+    if (!velocities || !bc || !times || !seg_rows || !row_offsets || !coeffs) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_dt(ctx, dt)) return rc;
+    return plan_chain(ctx, wp, B, m, velocities, dt, times, seg_rows, row_offsets, coeffs, status, traj, traj_capacity_rows, yaw,
+                      first_yaw, bc);
 }
 
 // ---------------------------------------------------------------- retiming to the flight limits

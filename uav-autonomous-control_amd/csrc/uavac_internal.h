@@ -176,6 +176,9 @@ int uavac_launch_solve_tw(uavac_ctx *ctx, const double *wp, const double *times,
 int uavac_launch_solve_bt(uavac_ctx *ctx, const double *wp, const double *times, int B, int m, double *coeffs,
                           int32_t *status, const int64_t *seg_offsets, const int64_t *guard_rows, int64_t guard_capacity,
                           const int32_t *active);
+// the solve with boundary derivatives (minsnap_solve_bc.hip): bc [B][6][3] (device) = (v, a, j) at the first and at the last waypoint
+int uavac_launch_solve_bc(uavac_ctx *ctx, const double *wp, const double *times, int B, int m, const double *bc, double *coeffs,
+                          int32_t *status, const int64_t *seg_offsets, const int64_t *guard_rows, int64_t guard_capacity);
 // One round of the obstacle loop on the device (minsnap_obstacles.hip): collision scan of the active missions' splines
 // (no rows stored) + midpoint insertion into the next waypoint arrays
 int uavac_launch_obstacle_scan_and_insert(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, const double *coeffs,

@@ -33,6 +33,25 @@ def kernel_register_counts(obj: str, kernel: str):
     return [(n, int(v), int(s)) for n, v, s in found]
 
 
+def kernel_private_bytes(obj: str, kernel: str):
+    """[(kernel name, private_segment_fixed_size)] -- the scratch memory per lane, which is 0 for a kernel that lives in registers --
+    of every kernel of the object file whose name contains `kernel`; None like `kernel_register_counts`."""
+    objdump, readelf = os.path.join(LLVM_BIN, "llvm-objdump"), os.path.join(LLVM_BIN, "llvm-readelf")
+    if not (os.path.exists(obj) and os.path.exists(objdump) and os.path.exists(readelf)):
+        return None
+    tmp = tempfile.mkdtemp()
+    try:
+        shutil.copy(obj, os.path.join(tmp, "o.o"))
+        subprocess.run([objdump, "--offloading", "o.o"], cwd=tmp, check=True, capture_output=True)
+        co = [f for f in os.listdir(tmp) if "gfx950" in f][0]
+        notes = subprocess.run([readelf, "--notes", os.path.join(tmp, co)], check=True, capture_output=True, text=True).stdout
+    finally:
+        shutil.rmtree(tmp)
+    # (the metadata lists a kernel's keys in alphabetical order: .name comes before .private_segment_fixed_size)
+    found = re.findall(r"\.name:\s+(\S*" + re.escape(kernel) + r"\S*)\s.*?\.private_segment_fixed_size:\s+(\d+)", notes, flags=re.S)
+    return [(n, int(v)) for n, v in found]
+
+
 def rollout_register_counts(obj: str = None):
     """The same for every control_rollout_kernel variant."""
     return kernel_register_counts(obj or os.path.join(PKG, "build", "control_rollout.o"), "control_rollout_kernel")
@@ -41,13 +60,16 @@ def rollout_register_counts(obj: str = None):
 def check_planning_registers():
     """The planning kernels' budgets: the chunk-streaming sampler without jerk / snap runs six waves per SIMD (<= 80 vector
     registers; with jerk / snap four: <= 128), the solve one or two (the variant that keeps five knots in registers: <= 512, the
-    others <= 256), the plan audit three (<= 168); none may spill (a spill in the sampler showed as 3 % more HBM writes and no other symptom, NOTES R4-2).
+    others <= 256), the solve with boundary derivatives two (<= 256, and no scratch memory at all: zero private-segment bytes), the
+    plan audit three (<= 168); none may spill (a spill in the sampler showed as 3 % more HBM writes and no other symptom, NOTES R4-2).
     Returns the counts, None when they cannot be read."""
     s = kernel_register_counts(os.path.join(PKG, "build", "minsnap_sample_stream.o"), "minsnap_sample_stream_kernel")
     k = kernel_register_counts(os.path.join(PKG, "build", "minsnap_solve_bt.o"), "minsnap_solve_bt_kernel")
     k2 = kernel_register_counts(os.path.join(PKG, "build", "minsnap_solve_tw.o"), "minsnap_solve_tw_kernel")
     a = kernel_register_counts(os.path.join(PKG, "build", "minsnap_audit.o"), "minsnap_audit_kernel")
-    if s is None or k is None or k2 is None or a is None:
+    bc_obj = os.path.join(PKG, "build", "minsnap_solve_bc.o")
+    kb, pb = kernel_register_counts(bc_obj, "minsnap_solve_bc_kernel"), kernel_private_bytes(bc_obj, "minsnap_solve_bc_kernel")
+    if s is None or k is None or k2 is None or a is None or kb is None or pb is None:
         return None
     k = k + k2                                        # (the two-ended solve: same budgets, same naming of the last template argument)
     bad = []
@@ -64,10 +86,16 @@ def check_planning_registers():
     for n, v, sp in a:                                # the plan audit: three waves per SIMD (built: 100 .. 146 registers)
         if v > 168 or sp:
             bad.append((n[:70], v, sp, 168))
-    if len(s) < 20 or len(k) < 20 or len(a) < 4 or bad:
+    for n, v, sp in kb:                               # the solve with boundary derivatives: two waves per SIMD (built: 211 / 217 registers)
+        if v > 256 or sp:
+            bad.append((n[:70], v, sp, 256))
+    for n, priv in pb:
+        if priv:
+            bad.append((n[:70], f"{priv} private-segment bytes", 0, 0))
+    if len(s) < 20 or len(k) < 20 or len(a) < 4 or len(kb) != 2 or len(pb) != 2 or bad:
         raise RuntimeError(f"planning kernels outside their register budgets (name, VGPRs, spills, limit): {bad}; {len(s)} sampler, "
-                           f"{len(k)} solve and {len(a)} audit variants found (compiler: {compiler_version()})")
-    return s + k + a
+                           f"{len(k)} solve, {len(kb)} boundary-solve and {len(a)} audit variants found (compiler: {compiler_version()})")
+    return s + k + a + kb
 
 
 def check_rollout_registers(obj: str = None):

@@ -92,6 +92,8 @@ _SIGNATURES = {
     "uavac_minsnap_row_counts_v_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P]),
     "uavac_minsnap_row_counts_ragged_v_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P]),
     "uavac_minsnap_plan_v_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
+    "uavac_minsnap_solve_bc_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "uavac_minsnap_plan_bc_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
     "uavac_minsnap_retime_factors_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_double, _P, _P, _P]),
     "uavac_minsnap_retime_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_double, _P, C.c_double, C.c_int] + [_P] * 10),
     "uavac_minsnap_row_offsets_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),

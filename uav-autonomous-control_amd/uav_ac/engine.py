@@ -49,6 +49,9 @@ class Plan:
     epoch: int = 0                   # bumped whenever the plan is re-solved / re-sampled in place (Engine.replan / solve / sample):
                                      # an attached Fleet then rebuilds the yaw scan it carries instead of trusting a stale one
     velocities: "object" = None      # (B,) f64, device: one cruise speed per mission (`velocity` is then NaN); None = the one `velocity`
+    boundary: "object" = None        # (B, 6, 3) f64, device: (v, a, j) at the first waypoint (rows 0-2) and at the last (rows 3-5); None =
+                                     # rest to rest.  Read again at every replan / solve.  Such a plan always has `velocities` (a scalar
+                                     # `velocity` is kept and broadcast)
 
     def mission(self, b: int) -> np.ndarray:
         """Rows of mission b as a fresh host array (N_b, 11) -- the reference's `full_trajectory`."""
@@ -265,7 +268,7 @@ class Engine:
 
     # -- planning ---------------------------------------------------------------
     def plan(self, waypoints, velocity=1.0, dt: float = 0.01, strict: bool = True, dense_yaw: bool = False,
-             placement_trials: int = 1, pool: bool = False, rows: bool = True) -> Plan:
+             placement_trials: int = 1, pool: bool = False, rows: bool = True, boundary=None) -> Plan:
         """Batched `MinimumSnap(path, None, velocity, dt).get_trajectory()` (minimum_snap.py:59-61,97-124).
         `strict`: raise UavacError(ESINGULAR) when a mission's knot system is singular (a repeated waypoint) instead of
         returning NaN coefficients for it; with strict=False inspect `plan.status`.
@@ -287,6 +290,12 @@ class Engine:
         one per mission (`uavac_minsnap_*_v_dev`; `plan.velocities`, and `plan.velocity` is NaN).  Mission b is then bit for bit what
         a scalar call at velocity[b] gives it.  A speed that is not positive and finite cannot be refused without a sync: it raises
         device flag 0 (`take_flags`) and leaves its mission without rows.
+        `boundary`: a (B, 6, 3) array or tensor -- velocity, acceleration, jerk at every mission's FIRST waypoint (rows 0-2) and at its
+        LAST one (rows 3-5), columns x y z -- for missions that start and / or end in motion (`uavac_minsnap_plan_bc_dev`, with rows
+        or rows-free; `Fleet.boundary()` gives the live velocities of a flying fleet).  None: rest to rest, the reference's
+        constraints.  Durations, row counts and offsets do not depend on it; row 0 of a mission then carries velocity v0.  The plan
+        keeps the tensor (`plan.boundary`, read again at every `replan` / `solve`: change it in place to replan from another state)
+        and cannot be retimed (`retime` raises).
         """
         torch = self._torch
         wp = self._dev(waypoints, torch.float64)
@@ -297,6 +306,14 @@ class Engine:
         B, m = int(wp.shape[0]), int(wp.shape[1]) - 1
         velocity, speeds = self._speeds(velocity, B)
         kw = dict(device=self.device)
+        if boundary is not None:
+            boundary = self._dev(boundary, torch.float64)
+            if tuple(boundary.shape) != (B, 6, 3):
+                raise ValueError(f"boundary must have shape (B, 6, 3) = ({B}, 6, 3), got {tuple(boundary.shape)}")
+            if not bool(torch.isfinite(boundary).all()):
+                raise ValueError("boundary must be finite")
+            if speeds is None:                                   # the chain with boundaries takes its speeds from the device
+                speeds = torch.full((B,), float(velocity), dtype=torch.float64, **kw)
         times = torch.empty((B, m), dtype=torch.float64, **kw)
         seg_rows = torch.empty((B, m), dtype=torch.int32, **kw)
         row_offsets = torch.empty((B + 1,), dtype=torch.int64, **kw)
@@ -308,7 +325,7 @@ class Engine:
                 raise ValueError("dense_yaw, pool and placement_trials are about the rows: not with rows=False")
             first_yaw = torch.empty((B,), dtype=torch.float64, **kw)
             plan = Plan(B, m, float(velocity), float(dt), wp, times, seg_rows, row_offsets, coeffs, status, None, 0, None, first_yaw,
-                        velocities=speeds)
+                        velocities=speeds, boundary=boundary)
             self.replan(plan)
             plan.epoch = 0
             plan.total_rows = int(row_offsets[-1].item())       # (the one host sync; the rows would have needed it to be allocated)
@@ -321,16 +338,22 @@ class Engine:
         else:
             self.ctx.call("uavac_minsnap_row_counts_v_dev", _ptr(wp), B, m, _ptr(speeds), float(dt), _ptr(times),
                           _ptr(seg_rows), _ptr(row_offsets))
-        self.ctx.call("uavac_minsnap_solve_dev", _ptr(wp), _ptr(times), B, m, _ptr(coeffs), _ptr(status))
+        if boundary is None:
+            self.ctx.call("uavac_minsnap_solve_dev", _ptr(wp), _ptr(times), B, m, _ptr(coeffs), _ptr(status))
         total = int(row_offsets[-1].item())                 # the one host sync: sizes the trajectory buffer
         pooled = pool and self._row_pool is not None and self._row_pool.shape[0] >= total
         traj = self._row_pool[:total] if pooled else torch.empty((total, nat.TRAJ_COLS), dtype=torch.float64, **kw)
         yaw = torch.empty((total,), dtype=torch.float64, **kw) if dense_yaw else None
         first_yaw = torch.empty((B,), dtype=torch.float64, **kw)
         plan = Plan(B, m, float(velocity), float(dt), wp, times, seg_rows, row_offsets, coeffs, status, traj, total, yaw, first_yaw,
-                    velocities=speeds)
+                    velocities=speeds, boundary=boundary)
         del traj                                                 # (place_rows may release the first draw: no second reference to it)
-        self.sample(plan)
+        if boundary is None:
+            self.sample(plan)
+        else:                                                    # the whole chain into the buffer just sized (uavac_minsnap_plan_bc_dev)
+            self.replan(plan)
+            plan.epoch = 0
+            plan.total_rows = total
         if int(placement_trials) > 1 and total > 0 and not pooled:
             self.place_rows(plan, int(placement_trials))
         if pool and not pooled:
@@ -419,7 +442,11 @@ class Engine:
             return                                               # (`empty_plan`: nothing to plan)
         self._bind_stream()
         cap = 0 if plan.traj is None else int(plan.traj.shape[0])
-        if getattr(plan, "velocities", None) is None:
+        if getattr(plan, "boundary", None) is not None:          # start / end in motion (read from the device at every replan, like the speeds)
+            self.ctx.call("uavac_minsnap_plan_bc_dev", _ptr(plan.waypoints), plan.B, plan.m, _ptr(plan.velocities), plan.dt,
+                          _ptr(plan.boundary), _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets), _ptr(plan.coeffs),
+                          _ptr(plan.status), _ptr(plan.traj), cap, _ptr(plan.yaw), _ptr(plan.first_yaw))
+        elif getattr(plan, "velocities", None) is None:
             self.ctx.call("uavac_minsnap_plan_dev", _ptr(plan.waypoints), plan.B, plan.m, plan.velocity, plan.dt,
                           _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets), _ptr(plan.coeffs), _ptr(plan.status),
                           _ptr(plan.traj), cap, _ptr(plan.yaw), _ptr(plan.first_yaw))
@@ -508,7 +535,8 @@ class Engine:
         legs at 3 m/s) at dt = 0.01, and larger for a coarser dt.  The default of 1e-3 clears that with room and costs 0.1 % of
         speed; a margin below the gap costs further passes, not correctness (`converged` tells).
         `plan`: a Plan, a RaggedBatch, or a RaggedPlan that has its batch; it is left as it is.  -> RetimeResult whose `.plan` is of
-        the same kind, with fresh buffers: rows-free if the input was, else with rows sampled ONCE at the end.  Missions whose plan
+        the same kind, with fresh buffers: rows-free if the input was, else with rows sampled ONCE at the end.  A plan with boundary
+        derivatives (`plan(..., boundary=...)`) is refused (ValueError): its curve moves when its durations change.  Missions whose plan
         is singular (or has no rows) keep their speed, report a NaN factor and converged = False; the device flags are left to the
         caller (`take_flags`)."""
         torch = self._torch
@@ -519,6 +547,9 @@ class Engine:
             plan = plan.batch
         if plan.waypoints is None:
             raise ValueError("retiming plans again from the waypoints: a plan assembled from gathered parts has none")
+        if getattr(plan, "boundary", None) is not None:
+            raise ValueError("a plan with boundary derivatives cannot be retimed: retiming rests on the curve staying where it is under a "
+                             "change of durations, and a curve with fixed physical end derivatives does not")
         ragged = hasattr(plan, "seg_offsets")
         B = int(plan.B)
         m = int(plan.max_m if ragged else plan.m)
@@ -935,8 +966,12 @@ class Engine:
         else:
             self.ctx.call("uavac_minsnap_row_counts_v_dev", _ptr(plan.waypoints), plan.B, plan.m, _ptr(plan.velocities), plan.dt,
                           _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets))
-        self.ctx.call("uavac_minsnap_solve_dev", _ptr(plan.waypoints), _ptr(plan.times), plan.B, plan.m,
-                      _ptr(plan.coeffs), _ptr(plan.status))
+        if getattr(plan, "boundary", None) is not None:
+            self.ctx.call("uavac_minsnap_solve_bc_dev", _ptr(plan.waypoints), _ptr(plan.times), None, plan.B, plan.m,
+                          _ptr(plan.boundary), _ptr(plan.coeffs), _ptr(plan.status))
+        else:
+            self.ctx.call("uavac_minsnap_solve_dev", _ptr(plan.waypoints), _ptr(plan.times), plan.B, plan.m,
+                          _ptr(plan.coeffs), _ptr(plan.status))
         plan.epoch += 1
 
     def sample(self, plan: Plan):

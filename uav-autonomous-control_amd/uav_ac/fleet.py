@@ -55,30 +55,37 @@ class Fleet:
         # evaluated; from two up, the row-fed kernel's 64 scattered row loads per wave and outer tick share the CU's address
         # path with the store waves' log stream (profiles/r04_tick_stamps_*.jsonl) and reading loses.
         # a Plan (one segment count for the whole batch) or a RaggedBatch (seg_offsets); a RaggedPlan has rows only
-        can = (hasattr(plan, "coeffs") and (hasattr(plan, "m") or hasattr(plan, "seg_offsets")) and
-               (getattr(plan, "first_yaw", None) is not None or getattr(plan, "yaw", None) is not None))
-        rows_free = getattr(plan, "traj", None) is None             # Engine.plan(..., rows=False): nothing to read rows from
-        self.from_plan = (can and (rows_free or plan.B >= self.PLAN_FED_MIN_BATCH)) if from_plan is None else bool(from_plan)
-        if self.from_plan and not can:
-            raise ValueError("this plan has no coefficients / first headings / yaw column to fly from")
-        if rows_free and not self.from_plan:
-            raise ValueError("a rows-free plan can only be flown plan-fed (from_plan=True)")
+        self.from_plan = self._feed(plan, from_plan)
         self.vehicle = vehicle if vehicle is not None else nat.Vehicle.default()
         self.B = plan.B
         self.state = torch.empty((nat.STATE_ROWS, self.B), dtype=torch.float64, device=engine.device)
         self.istate = torch.empty((nat.ISTATE_ROWS, self.B), dtype=torch.int32, device=engine.device)
         self._hover = bool(hover)
-        if positions is not None:
-            self._positions = engine._dev(positions, torch.float64)
-        elif hasattr(plan, "start_positions"):
-            self._positions = plan.start_positions.contiguous()
-        elif getattr(plan, "waypoints", None) is not None:
-            self._positions = plan.waypoints[:, 0, :].contiguous()
-        else:                                    # a plan assembled from gathered parts: c0 of the first spline IS the first waypoint
-            self._positions = plan.coeffs[:, 0, :].contiguous()
+        self._positions = engine._dev(positions, torch.float64) if positions is not None else self._start_positions(plan)
         self._plan_epoch = getattr(plan, "epoch", 0)
         self.score = None                        # [SCORE_ROWS][B] tracking scores, allocated by the first scored rollout
         self.reset()
+
+    @classmethod
+    def _feed(cls, plan, from_plan) -> bool:
+        """Whether a fleet on `plan` is plan-fed (the rule above); raises where the plan cannot be flown the way that was asked for."""
+        can = (hasattr(plan, "coeffs") and (hasattr(plan, "m") or hasattr(plan, "seg_offsets")) and
+               (getattr(plan, "first_yaw", None) is not None or getattr(plan, "yaw", None) is not None))
+        rows_free = getattr(plan, "traj", None) is None             # Engine.plan(..., rows=False): nothing to read rows from
+        fed = (can and (rows_free or plan.B >= cls.PLAN_FED_MIN_BATCH)) if from_plan is None else bool(from_plan)
+        if fed and not can:
+            raise ValueError("this plan has no coefficients / first headings / yaw column to fly from")
+        if rows_free and not fed:
+            raise ValueError("a rows-free plan can only be flown plan-fed (from_plan=True)")
+        return fed
+
+    @staticmethod
+    def _start_positions(plan):
+        if hasattr(plan, "start_positions"):
+            return plan.start_positions.contiguous()
+        if getattr(plan, "waypoints", None) is not None:
+            return plan.waypoints[:, 0, :].contiguous()
+        return plan.coeffs[:, 0, :].contiguous()    # a plan assembled from gathered parts: c0 of the first spline IS the first waypoint
 
     def reset(self):
         """`TrajectoryController.reset` (main.py:29-35) + vehicle back at its first waypoint, at rest."""
@@ -89,6 +96,33 @@ class Fleet:
         self._plan_epoch = getattr(self.plan, "epoch", 0)        # the carried yaw scan starts afresh
         if self.score is not None:
             self.reset_score()
+
+    def boundary(self):
+        """(B, 6, 3) f64 on the device, for `Engine.plan(..., boundary=...)`: row 0 = the vehicles' current world velocity (state rows
+        7-9), every other row zero -- a plan that starts at the speed the fleet flies at and ends at rest.  A fresh tensor: the caller
+        may fill in more (a goal velocity, an acceleration estimate)."""
+        torch = self.engine._torch
+        bc = torch.zeros((self.B, 6, 3), dtype=torch.float64, device=self.engine.device)
+        bc[:, 0, :] = self.state[7:10].t()
+        return bc
+
+    def follow(self, plan, from_plan=None):
+        """THE HANDOVER: the flying fleet takes a new plan and starts it at its row 0 with the next tick.  The vehicles keep what they
+        are -- state rows 0-25 (pose, rates, rotors, altitude integral, commands) and the sticky `collided` flag; cursor and inner step
+        (istate rows 0, 1) go to 0, so the next tick is an outer tick on the new plan's row 0, and the carried yaw scan is invalidated
+        (state row 26 = -1: the kernel rebuilds it from the new plan).  `from_plan` as in the constructor (None: its rule).  The
+        tracking scores belong to the plan they were accumulated on: they start afresh.  `reset()` afterwards goes to the NEW plan's
+        first waypoints.  Torch operations only, stream-ordered, no sync.  Typically `plan` starts where the vehicles are, at the speed
+        they have: waypoints from `fleet.X[0:3]`, `boundary=fleet.boundary()`."""
+        if plan.B != self.B:
+            raise ValueError(f"the fleet has {self.B} vehicles, the plan {plan.B} missions")
+        self.from_plan = self._feed(plan, from_plan)
+        self.plan = plan
+        self._positions = self._start_positions(plan)
+        self._plan_epoch = getattr(plan, "epoch", 0)
+        self.istate[0:2].zero_()
+        self.state[26].fill_(-1.0)
+        self.reset_score()
 
     def reset_score(self):
         """Tracking scores back to a fresh start (all zeros): the next scored rollout scores the missions from their cursor on."""
