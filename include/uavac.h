@@ -168,6 +168,8 @@ int uavac_clock_probe_dev(uavac_ctx *ctx, int window_us, int64_t *stamps);
  * chunk-streaming sampler, "sampler_group": 1 (default) .. 64 = consecutive missions per workgroup;
  * "sampler_waves" 1 = the one-wave-per-mission sampler (same rows bit for bit; faster into some row
  * buffers, slower into most: DESIGN K2).  "audit_lanes": 16 (default) or 64 = lanes per mission of uavac_minsnap_audit_dev.
+ * "timeopt_chunk": 0 (default: sized from UAVAC_TIMEOPT_SCRATCH_BYTES) or the missions per chunk of uavac_minsnap_optimize_times_dev
+ * (same results).
  * Defaults from the environment (UAVAC_ROLLOUT_ALIGN, UAVAC_YAW_GROUP, UAVAC_SAMPLER_WAVES, UAVAC_SAMPLER_GROUP) at uavac_create.
  * ONE option is not a tuning knob but part of the log layout: "log_pitch" = P doubles per log row,
  * 0 (default) = B.  With P >= B the rollouts write state_log [K][13][P] and cmd_log [K][12][P]
@@ -384,6 +386,69 @@ int uavac_minsnap_retime_dev(uavac_ctx *ctx, const double *wp, const int64_t *se
                              double dt, const double limits[4], double margin, int max_passes, double *times,
                              int32_t *seg_rows, int64_t *row_offsets, double *coeffs, int32_t *status, double *first_yaw,
                              double *audit, double *factors_total, int32_t *converged, int *passes);
+
+/* PLANS FROM GIVEN DURATIONS, THE SNAP COST, AND OPTIMISED SEGMENT TIMES (csrc/minsnap_timeopt.hip).  Every chain above takes its
+ * durations from upstream's rule T_s = |leg_s| / velocity [* 1.5 on the first and last leg] (minimum_snap.py:311-321); these four take
+ * them as they are given, measure a plan, and divide a mission's total time between its legs so that the snap cost falls -- the second
+ * half of the minimum-snap method (Mellinger & Kumar 2011).  Rest to rest only (no bc).  Throughout, seg_offsets == NULL: a uniform
+ * batch (wp [B][m+1][3], times [B][m], coeffs [B][8m][3]); otherwise the ragged layout of uavac_minsnap_solve_ragged_dev with m = the
+ * largest segment count.  Mission b of a ragged call equals a uniform call on it alone, and any split of a batch the whole, bit for bit.
+ *
+ * uavac_minsnap_row_counts_t_dev: seg_rows = ceil(T / dt) in fp64 -- the single IEEE division and ceil of uavac_minsnap_row_counts_dev,
+ * so seg_rows == len(np.arange(0, T, dt)) -- and row_offsets [B+1] by the same scan.  A duration that is not positive and finite
+ * raises sticky flag 0 and leaves its MISSION without rows (what a bad per-mission speed does); the other missions are unaffected.
+ *
+ * uavac_minsnap_plan_t_dev: the planning chain of uavac_minsnap_plan_v_dev with `times` an INPUT (never written) -- both forms: rows
+ * with a capacity, flag 2 and the all-or-nothing commit (a refused plan keeps seg_rows, row_offsets, coeffs, rows and first_yaw), and
+ * rows-free with traj == NULL.  Same kernels downstream of the durations: given the durations of a velocity chain it reproduces that
+ * chain bit for bit.  A ragged batch has no dense yaw column (yaw must be NULL), like uavac_minsnap_sample_ragged_dev.
+ *
+ * uavac_minsnap_cost_dev: cost [B] f64, J_b = sum over the mission's segments and the three axes of the integral of snap^2 over
+ * [0, T_s] -- upstream's c^T H c (_create_snap_cost_matrix, no 1/2).  ROUNDING (part of the contract): not computed from H, whose
+ * T^(r+c-7) terms of both signs cancel, but by the four-point Gauss-Legendre rule, exact for the degree-6 integrand and a sum of
+ * non-negative terms: half = 0.5 T; nodes x = -0.8611363115940526, -0.3399810435848563, +0.3399810435848563, +0.8611363115940526 in
+ * that order with weights w = 0.3478548451374538, 0.6521451548625461, 0.6521451548625461, 0.3478548451374538; t = half + half * x;
+ * snap per axis by Horner on (840 c7, 360 c6, 120 c5, 24 c4); q = (sx sx + sy sy) + sz sz; seg += (half * w) * q.  Nothing is
+ * contracted.  Sixteen lanes per mission: lane l adds its segments l, l + 16, ... in that order, the sixteen sums meet in a fixed xor
+ * tree (distances 8, 4, 2, 1) -- the result depends neither on the launch shape nor on the batch split.  A non-finite coefficient or
+ * duration anywhere in a mission gives NaN for that mission alone.
+ *
+ * uavac_minsnap_optimize_times_dev: times [.] in/out, cost_before / cost_after [B] f64, accepted [B] i32; every pointer a DEVICE
+ * pointer.  NO HOST SYNCHRONISATION: the iteration count is fixed, a mission with nothing left to gain idles, the whole loop is
+ * enqueued on the ctx stream (the ctx's scratch grows on the first call of a size, as everywhere).  Per mission with m >= 2 segments:
+ * T = the durations, total = sum(T0) in index order, J = cost(solve(T)), alpha = UAVAC_TIMEOPT_ALPHA0.  A mission with one segment,
+ * with a first cost that is not finite or with a duration that is not positive and finite is returned bit for bit, accepted = 0.
+ * Each of `iterations` iterations:
+ *   probes      h = UAVAC_TIMEOPT_PROBE_STEP * total / m; for i = 0 .. m-1: g_i = +1 at i, -1 / (m - 1) elsewhere,
+ *               d_i = (J(T + h g_i) - J) / h
+ *   direction   G_k = d_k - (sum_{i != k} d_i) / (m - 1), D = -G; max|D| zero or a d_i not finite: the mission sits this iteration
+ *               out, unchanged; otherwise D is scaled so that max|D| = min(T)
+ *   candidates  j = 0 .. UAVAC_TIMEOPT_CANDIDATES-1: a_j = alpha 2^-j, Tc = T + a_j D; dropped when min(Tc) <
+ *               UAVAC_TIMEOPT_FLOOR * min(T0), else Tc *= total / sum(Tc), solved and costed
+ *   selection   the candidate with the smallest cost STRICTLY below J (the lowest j on a tie; a NaN is never accepted) becomes T and
+ *               J, accepted += 1, alpha = min(UAVAC_TIMEOPT_ALPHA_MAX, 2 a_j); none: alpha *= 2^-UAVAC_TIMEOPT_CANDIDATES
+ * So cost_after <= cost_before, sum(T) is kept (to rounding) and min(T) >= UAVAC_TIMEOPT_FLOOR * min(T0).  cost_after is bit for bit
+ * uavac_minsnap_cost_dev of uavac_minsnap_solve_dev at the returned durations.  The m probes of all missions go through the solve as
+ * ONE batch, the candidates as a second; the batch is walked in chunks of missions sized from UAVAC_TIMEOPT_SCRATCH_BYTES of scratch
+ * (option "timeopt_chunk": missions per chunk, 0 = automatic; a tuning knob, same results).  The promise is a lower snap cost, not
+ * feasibility: audit the new plan (and against the cuboids again -- the curve passes the same waypoints, not the same points between).
+ * UAVAC_EINVAL before anything is enqueued: iterations < 0, B < 1, m outside 1 .. UAVAC_MAX_SEGMENTS, a NULL pointer (seg_offsets,
+ * status, traj, yaw and first_yaw may be NULL), dt not positive and finite. */
+#define UAVAC_TIMEOPT_PROBE_STEP 1.0e-6
+#define UAVAC_TIMEOPT_CANDIDATES 6
+#define UAVAC_TIMEOPT_ALPHA0 0.25
+#define UAVAC_TIMEOPT_ALPHA_MAX 0.5
+#define UAVAC_TIMEOPT_FLOOR 0.2
+#define UAVAC_TIMEOPT_SCRATCH_BYTES (256ull << 20)
+int uavac_minsnap_row_counts_t_dev(uavac_ctx *ctx, const double *times, const int64_t *seg_offsets, int B, int m, double dt,
+                                   int32_t *seg_rows, int64_t *row_offsets);
+int uavac_minsnap_plan_t_dev(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B, int m, const double *times,
+                             double dt, int32_t *seg_rows, int64_t *row_offsets, double *coeffs, int32_t *status, double *traj,
+                             int64_t traj_capacity_rows, double *yaw, double *first_yaw);
+int uavac_minsnap_cost_dev(uavac_ctx *ctx, const double *coeffs, const double *times, const int64_t *seg_offsets, int B, int m,
+                           double *cost);
+int uavac_minsnap_optimize_times_dev(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B, int m, double *times,
+                                     int iterations, double *cost_before, double *cost_after, int32_t *accepted);
 
 /* row_offsets [B+1] from per-segment row counts that exist already -- the second half of
  * uavac_minsnap_row_counts_dev on its own, for a plan whose seg_rows [B][m] came from elsewhere (the

@@ -224,6 +224,20 @@ int launch_counts(uavac_ctx *ctx, const double *wp, int B, int m, const double *
     return uavac_launch_row_counts_v(ctx, wp, B, m, velocities, dt, times, seg_rows, row_offsets, seg_offsets);
 }
 
+// ctx->d_plan holds at least `need` bytes: where a chain with a row capacity keeps what it computes before it is committed
+int ensure_plan_scratch(uavac_ctx *ctx, size_t need) {
+    if (need <= ctx->plan_cap) return UAVAC_OK;
+    UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));          // nothing enqueued may still use the old block
+    if (ctx->d_plan) UAVAC_HIP(ctx, hipFree(ctx->d_plan));
+    ctx->d_plan = nullptr;
+    ctx->plan_cap = 0;
+    void *p = nullptr;
+    UAVAC_HIP(ctx, hipMalloc(&p, need));
+    ctx->d_plan = static_cast<char *>(p);
+    ctx->plan_cap = need;
+    return UAVAC_OK;
+}
+
 // The planning chain behind uavac_minsnap_plan_dev (Vel = double), uavac_minsnap_plan_v_dev (Vel = const double *) and
 // uavac_minsnap_plan_bc_dev (the latter with bc != NULL: the solve with boundary derivatives in the solve's place); the
 // arguments have been validated.
@@ -252,16 +266,7 @@ int plan_chain(uavac_ctx *ctx, const double *wp, int B, int m, Vel velocity, dou
     const size_t nseg = (size_t)B * m;
     const size_t o_rows = uavac_arena_size(nseg * 8), o_offs = o_rows + uavac_arena_size(nseg * 4);
     const size_t need = o_offs + uavac_arena_size(((size_t)B + 1) * 8);
-    if (need > ctx->plan_cap) {
-        UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));          // nothing enqueued may still use the old block
-        if (ctx->d_plan) UAVAC_HIP(ctx, hipFree(ctx->d_plan));
-        ctx->d_plan = nullptr;
-        ctx->plan_cap = 0;
-        void *p = nullptr;
-        UAVAC_HIP(ctx, hipMalloc(&p, need));
-        ctx->d_plan = static_cast<char *>(p);
-        ctx->plan_cap = need;
-    }
+    if (int rc = ensure_plan_scratch(ctx, need)) return rc;
     double *times_s = reinterpret_cast<double *>(ctx->d_plan);
     int32_t *seg_rows_s = reinterpret_cast<int32_t *>(ctx->d_plan + o_rows);
     int64_t *row_offsets_s = reinterpret_cast<int64_t *>(ctx->d_plan + o_offs);
@@ -390,6 +395,9 @@ int uavac_set_option(uavac_ctx *ctx, const char *name, int value) {
     } else if (n == "audit_lanes") {
         if (value != 16 && value != 64) return uavac_fail(ctx, UAVAC_EINVAL, "audit_lanes is 16 or 64");
         ctx->audit_lanes = value;
+    } else if (n == "timeopt_chunk") {
+        if (value < 0) return uavac_fail(ctx, UAVAC_EINVAL, "timeopt_chunk is 0 (automatic) or a number of missions");
+        ctx->timeopt_chunk = value;
     } else if (n == "sampler_waves") {
         if (value != 1 && value != 2 && value != 4 && value != 8 && value != 16) return uavac_fail(ctx, UAVAC_EINVAL, "sampler_waves is 1, 2, 4, 8 or 16");
         ctx->sampler_waves = value;
@@ -744,6 +752,68 @@ int uavac_minsnap_retime_dev(uavac_ctx *ctx, const double *wp, const int64_t *se
         *passes = retimed + 1;
     }
     return UAVAC_OK;
+}
+
+// ---------------------------------------------------------------- given durations, the snap cost, optimised durations
+int uavac_minsnap_row_counts_t_dev(uavac_ctx *ctx, const double *times, const int64_t *seg_offsets, int B, int m, double dt,
+                                   int32_t *seg_rows, int64_t *row_offsets) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, times, B, m)) return rc;
+    if (!seg_rows || !row_offsets) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_dt(ctx, dt)) return rc;
+    return uavac_launch_row_counts_t(ctx, times, seg_offsets, B, m, dt, seg_rows, row_offsets);
+}
+
+int uavac_minsnap_plan_t_dev(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B, int m, const double *times, double dt,
+                             int32_t *seg_rows, int64_t *row_offsets, double *coeffs, int32_t *status, double *traj,
+                             int64_t traj_capacity_rows, double *yaw, double *first_yaw) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
+    if (!times || !seg_rows || !row_offsets || !coeffs) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_dt(ctx, dt)) return rc;
+    if (yaw && (!traj || seg_offsets)) return uavac_fail(ctx, UAVAC_EINVAL, "a dense yaw column needs the rows of a uniform batch");
+    if (!traj) {
+        // rows-free, as in plan_chain: nothing to refuse, the counts go straight into the caller's arrays
+        if (int rc = uavac_launch_row_counts_t(ctx, times, seg_offsets, B, m, dt, seg_rows, row_offsets)) return rc;
+        if (int rc = uavac_launch_coeff_solve(ctx, wp, times, B, m, coeffs, status, seg_offsets)) return rc;
+        return first_yaw ? uavac_launch_first_yaw(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, first_yaw) : UAVAC_OK;
+    }
+    if (traj_capacity_rows < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative capacity");
+    // With a row capacity, as in plan_chain: counts and offsets to ctx scratch, every later stage reads row_offsets_s[B] on the device
+    // and does nothing when the plan does not fit (the sampler raises flag 2).  A ragged batch has at most B * m segments.
+    const size_t nseg = (size_t)B * m;
+    const size_t o_offs = uavac_arena_size(nseg * 4);
+    if (int rc = ensure_plan_scratch(ctx, o_offs + uavac_arena_size(((size_t)B + 1) * 8))) return rc;
+    int32_t *seg_rows_s = reinterpret_cast<int32_t *>(ctx->d_plan);
+    int64_t *row_offsets_s = reinterpret_cast<int64_t *>(ctx->d_plan + o_offs);
+    if (int rc = uavac_launch_row_counts_t(ctx, times, seg_offsets, B, m, dt, seg_rows_s, row_offsets_s)) return rc;
+    if (int rc = uavac_launch_plan_t_commit(ctx, seg_rows_s, row_offsets_s, seg_offsets, B, m, traj_capacity_rows, seg_rows, row_offsets))
+        return rc;
+    if (int rc = uavac_launch_coeff_solve(ctx, wp, times, B, m, coeffs, status, seg_offsets, row_offsets_s + B, traj_capacity_rows)) return rc;
+    SampleExtras x;
+    x.yaw_dense = yaw;
+    x.first_yaw = first_yaw;
+    x.capacity_rows = traj_capacity_rows;
+    x.seg_offsets = seg_offsets;
+    if (seg_offsets) x.total_segments = (int64_t)nseg;        // (sizes the hit flags only, and there are none)
+    return uavac_launch_sample(ctx, coeffs, seg_rows_s, row_offsets_s, B, m, dt, traj, x);
+}
+
+int uavac_minsnap_cost_dev(uavac_ctx *ctx, const double *coeffs, const double *times, const int64_t *seg_offsets, int B, int m,
+                           double *cost) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
+    if (!times || !cost) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    return uavac_launch_cost(ctx, coeffs, times, seg_offsets, B, m, cost);
+}
+
+int uavac_minsnap_optimize_times_dev(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B, int m, double *times,
+                                     int iterations, double *cost_before, double *cost_after, int32_t *accepted) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
+    if (!times || !cost_before || !cost_after || !accepted) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (iterations < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative iterations");
+    return uavac_launch_optimize_times(ctx, wp, seg_offsets, B, m, times, iterations, cost_before, cost_after, accepted);
 }
 
 int uavac_minsnap_first_yaw_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B,

@@ -34,7 +34,8 @@ struct uavac_ctx {
     int sampler_group = 1;           // tuning: consecutive missions per workgroup of the streaming sampler
     int yaw_group = 8;               // tuning: chunks of the sampler's dense yaw column that leave together (1, 4, 8, 16)
     int audit_lanes = 16;            // tuning: lanes of a wavefront that walk one mission in the plan audit: 16 or 64 (minsnap_audit.hip; same results)
-    int rollout_align = 1;           // tuning: launch the 2-wave aligner kernel before a logged launch of shape 1
+    int timeopt_chunk = 0;           // tuning: missions per chunk of the duration optimisation (minsnap_timeopt.hip; same results); 0 = sized from UAVAC_TIMEOPT_SCRATCH_BYTES
+    int rollout_align = 1;          // tuning: launch the 2-wave aligner kernel before a logged launch of shape 1
     int late_handover = -1;          // tuning: -1 = the launcher picks per launch; 0 / 1 = slab handed over at the end of the tick / a third of a tick later
     int coeff_dma = -1;              // tuning: -1 = the launcher picks per launch; 0 / 1 / 2 = the plan-fed rollout's PMODE (control_rollout.hip)
     int solve_order = 1;             // which elimination order solves: 1 = two-ended, two lanes per mission (minsnap_solve_tw.hip; the default), 0 = one-ended (minsnap_solve_bt.hip: other rounding, kept as the cross-check)
@@ -231,6 +232,20 @@ struct RetimeLimits {
 };
 int uavac_launch_retime_factors(uavac_ctx *ctx, const double *audit, int B, const RetimeLimits &limits, double margin, int apply,
                                 double *velocities, double *factors, int32_t *counters, double *factors_total, int32_t *converged);
+// Plans from given durations, the snap cost and the optimisation of the durations (minsnap_timeopt.hip); seg_offsets as above.
+// seg_rows = ceil(times / dt) and row_offsets [B+1]; a duration that is not positive and finite raises flag 0 and leaves its mission
+// without rows
+int uavac_launch_row_counts_t(uavac_ctx *ctx, const double *times, const int64_t *seg_offsets, int B, int m, double dt,
+                              int32_t *seg_rows, int64_t *row_offsets);
+// seg_rows / row_offsets from scratch into the caller's arrays unless row_offsets_s[B] > capacity_rows (uavac_launch_plan_commit
+// without the durations, which are an input there)
+int uavac_launch_plan_t_commit(uavac_ctx *ctx, const int32_t *seg_rows_s, const int64_t *row_offsets_s, const int64_t *seg_offsets, int B,
+                               int m, int64_t capacity_rows, int32_t *seg_rows, int64_t *row_offsets);
+// cost [B] = integral of snap^2 over every mission
+int uavac_launch_cost(uavac_ctx *ctx, const double *coeffs, const double *times, const int64_t *seg_offsets, int B, int m, double *cost);
+// the whole optimisation loop, enqueued: times [.] in/out, cost_before / cost_after [B], accepted [B]
+int uavac_launch_optimize_times(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B, int m, double *times, int iterations,
+                                double *cost_before, double *cost_after, int32_t *accepted);
 // out [n] = value (minsnap_retime.hip)
 int uavac_launch_fill_f64(uavac_ctx *ctx, double *out, size_t n, double value);
 int uavac_launch_state_init(uavac_ctx *ctx, const VehK &V, const double *positions, int B, int hover, double *state,

@@ -98,6 +98,28 @@ def check_planning_registers():
     return s + k + a + kb
 
 
+TIMEOPT_KERNELS = ("row_counts_t_kernel", "plan_t_commit_kernel", "minsnap_cost_kernel", "timeopt_expand_kernel", "timeopt_init_kernel",
+                   "timeopt_probe_kernel", "timeopt_direction_kernel", "timeopt_candidate_kernel", "timeopt_select_kernel")
+
+
+def check_timeopt_kernels():
+    """The kernels of csrc/minsnap_timeopt.hip (plans from given durations, the snap cost, the bookkeeping of the duration
+    optimisation): every one must be there, none may spill or use scratch memory at all (zero private-segment bytes: their loops over
+    a mission's segments keep no per-segment arrays), and all run at least four waves per SIMD (<= 128 vector registers; built: the
+    cost kernel 64, the others 10 .. 40).  Returns {kernel: VGPRs} (the two row-count variants under their mangled names), None when
+    the counts cannot be read."""
+    obj = os.path.join(PKG, "build", "minsnap_timeopt.o")
+    regs, priv = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel")
+    if regs is None or priv is None:
+        return None
+    bad = [(n[:70], v, sp, 128) for n, v, sp in regs if v > 128 or sp] + [(n[:70], f"{p} private-segment bytes", 0, 0) for n, p in priv if p]
+    missing = [k for k in TIMEOPT_KERNELS if not any(k in n for n, _, _ in regs)]
+    if bad or missing or len(regs) != len(TIMEOPT_KERNELS) + 1 or len(priv) != len(regs):
+        raise RuntimeError(f"time-optimisation kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
+                           f"{len(regs)} kernels found (compiler: {compiler_version()})")
+    return {n: v for n, v, _ in regs}
+
+
 def check_rollout_registers(obj: str = None):
     """Raise RuntimeError when a rollout variant needs more than 256 vector registers or spills any; returns the counts."""
     counts = rollout_register_counts(obj)
@@ -337,13 +359,15 @@ def run_all(verbose: bool = False, write_stamp: bool = True) -> dict:
               lambda r: f"row prefetch of {r} row-fed scored rollout kernels verified the same way"),
              ("heading_prefetch", check_heading_prefetch, lambda r: f"{r} coefficient prefetches of the streaming sampler verified in the disassembly"),
              ("no_diagnostics", check_no_diagnostics, lambda r: "no diagnostic symbol exported"),
-             ("planning_registers", check_planning_registers, lambda r: f"{len(r)} sampler / solve kernels inside their register budgets, no spills"))
+             ("planning_registers", check_planning_registers, lambda r: f"{len(r)} sampler / solve kernels inside their register budgets, no spills"),
+             ("timeopt_kernels", check_timeopt_kernels,
+              lambda r: f"{len(r)} time-optimisation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"))
     for key, fn, say in steps:
         r = fn()
         if r is None:
             raise RuntimeError(f"build check '{key}' could not run (object files under {PKG}/build or the LLVM tools under {LLVM_BIN} are "
                                "missing): the library would ship unchecked")
-        result[key] = len(r) if isinstance(r, list) else r
+        result[key] = len(r) if isinstance(r, list) else r      # (the time-optimisation check: its {kernel: VGPRs} record)
         if verbose:
             print(f"build: {say(r)}")
     lib_path = os.path.join(PKG, "lib", "libuavac.so")

@@ -96,6 +96,10 @@ _SIGNATURES = {
     "uavac_minsnap_plan_bc_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
     "uavac_minsnap_retime_factors_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_double, _P, _P, _P]),
     "uavac_minsnap_retime_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_double, _P, C.c_double, C.c_int] + [_P] * 10),
+    "uavac_minsnap_row_counts_t_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P]),
+    "uavac_minsnap_plan_t_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
+    "uavac_minsnap_cost_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "uavac_minsnap_optimize_times_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
     "uavac_minsnap_row_offsets_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "uavac_minsnap_row_offsets_ragged_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     "uavac_minsnap_plan_ragged": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_double, _P, _P, _P, _P, C.c_int64]),

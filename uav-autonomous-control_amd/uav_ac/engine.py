@@ -52,6 +52,8 @@ class Plan:
     boundary: "object" = None        # (B, 6, 3) f64, device: (v, a, j) at the first waypoint (rows 0-2) and at the last (rows 3-5); None =
                                      # rest to rest.  Read again at every replan / solve.  Such a plan always has `velocities` (a scalar
                                      # `velocity` is kept and broadcast)
+    free_times: bool = False         # the durations were GIVEN (`Engine.plan(..., times=...)`, `Engine.optimize_times`), not derived from a
+                                     # speed: `velocity` is NaN, `velocities` None; replan / solve re-run the chain from `times` as they stand
 
     def mission(self, b: int) -> np.ndarray:
         """Rows of mission b as a fresh host array (N_b, 11) -- the reference's `full_trajectory`."""
@@ -134,6 +136,7 @@ class RaggedBatch:
     first_yaw: "object"              # (B,) f64
     hit: "object" = None             # (S,) i32 when a cuboid was given
     velocities: "object" = None      # (B,) f64, device: one cruise speed per mission (`velocity` is then NaN); None = the one `velocity`
+    free_times: bool = False         # the durations were given (`Engine.plan_ragged(..., times=...)`, `Engine.optimize_times`): see Plan
 
     def mission(self, b: int) -> np.ndarray:
         if self.traj is None:
@@ -183,6 +186,16 @@ class RetimeResult:
     passes: int              # retimings done (0: every mission was inside the limits, or max_passes = 0)
     converged: "object"      # (B,) bool: the mission's last audit asked for no retiming
     audit: PlanAudit         # the audit of `plan` (no cuboids)
+
+
+@dataclass
+class TimeOptResult:
+    """What `Engine.optimize_times` returns."""
+    plan: "object"           # a NEW free_times plan of the kind that was given (Plan / RaggedBatch) on the same waypoints, planned from the
+                             # optimised durations
+    cost_before: "object"    # (B,) f64, device: snap cost of the input's durations
+    cost_after: "object"     # (B,) f64: snap cost of `plan` (== Engine.cost(plan), bit for bit); <= cost_before
+    accepted: "object"       # (B,) i32: steps the mission took (0: its durations are the input's, bit for bit)
 
 
 @dataclass
@@ -268,7 +281,7 @@ class Engine:
 
     # -- planning ---------------------------------------------------------------
     def plan(self, waypoints, velocity=1.0, dt: float = 0.01, strict: bool = True, dense_yaw: bool = False,
-             placement_trials: int = 1, pool: bool = False, rows: bool = True, boundary=None) -> Plan:
+             placement_trials: int = 1, pool: bool = False, rows: bool = True, boundary=None, times=None) -> Plan:
         """Batched `MinimumSnap(path, None, velocity, dt).get_trajectory()` (minimum_snap.py:59-61,97-124).
         `strict`: raise UavacError(ESINGULAR) when a mission's knot system is singular (a repeated waypoint) instead of
         returning NaN coefficients for it; with strict=False inspect `plan.status`.
@@ -296,6 +309,12 @@ class Engine:
         constraints.  Durations, row counts and offsets do not depend on it; row 0 of a mission then carries velocity v0.  The plan
         keeps the tensor (`plan.boundary`, read again at every `replan` / `solve`: change it in place to replan from another state)
         and cannot be retimed (`retime` raises).
+        `times`: a (B, m) array or tensor of segment durations to plan from AS GIVEN (`uavac_minsnap_plan_t_dev`) instead of
+        upstream's |leg| / velocity rule -- rest to rest only: not with `boundary`, nor with a `velocity` other than the default.
+        The plan is `free_times`: `velocity` is NaN, `replan` / `solve` re-run the chain from `plan.times` as they stand (change them
+        in place and replan), `retime` raises.  Given the durations of a velocity plan it reproduces that plan bit for bit.  A
+        duration that is not positive and finite is a ValueError under `strict`; without it the duration raises device flag 0
+        (`take_flags`) and leaves its mission without rows.
         """
         torch = self._torch
         wp = self._dev(waypoints, torch.float64)
@@ -304,6 +323,14 @@ class Engine:
         if not bool(torch.isfinite(wp).all()):
             raise ValueError("waypoints must be finite")
         B, m = int(wp.shape[0]), int(wp.shape[1]) - 1
+        if times is not None:
+            self._refuse_with_times(velocity, boundary)
+            if pool or int(placement_trials) > 1:
+                raise ValueError("pool and placement_trials are not offered with times=")
+            tm = self._dev(times, torch.float64)
+            if tuple(tm.shape) != (B, m):
+                raise ValueError(f"times must have shape (B, m) = ({B}, {m}), got {tuple(tm.shape)}")
+            return self._plan_from_times(wp, tm.clone(), dt, rows, strict, dense_yaw=dense_yaw)
         velocity, speeds = self._speeds(velocity, B)
         kw = dict(device=self.device)
         if boundary is not None:
@@ -359,6 +386,52 @@ class Engine:
         if pool and not pooled:
             self._row_pool = plan.traj                           # (a larger pooled plan later replaces it)
         plan.pooled = bool(pool)
+        if strict:
+            self.check(plan)
+        return plan
+
+    @staticmethod
+    def _refuse_with_times(velocity, boundary):
+        if boundary is not None:
+            raise ValueError("times= plans rest to rest: not with boundary=")
+        if not (isinstance(velocity, (int, float, np.floating, np.integer)) and float(velocity) == 1.0):
+            raise ValueError("times= gives the durations themselves: not with a velocity")
+
+    def _plan_from_times(self, wp, times, dt: float, rows: bool, strict: bool, dense_yaw: bool = False, so=None, so_host=None,
+                         max_m: int = 0):
+        """The free_times plan of waypoints `wp` at durations `times` (device tensors; `times` becomes the plan's own): a Plan, or with
+        seg_offsets `so` / `so_host` a RaggedBatch of at most `max_m` segments per mission.  Rows-free: one call of
+        `uavac_minsnap_plan_t_dev`; with rows: the row counts first, to size the row buffer (the one host sync), then the chain."""
+        torch = self._torch
+        kw = dict(device=self.device)
+        ragged = so is not None
+        B = int(len(so_host) - 1 if ragged else wp.shape[0])
+        m = int(max_m if ragged else wp.shape[1] - 1)
+        seg_rows = torch.empty(times.shape, dtype=torch.int32, **kw)
+        row_offsets = torch.empty((B + 1,), dtype=torch.int64, **kw)
+        coeffs = torch.empty((times.numel(), 8, 3) if ragged else (B, 8 * m, 3), dtype=torch.float64, **kw)
+        status = torch.zeros((B,), dtype=torch.int32, **kw)
+        first_yaw = torch.empty((B,), dtype=torch.float64, **kw)
+        traj = yaw = None
+        self._bind_stream()
+        if strict and not bool(((times > 0) & torch.isfinite(times)).all()):      # (without strict: device flag 0, no rows)
+            raise ValueError("times must be positive and finite")
+        if rows:
+            self.ctx.call("uavac_minsnap_row_counts_t_dev", _ptr(times), _ptr(so), B, m, float(dt), _ptr(seg_rows), _ptr(row_offsets))
+            total = int(row_offsets[-1].item())
+            traj = torch.empty((total, nat.TRAJ_COLS), dtype=torch.float64, **kw)
+            yaw = torch.empty((total,), dtype=torch.float64, **kw) if dense_yaw else None
+        elif dense_yaw:
+            raise ValueError("dense_yaw is about the rows: not with rows=False")
+        self.ctx.call("uavac_minsnap_plan_t_dev", _ptr(wp), _ptr(so), B, m, _ptr(times), float(dt), _ptr(seg_rows), _ptr(row_offsets),
+                      _ptr(coeffs), _ptr(status), _ptr(traj), 0 if traj is None else int(traj.shape[0]), _ptr(yaw), _ptr(first_yaw))
+        total = int(row_offsets[-1].item())
+        if ragged:
+            plan = RaggedBatch(B, m, float("nan"), float(dt), so, so_host, wp, times, seg_rows, row_offsets, coeffs, status, traj, total,
+                               first_yaw, None, None, True)
+        else:
+            plan = Plan(B, m, float("nan"), float(dt), wp, times, seg_rows, row_offsets, coeffs, status, traj, total, yaw, first_yaw,
+                        free_times=True)
         if strict:
             self.check(plan)
         return plan
@@ -436,13 +509,18 @@ class Engine:
         the four launches.  The buffers keep their size: a plan that would need more rows than `plan.traj` holds is
         refused on the device AS A WHOLE (flag 2, see `take_flags`): every array of the plan keeps what it held, so the
         previous plan stays consistent and flyable.  A rows-free plan (`plan.traj` is None) runs the rows-free chain: times + row
-        counts, offsets, solve, first headings -- nothing to refuse.  Either way `plan.total_rows` is re-read from the device by
+        counts, offsets, solve, first headings -- nothing to refuse.  A `free_times` plan runs the chain from `plan.times` as they
+        stand (`uavac_minsnap_plan_t_dev`): change the durations in place, then replan.  Either way `plan.total_rows` is re-read from the device by
         whoever reads it next: the new waypoints may need more rows (rows-free) or fewer (rows that fit) than the old ones."""
         if plan.B == 0:
             return                                               # (`empty_plan`: nothing to plan)
         self._bind_stream()
         cap = 0 if plan.traj is None else int(plan.traj.shape[0])
-        if getattr(plan, "boundary", None) is not None:          # start / end in motion (read from the device at every replan, like the speeds)
+        if getattr(plan, "free_times", False):                   # given durations: the chain from plan.times as they stand, never from a speed
+            self.ctx.call("uavac_minsnap_plan_t_dev", _ptr(plan.waypoints), None, plan.B, plan.m, _ptr(plan.times), plan.dt,
+                          _ptr(plan.seg_rows), _ptr(plan.row_offsets), _ptr(plan.coeffs), _ptr(plan.status), _ptr(plan.traj), cap,
+                          _ptr(plan.yaw), _ptr(plan.first_yaw))
+        elif getattr(plan, "boundary", None) is not None:        # start / end in motion (read from the device at every replan, like the speeds)
             self.ctx.call("uavac_minsnap_plan_bc_dev", _ptr(plan.waypoints), plan.B, plan.m, _ptr(plan.velocities), plan.dt,
                           _ptr(plan.boundary), _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets), _ptr(plan.coeffs),
                           _ptr(plan.status), _ptr(plan.traj), cap, _ptr(plan.yaw), _ptr(plan.first_yaw))
@@ -536,7 +614,8 @@ class Engine:
         speed; a margin below the gap costs further passes, not correctness (`converged` tells).
         `plan`: a Plan, a RaggedBatch, or a RaggedPlan that has its batch; it is left as it is.  -> RetimeResult whose `.plan` is of
         the same kind, with fresh buffers: rows-free if the input was, else with rows sampled ONCE at the end.  A plan with boundary
-        derivatives (`plan(..., boundary=...)`) is refused (ValueError): its curve moves when its durations change.  Missions whose plan
+        derivatives (`plan(..., boundary=...)`) is refused (ValueError): its curve moves when its durations change; so is a `free_times`
+        plan, whose durations did not come from a speed.  Missions whose plan
         is singular (or has no rows) keep their speed, report a NaN factor and converged = False; the device flags are left to the
         caller (`take_flags`)."""
         torch = self._torch
@@ -550,6 +629,9 @@ class Engine:
         if getattr(plan, "boundary", None) is not None:
             raise ValueError("a plan with boundary derivatives cannot be retimed: retiming rests on the curve staying where it is under a "
                              "change of durations, and a curve with fixed physical end derivatives does not")
+        if getattr(plan, "free_times", False):
+            raise ValueError("a plan from given durations cannot be retimed: retiming recomputes the durations from cruise speeds, "
+                             "which would discard the given ones")
         ragged = hasattr(plan, "seg_offsets")
         B = int(plan.B)
         m = int(plan.max_m if ragged else plan.m)
@@ -584,6 +666,68 @@ class Engine:
                              wrapper.start_positions, wrapper.converged, out)
         empty = torch.empty((0, B), dtype=torch.int32, **kw)
         return RetimeResult(out, speeds, factors, int(passes.value), converged != 0, PlanAudit(*block.unbind(0), empty, empty, block))
+
+    def cost(self, plan):
+        """The snap cost of every mission of a Plan / RaggedBatch (or a RaggedPlan that has its batch) -> (B,) f64 on the device: the
+        sum over segments and axes of the integral of snap^2 over the segment, upstream's c^T H c (`uavac_minsnap_cost_dev`: by
+        four-point Gauss-Legendre quadrature, exact for the integrand and free of c^T H c's cancellation).  NaN for a mission with a
+        non-finite coefficient.  Stream-ordered, no sync."""
+        torch = self._torch
+        if isinstance(plan, RaggedPlan):
+            if plan.batch is None:
+                raise ValueError("this RaggedPlan has no batch, hence no coefficients")
+            plan = plan.batch
+        if plan.coeffs is None or plan.times is None:
+            raise ValueError("the cost needs the plan's coefficients and durations")
+        ragged = hasattr(plan, "seg_offsets")
+        out = torch.empty((int(plan.B),), dtype=torch.float64, device=self.device)
+        if plan.B == 0:
+            return out
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_cost_dev", _ptr(plan.coeffs), _ptr(plan.times), _ptr(plan.seg_offsets) if ragged else None,
+                      int(plan.B), int(plan.max_m if ragged else plan.m), _ptr(out))
+        return out
+
+    def optimize_times(self, plan, iterations: int = 8, rows: Optional[bool] = None) -> TimeOptResult:
+        """Divide every mission's total time between its legs so that the snap cost falls (`uavac_minsnap_optimize_times_dev`): the
+        second half of the minimum-snap method.  Per iteration m probe solves per mission give the gradient of the cost along
+        total-preserving directions, six step sizes along the projected descent direction are solved and costed, and the best one that
+        is strictly better is taken; all missions at once, no host sync inside the loop.  The total time of a mission is kept, no
+        duration falls below 0.2 of the mission's shortest, and the cost never rises.
+        `plan`: a rest-to-rest Plan or RaggedBatch (durations from a speed or given); it is left untouched.  One with `boundary` is
+        refused (ValueError).  -> TimeOptResult whose `.plan` is a NEW `free_times` plan on the same waypoints, planned by
+        `uavac_minsnap_plan_t_dev` from the optimised durations; `rows`: with or without rows (None: as the input has them).
+        `cost_after` is the cost of exactly that plan.
+        The promise is a lower snap cost, NOT feasibility: single missions can come out with a higher peak speed, so `audit` stays the
+        judge.  And the new curve passes the same waypoints but not the same points in between: a plan that came out of the obstacle
+        loop must be audited against its cuboids again -- `Engine.audit(result.plan, obstacles)`."""
+        torch = self._torch
+        if isinstance(plan, RaggedPlan):
+            if plan.batch is None:
+                raise ValueError("this RaggedPlan has no batch: optimise eng.plan_ragged(plan.final_waypoints, ...)")
+            plan = plan.batch
+        if getattr(plan, "boundary", None) is not None:
+            raise ValueError("the duration optimisation is rest to rest: not for a plan with boundary derivatives")
+        if plan.waypoints is None:
+            raise ValueError("the optimisation solves again from the waypoints: a plan assembled from gathered parts has none")
+        if int(iterations) < 0:
+            raise ValueError("iterations must be >= 0")
+        ragged = hasattr(plan, "seg_offsets")
+        B = int(plan.B)
+        m = int(plan.max_m if ragged else plan.m)
+        kw = dict(device=self.device)
+        times = plan.times.clone()
+        before = torch.empty((B,), dtype=torch.float64, **kw)
+        after = torch.empty((B,), dtype=torch.float64, **kw)
+        accepted = torch.empty((B,), dtype=torch.int32, **kw)
+        so = plan.seg_offsets if ragged else None
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_optimize_times_dev", _ptr(plan.waypoints), _ptr(so), B, m, _ptr(times), int(iterations),
+                      _ptr(before), _ptr(after), _ptr(accepted))
+        with_rows = (plan.traj is not None) if rows is None else bool(rows)
+        out = self._plan_from_times(plan.waypoints, times, plan.dt, with_rows, False, so=so,
+                                    so_host=plan.seg_offsets_host if ragged else None, max_m=m)
+        return TimeOptResult(out, before, after, accepted)
 
     def sample_range(self, plan: Plan, b0: int, b1: int):
         """The rows (and first headings) of missions [b0, b1) of a uniform plan, written where `sample(plan)` writes them: the
@@ -894,13 +1038,14 @@ class Engine:
         return RaggedPlan(B, float(velocity), float(dt), wps, offsets, traj, total, starts, converged)
 
     def plan_ragged(self, waypoints, velocity=1.0, dt: float = 0.01, cuboid=None, strict: bool = True,
-                    rows: bool = True) -> RaggedBatch:
+                    rows: bool = True, times=None) -> RaggedBatch:
         """`MinimumSnap(path_b, None, velocity, dt).get_trajectory()` for B paths of DIFFERENT lengths in one batch
         (minimum_snap.py:13-57 takes any path; `Engine.plan` wants equal lengths).  `waypoints`: B arrays (m_b + 1, 3),
         1 <= m_b <= UAVAC_MAX_SEGMENTS.  Mission b's rows and coefficients equal those of `plan` on it alone, bit for
         bit.  `cuboid` (6,): also return per-spline hit flags (the collision scan of minimum_snap.py:81-87).
         `rows=False`: no rows (`batch.traj` is None), the first headings from `uavac_minsnap_first_yaw_dev`; not with `cuboid`.
-        `velocity`: a number, or a (B,) tensor / array of one cruise speed per mission (see `plan`)."""
+        `velocity`: a number, or a (B,) tensor / array of one cruise speed per mission (see `plan`).
+        `times`: B arrays (m_b,) of segment durations to plan from as given (see `plan`; `batch.free_times`); not with `cuboid`."""
         torch = self._torch
         wps = [np.ascontiguousarray(w, dtype=np.float64) for w in waypoints]
         B = len(wps)
@@ -915,6 +1060,15 @@ class Engine:
         S = int(so_host[-1])
         wp = self._dev(np.concatenate(wps, axis=0), torch.float64)
         so = self._dev(so_host, torch.int64)
+        if times is not None:
+            self._refuse_with_times(velocity, None)
+            if cuboid is not None:
+                raise ValueError("times= with a cuboid is not offered: Engine.audit(batch, obstacles) reports the hits")
+            tms = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in times]
+            if len(tms) != B or any(t.shape[0] != c for t, c in zip(tms, counts)):
+                raise ValueError("times must be B arrays of shape (m_b,)")
+            return self._plan_from_times(wp, self._dev(np.concatenate(tms), torch.float64), dt, rows, strict, so=so, so_host=so_host,
+                                         max_m=max_m)
         batch = self._plan_ragged_tensors(wp, so, so_host, max_m, velocity, dt, cuboid, rows)
         if strict:
             self.check(batch)
@@ -958,9 +1112,13 @@ class Engine:
                            traj, total, first_yaw, hit, speeds)
 
     def solve(self, plan: Plan):
-        """Re-run times/row counts + coefficient solve into plan's buffers (no allocation, no sync)."""
+        """Re-run times/row counts + coefficient solve into plan's buffers (no allocation, no sync); a `free_times` plan keeps its
+        durations and re-runs the row counts and the solve from them."""
         self._bind_stream()
-        if getattr(plan, "velocities", None) is None:
+        if getattr(plan, "free_times", False):
+            self.ctx.call("uavac_minsnap_row_counts_t_dev", _ptr(plan.times), None, plan.B, plan.m, plan.dt, _ptr(plan.seg_rows),
+                          _ptr(plan.row_offsets))
+        elif getattr(plan, "velocities", None) is None:
             self.ctx.call("uavac_minsnap_row_counts_dev", _ptr(plan.waypoints), plan.B, plan.m, plan.velocity, plan.dt,
                           _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets))
         else:
