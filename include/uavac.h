@@ -169,7 +169,8 @@ int uavac_clock_probe_dev(uavac_ctx *ctx, int window_us, int64_t *stamps);
  * "sampler_waves" 1 = the one-wave-per-mission sampler (same rows bit for bit; faster into some row
  * buffers, slower into most: DESIGN K2).  "audit_lanes": 16 (default) or 64 = lanes per mission of uavac_minsnap_audit_dev.
  * "timeopt_chunk": 0 (default: sized from UAVAC_TIMEOPT_SCRATCH_BYTES) or the missions per chunk of uavac_minsnap_optimize_times_dev
- * (same results).
+ * (same results).  "separation_split": 0 (default: sized from B and G) or 1 .. UAVAC_SEP_MAX_SPLIT = workgroups that share the partners
+ * of one window of 64 missions in uavac_minsnap_separation_dev (same results).
  * Defaults from the environment (UAVAC_ROLLOUT_ALIGN, UAVAC_YAW_GROUP, UAVAC_SAMPLER_WAVES, UAVAC_SAMPLER_GROUP) at uavac_create.
  * ONE option is not a tuning knob but part of the log layout: "log_pitch" = P doubles per log row,
  * 0 (default) = B.  With P >= B the rollouts write state_log [K][13][P] and cmd_log [K][12][P]
@@ -302,6 +303,48 @@ int uavac_minsnap_first_yaw_dev(uavac_ctx *ctx, const double *coeffs, const int3
 #define UAVAC_AUDIT_MAX_CUBOIDS 16
 int uavac_minsnap_audit_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                             double dt, const double *cuboids, int n_cuboids, double *audit, int32_t *hit_rows, int32_t *first_hit);
+
+/* SEPARATION AUDIT: the fleet's audit against itself.  For every mission of a GROUP of missions that share an airspace: the closest
+ * approach to any other mission of the group, to which one and when; how many others come inside a protection radius and when the
+ * first one does -- from coefficients and row counts alone (csrc/minsnap_separation.hip): no row is written, nothing is read back,
+ * everything is enqueued on the ctx stream.  coeffs / seg_rows / seg_offsets / B / m / dt as in uavac_minsnap_audit_dev (seg_offsets
+ * NULL = uniform, otherwise ragged and clamped).
+ * CLOCK.  The missions of a group share one row clock k = 0, 1, ....  Mission b has N_b rows -- exactly the rows the sampler writes,
+ * walked as the plan audit walks them -- and start row S_b = start_rows[b] (i32, device; NULL: all 0).  At clock row k it stands at
+ * its own row clamp(k - S_b, 0, N_b - 1): before its start it waits on its first row, after its end it holds its last row (what the
+ * rollout flies once the cursor stops: the repeated last-row periods of the scored twins).  The group's horizon is H_g = max over
+ * its missions of S_b + N_b, and every pair is compared at every k in [0, H_g).
+ * GROUPS.  group_offsets [G+1] i64 (device), non-decreasing, group_offsets[0] = 0, group_offsets[G] = B: group g holds missions
+ * [group_offsets[g], group_offsets[g+1]); NULL (G is ignored) = one group of all B.  Missions of different groups are never compared.
+ * EXCLUDED MISSIONS.  A mission with no rows, or with any coefficient of its (clamped) segments not finite -- a singular knot system
+ * writes NaN coefficients --, is excluded: nobody is compared with it, and it reports sep NaN, partner -1, row -1, conflicts 0, first
+ * conflict -1, compared 0.  Everybody else reports in `compared` how many partners it WAS compared with, so a skipped neighbour is
+ * visible: a mission is clear iff conflicts == 0 and compared == its group's size - 1.  Finite coefficients whose samples overflow
+ * are outside the contract.
+ * OUTPUTS per mission b (structure of arrays, like the audit block):
+ *   sep  [B] f64: the minimum distance to any compared partner over [0, H_g); +inf when no partner was compared (a group of one, or
+ *        all the others excluded)
+ *   isep [UAVAC_SEP_ROWS][B] i32:  0 the partner's batch index      1 the clock row of the minimum      (both -1 when sep is +inf or NaN)
+ *        2 conflicts = the number of partners j with min_k d^2(b, j, k) < r^2      3 the first clock row at which any partner is
+ *        inside the radius (-1: none)      4 compared
+ * ROUNDING AND TIES are part of the contract, as for the plan audit.  Positions come from the sampler's own fma chain, t = (double)(int)(r
+ * - first row of the segment) * dt.  The distance is formed without contraction: dx = xi - xj, ..., d^2 = (dx * dx + dy * dy) + dz * dz
+ * with separately rounded products and sums; the minimum is taken of the squares and one correctly rounded sqrt comes last; r^2 =
+ * radius * radius is rounded once; inside means d^2 < r^2, strictly.  The minimum is the lexicographic minimum of (d^2, clock row,
+ * partner index): the lowest row first, then the lowest partner -- an exact reduction that does not depend on order.  Every output
+ * is therefore bit for bit what NumPy gives on the sampled rows with the same clamped indexing (uav_ac.scoring.separation_from_rows),
+ * whatever the launch shape or what else is in the batch: a group audited alone gives the same numbers with the partner indices
+ * shifted.  (Option "separation_split": 0 = automatic (default), 1 .. UAVAC_SEP_MAX_SPLIT = workgroups that share the partners of one
+ * window of 64 missions; a tuning knob, same results.)  Cost: pairs x horizon -- about 13 fp64 operations per pair and clock row.
+ * BAD INPUTS.  A negative start_rows[b] cannot be refused by the host: it is clamped to 0 and raises sticky flag 0 (uavac_take_flags),
+ * like a bad segment count; so does one above 2^29 (clamped to 2^29), and a mission of more than 2^29 rows, which is excluded.
+ * UAVAC_EINVAL before anything is enqueued: no context, a NULL required pointer (coeffs, seg_rows, sep, isep), B < 1, m outside 1 ..
+ * UAVAC_MAX_SEGMENTS, dt not positive and finite, radius negative or not finite, G < 1 when group_offsets != NULL. */
+#define UAVAC_SEP_ROWS 5
+#define UAVAC_SEP_MAX_SPLIT 64
+int uavac_minsnap_separation_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                 double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double *sep,
+                                 int32_t *isep);
 
 /* ONE CRUISE SPEED PER MISSION: the _v twins of uavac_minsnap_row_counts_dev, uavac_minsnap_row_counts_ragged_dev and
  * uavac_minsnap_plan_dev (both of its forms: rows with a capacity and flag 2 and the same all-or-nothing commit, and rows-free with

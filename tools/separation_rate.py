@@ -1,0 +1,151 @@
+"""The separation audit (`uavac_minsnap_separation_dev`, `Engine.separation`) against the only route to the same answers that existed
+before it: sample the rows, build every mission's clamped positions on its group's clock, compare all pairs of a group in torch on the
+GPU.  Eight segments (the bench's generator), velocity 3, dt 0.01, radius 0.5, no start rows, two shapes:
+
+    65 536 missions in groups of 64        4 096 missions in one group
+
+    separation_rate.py [OUT.jsonl] [rounds]
+
+The two routes must give the SAME answers (every output, bit for bit) before anything is timed.  hipEvents around each arm, warm-up
+first, the arms interleaved over rounds in one process; median, minimum and maximum per arm, one JSON line per arm with the device's
+identity.  Per arm: ms, ordered pair-rows per second (sum over groups of n (n - 1) H, what the kernel walks: it does not use d(i, j) =
+d(j, i)), and the share of the fp64 issue peak as DESIGN section 3 prices K1: fp64 wave-instructions over time over 614 G/s (78.6
+TFLOP/s = 39.3 T lane-FMA/s = 614 G wave-instructions/s), with the ten fp64 instructions a pair-row needs (three subtractions, three
+products, two sums, two compares; the position evaluations, 21 fmas per mission and row, are left out).
+
+The rows route, per call: `Engine.sample` into the plan's row buffer (allocated once, outside the timing); the index of every mission's
+row at every clock row of the common horizon, clamp(k, 0, N_b - 1), and the gather of the positions (G, n, H, 3); then, in chunks that
+keep a temporary under 1 GiB, d^2 = (dx dx + dy dy) + dz dz for all pairs of a group as (chunk, i, k, j), the diagonal set to +inf, the
+first minimum over (k, j), `any` over k for the conflicts and over j for the first conflict row.  Eager torch rounds every product and
+sum on its own, so the bits are the kernel's.  The extra arms are the kernel at other values of its one tuning option."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "uav-autonomous-control_amd")]
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from bench import FP64_WAVE_INSTR_PEAK, missions  # noqa: E402
+from uav_ac.fleet import Engine  # noqa: E402
+
+M, VEL, DT, RADIUS = 8, 3.0, 0.01, 0.5
+SHAPES = ((65536, 64), (4096, 4096))                     # (missions, group size)
+FP64_INSTR_PER_PAIR_ROW = 10
+TEMP_BYTES = 1 << 30
+
+
+def timed(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def rows_route(eng, plan, n, H, radius):
+    """-> (sep (B,), isep (5, B)) from sampled rows, groups of n consecutive missions, common horizon H."""
+    dev = plan.row_offsets.device
+    B, G = plan.B, plan.B // n
+    eng.sample(plan)
+    ro = plan.row_offsets
+    N = ro[1:] - ro[:-1]
+    k = torch.arange(H, device=dev)
+    idx = ro[:-1, None] + torch.minimum(k[None, :], (N - 1)[:, None])                     # start rows are 0: clamp(k, 0, N - 1)
+    P = plan.traj[:, 0:3][idx].reshape(G, n, H, 3)
+    r2 = radius * radius
+    sep = torch.empty((B,), dtype=torch.float64, device=dev)
+    isep = torch.empty((5, B), dtype=torch.int32, device=dev)
+    per_i = n * H * 8
+    ci = max(1, min(n, TEMP_BYTES // per_i))
+    cg = max(1, min(G, TEMP_BYTES // (per_i * ci))) if ci == n else 1
+    eye = torch.eye(n, dtype=torch.bool, device=dev)
+    for g0 in range(0, G, cg):
+        Pg = P[g0:g0 + cg]
+        for i0 in range(0, n, ci):
+            d2 = None
+            for c in range(3):
+                d = Pg[:, i0:i0 + ci, :, c][:, :, :, None] - Pg[:, :, :, c].transpose(1, 2)[:, None, :, :]     # (cg, ci, H, n)
+                d = d * d
+                d2 = d if d2 is None else d2 + d          # (dx dx + dy dy) + dz dz, left to right
+            d2.masked_fill_(eye[i0:i0 + ci][None, :, None, :], float("inf"))
+            flat = d2.reshape(d2.shape[0], d2.shape[1], H * n)
+            best = flat.argmin(dim=2)
+            dist = torch.sqrt(flat.gather(2, best[:, :, None])[:, :, 0])
+            inside = d2 < r2
+            conflicts = inside.any(dim=2).sum(dim=2)
+            hit_row = inside.any(dim=3)
+            first = torch.where(hit_row.any(dim=2), hit_row.to(torch.int8).argmax(dim=2), torch.full_like(best, -1))
+            base = (torch.arange(g0, g0 + Pg.shape[0], device=dev) * n)[:, None]
+            out = (base + torch.arange(i0, i0 + d2.shape[1], device=dev)[None, :]).reshape(-1)
+            sep[out] = dist.reshape(-1)
+            isep[0, out] = (base + best % n).reshape(-1).to(torch.int32)
+            isep[1, out] = (best // n).reshape(-1).to(torch.int32)
+            isep[2, out] = conflicts.reshape(-1).to(torch.int32)
+            isep[3, out] = first.reshape(-1).to(torch.int32)
+    isep[4] = n - 1
+    return sep, isep
+
+
+def main():
+    out_path = sys.argv[1] if len(sys.argv) > 1 else None
+    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    eng = Engine("cuda:0")
+    box = eng.ctx.device_identity()
+    lines = []
+    for B, n in SHAPES:
+        wps = missions(B, M, 0, B)
+        plan = eng.plan(wps, VEL, DT)
+        groups = None if n == B else n
+        lengths = (plan.row_offsets[1:] - plan.row_offsets[:-1]).cpu().numpy().reshape(B // n, n)
+        H = int(lengths.max())
+        pair_rows = int((lengths.max(axis=1).astype(np.int64) * n * (n - 1)).sum())
+
+        def kernel(split=0):
+            eng.ctx.set_option("separation_split", split)
+            return eng.separation(plan, RADIUS, groups=groups)
+
+        # the two routes agree before anything is timed: every output, bit for bit
+        a = kernel()
+        want_sep, want_isep = rows_route(eng, plan, n, H, RADIUS)
+        torch.cuda.synchronize()
+        differ = {"sep": int((a.min_distance != want_sep).sum()), "isep": int((a.block != want_isep).sum())}
+        print(json.dumps({"B": B, "group": n, "outputs that differ between the two routes": differ,
+                          "missions with a conflict": int((a.conflicts > 0).sum()), "closest pair m": float(a.min_distance.min())}), flush=True)
+        assert differ == {"sep": 0, "isep": 0}, differ
+
+        arms = {"kernel, split automatic": (kernel, 5)}
+        for split in ((1, 2, 4, 8, 12, 16, 24, 32, 64) if n == B else (1,)):
+            arms[f"kernel, split {split}"] = (lambda s=split: kernel(s), 5)
+        arms["rows route: sample + clamped positions + pairwise torch"] = (lambda: rows_route(eng, plan, n, H, RADIUS), 1)
+        arms["rows route, sampler only"] = (lambda: eng.sample(plan), 5)
+        for fn, _ in arms.values():                      # warm-up of every arm
+            fn()
+        torch.cuda.synchronize()
+        times = {name: [] for name in arms}
+        for _ in range(rounds):
+            for name, (fn, reps) in arms.items():
+                times[name].append(timed(fn, reps))
+        eng.ctx.set_option("separation_split", 0)
+        for name, ts in times.items():
+            med = float(np.median(ts))
+            rate = pair_rows / (med * 1e-3)
+            line = {"arm": name, "B": B, "group": n, "m": M, "horizon_rows": H, "pair_rows": pair_rows, "median_ms": round(med, 4),
+                    "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4), "rounds": rounds, "box": box}
+            if "sampler only" not in name:
+                line["pair_rows_per_s"] = rate
+                line["fp64_issue_frac"] = round(rate / 64.0 * FP64_INSTR_PER_PAIR_ROW / FP64_WAVE_INSTR_PEAK, 4)
+            lines.append(json.dumps(line))
+            print(lines[-1], flush=True)
+        del plan, a, want_sep, want_isep
+        torch.cuda.empty_cache()
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -28,6 +28,18 @@ __device__ __forceinline__ void minsnap_eval_row(const double *c, double t, doub
     ax = 2.0 * d2x; ay = 2.0 * d2y; az = 2.0 * d2z;
 }
 
+// The position of the same sample alone: the `p` chain of minsnap_eval_row -- the same seven fmas per axis in the same order, which
+// do not read the derivative sums -- hence the same bits (the separation audit compares positions only, minsnap_separation.hip).
+template <int STRIDE>
+__device__ __forceinline__ void minsnap_eval_pos(const double *c, double t, double &px, double &py, double &pz) {
+    px = c[minsnap_coeff_index<STRIDE>(21)]; py = c[minsnap_coeff_index<STRIDE>(22)]; pz = c[minsnap_coeff_index<STRIDE>(23)];
+#pragma unroll
+    for (int i = 6; i >= 0; --i) {
+        px = fma(px, t, c[minsnap_coeff_index<STRIDE>(3 * i)]); py = fma(py, t, c[minsnap_coeff_index<STRIDE>(3 * i + 1)]);
+        pz = fma(pz, t, c[minsnap_coeff_index<STRIDE>(3 * i + 2)]);
+    }
+}
+
 // One axis of the same sample (axis a = 0, 1, 2): the identical fma sequence as minsnap_eval_row, hence the same bits; the
 // sampler evaluates axis after axis and stages each at once, which keeps a third of the coefficients and sums in registers.
 template <int STRIDE>

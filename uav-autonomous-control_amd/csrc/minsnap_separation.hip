@@ -1,0 +1,358 @@
+// The fleet's audit against itself (gfx950): for every mission of a group that shares an airspace, the closest approach to any other
+// mission of the group -- how near, to whom, at which row of the group's clock --, how many others come inside a protection radius and
+// when the first one does.  From coefficients and row counts alone, like the plan audit (minsnap_audit.hip): no row is written, nothing
+// is read back.  The contract -- the clock, the groups, the excluded missions, rounding and ties -- is in include/uavac.h
+// (uavac_minsnap_separation_dev); uav_ac.scoring.separation_from_rows states it in NumPy on sampled rows, and the results are the same bits.
+//
+// Three launches on the ctx stream:
+//   separation_prepass_kernel   per mission (sixteen lanes each): its row total N, its start row clamped to >= 0, and whether it is
+//                               EXCLUDED (no rows, or a coefficient that is not finite) -- kept as N = 0 in ctx scratch
+//   minsnap_separation_kernel   the pairs.  A workgroup owns the 64 consecutive missions [64 x, 64 x + 64) of the batch, one per lane (i),
+//                               and visits every group that reaches into this window, with the lanes of other groups idle.  Per group
+//                               it walks the group's missions in j-tiles of 64 and, per j-tile, the group's clock from 0 to its horizon
+//                               in chunks of 32 rows.  Its four wavefronts split each chunk: wave w takes rows 8 w .. 8 w + 7.  For its
+//                               rows a wave first evaluates the j-tile's positions into its own quarter of the LDS tile (lane = j: the
+//                               audit's forward segment walk, position-only Horner, the segment's coefficients fetched per chunk), then
+//                               each lane evaluates its OWN position once per row (its segment's coefficients stay in registers for the chunk) and
+//                               reads the 64 partners' positions as LDS broadcasts (every lane reads the same address).  A wave reads
+//                               only what it wrote itself: no workgroup barrier inside the clock loop.
+//                               Excluded partners and lanes past the group's end are NaN positions: a NaN distance is never below
+//                               anything, so they cost no instruction; the lane's own entry is turned into +inf in the one tile that
+//                               holds it.  Per row the lane keeps the row's minimum and its partner (strict <, partners ascending), per
+//                               j-tile the minimum and its row (strict <, rows ascending), one bit per partner that came inside the
+//                               radius, and the first row with anybody inside.  At the end of a j-tile the four waves meet (through the
+//                               LDS tile, which is dead by then): the minima merge by the full lexicographic order (d^2, row, partner),
+//                               the bits by OR -- their popcount is the tile's share of `conflicts` --, the first rows by min.
+//                               gridDim.y = P workgroups share a window: workgroup p takes j-tiles p, p + P, ... and leaves one
+//                               partial record per mission in scratch
+//   separation_merge_kernel     per mission: the P partial records merged the same way, one correctly rounded sqrt, the sentinels
+// Every reduction is a lexicographic minimum, an integer sum over disjoint partners, an OR or an integer minimum: exact and independent
+// of order, so the outputs depend neither on P, nor on the tile or chunk sizes, nor on what else is in the batch; each output has one
+// writer and there are no atomics but the sticky flag.  The price is the factor 2 of not using d(i, j) = d(j, i).
+//
+// ROUNDING (part of the contract): positions by the sampler's fma chain (minsnap_eval_pos), the distance WITHOUT contraction: dx = xi -
+// xj, ..., d^2 = (dx dx + dy dy) + dz dz, each product and sum rounded on its own.
+
+#include "uavac_internal.h"
+#include "minsnap_eval.h"
+
+#include <cmath>
+#include <limits>
+
+namespace {
+
+constexpr int kTile = 64;                                   // missions per i-window and per j-tile: one per lane
+constexpr int kWaves = 4;                                   // wavefronts per workgroup
+constexpr int kRows = 8;                                    // clock rows of a chunk per wavefront
+constexpr int kChunk = kWaves * kRows;                      // clock rows per chunk
+constexpr int kThreads = 64 * kWaves;
+constexpr int kRegion = kRows * kTile * 3;                  // doubles of the LDS tile per wavefront (12 KB; 48 KB per workgroup)
+constexpr int kNone = 0x7fffffff;                           // "no row / no partner" while a minimum is being formed
+constexpr int kMaxClock = 1 << 29;                          // start rows and row totals above this cannot be clocked with int
+constexpr int kUnroll = 8;                                  // partners per unrolled step of the pair loop
+constexpr int kPreLanes = 16;                               // lanes per mission of the pre-pass
+
+// First segment and segment count of mission b: uniform (so == NULL) or ragged, clamped to 1 .. m like every ragged kernel clamps it.
+struct Mission {
+    long long s0;
+    int m;
+};
+__device__ __forceinline__ Mission mission_of(const int64_t *__restrict__ so, int b, int m_uniform) {
+    Mission M;
+    if (so) {
+        M.s0 = so[b];
+        const long long n = so[b + 1] - M.s0;
+        M.m = (int)(n < 1 ? 1 : (n > m_uniform ? m_uniform : n));
+    } else {
+        M.s0 = (long long)b * m_uniform;
+        M.m = m_uniform;
+    }
+    return M;
+}
+
+// (d, k, j) before (D, K, J) in the order of the contract: the smaller distance, then the lower row, then the lower partner
+__device__ __forceinline__ bool lex_less(double d, int k, int j, double D, int K, int J) {
+    return d < D || (d == D && (k < K || (k == K && j < J)));
+}
+
+// ------------------------------------------------------------------------------------------------------------------ pre-pass
+__global__ void __launch_bounds__(kThreads) separation_prepass_kernel(const double *__restrict__ coeffs, const int32_t *__restrict__ seg_rows,
+                                                                      const int64_t *__restrict__ seg_offsets, int B, int m,
+                                                                      const int32_t *__restrict__ start_rows, int32_t *__restrict__ n_rows,
+                                                                      int32_t *__restrict__ start, int32_t *__restrict__ flags) {
+    constexpr int kPerWave = 64 / kPreLanes;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int g = lane / kPreLanes, l = lane % kPreLanes;
+    const int b = (blockIdx.x * kWaves + w) * kPerWave + g;
+    const bool live = b < B;
+    const Mission M = mission_of(seg_offsets, live ? b : B - 1, m);
+    const int32_t *rows_of = seg_rows + M.s0;
+    const double *cm = coeffs + (size_t)M.s0 * 24;
+    long long total = 0;                                     // the mission's rows: what the sampler's row offsets give it
+    for (int s = 0; s < M.m; ++s) total += rows_of[s];
+    double z = 0.0;                                          // stays 0 while every coefficient is finite (0 * inf and 0 * NaN are NaN)
+    for (int k = l; k < M.m * 24; k += kPreLanes) z = fma(0.0, cm[k], z);
+#pragma unroll
+    for (int d = kPreLanes / 2; d >= 1; d >>= 1) z += __shfl_xor(z, d);
+    if (live && l == 0) {
+        int s = start_rows ? start_rows[b] : 0;
+        bool bad = s < 0 || s > kMaxClock;                   // cannot be refused by the host: clamped, and flag 0
+        s = s < 0 ? 0 : (s > kMaxClock ? kMaxClock : s);
+        const bool too_long = total > kMaxClock;
+        const bool excluded = !(z == 0.0) || total < 1 || too_long;
+        n_rows[b] = excluded ? 0 : (int)total;
+        start[b] = s;
+        if (bad || too_long) atomicOr(&flags[0], 1);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the pairs
+// the segment of a mission's row r, walked forward from where the lane stood (rows only grow): the audit's walk
+__device__ __forceinline__ void seek(const int32_t *__restrict__ rows_of, int mb, int r, int &s, int &base, int &cnt) {
+    while (s + 1 < mb && r >= base + cnt) { base += cnt; ++s; cnt = rows_of[s]; }
+}
+
+// One row of the lane's own mission against the 64 positions of a j-tile at the same clock row (row [64][3] in LDS, the same for every
+// lane).  rm / rkey: the row's minimum and the tile-local partner that gave it first; mask: bit jj is set once partner jj came inside.
+template <bool SELF>
+__device__ __forceinline__ void pair_row(const double *row, double xi, double yi, double zi, double r2, int selfjj, double &rm, int &rkey,
+                                         unsigned long long &mask) {
+#pragma clang fp contract(off)
+    const double inf = std::numeric_limits<double>::infinity();
+#pragma nounroll
+    for (int q = 0; q < kTile / kUnroll; ++q) {
+        unsigned in = 0;
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int jj = q * kUnroll + u;
+            const double dx = xi - row[3 * jj], dy = yi - row[3 * jj + 1], dz = zi - row[3 * jj + 2];
+            const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
+            double d2 = (xx + yy) + zz;
+            if (SELF && jj == selfjj) d2 = inf;              // the lane's own mission is nobody's partner
+            if (d2 < rm) { rm = d2; rkey = jj; }
+            if (d2 < r2) in |= 1u << u;
+        }
+        mask |= (unsigned long long)in << (kUnroll * q);
+    }
+}
+
+__global__ void __launch_bounds__(kThreads, 3) minsnap_separation_kernel(
+    const double *__restrict__ coeffs, const int32_t *__restrict__ seg_rows, const int64_t *__restrict__ seg_offsets, int B, int m, double dt,
+    const int64_t *__restrict__ group_offsets, int G, const int32_t *__restrict__ n_rows, const int32_t *__restrict__ start, double r2,
+    double *__restrict__ part_d2, int32_t *__restrict__ part_i) {
+    __shared__ double tile[kWaves * kRegion];
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int P = gridDim.y, p = blockIdx.y;
+    const int w0 = blockIdx.x * kTile, w1 = w0 + kTile;      // the window of missions this workgroup owns
+    const int b = w0 + lane;
+    const bool live = b < B;
+    const int bb = live ? b : B - 1;
+    const Mission Mi = mission_of(seg_offsets, bb, m);
+    const int32_t *irows = seg_rows + Mi.s0;
+    const double *icm = coeffs + (size_t)Mi.s0 * 24;
+    const int ni = n_rows[bb], si = start[bb];
+    double *mine = tile + w * kRegion;                       // this wavefront's quarter of the tile
+
+    int g = 0;                                               // the group that holds mission w0: the last one that starts at or before it
+    if (group_offsets) {
+        int lo = 0, hi = G;
+        while (hi - lo > 1) {
+            const int mid = lo + (hi - lo) / 2;
+            if (group_offsets[mid] <= w0) lo = mid; else hi = mid;
+        }
+        g = lo;
+    }
+    for (; g < G; ++g) {                                     // (uniform: every thread of the workgroup sees the same groups)
+        const long long a0 = group_offsets ? group_offsets[g] : 0, a1 = group_offsets ? group_offsets[g + 1] : B;
+        const int g0 = (int)(a0 < 0 ? 0 : (a0 > B ? B : a0));            // clamped: malformed offsets must not leave the batch
+        const int g1 = (int)(a1 < g0 ? g0 : (a1 > B ? B : a1));
+        if (g0 >= w1 || g0 >= B) break;
+        if (g1 <= w0 || g1 == g0) continue;
+        const bool act = live && b >= g0 && b < g1;
+
+        // the group's horizon and how many of its missions take part
+        int h = 0, cnt = 0;
+        for (int j = g0 + (int)threadIdx.x; j < g1; j += kThreads) {
+            const int n = n_rows[j];
+            if (n > 0) { h = max(h, start[j] + n); ++cnt; }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { h = max(h, __shfl_xor(h, d)); cnt += __shfl_xor(cnt, d); }
+        int *meet = reinterpret_cast<int *>(tile);
+        if (lane == 0) { meet[2 * w] = h; meet[2 * w + 1] = cnt; }
+        __syncthreads();
+        int H = 0, n_in = 0;
+#pragma unroll
+        for (int v = 0; v < kWaves; ++v) { H = max(H, meet[2 * v]); n_in += meet[2 * v + 1]; }
+        __syncthreads();
+
+        double gb = inf;                                     // the group's results so far (held by wavefront 0)
+        int gk = kNone, gj = kNone, gconf = 0, gfirst = kNone;
+        const int n_tiles = (g1 - g0 + kTile - 1) / kTile;
+        for (int t = n_in >= 2 ? p : n_tiles; t < n_tiles; t += P) {
+            const int j0 = g0 + t * kTile;
+            const bool jvalid = j0 + lane < g1;
+            const int jb = jvalid ? j0 + lane : g1 - 1;
+            const Mission Mj = mission_of(seg_offsets, jb, m);
+            const int32_t *jrows = seg_rows + Mj.s0;
+            const double *jcm = coeffs + (size_t)Mj.s0 * 24;
+            const int nj = jvalid ? n_rows[jb] : 0, sj = start[jb];
+            int js = 0, jbase = 0, jcnt = jrows[0];
+            int is = 0, ibase = 0, icnt = irows[0];
+            const int selfjj = b - j0;
+            const bool self_tile = j0 < w1 && j0 + kTile > w0;
+            double tb = inf;                                 // this wavefront's results of the tile
+            int tk = kNone, tj = kNone, tfirst = kNone;
+            unsigned long long mask = 0;
+            for (int k0 = w * kRows; k0 < H; k0 += kChunk) {
+                {                                            // the j-tile's positions at this wavefront's rows of the chunk
+                    // (the segment of the chunk's first row is fetched unconditionally: the 24 coefficients then live from here to
+                    // the end of this block only, not around the clock loop)
+                    double cj[24];
+                    seek(jrows, Mj.m, min(max(k0 - sj, 0), nj - 1), js, jbase, jcnt);
+                    int jloaded = js;
+#pragma unroll
+                    for (int q = 0; q < 24; ++q) cj[q] = jcm[js * 24 + q];
+#pragma nounroll
+                    for (int r = 0; r < kRows && k0 + r < H; ++r) {
+                        const int row = min(max(k0 + r - sj, 0), nj - 1);
+                        seek(jrows, Mj.m, row, js, jbase, jcnt);
+                        if (js != jloaded) {
+#pragma unroll
+                            for (int q = 0; q < 24; ++q) cj[q] = jcm[js * 24 + q];
+                            jloaded = js;
+                        }
+                        double x, y, z;
+                        minsnap_eval_pos<1>(cj, (double)(int)(row - jbase) * dt, x, y, z);
+                        double *o = mine + (r * kTile + lane) * 3;
+                        o[0] = nj > 0 ? x : nan; o[1] = nj > 0 ? y : nan; o[2] = nj > 0 ? z : nan;
+                    }
+                }
+                lds_wave_fence();                            // (a wavefront reads only its own quarter)
+                double c[24];                                // the lane's own segment, fetched per chunk in the same way
+                seek(irows, Mi.m, min(max(k0 - si, 0), ni - 1), is, ibase, icnt);
+                int iloaded = is;
+#pragma unroll
+                for (int q = 0; q < 24; ++q) c[q] = icm[is * 24 + q];
+#pragma nounroll
+                for (int r = 0; r < kRows && k0 + r < H; ++r) {
+                    const int k = k0 + r;
+                    const int row = min(max(k - si, 0), ni - 1);
+                    seek(irows, Mi.m, row, is, ibase, icnt);
+                    if (is != iloaded) {
+#pragma unroll
+                        for (int q = 0; q < 24; ++q) c[q] = icm[is * 24 + q];
+                        iloaded = is;
+                    }
+                    double xi, yi, zi;
+                    minsnap_eval_pos<1>(c, (double)(int)(row - ibase) * dt, xi, yi, zi);
+                    double rm = inf;
+                    int rkey = 0;
+                    if (self_tile) pair_row<true>(mine + r * kTile * 3, xi, yi, zi, r2, selfjj, rm, rkey, mask);
+                    else pair_row<false>(mine + r * kTile * 3, xi, yi, zi, r2, selfjj, rm, rkey, mask);
+                    if (rm < tb) { tb = rm; tk = k; tj = j0 + rkey; }
+                    if (rm < r2) tfirst = min(tfirst, k);
+                }
+                lds_wave_fence();
+            }
+            // the four wavefronts meet: 1 .. 3 leave their results in their quarters, wavefront 0 merges
+            if (w != 0) {
+                int *q = reinterpret_cast<int *>(mine + 2 * kTile);
+                mine[lane] = tb;
+                reinterpret_cast<unsigned long long *>(mine)[kTile + lane] = mask;
+                q[lane] = tk; q[kTile + lane] = tj; q[2 * kTile + lane] = tfirst;
+            }
+            __syncthreads();
+            if (w == 0) {
+#pragma unroll
+                for (int v = 1; v < kWaves; ++v) {
+                    const double *o = tile + v * kRegion;
+                    const int *q = reinterpret_cast<const int *>(o + 2 * kTile);
+                    const double od = o[lane];
+                    const int ok = q[lane], oj = q[kTile + lane];
+                    if (lex_less(od, ok, oj, tb, tk, tj)) { tb = od; tk = ok; tj = oj; }
+                    mask |= reinterpret_cast<const unsigned long long *>(o)[kTile + lane];
+                    tfirst = min(tfirst, q[2 * kTile + lane]);
+                }
+                gconf += __popcll(mask);
+                if (lex_less(tb, tk, tj, gb, gk, gj)) { gb = tb; gk = tk; gj = tj; }
+                gfirst = min(gfirst, tfirst);
+            }
+            __syncthreads();
+        }
+        if (w == 0 && act) {                                 // one partial record per mission and share p (an excluded mission's is ignored)
+            const size_t at = (size_t)p * 5 * B + b;
+            part_d2[(size_t)p * B + b] = gb;
+            part_i[at] = gj; part_i[at + B] = gk; part_i[at + 2 * (size_t)B] = gconf; part_i[at + 3 * (size_t)B] = gfirst;
+            part_i[at + 4 * (size_t)B] = n_in - 1;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the merge
+__global__ void __launch_bounds__(kThreads) separation_merge_kernel(const int32_t *__restrict__ n_rows, int B, int P,
+                                                                    const double *__restrict__ part_d2, const int32_t *__restrict__ part_i,
+                                                                    double *__restrict__ sep, int32_t *__restrict__ isep) {
+    const int b = blockIdx.x * kThreads + threadIdx.x;
+    if (b >= B) return;
+    const size_t Bs = (size_t)B;
+    if (n_rows[b] == 0) {                                    // excluded: compared with nobody, and nobody with it
+        sep[b] = std::numeric_limits<double>::quiet_NaN();
+        isep[b] = -1; isep[Bs + b] = -1; isep[2 * Bs + b] = 0; isep[3 * Bs + b] = -1; isep[4 * Bs + b] = 0;
+        return;
+    }
+    double d = std::numeric_limits<double>::infinity();
+    int k = kNone, j = kNone, conf = 0, first = kNone;
+    for (int p = 0; p < P; ++p) {
+        const size_t at = (size_t)p * 5 * Bs + b;
+        const double od = part_d2[(size_t)p * Bs + b];
+        const int oj = part_i[at], ok = part_i[at + Bs];
+        if (lex_less(od, ok, oj, d, k, j)) { d = od; k = ok; j = oj; }
+        conf += part_i[at + 2 * Bs];
+        first = min(first, part_i[at + 3 * Bs]);
+    }
+    const bool any = k != kNone;
+    sep[b] = sqrt(d);                                        // (+inf when no partner was compared)
+    isep[b] = any ? j : -1;
+    isep[Bs + b] = any ? k : -1;
+    isep[2 * Bs + b] = conf;
+    isep[3 * Bs + b] = first == kNone ? -1 : first;
+    isep[4 * Bs + b] = part_i[4 * Bs + b];
+}
+
+}  // namespace
+
+int uavac_launch_separation(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
+                            const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double *sep, int32_t *isep) {
+    const int windows = (B + kTile - 1) / kTile;
+    // Shares per window: a window's workgroups split the j-tiles of its group.  The host knows the groups' sizes only on average (B / G:
+    // the offsets are on the device), which is enough to see whether the windows alone give the chip enough workgroups to balance --
+    // about four per SIMD -- or whether a few large groups have to be spread.  Measured at 4 096 missions in one group (64 windows):
+    // 1 / 8 / 12 / 24 / 64 shares take 85.7 / 13.0 / 10.9 / 10.2 / 9.8 ms.  The results do not depend on it (option "separation_split").
+    int P = ctx->separation_split;
+    if (P <= 0) {
+        const int groups = group_offsets ? G : 1;
+        const int tiles = (B / groups + kTile - 1) / kTile;
+        const int wanted = ctx->n_simds * 4;
+        P = (wanted + windows - 1) / windows;
+        P = P > tiles ? tiles : P;
+    }
+    P = P < 1 ? 1 : (P > UAVAC_SEP_MAX_SPLIT ? UAVAC_SEP_MAX_SPLIT : P);
+    const size_t Bs = (size_t)B;
+    if (int rc = uavac_arena_reserve(ctx, 2 * uavac_arena_size(Bs * 4) + uavac_arena_size(P * Bs * 8) + uavac_arena_size(P * 5 * Bs * 4)))
+        return rc;
+    int32_t *n_rows = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4)), *start = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4));
+    double *part_d2 = static_cast<double *>(uavac_arena_take(ctx, P * Bs * 8));
+    int32_t *part_i = static_cast<int32_t *>(uavac_arena_take(ctx, P * 5 * Bs * 4));
+    if (!n_rows || !start || !part_d2 || !part_i) return uavac_fail(ctx, UAVAC_ENOMEM, "separation audit: scratch arena too small");
+    const int per_wg = kWaves * (64 / kPreLanes);
+    hipLaunchKernelGGL(separation_prepass_kernel, dim3((B + per_wg - 1) / per_wg), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows,
+                       seg_offsets, B, m, start_rows, n_rows, start, ctx->d_flags);
+    hipLaunchKernelGGL(minsnap_separation_kernel, dim3(windows, P), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows, seg_offsets, B, m, dt,
+                       group_offsets, group_offsets ? G : 1, n_rows, start, radius * radius, part_d2, part_i);
+    hipLaunchKernelGGL(separation_merge_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, ctx->stream, n_rows, B, P, part_d2,
+                       part_i, sep, isep);
+    UAVAC_HIP(ctx, hipGetLastError());
+    return UAVAC_OK;
+}

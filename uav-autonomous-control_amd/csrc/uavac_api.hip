@@ -395,6 +395,9 @@ int uavac_set_option(uavac_ctx *ctx, const char *name, int value) {
     } else if (n == "audit_lanes") {
         if (value != 16 && value != 64) return uavac_fail(ctx, UAVAC_EINVAL, "audit_lanes is 16 or 64");
         ctx->audit_lanes = value;
+    } else if (n == "separation_split") {
+        if (value < 0 || value > UAVAC_SEP_MAX_SPLIT) return uavac_fail(ctx, UAVAC_EINVAL, "separation_split is 0 (automatic) or 1 .. UAVAC_SEP_MAX_SPLIT");
+        ctx->separation_split = value;
     } else if (n == "timeopt_chunk") {
         if (value < 0) return uavac_fail(ctx, UAVAC_EINVAL, "timeopt_chunk is 0 (automatic) or a number of missions");
         ctx->timeopt_chunk = value;
@@ -836,6 +839,18 @@ int uavac_minsnap_audit_dev(uavac_ctx *ctx, const double *coeffs, const int32_t 
     if (n_cuboids == 0 ? (cuboids || hit_rows || first_hit) : (!cuboids || !hit_rows || !first_hit))
         return uavac_fail(ctx, UAVAC_EINVAL, "cuboids, hit_rows and first_hit go with n_cuboids > 0: all three or none");
     return uavac_launch_audit(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, cuboids, n_cuboids, audit, hit_rows, first_hit);
+}
+
+int uavac_minsnap_separation_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                 double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double *sep,
+                                 int32_t *isep) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
+    if (!seg_rows || !sep || !isep) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
+    if (!std::isfinite(radius) || radius < 0.0) return uavac_fail(ctx, UAVAC_EINVAL, "radius must be finite and >= 0");
+    if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
+    return uavac_launch_separation(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, sep, isep);
 }
 
 int uavac_minsnap_row_offsets_dev(uavac_ctx *ctx, const int32_t *seg_rows, int B, int m, int64_t *row_offsets) {

@@ -34,6 +34,7 @@ struct uavac_ctx {
     int sampler_group = 1;           // tuning: consecutive missions per workgroup of the streaming sampler
     int yaw_group = 8;               // tuning: chunks of the sampler's dense yaw column that leave together (1, 4, 8, 16)
     int audit_lanes = 16;            // tuning: lanes of a wavefront that walk one mission in the plan audit: 16 or 64 (minsnap_audit.hip; same results)
+    int separation_split = 0;        // tuning: workgroups that share the j-tiles of one window of the separation audit (minsnap_separation.hip; same results); 0 = sized from the batch
     int timeopt_chunk = 0;           // tuning: missions per chunk of the duration optimisation (minsnap_timeopt.hip; same results); 0 = sized from UAVAC_TIMEOPT_SCRATCH_BYTES
     int rollout_align = 1;          // tuning: launch the 2-wave aligner kernel before a logged launch of shape 1
     int late_handover = -1;          // tuning: -1 = the launcher picks per launch; 0 / 1 = slab handed over at the end of the tick / a third of a tick later
@@ -224,6 +225,9 @@ int uavac_launch_first_yaw(uavac_ctx *ctx, const double *coeffs, const int32_t *
 // hit_rows / first_hit [n_cuboids][B]
 int uavac_launch_audit(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                        double dt, const double *cuboids, int n_cuboids, double *audit, int32_t *hit_rows, int32_t *first_hit);
+// the fleet's audit against itself (minsnap_separation.hip): sep [B], isep [UAVAC_SEP_ROWS][B]; scratch from the ctx arena
+int uavac_launch_separation(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
+                            const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double *sep, int32_t *isep);
 // Retiming factors from an audit block (minsnap_retime.hip): factors [B], counters [2] += {missions slowed down, missions with a
 // NaN peak}; apply != 0 divides the velocities of the missions over a limit by their factor.  The loop's extras (each may be NULL):
 // factors_total [B] *= the factor applied (NaN for a NaN mission), converged [B] = 1 where the factor is 1.0, else 0.

@@ -178,6 +178,20 @@ class PlanAudit:
 
 
 @dataclass
+class SeparationAudit:
+    """The fleet's audit against itself (`Engine.separation`, include/uavac.h uavac_minsnap_separation_dev): device tensors, per
+    mission over the shared row clock of its group.  An excluded mission (no rows, or a coefficient that is not finite) reports NaN /
+    -1 / -1 / 0 / -1 / 0.  `uav_ac.scoring.separation_ok` turns it into verdicts."""
+    min_distance: "object"   # (B,) f64: closest approach to any other mission of the group; +inf when there was nobody to compare with
+    partner: "object"        # (B,) i32: batch index of that mission (-1 with +inf / NaN)
+    row: "object"            # (B,) i32: clock row of the closest approach (-1 with +inf / NaN)
+    conflicts: "object"      # (B,) i32: how many other missions come inside the radius
+    first_conflict: "object"  # (B,) i32: first clock row with anybody inside the radius (-1: none)
+    compared: "object"       # (B,) i32: how many partners the mission was compared with (group size - 1 unless some are excluded)
+    block: "object" = None   # the [SEP_ROWS][B] i32 block the five rows above are views of
+
+
+@dataclass
 class RetimeResult:
     """What `Engine.retime` returns: the plan at speeds that keep every converged mission inside the flight limits."""
     plan: "object"           # of the kind that was given (Plan / RaggedBatch / RaggedPlan), planned at `velocities`; with rows if it had rows
@@ -597,6 +611,45 @@ class Engine:
                       B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(cub) if n else None, n, _ptr(block),
                       _ptr(hit_rows) if n else None, _ptr(first_hit) if n else None)
         return PlanAudit(*block.unbind(0), hit_rows, first_hit, block)
+
+    def separation(self, plan, radius: float, groups=None, start_rows=None) -> SeparationAudit:
+        """The plan's missions audited against each other (`uavac_minsnap_separation_dev`): per mission the closest approach to any
+        other mission of its group, to which one and at which row of the group's shared clock, how many others come inside `radius`
+        (metres) and when the first one does -- computed from coefficients and row counts, bit for bit what NumPy gives on the sampled
+        rows (`uav_ac.scoring.separation_from_rows`).  `plan`: what `Engine.audit` takes (a Plan with rows or rows-free, a RaggedBatch,
+        a RaggedPlan through its batch).  `groups`: None = all missions share one airspace; an int = consecutive groups of that many
+        missions (the last one shorter); or the offsets (G + 1,) themselves, ascending from 0 to B (array or tensor).  `start_rows`
+        (B,) i32: the clock row at which each mission starts (None: all 0); before it a mission waits on its first row, after its end
+        it holds its last.  Never reads `plan.traj`; stream-ordered like the other _dev calls, no sync."""
+        torch = self._torch
+        if isinstance(plan, RaggedPlan):
+            batch = plan.batch
+            if batch is None:
+                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
+            plan = batch
+        ragged = hasattr(plan, "seg_offsets")
+        B = int(plan.B)
+        go, G = None, 0
+        if groups is not None:
+            if isinstance(groups, (int, np.integer)):
+                if groups < 1:
+                    raise ValueError("a group size must be >= 1")
+                groups = list(range(0, B, int(groups))) + [B]
+            go = self._dev(groups, torch.int64).reshape(-1)
+            G = int(go.numel()) - 1
+            if G < 1:
+                raise ValueError("group offsets hold at least two entries")
+        start = None
+        if start_rows is not None:
+            start = self._dev(start_rows, torch.int32).reshape(-1)
+            if start.numel() != B:
+                raise ValueError(f"one start row per mission: expected {B}, got {start.numel()}")
+        sep = torch.empty((B,), dtype=torch.float64, device=self.device)
+        block = torch.empty((nat.SEP_ROWS, B), dtype=torch.int32, device=self.device)
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_separation_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
+                      B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(go), G, _ptr(start), float(radius), _ptr(sep), _ptr(block))
+        return SeparationAudit(sep, *block.unbind(0), block)
 
     DEFAULT_RETIME_MARGIN = 1e-3
 

@@ -11,6 +11,10 @@ distance to the goal < 0.5 m, no collision.  `summarize` turns a score block int
 uavac_minsnap_audit_dev) with the flight limits the control law clips its targets to.  `retime_factors` says by how much each
 mission has to be slowed down to pass it: the CPU statement of the rule the retiming kernel implements (include/uavac.h
 uavac_minsnap_retime_factors_dev), NumPy on the host, bit for bit.
+
+`separation_from_rows` is the same kind of statement for the fleet's audit against itself (`Engine.separation`, include/uavac.h
+uavac_minsnap_separation_dev): closest approach, partner, clock row, conflicts inside a radius, recomputed from sampled rows in NumPy,
+bit for bit; `separation_ok` judges a separation audit.
 """
 from __future__ import annotations
 
@@ -143,3 +147,90 @@ def retime_factors(audit, vehicle=None, margin: float = DEFAULT_RETIME_MARGIN, v
         v[retimed] = v[retimed] / factors[retimed]
         out["velocities"] = v
     return out
+
+
+SEP_PARTNER, SEP_ROW, SEP_CONFLICTS, SEP_FIRST_CONFLICT, SEP_COMPARED = range(nat.SEP_ROWS)      # isep rows (include/uavac.h)
+
+
+def separation_from_rows(rows, row_offsets, radius, group_offsets=None, start_rows=None):
+    """The separation audit recomputed from SAMPLED rows -- the SPECIFICATION of `uavac_minsnap_separation_dev`
+    (csrc/minsnap_separation.hip), which is tested against it bit for bit.  NumPy on the host.
+    `rows` (N, >= 3): positions in columns 0-2, missions back to back; `row_offsets` (B + 1,); `group_offsets` (G + 1,) or None = one
+    group; `start_rows` (B,) or None = all 0 (a negative one counts as 0).
+
+    The missions of a group share a row clock k = 0, 1, ...; mission b stands at its own row clamp(k - S_b, 0, N_b - 1) -- it waits on
+    its first row before its start and holds its last row after its end -- and every pair of the group is compared at every k below
+    the horizon H_g = max(S_b + N_b).  A mission without rows or with a position that is not finite (what a non-finite coefficient
+    gives) is EXCLUDED: compared with nobody, it reports NaN / -1 / -1 / 0 / -1 / 0.  Rounding and ties as the kernel has them: d^2 =
+    (dx * dx + dy * dy) + dz * dz with separately rounded products and sums, the minimum taken of the squares, one sqrt at the end, r^2 =
+    radius * radius, inside means d^2 < r^2 strictly, and the minimum is the lexicographic one of (d^2, clock row, partner index).
+    -> (sep (B,) f64, isep (SEP_ROWS, B) i32): minimum distance (+inf: nobody to compare with); partner, clock row of the minimum (-1
+    with +inf / NaN), conflicts (partners that come inside the radius), first clock row with a partner inside (-1: none), compared."""
+    rows = _host(rows)
+    ro = np.asarray(row_offsets.detach().cpu().numpy() if hasattr(row_offsets, "detach") else row_offsets, dtype=np.int64).reshape(-1)
+    B = len(ro) - 1
+    radius = float(radius)
+    if not (np.isfinite(radius) and radius >= 0.0):
+        raise ValueError("radius must be finite and >= 0")
+    go = np.array([0, B], dtype=np.int64) if group_offsets is None else np.asarray(
+        group_offsets.detach().cpu().numpy() if hasattr(group_offsets, "detach") else group_offsets, dtype=np.int64).reshape(-1)
+    if len(go) < 2 or go[0] != 0 or go[-1] != B or (np.diff(go) < 0).any():
+        raise ValueError("group_offsets must ascend from 0 to B")
+    S = np.zeros(B, dtype=np.int64) if start_rows is None else np.maximum(0, np.asarray(
+        start_rows.detach().cpu().numpy() if hasattr(start_rows, "detach") else start_rows, dtype=np.int64).reshape(-1))
+    if len(S) != B:
+        raise ValueError("one start row per mission")
+    r2 = radius * radius
+    N = np.diff(ro)
+    pos = [rows[ro[b]:ro[b + 1], 0:3] for b in range(B)]
+    included = np.array([N[b] > 0 and bool(np.isfinite(pos[b]).all()) for b in range(B)], dtype=bool)
+    sep = np.full(B, np.nan)
+    isep = np.zeros((nat.SEP_ROWS, B), dtype=np.int32)
+    isep[[SEP_PARTNER, SEP_ROW, SEP_FIRST_CONFLICT]] = -1
+    for g in range(len(go) - 1):
+        members = [b for b in range(int(go[g]), int(go[g + 1])) if included[b]]
+        if not members:
+            continue
+        H = int(max(S[b] + N[b] for b in members))
+        k = np.arange(H)
+        P = np.stack([pos[b][np.clip(k - S[b], 0, N[b] - 1)] for b in members])          # (n, H, 3): where everybody stands at clock row k
+        idx = np.asarray(members)
+        for a, b in enumerate(members):
+            isep[SEP_COMPARED, b] = len(members) - 1
+            if len(members) == 1:
+                sep[b] = np.inf
+                continue
+            others = np.delete(np.arange(len(members)), a)
+            dx, dy, dz = (P[a, :, c][:, None] - P[others, :, c].T for c in range(3))     # (H, n - 1): rows first, partners ascending
+            d2 = (dx * dx + dy * dy) + dz * dz
+            flat = int(np.argmin(d2))                                                     # the first minimum: lowest row, then lowest partner
+            row, j = divmod(flat, len(others))
+            sep[b] = np.sqrt(d2[row, j])
+            isep[SEP_PARTNER, b], isep[SEP_ROW, b] = idx[others[j]], row
+            inside = d2 < r2
+            isep[SEP_CONFLICTS, b] = int(inside.any(axis=0).sum())
+            hit_rows = np.flatnonzero(inside.any(axis=1))
+            isep[SEP_FIRST_CONFLICT, b] = hit_rows[0] if len(hit_rows) else -1
+    return sep, isep
+
+
+def separation_ok(sep, group_sizes=None) -> dict:
+    """A separation audit (`Engine.separation` -> SeparationAudit, or anything with `min_distance`, `conflicts` and `compared`; tensors
+    on any device or arrays) -> dict of (B,) bool host arrays: `clear` (nobody comes inside the radius: conflicts == 0), `complete`
+    (the mission was compared with every other mission of its group: compared == size - 1; needs `group_sizes`, the size of each
+    mission's group, (B,) or one number -- without it `complete` is all False) and `ok` (both).  A mission whose minimum distance is NaN
+    -- an excluded one: no rows, or a singular plan -- fails all three: a plan that was not checked never looks clear."""
+    dist = _host(sep.min_distance).reshape(-1)
+    conflicts = np.asarray(_host(sep.conflicts)).reshape(-1)
+    compared = np.asarray(_host(sep.compared)).reshape(-1)
+    finite = ~np.isnan(dist)
+    clear = finite & (conflicts == 0)
+    if group_sizes is None:
+        complete = np.zeros(len(dist), dtype=bool)
+    else:
+        sizes = np.broadcast_to(np.asarray(_host(group_sizes)).reshape(-1), dist.shape) if np.size(group_sizes) == 1 else \
+            np.asarray(_host(group_sizes)).reshape(-1)
+        if len(sizes) != len(dist):
+            raise ValueError("one group size per mission (or one number)")
+        complete = finite & (compared == sizes - 1)
+    return {"clear": clear, "complete": complete, "ok": clear & complete}
