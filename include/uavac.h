@@ -346,6 +346,49 @@ int uavac_minsnap_separation_dev(uavac_ctx *ctx, const double *coeffs, const int
                                  double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double *sep,
                                  int32_t *isep);
 
+/* STAGGER: the call that acts on the separation audit's verdict -- prioritised deconfliction by start delay.  Within a group the
+ * missions are taken in ascending batch index, which is the priority (the lowest index is never delayed), and each one is granted the
+ * smallest start delay that keeps it outside the protection radius of every mission decided before it -- from coefficients and row
+ * counts alone (csrc/minsnap_stagger.hip): no row is written, nothing is read back, everything is enqueued on the ctx stream, scratch
+ * comes from the ctx arena.  coeffs / seg_rows / seg_offsets / B / m / dt / group_offsets / G / start_rows / radius exactly as in
+ * uavac_minsnap_separation_dev, and CLOCK, GROUPS, EXCLUDED MISSIONS and ROUNDING are the ones stated there: mission b with start s
+ * stands at its own row clamp(k - s, 0, N_b - 1); d^2 = (dx * dx + dy * dy) + dz * dz without contraction; r^2 = radius * radius
+ * rounded once; inside means d^2 < r^2, strictly.  start_rows[b] is the BASE start S_b (NULL: all 0), clamped to 0 .. 2^29.
+ * THE RULE.  Per group, the included missions in ascending batch index.  Mission i examines the candidates q = 0, 1, ..., max_steps in
+ * that order; candidate q has start s = S_i + q * step.  A candidate is CLEAR iff for every included mission j < i of the group, at
+ * its granted start T_j, and every clock row k in [0, max(s + N_i, T_j + N_j)) the two are not inside the radius (past that row both
+ * hold their last rows, so any longer horizon gives the same answer; before min(s, T_j) both wait on their first rows).  The first
+ * clear candidate is granted: T_i = s, steps = q.  If none is clear the mission is UNRESOLVED: steps = -1, T_i = S_i -- it stays where
+ * it was and remains a partner for every later mission.
+ * OUTPUT istag [UAVAC_STAGGER_ROWS][B] i32 (device), per mission b:  0 the granted start row T_b      1 steps, the candidate index
+ * granted; -1 = unresolved; -2 = not examined (an excluded mission, or a group above UAVAC_STAGGER_MAX_GROUP)      2 earlier = the
+ * number of missions it was checked against: the included missions before it in its group, so a skipped neighbour is visible like
+ * `compared` in the audit.  A mission that was not examined reports its clamped base start, -2 and 0, and nobody is checked against
+ * an excluded one.
+ * Every output is an integer decided by comparisons of d^2 with r^2 on the audit's arithmetic, so it is exactly what NumPy gives on
+ * the sampled rows (uav_ac.scoring.stagger_from_rows), whatever else is in the batch: a group staggered alone gives the same numbers.
+ * WHAT THE RESULT GUARANTEES.  uavac_minsnap_separation_dev on the same plan, groups and radius with start_rows = istag[0] finds no
+ * pair of RESOLVED missions (steps >= 0) inside the radius; in a group all of whose missions are resolved, conflicts == 0 everywhere.
+ * WHAT IT IS NOT.  A greedy answer in priority order, not a minimum of the total delay; a later mission never moves an earlier one.
+ * Two missions that share a first or last waypoint can never be resolved by waiting: they wait on, or hold, the same point.  Flying
+ * a delayed start is not part of this library's rollout: the result feeds the audit and whoever schedules the launches.
+ * Cost: about 13 fp64 operations per (mission, candidate lane, earlier partner, clock row); 64 candidates ride in the lanes of one
+ * pass, so a mission that is clear at q = 0 costs one pass over its earlier partners; one workgroup per group, the missions of a
+ * group one after the other.
+ * BAD INPUTS.  As in the audit a start_rows[b] outside 0 .. 2^29 is clamped and raises sticky flag 0, and a mission of more than 2^29
+ * rows is excluded and raises it.  A group of more than UAVAC_STAGGER_MAX_GROUP missions (its offsets are on the device) cannot be
+ * refused by the host: all of its missions report their base start, -2 and 0, flag 0 is raised, the other groups are unaffected.
+ * UAVAC_EINVAL before anything is enqueued: everything uavac_minsnap_separation_dev refuses (no context, a NULL required pointer --
+ * coeffs, seg_rows, istag --, B < 1, m outside 1 .. UAVAC_MAX_SEGMENTS, dt not positive and finite, radius negative or not finite,
+ * G < 1 when group_offsets != NULL), step < 1, max_steps outside 0 .. UAVAC_STAGGER_MAX_STEPS, (long long)step * max_steps > 2^29,
+ * group_offsets == NULL with B > UAVAC_STAGGER_MAX_GROUP. */
+#define UAVAC_STAGGER_ROWS 3
+#define UAVAC_STAGGER_MAX_STEPS 1023
+#define UAVAC_STAGGER_MAX_GROUP 256
+int uavac_minsnap_stagger_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                              double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius,
+                              int step, int max_steps, int32_t *istag);
+
 /* ONE CRUISE SPEED PER MISSION: the _v twins of uavac_minsnap_row_counts_dev, uavac_minsnap_row_counts_ragged_dev and
  * uavac_minsnap_plan_dev (both of its forms: rows with a capacity and flag 2 and the same all-or-nothing commit, and rows-free with
  * traj == NULL) take velocities [B] (device) where those take `velocity` -- what a fleet of MinimumSnap(path, obstacles, velocity,

@@ -853,6 +853,23 @@ int uavac_minsnap_separation_dev(uavac_ctx *ctx, const double *coeffs, const int
     return uavac_launch_separation(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, sep, isep);
 }
 
+int uavac_minsnap_stagger_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                              double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, int step,
+                              int max_steps, int32_t *istag) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
+    if (!seg_rows || !istag) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
+    if (!std::isfinite(radius) || radius < 0.0) return uavac_fail(ctx, UAVAC_EINVAL, "radius must be finite and >= 0");
+    if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
+    if (step < 1) return uavac_fail(ctx, UAVAC_EINVAL, "step must be >= 1");
+    if (max_steps < 0 || max_steps > UAVAC_STAGGER_MAX_STEPS) return uavac_fail(ctx, UAVAC_EINVAL, "max_steps must be in [0, UAVAC_STAGGER_MAX_STEPS]");
+    if ((long long)step * max_steps > (1LL << 29)) return uavac_fail(ctx, UAVAC_EINVAL, "step * max_steps must not exceed 2^29 rows");
+    if (!group_offsets && B > UAVAC_STAGGER_MAX_GROUP)
+        return uavac_fail(ctx, UAVAC_EINVAL, "one group of all B: B must not exceed UAVAC_STAGGER_MAX_GROUP");
+    return uavac_launch_stagger(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, step, max_steps, istag);
+}
+
 int uavac_minsnap_row_offsets_dev(uavac_ctx *ctx, const int32_t *seg_rows, int B, int m, int64_t *row_offsets) {
     UAVAC_ENTER(ctx);
     if (int rc = check_plan_args(ctx, seg_rows, B, m)) return rc;

@@ -228,6 +228,10 @@ int uavac_launch_audit(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_
 // the fleet's audit against itself (minsnap_separation.hip): sep [B], isep [UAVAC_SEP_ROWS][B]; scratch from the ctx arena
 int uavac_launch_separation(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
                             const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double *sep, int32_t *isep);
+// the call that acts on it (minsnap_stagger.hip): start delays by priority, istag [UAVAC_STAGGER_ROWS][B]; scratch from the ctx arena
+int uavac_launch_stagger(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
+                         const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, int step, int max_steps,
+                         int32_t *istag);
 // Retiming factors from an audit block (minsnap_retime.hip): factors [B], counters [2] += {missions slowed down, missions with a
 // NaN peak}; apply != 0 divides the velocities of the missions over a limit by their factor.  The loop's extras (each may be NULL):
 // factors_total [B] *= the factor applied (NaN for a NaN mission), converged [B] = 1 where the factor is 1.0, else 0.

@@ -140,6 +140,27 @@ def check_separation_kernels():
     return {n: v for n, v, _ in regs}
 
 
+STAGGER_KERNELS = ("stagger_prepass_kernel", "minsnap_stagger_kernel")
+
+
+def check_stagger_kernels():
+    """The kernels of csrc/minsnap_stagger.hip (start delays that clear the separation audit): both must be there, none may spill or
+    use scratch memory at all (zero private-segment bytes: the two coefficient sets of the decision kernel are indexed by constants
+    only), and the decision kernel, whose 48 KB LDS tile plus 1 KB of granted starts admits three workgroups per CU, must run three
+    waves per SIMD (<= 168 vector registers; built: 129, the pre-pass 14).  Returns {kernel: VGPRs}, None when the counts cannot be
+    read."""
+    obj = os.path.join(PKG, "build", "minsnap_stagger.o")
+    regs, priv = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel")
+    if regs is None or priv is None:
+        return None
+    bad = [(n[:70], v, sp, 168) for n, v, sp in regs if v > 168 or sp] + [(n[:70], f"{p} private-segment bytes", 0, 0) for n, p in priv if p]
+    missing = [k for k in STAGGER_KERNELS if not any(k in n for n, _, _ in regs)]
+    if bad or missing or len(regs) != len(STAGGER_KERNELS) or len(priv) != len(regs):
+        raise RuntimeError(f"stagger kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
+                           f"{len(regs)} kernels found (compiler: {compiler_version()})")
+    return {n: v for n, v, _ in regs}
+
+
 def check_rollout_registers(obj: str = None):
     """Raise RuntimeError when a rollout variant needs more than 256 vector registers or spills any; returns the counts."""
     counts = rollout_register_counts(obj)
@@ -383,13 +404,15 @@ def run_all(verbose: bool = False, write_stamp: bool = True) -> dict:
              ("timeopt_kernels", check_timeopt_kernels,
               lambda r: f"{len(r)} time-optimisation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("separation_kernels", check_separation_kernels,
-              lambda r: f"{len(r)} separation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"))
+              lambda r: f"{len(r)} separation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
+             ("stagger_kernels", check_stagger_kernels,
+              lambda r: f"{len(r)} stagger kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"))
     for key, fn, say in steps:
         r = fn()
         if r is None:
             raise RuntimeError(f"build check '{key}' could not run (object files under {PKG}/build or the LLVM tools under {LLVM_BIN} are "
                                "missing): the library would ship unchecked")
-        result[key] = len(r) if isinstance(r, list) else r      # (the time-optimisation and separation checks: their {kernel: VGPRs} records)
+        result[key] = len(r) if isinstance(r, list) else r      # (the time-optimisation, separation and stagger checks: their {kernel: VGPRs} records)
         if verbose:
             print(f"build: {say(r)}")
     lib_path = os.path.join(PKG, "lib", "libuavac.so")

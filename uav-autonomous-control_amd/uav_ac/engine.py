@@ -192,6 +192,17 @@ class SeparationAudit:
 
 
 @dataclass
+class StaggerResult:
+    """Start delays that clear the separation audit (`Engine.stagger`, include/uavac.h uavac_minsnap_stagger_dev): device tensors, per
+    mission.  `Engine.separation(plan, radius, groups, start_rows=result.start_rows)` confirms it; `uav_ac.scoring.stagger_ok` turns
+    it into verdicts."""
+    start_rows: "object"     # (B,) i32: the granted start row (the base start for an unresolved or unexamined mission)
+    steps: "object"          # (B,) i32: the candidate index granted (delay = steps * step rows); -1 unresolved; -2 not examined
+    earlier: "object"        # (B,) i32: how many missions it was checked against (the included missions before it in its group)
+    block: "object" = None   # the [STAGGER_ROWS][B] i32 block the three rows above are views of
+
+
+@dataclass
 class RetimeResult:
     """What `Engine.retime` returns: the plan at speeds that keep every converged mission inside the flight limits."""
     plan: "object"           # of the kind that was given (Plan / RaggedBatch / RaggedPlan), planned at `velocities`; with rows if it had rows
@@ -650,6 +661,62 @@ class Engine:
         self.ctx.call("uavac_minsnap_separation_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
                       B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(go), G, _ptr(start), float(radius), _ptr(sep), _ptr(block))
         return SeparationAudit(sep, *block.unbind(0), block)
+
+    def stagger(self, plan, radius: float, groups=None, start_rows=None, step: int = 1, max_steps: int = 255) -> StaggerResult:
+        """Prioritised deconfliction by start delay (`uavac_minsnap_stagger_dev`): the call that acts on `Engine.separation`'s
+        verdict.  Within a group the missions are taken in ascending batch index -- the lowest index is never delayed --, and each
+        gets the smallest start `start_rows[b] + q * step`, q = 0 .. `max_steps`, that keeps it outside `radius` of every mission
+        decided before it over the whole shared clock; a mission for which no candidate is clear stays at its base start with
+        steps = -1 (two missions that share a first or last waypoint can never be resolved by waiting).  A greedy answer in priority
+        order, not a minimum of the total delay.  Exactly what NumPy gives on the sampled rows (`uav_ac.scoring.stagger_from_rows`).
+        `plan`, `groups` and `start_rows` (the BASE starts) as `Engine.separation` takes them; a group of more than
+        `STAGGER_MAX_GROUP` missions is a ValueError when the groups are given as an int or on the host -- offsets that are a device
+        tensor go through, the missions of such a group report steps = -2 and sticky flag 0 is raised (`take_flags`).  Never reads
+        `plan.traj`; stream-ordered, no sync.  Confirm with `Engine.separation(plan, radius, groups, start_rows=result.start_rows)`:
+        no pair of resolved missions is inside the radius.  The rollout has no start row: flying the delays is the scheduler's job."""
+        torch = self._torch
+        if isinstance(plan, RaggedPlan):
+            batch = plan.batch
+            if batch is None:
+                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
+            plan = batch
+        ragged = hasattr(plan, "seg_offsets")
+        B = int(plan.B)
+        step, max_steps = int(step), int(max_steps)
+        if step < 1:
+            raise ValueError("step must be >= 1")
+        if not (0 <= max_steps <= nat.STAGGER_MAX_STEPS):
+            raise ValueError(f"max_steps must be in 0 .. {nat.STAGGER_MAX_STEPS}")
+        if step * max_steps > 2 ** 29:
+            raise ValueError("step * max_steps must not exceed 2^29 rows")
+        go, G = None, 0
+        if groups is None:
+            if B > nat.STAGGER_MAX_GROUP:
+                raise ValueError(f"one group of {B} missions; at most {nat.STAGGER_MAX_GROUP} per group")
+        else:
+            if isinstance(groups, (int, np.integer)):
+                if groups < 1:
+                    raise ValueError("a group size must be >= 1")
+                groups = list(range(0, B, int(groups))) + [B]
+            if not (hasattr(groups, "is_cuda") and groups.is_cuda):
+                sizes = np.diff(np.asarray(groups.numpy() if hasattr(groups, "numpy") else groups, dtype=np.int64).reshape(-1))
+                if sizes.size and sizes.max() > nat.STAGGER_MAX_GROUP:
+                    raise ValueError(f"a group of {int(sizes.max())} missions; at most {nat.STAGGER_MAX_GROUP} per group")
+            go = self._dev(groups, torch.int64).reshape(-1)
+            G = int(go.numel()) - 1
+            if G < 1:
+                raise ValueError("group offsets hold at least two entries")
+        start = None
+        if start_rows is not None:
+            start = self._dev(start_rows, torch.int32).reshape(-1)
+            if start.numel() != B:
+                raise ValueError(f"one start row per mission: expected {B}, got {start.numel()}")
+        block = torch.empty((nat.STAGGER_ROWS, B), dtype=torch.int32, device=self.device)
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_stagger_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
+                      B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(go), G, _ptr(start), float(radius), step, max_steps,
+                      _ptr(block))
+        return StaggerResult(*block.unbind(0), block)
 
     DEFAULT_RETIME_MARGIN = 1e-3
 

@@ -14,7 +14,8 @@ uavac_minsnap_retime_factors_dev), NumPy on the host, bit for bit.
 
 `separation_from_rows` is the same kind of statement for the fleet's audit against itself (`Engine.separation`, include/uavac.h
 uavac_minsnap_separation_dev): closest approach, partner, clock row, conflicts inside a radius, recomputed from sampled rows in NumPy,
-bit for bit; `separation_ok` judges a separation audit.
+bit for bit; `separation_ok` judges a separation audit.  `stagger_from_rows` states the rule of the call that acts on that audit
+(`Engine.stagger`, uavac_minsnap_stagger_dev: start delays by priority) on sampled rows, and `stagger_ok` judges its result.
 """
 from __future__ import annotations
 
@@ -234,3 +235,91 @@ def separation_ok(sep, group_sizes=None) -> dict:
             raise ValueError("one group size per mission (or one number)")
         complete = finite & (compared == sizes - 1)
     return {"clear": clear, "complete": complete, "ok": clear & complete}
+
+
+STAG_START, STAG_STEPS, STAG_EARLIER = range(nat.STAGGER_ROWS)                                   # istag rows (include/uavac.h)
+_MAX_CLOCK = 1 << 29
+
+
+def stagger_from_rows(rows, row_offsets, radius, group_offsets=None, start_rows=None, step=1, max_steps=255):
+    """Prioritised deconfliction by start delay, decided on SAMPLED rows -- the SPECIFICATION of `uavac_minsnap_stagger_dev`
+    (csrc/minsnap_stagger.hip), which is tested against it exactly.  NumPy on the host.
+    `rows`, `row_offsets`, `radius`, `group_offsets` as `separation_from_rows` takes them, and the clock, the excluded missions and
+    the arithmetic are the same: mission b with start s stands at its own row clamp(k - s, 0, N_b - 1); d^2 = (dx * dx + dy * dy) +
+    dz * dz; r^2 = radius * radius; inside means d^2 < r^2 strictly.  `start_rows` (B,) or None = all 0: the BASE starts S_b, clamped
+    to 0 .. 2^29.
+
+    Per group the included missions in ascending batch index -- the priority: the lowest index is never delayed.  Mission i examines
+    the candidates q = 0, 1, ..., max_steps in that order, candidate q with start s = S_i + q * step; it is clear iff for every
+    included mission j < i of the group at its granted start T_j and every clock row k in [0, max(s + N_i, T_j + N_j)) the two are
+    not inside the radius (past that row both hold their last rows: any longer horizon gives the same answer).  The first clear
+    candidate is granted: T_i = s, steps = q; if none is clear the mission is unresolved: steps = -1, T_i = S_i, and it remains a
+    partner for every later mission.  An excluded mission, and every mission of a group of more than STAGGER_MAX_GROUP, is not
+    examined: its clamped base start, steps = -2, earlier = 0; nobody is checked against an excluded mission.
+    -> istag (STAGGER_ROWS, B) i32: the granted start row; steps; earlier (how many missions it was checked against)."""
+    rows = _host(rows)
+    ro = np.asarray(row_offsets.detach().cpu().numpy() if hasattr(row_offsets, "detach") else row_offsets, dtype=np.int64).reshape(-1)
+    B = len(ro) - 1
+    radius, step, max_steps = float(radius), int(step), int(max_steps)
+    if not (np.isfinite(radius) and radius >= 0.0):
+        raise ValueError("radius must be finite and >= 0")
+    if step < 1 or not (0 <= max_steps <= nat.STAGGER_MAX_STEPS) or step * max_steps > _MAX_CLOCK:
+        raise ValueError(f"step must be >= 1, max_steps in 0 .. {nat.STAGGER_MAX_STEPS}, step * max_steps at most 2^29")
+    go = np.array([0, B], dtype=np.int64) if group_offsets is None else np.asarray(
+        group_offsets.detach().cpu().numpy() if hasattr(group_offsets, "detach") else group_offsets, dtype=np.int64).reshape(-1)
+    if len(go) < 2 or go[0] != 0 or go[-1] != B or (np.diff(go) < 0).any():
+        raise ValueError("group_offsets must ascend from 0 to B")
+    S = np.zeros(B, dtype=np.int64) if start_rows is None else np.clip(np.asarray(
+        start_rows.detach().cpu().numpy() if hasattr(start_rows, "detach") else start_rows, dtype=np.int64).reshape(-1), 0, _MAX_CLOCK)
+    if len(S) != B:
+        raise ValueError("one start row per mission")
+    r2 = radius * radius
+    N = np.diff(ro)
+    pos = [rows[ro[b]:ro[b + 1], 0:3] for b in range(B)]
+    included = np.array([0 < N[b] <= _MAX_CLOCK and bool(np.isfinite(pos[b]).all()) for b in range(B)], dtype=bool)
+    istag = np.zeros((nat.STAGGER_ROWS, B), dtype=np.int32)
+    istag[STAG_START], istag[STAG_STEPS] = S, -2
+    for g in range(len(go) - 1):
+        g0, g1 = int(go[g]), int(go[g + 1])
+        if g1 - g0 > nat.STAGGER_MAX_GROUP:
+            continue
+        done = []                                                                     # the included missions decided so far
+        T = {}
+        for i in range(g0, g1):
+            if not included[i]:
+                continue
+            istag[STAG_EARLIER, i] = len(done)
+            T[i], steps = int(S[i]), -1
+            if done:
+                h_prev = max(T[j] + int(N[j]) for j in done)
+                h_max = max(h_prev, int(S[i]) + max_steps * step + int(N[i]))
+                k = np.arange(h_max)
+                others = np.stack([pos[j][np.clip(k - T[j], 0, N[j] - 1)] for j in done])                 # (n, h_max, 3)
+            for q in range(max_steps + 1):
+                s = int(S[i]) + q * step
+                clear = True
+                if done:
+                    H = max(h_prev, s + int(N[i]))
+                    own = pos[i][np.clip(k[:H] - s, 0, N[i] - 1)]                     # (H, 3): where the candidate stands at clock row k
+                    dx, dy, dz = (own[None, :, c] - others[:, :H, c] for c in range(3))
+                    clear = not bool(((dx * dx + dy * dy) + dz * dz < r2).any())
+                if clear:
+                    T[i], steps = s, q
+                    break
+            istag[STAG_START, i], istag[STAG_STEPS, i] = T[i], steps
+            done.append(i)
+    return istag
+
+
+def stagger_ok(istag) -> dict:
+    """A stagger result (`Engine.stagger` -> StaggerResult, anything with `steps`, or the [STAGGER_ROWS][B] block itself; tensors on
+    any device or arrays) -> dict of (B,) bool host arrays: `resolved` (steps >= 0: a start was granted) and `examined` (steps !=
+    -2).  A mission that was not examined -- an excluded one, or one of an oversized group -- never looks resolved."""
+    if hasattr(istag, "steps"):
+        steps = np.asarray(_host(istag.steps)).reshape(-1)
+    else:
+        block = np.asarray(_host(istag))
+        if block.ndim != 2 or block.shape[0] != nat.STAGGER_ROWS:
+            raise ValueError(f"a stagger block is [{nat.STAGGER_ROWS}][B], got {block.shape}")
+        steps = block[STAG_STEPS]
+    return {"resolved": steps >= 0, "examined": steps != -2}
