@@ -170,7 +170,7 @@ int uavac_clock_probe_dev(uavac_ctx *ctx, int window_us, int64_t *stamps);
  * buffers, slower into most: DESIGN K2).  "audit_lanes": 16 (default) or 64 = lanes per mission of uavac_minsnap_audit_dev.
  * "timeopt_chunk": 0 (default: sized from UAVAC_TIMEOPT_SCRATCH_BYTES) or the missions per chunk of uavac_minsnap_optimize_times_dev
  * (same results).  "separation_split": 0 (default: sized from B and G) or 1 .. UAVAC_SEP_MAX_SPLIT = workgroups that share the partners
- * of one window of 64 missions in uavac_minsnap_separation_dev (same results).
+ * of one window of 64 missions in uavac_minsnap_separation_dev and uavac_flown_separation_dev (same results).
  * Defaults from the environment (UAVAC_ROLLOUT_ALIGN, UAVAC_YAW_GROUP, UAVAC_SAMPLER_WAVES, UAVAC_SAMPLER_GROUP) at uavac_create.
  * ONE option is not a tuning knob but part of the log layout: "log_pitch" = P doubles per log row,
  * 0 (default) = B.  With P >= B the rollouts write state_log [K][13][P] and cmd_log [K][12][P]
@@ -370,8 +370,8 @@ int uavac_minsnap_separation_dev(uavac_ctx *ctx, const double *coeffs, const int
  * WHAT THE RESULT GUARANTEES.  uavac_minsnap_separation_dev on the same plan, groups and radius with start_rows = istag[0] finds no
  * pair of RESOLVED missions (steps >= 0) inside the radius; in a group all of whose missions are resolved, conflicts == 0 everywhere.
  * WHAT IT IS NOT.  A greedy answer in priority order, not a minimum of the total delay; a later mission never moves an earlier one.
- * Two missions that share a first or last waypoint can never be resolved by waiting: they wait on, or hold, the same point.  Flying
- * a delayed start is not part of this library's rollout: the result feeds the audit and whoever schedules the launches.
+ * Two missions that share a first or last waypoint can never be resolved by waiting: they wait on, or hold, the same point.  To FLY
+ * the granted starts make them part of the plan (uavac_minsnap_delay_dev below): the rollout's cursor has no start row and needs none.
  * Cost: about 13 fp64 operations per (mission, candidate lane, earlier partner, clock row); 64 candidates ride in the lanes of one
  * pass, so a mission that is clear at q = 0 costs one pass over its earlier partners; one workgroup per group, the missions of a
  * group one after the other.
@@ -388,6 +388,60 @@ int uavac_minsnap_separation_dev(uavac_ctx *ctx, const double *coeffs, const int
 int uavac_minsnap_stagger_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                               double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius,
                               int step, int max_steps, int32_t *istag);
+
+/* DELAY AS A PLAN TRANSFORM: how start rows -- istag[0] of uavac_minsnap_stagger_dev, or any start_rows of the separation audit -- are
+ * flown.  Mission b of the input (coeffs / times / seg_rows / seg_offsets / B / m / dt as in uavac_minsnap_audit_dev: seg_offsets NULL =
+ * uniform, otherwise ragged with segment counts clamped to 1 .. m) has m_b segments and start row S_b = start_rows[b] (i32, device,
+ * required).  The output is a RAGGED plan (csrc/minsnap_delay.hip):
+ *   S_b == 0: the mission's m_b segments, copied as they are.
+ *   S_b  > 0: m_b + 1 segments: a HOLD segment first -- c0 = c0 of the mission's first segment bit for bit, c1 .. c7 = 0, seg_rows = S_b,
+ *             duration (double)S_b * dt -- then its own segments unchanged.
+ * The sampler therefore writes S_b hold rows -- the position c0, velocity and acceleration 0, spline id 0 -- followed by the mission's
+ * original rows bit for bit with their spline ids moved up by one.  A hold row is below MIN_HORIZONTAL_SPEED_FOR_YAW, so its yaw is
+ * the mission's first heading, as for every leading row without a heading: first_yaw [B] of the delayed plan is the input's, and every
+ * original row keeps its yaw.  (A hold row is NOT row 0 repeated: a solved mission's row 0 carries velocities of rounding size; only
+ * its position is exactly c0.)  That position is what the separation audit's clock means by "waits on its first row":
+ * uavac_minsnap_separation_dev on the delayed plan gives, bit for bit, what it gives on the input with start_rows.  A plan that starts
+ * in motion (uavac_minsnap_plan_bc_dev) is accepted: its hold stands still and its first own row moves, which is the clock's meaning too.
+ * Two calls, in the order row counts -> offsets -> allocate -> sample has everywhere here; everything is enqueued on the ctx stream and
+ * the library reads nothing back:
+ *   uavac_minsnap_delay_offsets_dev  out_seg_offsets [B+1] i64 = exclusive prefix sum of m_b + (S_b > 0).  The caller reads
+ *                                    out_seg_offsets[B], the delayed plan's segment total, to size the buffers.
+ *   uavac_minsnap_delay_dev          out_coeffs [S'][8][3], out_seg_rows [S'] and -- iff times != NULL -- out_times [S'], S' = that total.
+ * Row offsets of the result: uavac_minsnap_row_offsets_ragged_dev(out_seg_rows, out_seg_offsets, B, m + 1).
+ * BAD INPUTS follow the separation audit: a start row below 0 or above 2^29 is clamped and raises sticky flag 0 (uavac_take_flags).
+ * UAVAC_EINVAL before anything is enqueued: no context, a NULL required pointer (start_rows and out_seg_offsets; for the second call
+ * also coeffs, seg_rows, out_coeffs, out_seg_rows), B < 1, m outside 1 .. UAVAC_MAX_SEGMENTS - 1 (a delayed mission needs one more
+ * segment), dt not positive and finite, times == NULL xor out_times == NULL. */
+int uavac_minsnap_delay_offsets_dev(uavac_ctx *ctx, const int64_t *seg_offsets, int B, int m, const int32_t *start_rows,
+                                    int64_t *out_seg_offsets);
+int uavac_minsnap_delay_dev(uavac_ctx *ctx, const double *coeffs, const double *times, const int32_t *seg_rows, const int64_t *seg_offsets,
+                            int B, int m, double dt, const int32_t *start_rows, const int64_t *out_seg_offsets, double *out_coeffs,
+                            double *out_times, int32_t *out_seg_rows);
+
+/* FLOWN SEPARATION: the separation audit of a FLIGHT.  uavac_minsnap_separation_dev speaks about plans; the vehicles track them with an
+ * error.  This call reads the positions in a rollout's state log and reports, in the same terms and with the same exactness, how close
+ * the vehicles came (csrc/flown_separation.hip): nothing is read back, everything is enqueued on the ctx stream, scratch from the arena.
+ *   state_log [K][13][pitch] f64 (device) as the rollouts write it: positions are rows 0-2; pitch >= B doubles per row (option
+ *             "log_pitch"); columns B .. pitch - 1 are never read.  The CLOCK is the tick k = 0 .. K - 1 (the log's first index: clock row
+ *             of the plan = k / inner_per_outer).
+ *   group_offsets, G, radius, sep [B], isep [UAVAC_SEP_ROWS][B] exactly as in uavac_minsnap_separation_dev.
+ * For vehicle i, a partner j != i of its group and tick k: dx = xi - xj, ..., d^2 = (dx * dx + dy * dy) + dz * dz without contraction;
+ * r^2 = radius * radius rounded once; inside means d^2 < r^2, strictly.  A pair-tick is VALID iff its d^2 is not NaN.
+ *   sep       one correctly rounded sqrt of the lexicographic minimum of (d^2, tick, partner) over the valid pair-ticks
+ *   isep  0   that partner      1 that tick      2 conflicts = the partners with some valid pair-tick inside the radius
+ *         3   the first tick with anybody inside (-1: none)      4 compared = the partners with at least one valid pair-tick
+ * With no valid pair-tick at all -- a group of one, or a vehicle whose log is NaN throughout --: sep = +inf and -1 / -1 / 0 / -1 / 0.
+ * `compared` makes a vehicle whose log holds NaN visible: uav_ac.scoring.separation_ok applies unchanged.  Positions that are
+ * infinite, or whose differences overflow, are outside the contract (they do not fault).
+ * Every reduction is a lexicographic minimum, an integer sum over disjoint partners, an OR or an integer minimum, so every output is bit
+ * for bit what NumPy gives on the log (uav_ac.scoring.separation_from_log) whatever the launch shape (option "separation_split" applies
+ * as it does to the plan audit), the pitch, or what else is in the batch: a group audited alone gives the same numbers with the partner
+ * indices shifted.  Cost: pairs x ticks, about 13 fp64 operations per pair-tick; the log's positions are read once per j-tile of 64.
+ * UAVAC_EINVAL before anything is enqueued: no context, NULL state_log, sep or isep, K < 1, B < 1, pitch < B, radius negative or not
+ * finite, G < 1 when group_offsets != NULL. */
+int uavac_flown_separation_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
+                               double radius, double *sep, int32_t *isep);
 
 /* ONE CRUISE SPEED PER MISSION: the _v twins of uavac_minsnap_row_counts_dev, uavac_minsnap_row_counts_ragged_dev and
  * uavac_minsnap_plan_dev (both of its forms: rows with a capacity and flag 2 and the same all-or-nothing commit, and rows-free with

@@ -29,27 +29,24 @@
 // Every reduction is a lexicographic minimum, an integer sum over disjoint partners, an OR or an integer minimum: exact and independent
 // of order, so the outputs depend neither on P, nor on the tile or chunk sizes, nor on what else is in the batch; each output has one
 // writer and there are no atomics but the sticky flag.  The price is the factor 2 of not using d(i, j) = d(j, i).
+// The reduction itself -- the pair loop of a row, the order, the meeting of the waves, the merge of the partial records -- is in
+// separation_reduce.h, shared with the audit of a FLIGHT (flown_separation.hip), which reads its positions from a state log.
 //
 // ROUNDING (part of the contract): positions by the sampler's fma chain (minsnap_eval_pos), the distance WITHOUT contraction: dx = xi -
 // xj, ..., d^2 = (dx dx + dy dy) + dz dz, each product and sum rounded on its own.
 
 #include "uavac_internal.h"
 #include "minsnap_eval.h"
+#include "separation_reduce.h"
 
 #include <cmath>
 #include <limits>
 
 namespace {
 
-constexpr int kTile = 64;                                   // missions per i-window and per j-tile: one per lane
-constexpr int kWaves = 4;                                   // wavefronts per workgroup
-constexpr int kRows = 8;                                    // clock rows of a chunk per wavefront
-constexpr int kChunk = kWaves * kRows;                      // clock rows per chunk
-constexpr int kThreads = 64 * kWaves;
-constexpr int kRegion = kRows * kTile * 3;                  // doubles of the LDS tile per wavefront (12 KB; 48 KB per workgroup)
-constexpr int kNone = 0x7fffffff;                           // "no row / no partner" while a minimum is being formed
+using namespace sepred;                                     // the tile's shape and the reduction: shared with flown_separation.hip
+
 constexpr int kMaxClock = 1 << 29;                          // start rows and row totals above this cannot be clocked with int
-constexpr int kUnroll = 8;                                  // partners per unrolled step of the pair loop
 constexpr int kPreLanes = 16;                               // lanes per mission of the pre-pass
 
 // First segment and segment count of mission b: uniform (so == NULL) or ragged, clamped to 1 .. m like every ragged kernel clamps it.
@@ -68,11 +65,6 @@ __device__ __forceinline__ Mission mission_of(const int64_t *__restrict__ so, in
         M.m = m_uniform;
     }
     return M;
-}
-
-// (d, k, j) before (D, K, J) in the order of the contract: the smaller distance, then the lower row, then the lower partner
-__device__ __forceinline__ bool lex_less(double d, int k, int j, double D, int K, int J) {
-    return d < D || (d == D && (k < K || (k == K && j < J)));
 }
 
 // ------------------------------------------------------------------------------------------------------------------ pre-pass
@@ -110,30 +102,6 @@ __global__ void __launch_bounds__(kThreads) separation_prepass_kernel(const doub
 // the segment of a mission's row r, walked forward from where the lane stood (rows only grow): the audit's walk
 __device__ __forceinline__ void seek(const int32_t *__restrict__ rows_of, int mb, int r, int &s, int &base, int &cnt) {
     while (s + 1 < mb && r >= base + cnt) { base += cnt; ++s; cnt = rows_of[s]; }
-}
-
-// One row of the lane's own mission against the 64 positions of a j-tile at the same clock row (row [64][3] in LDS, the same for every
-// lane).  rm / rkey: the row's minimum and the tile-local partner that gave it first; mask: bit jj is set once partner jj came inside.
-template <bool SELF>
-__device__ __forceinline__ void pair_row(const double *row, double xi, double yi, double zi, double r2, int selfjj, double &rm, int &rkey,
-                                         unsigned long long &mask) {
-#pragma clang fp contract(off)
-    const double inf = std::numeric_limits<double>::infinity();
-#pragma nounroll
-    for (int q = 0; q < kTile / kUnroll; ++q) {
-        unsigned in = 0;
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            const int jj = q * kUnroll + u;
-            const double dx = xi - row[3 * jj], dy = yi - row[3 * jj + 1], dz = zi - row[3 * jj + 2];
-            const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
-            double d2 = (xx + yy) + zz;
-            if (SELF && jj == selfjj) d2 = inf;              // the lane's own mission is nobody's partner
-            if (d2 < rm) { rm = d2; rkey = jj; }
-            if (d2 < r2) in |= 1u << u;
-        }
-        mask |= (unsigned long long)in << (kUnroll * q);
-    }
 }
 
 __global__ void __launch_bounds__(kThreads, 3) minsnap_separation_kernel(
@@ -257,36 +225,18 @@ __global__ void __launch_bounds__(kThreads, 3) minsnap_separation_kernel(
                 lds_wave_fence();
             }
             // the four wavefronts meet: 1 .. 3 leave their results in their quarters, wavefront 0 merges
-            if (w != 0) {
-                int *q = reinterpret_cast<int *>(mine + 2 * kTile);
-                mine[lane] = tb;
-                reinterpret_cast<unsigned long long *>(mine)[kTile + lane] = mask;
-                q[lane] = tk; q[kTile + lane] = tj; q[2 * kTile + lane] = tfirst;
-            }
+            if (w != 0) sep_waves_leave(mine, lane, tb, tk, tj, mask, tfirst);
             __syncthreads();
             if (w == 0) {
-#pragma unroll
-                for (int v = 1; v < kWaves; ++v) {
-                    const double *o = tile + v * kRegion;
-                    const int *q = reinterpret_cast<const int *>(o + 2 * kTile);
-                    const double od = o[lane];
-                    const int ok = q[lane], oj = q[kTile + lane];
-                    if (lex_less(od, ok, oj, tb, tk, tj)) { tb = od; tk = ok; tj = oj; }
-                    mask |= reinterpret_cast<const unsigned long long *>(o)[kTile + lane];
-                    tfirst = min(tfirst, q[2 * kTile + lane]);
-                }
+                sep_waves_meet(tile, lane, tb, tk, tj, mask, tfirst);
                 gconf += __popcll(mask);
                 if (lex_less(tb, tk, tj, gb, gk, gj)) { gb = tb; gk = tk; gj = tj; }
                 gfirst = min(gfirst, tfirst);
             }
             __syncthreads();
         }
-        if (w == 0 && act) {                                 // one partial record per mission and share p (an excluded mission's is ignored)
-            const size_t at = (size_t)p * 5 * B + b;
-            part_d2[(size_t)p * B + b] = gb;
-            part_i[at] = gj; part_i[at + B] = gk; part_i[at + 2 * (size_t)B] = gconf; part_i[at + 3 * (size_t)B] = gfirst;
-            part_i[at + 4 * (size_t)B] = n_in - 1;
-        }
+        // one partial record per mission and share p (an excluded mission's is ignored); its fifth row: the partners that took part
+        if (w == 0 && act) sep_leave_partial(part_d2, part_i, p, b, B, gb, gj, gk, gconf, gfirst, n_in - 1);
     }
 }
 
@@ -302,23 +252,10 @@ __global__ void __launch_bounds__(kThreads) separation_merge_kernel(const int32_
         isep[b] = -1; isep[Bs + b] = -1; isep[2 * Bs + b] = 0; isep[3 * Bs + b] = -1; isep[4 * Bs + b] = 0;
         return;
     }
-    double d = std::numeric_limits<double>::infinity();
-    int k = kNone, j = kNone, conf = 0, first = kNone;
-    for (int p = 0; p < P; ++p) {
-        const size_t at = (size_t)p * 5 * Bs + b;
-        const double od = part_d2[(size_t)p * Bs + b];
-        const int oj = part_i[at], ok = part_i[at + Bs];
-        if (lex_less(od, ok, oj, d, k, j)) { d = od; k = ok; j = oj; }
-        conf += part_i[at + 2 * Bs];
-        first = min(first, part_i[at + 3 * Bs]);
-    }
-    const bool any = k != kNone;
-    sep[b] = sqrt(d);                                        // (+inf when no partner was compared)
-    isep[b] = any ? j : -1;
-    isep[Bs + b] = any ? k : -1;
-    isep[2 * Bs + b] = conf;
-    isep[3 * Bs + b] = first == kNone ? -1 : first;
-    isep[4 * Bs + b] = part_i[4 * Bs + b];
+    double d;
+    int k, j, conf, first;
+    sep_merge_partials(part_d2, part_i, P, b, B, d, k, j, conf, first);
+    sep_write(sep, isep, b, B, d, k, j, conf, first, part_i[4 * Bs + b]);      // (compared: the same in every share)
 }
 
 }  // namespace

@@ -870,6 +870,43 @@ int uavac_minsnap_stagger_dev(uavac_ctx *ctx, const double *coeffs, const int32_
     return uavac_launch_stagger(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, step, max_steps, istag);
 }
 
+int uavac_minsnap_delay_offsets_dev(uavac_ctx *ctx, const int64_t *seg_offsets, int B, int m, const int32_t *start_rows,
+                                    int64_t *out_seg_offsets) {
+    UAVAC_ENTER(ctx);
+    if (!start_rows || !out_seg_offsets) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
+    if (m < 1 || m > UAVAC_MAX_SEGMENTS - 1)
+        return uavac_fail(ctx, UAVAC_EINVAL, "m must be in [1, UAVAC_MAX_SEGMENTS - 1]: a delayed mission needs one more segment");
+    return uavac_launch_delay_offsets(ctx, seg_offsets, B, m, start_rows, out_seg_offsets);
+}
+
+int uavac_minsnap_delay_dev(uavac_ctx *ctx, const double *coeffs, const double *times, const int32_t *seg_rows, const int64_t *seg_offsets,
+                            int B, int m, double dt, const int32_t *start_rows, const int64_t *out_seg_offsets, double *out_coeffs,
+                            double *out_times, int32_t *out_seg_rows) {
+    UAVAC_ENTER(ctx);
+    if (!coeffs || !seg_rows || !start_rows || !out_seg_offsets || !out_coeffs || !out_seg_rows)
+        return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
+    if (m < 1 || m > UAVAC_MAX_SEGMENTS - 1)
+        return uavac_fail(ctx, UAVAC_EINVAL, "m must be in [1, UAVAC_MAX_SEGMENTS - 1]: a delayed mission needs one more segment");
+    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
+    if (!times != !out_times) return uavac_fail(ctx, UAVAC_EINVAL, "times and out_times go together: both or none");
+    return uavac_launch_delay(ctx, coeffs, times, seg_rows, seg_offsets, B, m, dt, start_rows, out_seg_offsets, out_coeffs, out_times,
+                              out_seg_rows);
+}
+
+int uavac_flown_separation_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
+                               double radius, double *sep, int32_t *isep) {
+    UAVAC_ENTER(ctx);
+    if (!state_log || !sep || !isep) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (K < 1) return uavac_fail(ctx, UAVAC_EINVAL, "K must be >= 1");
+    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
+    if (pitch < B) return uavac_fail(ctx, UAVAC_EINVAL, "pitch must be >= B");
+    if (!std::isfinite(radius) || radius < 0.0) return uavac_fail(ctx, UAVAC_EINVAL, "radius must be finite and >= 0");
+    if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
+    return uavac_launch_flown_separation(ctx, state_log, K, B, pitch, group_offsets, G, radius, sep, isep);
+}
+
 int uavac_minsnap_row_offsets_dev(uavac_ctx *ctx, const int32_t *seg_rows, int B, int m, int64_t *row_offsets) {
     UAVAC_ENTER(ctx);
     if (int rc = check_plan_args(ctx, seg_rows, B, m)) return rc;

@@ -34,7 +34,7 @@ struct uavac_ctx {
     int sampler_group = 1;           // tuning: consecutive missions per workgroup of the streaming sampler
     int yaw_group = 8;               // tuning: chunks of the sampler's dense yaw column that leave together (1, 4, 8, 16)
     int audit_lanes = 16;            // tuning: lanes of a wavefront that walk one mission in the plan audit: 16 or 64 (minsnap_audit.hip; same results)
-    int separation_split = 0;        // tuning: workgroups that share the j-tiles of one window of the separation audit (minsnap_separation.hip; same results); 0 = sized from the batch
+    int separation_split = 0;        // tuning: workgroups that share the j-tiles of one window of the separation audits (minsnap_separation.hip, flown_separation.hip; same results); 0 = sized from the batch
     int timeopt_chunk = 0;           // tuning: missions per chunk of the duration optimisation (minsnap_timeopt.hip; same results); 0 = sized from UAVAC_TIMEOPT_SCRATCH_BYTES
     int rollout_align = 1;          // tuning: launch the 2-wave aligner kernel before a logged launch of shape 1
     int late_handover = -1;          // tuning: -1 = the launcher picks per launch; 0 / 1 = slab handed over at the end of the tick / a third of a tick later
@@ -232,6 +232,15 @@ int uavac_launch_separation(uavac_ctx *ctx, const double *coeffs, const int32_t 
 int uavac_launch_stagger(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
                          const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, int step, int max_steps,
                          int32_t *istag);
+// the delays as part of the plan (minsnap_delay.hip): out_seg_offsets [B+1] = prefix sum of m_b + (S_b > 0); then the delayed plan's
+// coefficients, durations (times / out_times may both be NULL) and row counts, a leading hold segment for every mission with S_b > 0
+int uavac_launch_delay_offsets(uavac_ctx *ctx, const int64_t *seg_offsets, int B, int m, const int32_t *start_rows, int64_t *out_seg_offsets);
+int uavac_launch_delay(uavac_ctx *ctx, const double *coeffs, const double *times, const int32_t *seg_rows, const int64_t *seg_offsets, int B,
+                       int m, double dt, const int32_t *start_rows, const int64_t *out_seg_offsets, double *out_coeffs, double *out_times,
+                       int32_t *out_seg_rows);
+// the separation the fleet flew (flown_separation.hip): the audit's outputs from the positions of a state log [K][13][pitch]
+int uavac_launch_flown_separation(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
+                                  double radius, double *sep, int32_t *isep);
 // Retiming factors from an audit block (minsnap_retime.hip): factors [B], counters [2] += {missions slowed down, missions with a
 // NaN peak}; apply != 0 divides the velocities of the missions over a limit by their factor.  The loop's extras (each may be NULL):
 // factors_total [B] *= the factor applied (NaN for a NaN mission), converged [B] = 1 where the factor is 1.0, else 0.

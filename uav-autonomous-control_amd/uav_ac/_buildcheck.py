@@ -161,6 +161,45 @@ def check_stagger_kernels():
     return {n: v for n, v, _ in regs}
 
 
+FLOWN_SEPARATION_KERNELS = ("flown_separation_kernel", "flown_merge_kernel")
+
+
+def check_flown_separation_kernels():
+    """The kernels of csrc/flown_separation.hip (the separation the fleet flew, from a state log): both must be there, none may spill or
+    use scratch memory at all (zero private-segment bytes), and the pair kernel, whose 48 KB LDS tile admits three workgroups per CU
+    like the plan audit's, must run three waves per SIMD (<= 168 vector registers; built: 143, the merge 18).  Returns {kernel: VGPRs},
+    None when the counts cannot be read."""
+    obj = os.path.join(PKG, "build", "flown_separation.o")
+    regs, priv = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel")
+    if regs is None or priv is None:
+        return None
+    bad = [(n[:70], v, sp, 168) for n, v, sp in regs if v > 168 or sp] + [(n[:70], f"{p} private-segment bytes", 0, 0) for n, p in priv if p]
+    missing = [k for k in FLOWN_SEPARATION_KERNELS if not any(k in n for n, _, _ in regs)]
+    if bad or missing or len(regs) != len(FLOWN_SEPARATION_KERNELS) or len(priv) != len(regs):
+        raise RuntimeError(f"flown-separation kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
+                           f"{len(regs)} kernels found (compiler: {compiler_version()})")
+    return {n: v for n, v, _ in regs}
+
+
+DELAY_KERNELS = ("delay_counts_kernel", "minsnap_delay_kernel")
+
+
+def check_delay_kernels():
+    """The kernels of csrc/minsnap_delay.hip (start delays as a leading hold segment of the plan): both must be there, none may spill or
+    use scratch memory at all, and both are plain copies that run at least eight waves per SIMD (<= 64 vector registers; built: 24
+    each).  Returns {kernel: VGPRs}, None when the counts cannot be read."""
+    obj = os.path.join(PKG, "build", "minsnap_delay.o")
+    regs, priv = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel")
+    if regs is None or priv is None:
+        return None
+    bad = [(n[:70], v, sp, 64) for n, v, sp in regs if v > 64 or sp] + [(n[:70], f"{p} private-segment bytes", 0, 0) for n, p in priv if p]
+    missing = [k for k in DELAY_KERNELS if not any(k in n for n, _, _ in regs)]
+    if bad or missing or len(regs) != len(DELAY_KERNELS) or len(priv) != len(regs):
+        raise RuntimeError(f"delay kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
+                           f"{len(regs)} kernels found (compiler: {compiler_version()})")
+    return {n: v for n, v, _ in regs}
+
+
 def check_rollout_registers(obj: str = None):
     """Raise RuntimeError when a rollout variant needs more than 256 vector registers or spills any; returns the counts."""
     counts = rollout_register_counts(obj)
@@ -406,13 +445,17 @@ def run_all(verbose: bool = False, write_stamp: bool = True) -> dict:
              ("separation_kernels", check_separation_kernels,
               lambda r: f"{len(r)} separation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("stagger_kernels", check_stagger_kernels,
-              lambda r: f"{len(r)} stagger kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"))
+              lambda r: f"{len(r)} stagger kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
+             ("delay_kernels", check_delay_kernels,
+              lambda r: f"{len(r)} delay kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
+             ("flown_separation_kernels", check_flown_separation_kernels,
+              lambda r: f"{len(r)} flown-separation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"))
     for key, fn, say in steps:
         r = fn()
         if r is None:
             raise RuntimeError(f"build check '{key}' could not run (object files under {PKG}/build or the LLVM tools under {LLVM_BIN} are "
                                "missing): the library would ship unchecked")
-        result[key] = len(r) if isinstance(r, list) else r      # (the time-optimisation, separation and stagger checks: their {kernel: VGPRs} records)
+        result[key] = len(r) if isinstance(r, list) else r      # (the time-optimisation, separation, stagger, delay and flown-separation checks: their {kernel: VGPRs} records)
         if verbose:
             print(f"build: {say(r)}")
     lib_path = os.path.join(PKG, "lib", "libuavac.so")

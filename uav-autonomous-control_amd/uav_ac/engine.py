@@ -184,7 +184,7 @@ class SeparationAudit:
     -1 / -1 / 0 / -1 / 0.  `uav_ac.scoring.separation_ok` turns it into verdicts."""
     min_distance: "object"   # (B,) f64: closest approach to any other mission of the group; +inf when there was nobody to compare with
     partner: "object"        # (B,) i32: batch index of that mission (-1 with +inf / NaN)
-    row: "object"            # (B,) i32: clock row of the closest approach (-1 with +inf / NaN)
+    row: "object"            # (B,) i32: clock row of the closest approach (-1 with +inf / NaN); from `Engine.flown_separation`: the tick
     conflicts: "object"      # (B,) i32: how many other missions come inside the radius
     first_conflict: "object"  # (B,) i32: first clock row with anybody inside the radius (-1: none)
     compared: "object"       # (B,) i32: how many partners the mission was compared with (group size - 1 unless some are excluded)
@@ -673,7 +673,8 @@ class Engine:
         `STAGGER_MAX_GROUP` missions is a ValueError when the groups are given as an int or on the host -- offsets that are a device
         tensor go through, the missions of such a group report steps = -2 and sticky flag 0 is raised (`take_flags`).  Never reads
         `plan.traj`; stream-ordered, no sync.  Confirm with `Engine.separation(plan, radius, groups, start_rows=result.start_rows)`:
-        no pair of resolved missions is inside the radius.  The rollout has no start row: flying the delays is the scheduler's job."""
+        no pair of resolved missions is inside the radius.  To fly the granted starts make them part of the plan:
+        `Engine.delay(plan, result.start_rows)` (the rollout's cursor has no start row and needs none)."""
         torch = self._torch
         if isinstance(plan, RaggedPlan):
             batch = plan.batch
@@ -717,6 +718,97 @@ class Engine:
                       B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(go), G, _ptr(start), float(radius), step, max_steps,
                       _ptr(block))
         return StaggerResult(*block.unbind(0), block)
+
+    def delay(self, plan, start_rows, rows: bool = False) -> RaggedBatch:
+        """Start delays as part of the plan (`uavac_minsnap_delay_dev`): every mission with start row S > 0 gets a leading HOLD segment
+        -- c0 of its first segment, c1 .. c7 = 0, S rows, duration S * dt -- and keeps its own segments unchanged; a mission with S = 0
+        is copied as it is.  The sampler then writes S hold rows (the first position, zero velocity and acceleration, the mission's
+        first heading, spline id 0) followed by the original rows bit for bit (`uav_ac.scoring.delay_rows`), and
+        `Engine.separation(delayed, radius, groups)` equals `Engine.separation(plan, radius, groups, start_rows=start_rows)` bit for
+        bit.  `plan`: what `Engine.separation` takes (a Plan with rows or rows-free, a RaggedBatch, a RaggedPlan through its batch);
+        it is left as it is.  `start_rows` (B,) array or tensor, e.g. `StaggerResult.start_rows`; one outside 0 .. 2^29 is clamped and
+        raises sticky flag 0 (`take_flags`).  A plan that starts in motion (`boundary=`) is accepted: its hold stands still and its
+        first own row moves, which is what the audit's clock means by "waits on its first row" too.
+        -> a rows-free RaggedBatch (`rows=True`: with rows, through `sample_rows`) of at most m + 1 segments per mission, assembled like
+        `ragged_from_parts`: `waypoints` None (it cannot be re-planned from waypoints; `start_positions` falls back to c0),
+        `free_times` True, `first_yaw` the input's (`Engine.first_yaw(plan)` if it carries none), velocity and dt carried over.
+        `eng.fleet(delayed)` and `fleet.follow(delayed)` fly it plan-fed like any rows-free ragged batch; `fleet.tracking()` scores the
+        hold rows like any others.  ONE host sync: the read of the (B + 1,) segment offsets (with the row total), which a RaggedBatch
+        carries on the host.  A plan whose missions already have UAVAC_MAX_SEGMENTS segments is a ValueError."""
+        torch = self._torch
+        if isinstance(plan, RaggedPlan):
+            batch = plan.batch
+            if batch is None:
+                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
+            plan = batch
+        ragged = hasattr(plan, "seg_offsets")
+        B, m = int(plan.B), int(plan.max_m if ragged else plan.m)
+        if m >= nat.MAX_SEGMENTS:
+            raise ValueError(f"a mission of {m} segments cannot take a hold segment: at most {nat.MAX_SEGMENTS} per mission")
+        start = self._dev(start_rows, torch.int32).reshape(-1)
+        if start.numel() != B:
+            raise ValueError(f"one start row per mission: expected {B}, got {start.numel()}")
+        kw = dict(device=self.device)
+        S_in = int(plan.seg_offsets_host[-1]) if ragged else B * m
+        so_in = _ptr(plan.seg_offsets) if ragged else None
+        # (buffers for the largest result, S_in + B segments, narrowed once the offsets are known: the one read comes last)
+        tail = torch.empty((B + 2,), dtype=torch.int64, **kw)            # the segment offsets (B + 1,) and, behind them, the row total
+        co = torch.empty((S_in + B, 8, 3), dtype=torch.float64, **kw)
+        sr = torch.empty((S_in + B,), dtype=torch.int32, **kw)
+        tm = None if plan.times is None else torch.empty((S_in + B,), dtype=torch.float64, **kw)
+        row_offsets = torch.empty((B + 1,), dtype=torch.int64, **kw)
+        first_yaw = plan.first_yaw.clone() if getattr(plan, "first_yaw", None) is not None else self.first_yaw(plan)
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_delay_offsets_dev", so_in, B, m, _ptr(start), _ptr(tail))
+        self.ctx.call("uavac_minsnap_delay_dev", _ptr(plan.coeffs), _ptr(plan.times), _ptr(plan.seg_rows), so_in, B, m, float(plan.dt),
+                      _ptr(start), _ptr(tail), _ptr(co), _ptr(tm), _ptr(sr))
+        self.ctx.call("uavac_minsnap_row_offsets_ragged_dev", _ptr(sr), _ptr(tail), B, m + 1, _ptr(row_offsets))
+        tail[B + 1:].copy_(row_offsets[B:])
+        host = tail.cpu().numpy()                                        # the one sync
+        so_host, total = host[:B + 1].copy(), int(host[B + 1])
+        S = int(so_host[-1])
+        out = RaggedBatch(B, m + 1, float(plan.velocity), float(plan.dt), tail[:B + 1], so_host, None, None if tm is None else tm[:S],
+                          sr[:S], row_offsets, co[:S], torch.zeros((B,), dtype=torch.int32, **kw), None, total, first_yaw, None, None,
+                          True)
+        return self.sample_rows(out) if rows else out
+
+    def flown_separation(self, state_log, radius: float, groups=None) -> SeparationAudit:
+        """The separation the fleet FLEW (`uavac_flown_separation_dev`): `Engine.separation` speaks about plans, this about the
+        vehicles, which track them with an error -- from the positions in a rollout's state log, on the device, without pulling the
+        log to the host.  `state_log`: the (K, 13, B) view that `fleet.rollout(K, state_log=True)` returns (at whatever log pitch), or
+        a dense caller tensor: float64 with stride(2) == 1 and stride(0) == 13 * stride(1) (the pitch is stride(1)); anything else is a
+        ValueError.  `radius` and `groups` as in `Engine.separation`.
+        -> SeparationAudit in the same terms, bit for bit what NumPy gives on the log (`uav_ac.scoring.separation_from_log`): the
+        closest approach to any other vehicle of the group, that partner, and in `row` the TICK of the closest approach (clock row of
+        the plan = tick // F, with F the vehicle's inner ticks per outer tick, `inner_per_outer`); `conflicts` and `first_conflict`
+        (a tick too) against `radius`; `compared` = the partners with at least one pair-tick whose distance is a number, so a vehicle
+        whose log holds NaN is visible.  A vehicle with nobody to compare with reports +inf / -1 / -1 / 0 / -1 / 0.
+        `uav_ac.scoring.separation_ok` applies unchanged.  Stream-ordered like the other _dev calls, no sync."""
+        torch = self._torch
+        if not isinstance(state_log, torch.Tensor) or state_log.dim() != 3 or state_log.dtype != torch.float64 \
+                or state_log.device != self.device:
+            raise ValueError("state_log must be a float64 tensor (K, 13, B) on the engine's device")
+        K, R, B = (int(v) for v in state_log.shape)
+        if R != nat.STATE_LOG_ROWS or K < 1 or B < 1:
+            raise ValueError(f"state_log must have shape (K >= 1, {nat.STATE_LOG_ROWS}, B >= 1), got {tuple(state_log.shape)}")
+        pitch = int(state_log.stride(1))
+        if state_log.stride(2) != 1 or pitch < B or (K > 1 and state_log.stride(0) != nat.STATE_LOG_ROWS * pitch):
+            raise ValueError("state_log must be laid out [K][13][pitch]: stride(2) == 1, stride(1) = pitch >= B, stride(0) == 13 * pitch")
+        go, G = None, 0
+        if groups is not None:
+            if isinstance(groups, (int, np.integer)):
+                if groups < 1:
+                    raise ValueError("a group size must be >= 1")
+                groups = list(range(0, B, int(groups))) + [B]
+            go = self._dev(groups, torch.int64).reshape(-1)
+            G = int(go.numel()) - 1
+            if G < 1:
+                raise ValueError("group offsets hold at least two entries")
+        sep = torch.empty((B,), dtype=torch.float64, device=self.device)
+        block = torch.empty((nat.SEP_ROWS, B), dtype=torch.int32, device=self.device)
+        self._bind_stream()
+        self.ctx.call("uavac_flown_separation_dev", _ptr(state_log), K, B, pitch, _ptr(go), G, float(radius), _ptr(sep), _ptr(block))
+        return SeparationAudit(sep, *block.unbind(0), block)
 
     DEFAULT_RETIME_MARGIN = 1e-3
 

@@ -16,6 +16,9 @@ uavac_minsnap_retime_factors_dev), NumPy on the host, bit for bit.
 uavac_minsnap_separation_dev): closest approach, partner, clock row, conflicts inside a radius, recomputed from sampled rows in NumPy,
 bit for bit; `separation_ok` judges a separation audit.  `stagger_from_rows` states the rule of the call that acts on that audit
 (`Engine.stagger`, uavac_minsnap_stagger_dev: start delays by priority) on sampled rows, and `stagger_ok` judges its result.
+`delay_rows` states on sampled rows what the delay transform (`Engine.delay`, uavac_minsnap_delay_dev) makes of a plan and its start
+rows, and `separation_from_log` is `separation_from_rows` for a FLIGHT: the rule of `Engine.flown_separation`
+(uavac_flown_separation_dev) on the positions of a rollout's state log.
 """
 from __future__ import annotations
 
@@ -151,6 +154,7 @@ def retime_factors(audit, vehicle=None, margin: float = DEFAULT_RETIME_MARGIN, v
 
 
 SEP_PARTNER, SEP_ROW, SEP_CONFLICTS, SEP_FIRST_CONFLICT, SEP_COMPARED = range(nat.SEP_ROWS)      # isep rows (include/uavac.h)
+_MAX_CLOCK = 1 << 29                                                                           # the largest start row the shared clock takes
 
 
 def separation_from_rows(rows, row_offsets, radius, group_offsets=None, start_rows=None):
@@ -237,8 +241,95 @@ def separation_ok(sep, group_sizes=None) -> dict:
     return {"clear": clear, "complete": complete, "ok": clear & complete}
 
 
+def separation_from_log(log, radius, group_offsets=None):
+    """The separation the fleet FLEW, recomputed from a state log -- the SPECIFICATION of `uavac_flown_separation_dev`
+    (csrc/flown_separation.hip), which is tested against it bit for bit.  NumPy on the host.
+    `log` (K, >= 3, B): the positions in rows 0-2 of every tick, as `Fleet.rollout(K, state_log=True)` returns them (a view at another
+    pitch is fine: only columns 0 .. B - 1 exist here); `group_offsets` (G + 1,) or None = one group.
+
+    The clock is the tick k = 0 .. K - 1.  For vehicle i and a partner j != i of its group: d^2 = (dx * dx + dy * dy) + dz * dz with
+    separately rounded products and sums, r^2 = radius * radius, inside means d^2 < r^2 strictly.  A pair-tick is VALID iff its d^2 is not
+    NaN.  The minimum is the lexicographic one of (d^2, tick, partner index) over the valid pair-ticks, one sqrt at the end.
+    -> (sep (B,) f64, isep (SEP_ROWS, B) i32): minimum distance; partner, tick of the minimum, conflicts (partners with a valid pair-tick
+    inside the radius), first tick with a partner inside (-1: none), compared (partners with at least one valid pair-tick).  No valid
+    pair-tick at all -- a group of one, a vehicle that is NaN throughout --: +inf and -1 / -1 / 0 / -1 / 0."""
+    log = _host(log)
+    if log.ndim != 3 or log.shape[0] < 1 or log.shape[1] < 3 or log.shape[2] < 1:
+        raise ValueError("log must have shape (K, >= 3, B) with K >= 1 and B >= 1")
+    K, B = log.shape[0], log.shape[2]
+    radius = float(radius)
+    if not (np.isfinite(radius) and radius >= 0.0):
+        raise ValueError("radius must be finite and >= 0")
+    go = np.array([0, B], dtype=np.int64) if group_offsets is None else np.asarray(
+        group_offsets.detach().cpu().numpy() if hasattr(group_offsets, "detach") else group_offsets, dtype=np.int64).reshape(-1)
+    if len(go) < 2 or go[0] != 0 or go[-1] != B or (np.diff(go) < 0).any():
+        raise ValueError("group_offsets must ascend from 0 to B")
+    r2 = radius * radius
+    sep = np.full(B, np.inf)
+    isep = np.zeros((nat.SEP_ROWS, B), dtype=np.int32)
+    isep[[SEP_PARTNER, SEP_ROW, SEP_FIRST_CONFLICT]] = -1
+    for g in range(len(go) - 1):
+        g0, g1 = int(go[g]), int(go[g + 1])
+        if g1 - g0 < 2:
+            continue
+        P = np.ascontiguousarray(log[:, 0:3, g0:g1])                                       # (K, 3, n): ticks first, partners ascending
+        for a in range(g1 - g0):
+            others = np.delete(np.arange(g1 - g0), a)
+            with np.errstate(invalid="ignore", over="ignore"):
+                dx, dy, dz = (P[:, c, a][:, None] - P[:, c, others] for c in range(3))     # (K, n - 1)
+                d2 = (dx * dx + dy * dy) + dz * dz
+            valid = ~np.isnan(d2)
+            if not valid.any():
+                continue
+            b = g0 + a
+            flat = int(np.argmin(np.where(valid, d2, np.inf)))                             # the first minimum: lowest tick, then lowest partner
+            tick, j = divmod(flat, len(others))
+            if valid[tick, j]:
+                sep[b] = np.sqrt(d2[tick, j])
+                isep[SEP_PARTNER, b], isep[SEP_ROW, b] = g0 + others[j], tick
+            inside = d2 < r2
+            isep[SEP_CONFLICTS, b] = int(inside.any(axis=0).sum())
+            hit = np.flatnonzero(inside.any(axis=1))
+            isep[SEP_FIRST_CONFLICT, b] = hit[0] if len(hit) else -1
+            isep[SEP_COMPARED, b] = int(valid.any(axis=0).sum())
+    return sep, isep
+
+
+def delay_rows(rows, row_offsets, start_rows, first_yaw):
+    """The delay transform on SAMPLED rows -- the rule `uavac_minsnap_delay_dev` (csrc/minsnap_delay.hip) is tested against: the rows the
+    sampler writes for the delayed plan.  NumPy on the host.
+    `rows` (N, 11), missions back to back; `row_offsets` (B + 1,); `start_rows` (B,), clamped to 0 .. 2^29; `first_yaw` (B,): each
+    mission's first heading (`plan.first_yaw`, `Engine.first_yaw`).
+    Mission b becomes S_b HOLD rows followed by its own rows.  A hold row holds the position of the mission's row 0 (which is c0 of its
+    first segment exactly), zero velocity and zero acceleration, the yaw first_yaw[b] and spline id 0 -- NOT row 0 repeated: a solved
+    mission's row 0 carries velocities of rounding size.  The mission's own rows keep every bit; with S_b > 0 their spline ids move up
+    by one.  A mission without rows cannot be delayed from rows (ValueError).
+    -> (rows' (N + sum S, 11) f64, row_offsets' (B + 1,) i64)."""
+    rows = _host(rows)
+    ro = np.asarray(_host(row_offsets), dtype=np.int64).reshape(-1)
+    B = len(ro) - 1
+    S = np.clip(np.asarray(_host(start_rows), dtype=np.int64).reshape(-1), 0, _MAX_CLOCK)
+    fy = np.asarray(_host(first_yaw), dtype=np.float64).reshape(-1)
+    if len(S) != B or len(fy) != B:
+        raise ValueError("one start row and one first heading per mission")
+    out_ro = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(np.diff(ro) + S, out=out_ro[1:])
+    out = np.zeros((int(out_ro[-1]), rows.shape[1]), dtype=np.float64)
+    for b in range(B):
+        own = rows[ro[b]:ro[b + 1]]
+        at = int(out_ro[b])
+        if S[b] > 0:
+            if len(own) == 0:
+                raise ValueError(f"mission {b} has no rows: its hold position is not among the rows")
+            out[at:at + S[b], 0:3] = own[0, 0:3]
+            out[at:at + S[b], 9] = fy[b]
+        out[at + S[b]:int(out_ro[b + 1])] = own
+        if S[b] > 0:
+            out[at + S[b]:int(out_ro[b + 1]), 10] += 1.0
+    return out, out_ro
+
+
 STAG_START, STAG_STEPS, STAG_EARLIER = range(nat.STAGGER_ROWS)                                   # istag rows (include/uavac.h)
-_MAX_CLOCK = 1 << 29
 
 
 def stagger_from_rows(rows, row_offsets, radius, group_offsets=None, start_rows=None, step=1, max_steps=255):
