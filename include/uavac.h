@@ -419,6 +419,58 @@ int uavac_minsnap_delay_dev(uavac_ctx *ctx, const double *coeffs, const double *
                             int B, int m, double dt, const int32_t *start_rows, const int64_t *out_seg_offsets, double *out_coeffs,
                             double *out_times, int32_t *out_seg_rows);
 
+/* LAYER: prioritised deconfliction by OFFSET -- the second lever on the separation audit's verdict.  uavac_minsnap_stagger_dev makes a
+ * mission wait; this call moves it, by whole steps of `delta` (metres; NED, so delta_z < 0 is one flight level UP; any direction is
+ * allowed, a lateral offset is the same code).  From coefficients and row counts alone (csrc/minsnap_layer.hip): no row is written,
+ * nothing is read back, everything is enqueued on the ctx stream, scratch comes from the ctx arena.  coeffs / seg_rows / seg_offsets /
+ * B / m / dt / group_offsets / G / start_rows / radius exactly as in uavac_minsnap_stagger_dev, and CLOCK, GROUPS, EXCLUDED MISSIONS,
+ * the priority (ascending batch index; the lowest index is never moved) and the group limit are the ones stated there.  start_rows[b]
+ * are FIXED starts here (NULL: all 0; clamped to 0 .. 2^29) -- istag[0] of a stagger call, for instance: nobody is delayed by this call.
+ * CANDIDATES.  Mission i examines the layers q = 0, 1, ..., max_steps in that order.  Layer q is the mission with the offset o_a =
+ * fl((double)q * delta_a) added to c0 of EVERY one of its segments on the axes a = x, y, z: c0'_a = fl(c0_a + o_a) -- the product and
+ * the sum are rounded one after the other, never as one fma.  Layer 0 is the mission as it is, bit for bit: nothing is added.
+ * Positions are the sampler's fma chain on those coefficients (only its last fma per axis sees c0), partners j < i stand on their
+ * GRANTED layers, the distance and the comparison are the audit's: d^2 = (dx * dx + dy * dy) + dz * dz without contraction, inside
+ * means d^2 < r^2 strictly.  A candidate is CLEAR iff for every included mission j < i of the group and every clock row k in [0,
+ * max(S_i + N_i, S_j + N_j)) the two are not inside the radius.  The first clear candidate is granted; a mission with none is
+ * UNRESOLVED: steps = -1, it stays on layer 0 and remains a partner for every later mission.
+ * OUTPUTS (device).  ilayer [UAVAC_LAYER_ROWS][B] i32, per mission b:  0 the granted layer (0 when unresolved or not examined)      1
+ * steps, the candidate index granted; -1 = unresolved; -2 = not examined (an excluded mission, or a group above UAVAC_LAYER_MAX_GROUP)
+ * 2 earlier = the included missions before it in its group.  offsets [B][3] f64: fl((double)layer * delta_a) of the granted layer,
+ * ready for uavac_minsnap_shift_dev.  Every output is decided by comparisons of d^2 with r^2, so it is exactly what NumPy gives on the
+ * sampled rows of the shifted plans (uav_ac.scoring.layer_from_rows), whatever else is in the batch.
+ * WHAT THE RESULT GUARANTEES.  uavac_minsnap_separation_dev on the SHIFTED plan (uavac_minsnap_shift_dev with `offsets`), same groups,
+ * radius and start_rows, finds no pair of RESOLVED missions inside the radius: the search evaluated exactly those coefficients.
+ * WHAT IT IS NOT.  A greedy answer in priority order, not a minimum of the total displacement.  It knows nothing about obstacles: a
+ * layer can move a mission into a cuboid, so uavac_minsnap_audit_dev has to be run again on the shifted plan.  An all-zero delta is
+ * legal (every steps is then 0, -1 or -2); a delta so large that q * delta or a position overflows is outside the contract.
+ * Cost: as stagger's, about 13 fp64 operations per (mission, candidate lane, earlier partner, clock row); 64 layers ride in the lanes of
+ * one pass.
+ * BAD INPUTS.  As in stagger: a start_rows[b] outside 0 .. 2^29 is clamped and raises sticky flag 0, a mission of more than 2^29 rows
+ * is excluded and raises it, a group above UAVAC_LAYER_MAX_GROUP given on the device reports 0 / -2 / 0 for all of its missions and
+ * raises it.  UAVAC_EINVAL before anything is enqueued: everything uavac_minsnap_separation_dev refuses (required pointers: coeffs,
+ * seg_rows, ilayer, offsets), a delta that is not finite, max_steps outside 0 .. UAVAC_LAYER_MAX_STEPS, group_offsets == NULL with
+ * B > UAVAC_LAYER_MAX_GROUP. */
+#define UAVAC_LAYER_ROWS 3
+#define UAVAC_LAYER_MAX_STEPS 1023
+#define UAVAC_LAYER_MAX_GROUP 256
+int uavac_minsnap_layer_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                            double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double delta_x,
+                            double delta_y, double delta_z, int max_steps, int32_t *ilayer, double *offsets);
+
+/* OFFSET AS A PLAN TRANSFORM: how the granted layers are flown and audited.  out_coeffs = coeffs (the same layout: [B][8 m][3] uniform
+ * with seg_offsets == NULL, or [total_segments][8][3] ragged with seg_offsets [B+1]; total_segments is ignored for a uniform batch)
+ * with c0'[a] = fl(c0[a] + offsets[b][a]) in every segment of mission b; c1 .. c7 are copied bit for bit, and so is every segment of a
+ * mission whose three offsets are all +-0 (a -0.0 stays -0.0).  offsets [B][3] f64 (device), e.g. the output of uavac_minsnap_layer_dev;
+ * non-finite offsets pass through, and the mission then counts as excluded downstream like any non-finite plan.  Durations, row
+ * counts, offsets tables and first headings of the shifted plan are the input's.  The sampled rows of the shifted plan differ from the
+ * input's in columns 0-2 only.  out_coeffs may be coeffs itself (in place).  One kernel on the ctx stream; nothing is read back.
+ * The obstacle audit has to be re-run on the shifted plan.
+ * UAVAC_EINVAL before anything is enqueued: no context, a NULL pointer (coeffs, offsets, out_coeffs), B < 1, m outside 1 ..
+ * UAVAC_MAX_SEGMENTS, seg_offsets != NULL with total_segments outside 1 .. B * m. */
+int uavac_minsnap_shift_dev(uavac_ctx *ctx, const double *coeffs, const int64_t *seg_offsets, int B, int m, int64_t total_segments,
+                            const double *offsets, double *out_coeffs);
+
 /* FLOWN SEPARATION: the separation audit of a FLIGHT.  uavac_minsnap_separation_dev speaks about plans; the vehicles track them with an
  * error.  This call reads the positions in a rollout's state log and reports, in the same terms and with the same exactness, how close
  * the vehicles came (csrc/flown_separation.hip): nothing is read back, everything is enqueued on the ctx stream, scratch from the arena.

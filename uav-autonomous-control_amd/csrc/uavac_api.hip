@@ -895,6 +895,33 @@ int uavac_minsnap_delay_dev(uavac_ctx *ctx, const double *coeffs, const double *
                               out_seg_rows);
 }
 
+int uavac_minsnap_layer_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                            double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double delta_x,
+                            double delta_y, double delta_z, int max_steps, int32_t *ilayer, double *offsets) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
+    if (!seg_rows || !ilayer || !offsets) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
+    if (!std::isfinite(radius) || radius < 0.0) return uavac_fail(ctx, UAVAC_EINVAL, "radius must be finite and >= 0");
+    if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
+    if (!std::isfinite(delta_x) || !std::isfinite(delta_y) || !std::isfinite(delta_z)) return uavac_fail(ctx, UAVAC_EINVAL, "delta must be finite");
+    if (max_steps < 0 || max_steps > UAVAC_LAYER_MAX_STEPS) return uavac_fail(ctx, UAVAC_EINVAL, "max_steps must be in [0, UAVAC_LAYER_MAX_STEPS]");
+    if (!group_offsets && B > UAVAC_LAYER_MAX_GROUP)
+        return uavac_fail(ctx, UAVAC_EINVAL, "one group of all B: B must not exceed UAVAC_LAYER_MAX_GROUP");
+    return uavac_launch_layer(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, delta_x, delta_y, delta_z,
+                              max_steps, ilayer, offsets);
+}
+
+int uavac_minsnap_shift_dev(uavac_ctx *ctx, const double *coeffs, const int64_t *seg_offsets, int B, int m, int64_t total_segments,
+                            const double *offsets, double *out_coeffs) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
+    if (!offsets || !out_coeffs) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (seg_offsets && (total_segments < 1 || total_segments > (int64_t)B * m))
+        return uavac_fail(ctx, UAVAC_EINVAL, "total_segments must be in [1, B * m] for a ragged batch");
+    return uavac_launch_shift(ctx, coeffs, seg_offsets, B, m, total_segments, offsets, out_coeffs);
+}
+
 int uavac_flown_separation_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
                                double radius, double *sep, int32_t *isep) {
     UAVAC_ENTER(ctx);

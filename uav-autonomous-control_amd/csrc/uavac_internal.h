@@ -238,6 +238,13 @@ int uavac_launch_delay_offsets(uavac_ctx *ctx, const int64_t *seg_offsets, int B
 int uavac_launch_delay(uavac_ctx *ctx, const double *coeffs, const double *times, const int32_t *seg_rows, const int64_t *seg_offsets, int B,
                        int m, double dt, const int32_t *start_rows, const int64_t *out_seg_offsets, double *out_coeffs, double *out_times,
                        int32_t *out_seg_rows);
+// deconfliction by offset layers at fixed starts (minsnap_layer.hip): ilayer [UAVAC_LAYER_ROWS][B], offsets [B][3]; scratch from the ctx
+// arena; and the offsets as part of the plan: out_coeffs = coeffs with offsets[b] added to c0 of every segment of mission b
+int uavac_launch_layer(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
+                       const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double delta_x, double delta_y,
+                       double delta_z, int max_steps, int32_t *ilayer, double *offsets);
+int uavac_launch_shift(uavac_ctx *ctx, const double *coeffs, const int64_t *seg_offsets, int B, int m, int64_t total_segments,
+                       const double *offsets, double *out_coeffs);
 // the separation the fleet flew (flown_separation.hip): the audit's outputs from the positions of a state log [K][13][pitch]
 int uavac_launch_flown_separation(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
                                   double radius, double *sep, int32_t *isep);

@@ -15,9 +15,9 @@ LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 VGPR_LIMIT = 256
 
 
-def kernel_register_counts(obj: str, kernel: str):
-    """[(kernel name, vgpr_count, vgpr_spill_count)] of every kernel of the object file whose name contains `kernel`, or None
-    when the object file or the LLVM tools are not there (a library that was built elsewhere)."""
+def _kernel_notes(obj: str):
+    """The metadata notes of the gfx950 code object inside an object file, or None when the object file or the LLVM tools are not
+    there (a library that was built elsewhere)."""
     objdump, readelf = os.path.join(LLVM_BIN, "llvm-objdump"), os.path.join(LLVM_BIN, "llvm-readelf")
     if not (os.path.exists(obj) and os.path.exists(objdump) and os.path.exists(readelf)):
         return None
@@ -29,6 +29,15 @@ def kernel_register_counts(obj: str, kernel: str):
         notes = subprocess.run([readelf, "--notes", os.path.join(tmp, co)], check=True, capture_output=True, text=True).stdout
     finally:
         shutil.rmtree(tmp)
+    return notes
+
+
+def kernel_register_counts(obj: str, kernel: str):
+    """[(kernel name, vgpr_count, vgpr_spill_count)] of every kernel of the object file whose name contains `kernel`, or None
+    when the object file or the LLVM tools are not there (a library that was built elsewhere)."""
+    notes = _kernel_notes(obj)
+    if notes is None:
+        return None
     found = re.findall(r"\.name:\s+(\S*" + re.escape(kernel) + r"\S*).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", notes, flags=re.S)
     return [(n, int(v), int(s)) for n, v, s in found]
 
@@ -36,17 +45,9 @@ def kernel_register_counts(obj: str, kernel: str):
 def kernel_private_bytes(obj: str, kernel: str):
     """[(kernel name, private_segment_fixed_size)] -- the scratch memory per lane, which is 0 for a kernel that lives in registers --
     of every kernel of the object file whose name contains `kernel`; None like `kernel_register_counts`."""
-    objdump, readelf = os.path.join(LLVM_BIN, "llvm-objdump"), os.path.join(LLVM_BIN, "llvm-readelf")
-    if not (os.path.exists(obj) and os.path.exists(objdump) and os.path.exists(readelf)):
+    notes = _kernel_notes(obj)
+    if notes is None:
         return None
-    tmp = tempfile.mkdtemp()
-    try:
-        shutil.copy(obj, os.path.join(tmp, "o.o"))
-        subprocess.run([objdump, "--offloading", "o.o"], cwd=tmp, check=True, capture_output=True)
-        co = [f for f in os.listdir(tmp) if "gfx950" in f][0]
-        notes = subprocess.run([readelf, "--notes", os.path.join(tmp, co)], check=True, capture_output=True, text=True).stdout
-    finally:
-        shutil.rmtree(tmp)
     # (the metadata lists a kernel's keys in alphabetical order: .name comes before .private_segment_fixed_size)
     found = re.findall(r"\.name:\s+(\S*" + re.escape(kernel) + r"\S*)\s.*?\.private_segment_fixed_size:\s+(\d+)", notes, flags=re.S)
     return [(n, int(v)) for n, v in found]
@@ -196,6 +197,54 @@ def check_delay_kernels():
     missing = [k for k in DELAY_KERNELS if not any(k in n for n, _, _ in regs)]
     if bad or missing or len(regs) != len(DELAY_KERNELS) or len(priv) != len(regs):
         raise RuntimeError(f"delay kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
+                           f"{len(regs)} kernels found (compiler: {compiler_version()})")
+    return {n: v for n, v, _ in regs}
+
+
+LAYER_KERNELS = ("layer_prepass_kernel", "minsnap_layer_kernel", "minsnap_shift_kernel")
+LDS_BYTES_PER_CU = 160 * 1024
+VGPRS_AT_WAVES_PER_SIMD = {8: 64, 7: 72, 6: 80, 5: 96, 4: 128, 3: 168, 2: 256, 1: 512}     # the largest allocation that still runs that many
+
+
+def kernel_lds_bytes(obj: str, kernel: str):
+    """[(kernel name, group_segment_fixed_size)] -- the static LDS of a workgroup -- of every kernel of the object file whose name
+    contains `kernel`; None like `kernel_register_counts`."""
+    notes = _kernel_notes(obj)
+    if notes is None:
+        return None
+    # (the metadata lists a kernel's keys in alphabetical order: .group_segment_fixed_size comes before .name)
+    found = re.findall(r"\.group_segment_fixed_size:\s+(\d+)(?:(?!\.group_segment_fixed_size:).)*?\.name:\s+(\S*" + re.escape(kernel) + r"\S*)",
+                       notes, flags=re.S)
+    return [(n, int(v)) for v, n in found]
+
+
+def check_layer_kernels():
+    """The kernels of csrc/minsnap_layer.hip (offset layers that clear the separation audit, and the offset transform): all three must
+    be there, none may spill or use scratch memory at all (zero private-segment bytes: the coefficient sets of the decision kernel are
+    indexed by constants only).  The register limit of each follows from the LDS it ends up with: workgroups of four waves, so
+    min(8, 160 KiB // LDS) workgroups per CU are as many waves per SIMD, and the kernel must fit the allocation that still runs that
+    many (built: the decision kernel 50192 B of LDS -- the 48 KB tile, 1 KB of granted layers, two words -- hence three and <= 168,
+    at 139; the pre-pass and the transform no LDS, hence eight and <= 64, at 14 and 21).  Returns {kernel: VGPRs}, None when the
+    counts cannot be read."""
+    obj = os.path.join(PKG, "build", "minsnap_layer.o")
+    regs, priv, lds = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel"), kernel_lds_bytes(obj, "_kernel")
+    if regs is None or priv is None or lds is None:
+        return None
+    lds = dict(lds)
+    bad = [(n[:70], f"{p} private-segment bytes", 0, 0) for n, p in priv if p]
+    for n, v, sp in regs:
+        if n not in lds:
+            bad.append((n[:70], "no LDS size found", 0, 0))
+            continue
+        waves = min(8, LDS_BYTES_PER_CU // lds[n]) if lds[n] else 8
+        limit = VGPRS_AT_WAVES_PER_SIMD.get(waves, 0)          # (a workgroup that does not fit a CU at all: limit 0)
+        if "minsnap_layer_kernel" in n and waves < 3:
+            bad.append((n[:70], f"{lds[n]} bytes of LDS: fewer than three workgroups per CU", 0, 0))
+        if v > limit or sp:
+            bad.append((n[:70], v, sp, limit))
+    missing = [k for k in LAYER_KERNELS if not any(k in n for n, _, _ in regs)]
+    if bad or missing or len(regs) != len(LAYER_KERNELS) or len(priv) != len(regs):
+        raise RuntimeError(f"layer kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
                            f"{len(regs)} kernels found (compiler: {compiler_version()})")
     return {n: v for n, v, _ in regs}
 
@@ -449,7 +498,9 @@ def run_all(verbose: bool = False, write_stamp: bool = True) -> dict:
              ("delay_kernels", check_delay_kernels,
               lambda r: f"{len(r)} delay kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("flown_separation_kernels", check_flown_separation_kernels,
-              lambda r: f"{len(r)} flown-separation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"))
+              lambda r: f"{len(r)} flown-separation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
+             ("layer_kernels", check_layer_kernels,
+              lambda r: f"{len(r)} layer kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"))
     for key, fn, say in steps:
         r = fn()
         if r is None:

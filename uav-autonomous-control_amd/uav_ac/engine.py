@@ -203,6 +203,18 @@ class StaggerResult:
 
 
 @dataclass
+class LayerResult:
+    """Offset layers that clear the separation audit at fixed starts (`Engine.layer`, include/uavac.h uavac_minsnap_layer_dev): device
+    tensors, per mission.  `Engine.separation(Engine.shift(plan, result.offsets), radius, groups, start_rows)` confirms it;
+    `uav_ac.scoring.layer_ok` turns it into verdicts."""
+    layers: "object"         # (B,) i32: the granted layer (0 for an unresolved or unexamined mission)
+    steps: "object"          # (B,) i32: the candidate index granted (== layers); -1 unresolved; -2 not examined
+    earlier: "object"        # (B,) i32: how many missions it was checked against (the included missions before it in its group)
+    block: "object" = None   # the [LAYER_ROWS][B] i32 block the three rows above are views of
+    offsets: "object" = None  # (B, 3) f64: the granted layer * delta, what `Engine.shift` takes
+
+
+@dataclass
 class RetimeResult:
     """What `Engine.retime` returns: the plan at speeds that keep every converged mission inside the flight limits."""
     plan: "object"           # of the kind that was given (Plan / RaggedBatch / RaggedPlan), planned at `velocities`; with rows if it had rows
@@ -770,6 +782,107 @@ class Engine:
         out = RaggedBatch(B, m + 1, float(plan.velocity), float(plan.dt), tail[:B + 1], so_host, None, None if tm is None else tm[:S],
                           sr[:S], row_offsets, co[:S], torch.zeros((B,), dtype=torch.int32, **kw), None, total, first_yaw, None, None,
                           True)
+        return self.sample_rows(out) if rows else out
+
+    def layer(self, plan, radius: float, groups=None, start_rows=None, delta=(0.0, 0.0, -0.5), max_steps: int = 63) -> LayerResult:
+        """Prioritised deconfliction by offset (`uavac_minsnap_layer_dev`): the second lever on `Engine.separation`'s verdict, for the
+        conflicts that waiting cannot resolve (a shared first or last waypoint, a crossing of a busy region).  `start_rows` are FIXED
+        starts -- `StaggerResult.start_rows`, for instance; nobody is delayed by this call.  Within a group the missions are taken in
+        ascending batch index -- the lowest index is never moved --, and each gets the lowest layer q = 0 .. `max_steps` -- the mission
+        with q * `delta` (three finite metres, NED: a negative z is UP; any direction is allowed) added to c0 of every segment -- that
+        keeps it outside `radius` of every mission decided before it, on its granted layer, over the whole shared clock; a mission for
+        which no layer is clear stays on layer 0 with steps = -1.  A greedy answer in priority order, not a minimum of the total
+        displacement.  Exactly what NumPy gives on the sampled rows of the shifted plans (`uav_ac.scoring.layer_from_rows`).
+        `plan` and `groups` as `Engine.stagger` takes them, with the same limit of `LAYER_MAX_GROUP` missions per group.  Never reads
+        `plan.traj`; stream-ordered, no sync.  Make the result part of the plan with `Engine.shift(plan, result.offsets)`;
+        `Engine.separation(shifted, radius, groups, start_rows)` then finds no pair of resolved missions inside the radius.  The search
+        knows nothing about obstacles: run `Engine.audit(shifted, obstacles)` again, a layer can move a mission into a cuboid."""
+        torch = self._torch
+        if isinstance(plan, RaggedPlan):
+            batch = plan.batch
+            if batch is None:
+                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
+            plan = batch
+        ragged = hasattr(plan, "seg_offsets")
+        B = int(plan.B)
+        max_steps = int(max_steps)
+        if not (0 <= max_steps <= nat.LAYER_MAX_STEPS):
+            raise ValueError(f"max_steps must be in 0 .. {nat.LAYER_MAX_STEPS}")
+        d = np.asarray(delta.detach().cpu().numpy() if hasattr(delta, "detach") else delta, dtype=np.float64).reshape(-1)
+        if d.size != 3 or not np.isfinite(d).all():
+            raise ValueError("delta must be three finite numbers")
+        go, G = None, 0
+        if groups is None:
+            if B > nat.LAYER_MAX_GROUP:
+                raise ValueError(f"one group of {B} missions; at most {nat.LAYER_MAX_GROUP} per group")
+        else:
+            if isinstance(groups, (int, np.integer)):
+                if groups < 1:
+                    raise ValueError("a group size must be >= 1")
+                groups = list(range(0, B, int(groups))) + [B]
+            if not (hasattr(groups, "is_cuda") and groups.is_cuda):
+                sizes = np.diff(np.asarray(groups.numpy() if hasattr(groups, "numpy") else groups, dtype=np.int64).reshape(-1))
+                if sizes.size and sizes.max() > nat.LAYER_MAX_GROUP:
+                    raise ValueError(f"a group of {int(sizes.max())} missions; at most {nat.LAYER_MAX_GROUP} per group")
+            go = self._dev(groups, torch.int64).reshape(-1)
+            G = int(go.numel()) - 1
+            if G < 1:
+                raise ValueError("group offsets hold at least two entries")
+        start = None
+        if start_rows is not None:
+            start = self._dev(start_rows, torch.int32).reshape(-1)
+            if start.numel() != B:
+                raise ValueError(f"one start row per mission: expected {B}, got {start.numel()}")
+        block = torch.empty((nat.LAYER_ROWS, B), dtype=torch.int32, device=self.device)
+        offsets = torch.empty((B, 3), dtype=torch.float64, device=self.device)
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_layer_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
+                      B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(go), G, _ptr(start), float(radius), float(d[0]), float(d[1]),
+                      float(d[2]), max_steps, _ptr(block), _ptr(offsets))
+        return LayerResult(*block.unbind(0), block, offsets)
+
+    def shift(self, plan, offsets, rows: bool = False) -> RaggedBatch:
+        """Offsets as part of the plan (`uavac_minsnap_shift_dev`): every segment of mission b gets c0' = c0 + offsets[b] (one rounded
+        sum per axis); c1 .. c7, the durations, the row counts and the first headings keep every bit, and so does a mission whose three
+        offsets are all zero (`uav_ac.scoring.shift_coeffs`).  The sampled rows of the result differ from the input's in columns 0:3
+        only.  `offsets` (B, 3) array or tensor, e.g. `LayerResult.offsets`; non-finite ones pass through, and the mission then counts as
+        excluded downstream like any non-finite plan.  `plan`: what `Engine.delay` takes (a Plan with rows or rows-free, a RaggedBatch,
+        a RaggedPlan through its batch); it is left as it is.
+        -> a rows-free RaggedBatch (`rows=True`: with rows, through `sample_rows`) with the input's segment counts, assembled like
+        `ragged_from_parts`: `waypoints` None (`start_positions` falls back to c0, the SHIFTED first waypoint), `free_times` True,
+        `first_yaw` the input's (`Engine.first_yaw(plan)` if it carries none), velocity and dt carried over.  `eng.fleet(shifted)`,
+        `fleet.follow(shifted)` and `Engine.delay(shifted, starts)` work unchanged.  No host sync: the segment counts and the row total
+        are on the host already.  The OBSTACLE AUDIT has to be re-run on the result (`Engine.audit(shifted, obstacles)`): an offset
+        can move a mission into a cuboid that the original plan avoided."""
+        torch = self._torch
+        if isinstance(plan, RaggedPlan):
+            batch = plan.batch
+            if batch is None:
+                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
+            plan = batch
+        ragged = hasattr(plan, "seg_offsets")
+        B, m = int(plan.B), int(plan.max_m if ragged else plan.m)
+        off = self._dev(offsets, torch.float64).reshape(-1)
+        if off.numel() != 3 * B:
+            raise ValueError(f"one offset (x, y, z) per mission: expected ({B}, 3), got {off.numel()} numbers")
+        off = off.contiguous()
+        kw = dict(device=self.device)
+        if ragged:
+            so_host = np.asarray(plan.seg_offsets_host, dtype=np.int64).copy()
+            so = plan.seg_offsets.clone()
+        else:
+            so_host = np.arange(B + 1, dtype=np.int64) * m
+            so = torch.arange(B + 1, dtype=torch.int64, **kw) * m
+        S = int(so_host[-1])
+        src = plan.coeffs.reshape(S, 8, 3)
+        co = torch.empty((S, 8, 3), dtype=torch.float64, **kw)
+        first_yaw = plan.first_yaw.clone() if getattr(plan, "first_yaw", None) is not None else self.first_yaw(plan)
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_shift_dev", _ptr(src), _ptr(so) if ragged else None, B, m, S, _ptr(off), _ptr(co))
+        tm = None if plan.times is None else plan.times.reshape(-1).clone()
+        out = RaggedBatch(B, m, float(plan.velocity), float(plan.dt), so, so_host, None, tm, plan.seg_rows.reshape(-1).clone(),
+                          plan.row_offsets.clone(), co, torch.zeros((B,), dtype=torch.int32, **kw), None, int(plan.total_rows), first_yaw,
+                          None, None, True)
         return self.sample_rows(out) if rows else out
 
     def flown_separation(self, state_log, radius: float, groups=None) -> SeparationAudit:

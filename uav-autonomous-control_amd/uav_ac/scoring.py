@@ -18,7 +18,9 @@ bit for bit; `separation_ok` judges a separation audit.  `stagger_from_rows` sta
 (`Engine.stagger`, uavac_minsnap_stagger_dev: start delays by priority) on sampled rows, and `stagger_ok` judges its result.
 `delay_rows` states on sampled rows what the delay transform (`Engine.delay`, uavac_minsnap_delay_dev) makes of a plan and its start
 rows, and `separation_from_log` is `separation_from_rows` for a FLIGHT: the rule of `Engine.flown_separation`
-(uavac_flown_separation_dev) on the positions of a rollout's state log.
+(uavac_flown_separation_dev) on the positions of a rollout's state log.  `layer_from_rows` states the rule of the second lever on
+the audit (`Engine.layer`, uavac_minsnap_layer_dev: offset layers by priority at fixed starts), `layer_ok` judges its result, and
+`shift_coeffs` states the transform that makes granted offsets part of the plan (`Engine.shift`, uavac_minsnap_shift_dev).
 """
 from __future__ import annotations
 
@@ -413,4 +415,123 @@ def stagger_ok(istag) -> dict:
         if block.ndim != 2 or block.shape[0] != nat.STAGGER_ROWS:
             raise ValueError(f"a stagger block is [{nat.STAGGER_ROWS}][B], got {block.shape}")
         steps = block[STAG_STEPS]
+    return {"resolved": steps >= 0, "examined": steps != -2}
+
+
+LAYER_LAYER, LAYER_STEPS, LAYER_EARLIER = range(nat.LAYER_ROWS)                                  # ilayer rows (include/uavac.h)
+
+
+def shift_coeffs(coeffs, seg_offsets_or_m, offsets):
+    """The offset transform on coefficients -- the rule `uavac_minsnap_shift_dev` (csrc/minsnap_layer.hip) is tested against bit for
+    bit.  NumPy on the host, elementwise.
+    `coeffs`: anything that reshapes to (S, 8, 3) -- a Plan's (B, 8 m, 3) or a RaggedBatch's (S, 8, 3).  `seg_offsets_or_m`: the ragged
+    batch's segment offsets (B + 1,), or an int m = segments per mission of a uniform batch.  `offsets` (B, 3).
+    Every segment of mission b gets c0'[a] = c0[a] + offsets[b][a] (one rounded sum); c1 .. c7 keep every bit, and a mission whose three
+    offsets are all +-0 is not touched at all (a -0.0 stays -0.0).  Non-finite offsets pass through.
+    -> a new array of the shape of `coeffs`."""
+    co = np.array(_host(coeffs), dtype=np.float64)
+    out = co.reshape(-1, 8, 3)
+    off = np.asarray(_host(offsets), dtype=np.float64).reshape(-1, 3)
+    B = len(off)
+    if np.ndim(seg_offsets_or_m) == 0:
+        m = int(seg_offsets_or_m)
+        if m < 1 or B * m != len(out):
+            raise ValueError(f"{len(out)} segments are not {B} missions of {m}")
+        so = np.arange(B + 1, dtype=np.int64) * m
+    else:
+        so = np.asarray(_host(seg_offsets_or_m), dtype=np.int64).reshape(-1)
+        if len(so) != B + 1 or so[0] != 0 or so[-1] != len(out) or (np.diff(so) < 0).any():
+            raise ValueError("seg_offsets must ascend from 0 to the number of segments, one entry per mission and one more")
+    for b in range(B):
+        if (off[b] == 0.0).all():
+            continue
+        with np.errstate(invalid="ignore", over="ignore"):
+            out[so[b]:so[b + 1], 0, :] = out[so[b]:so[b + 1], 0, :] + off[b]
+    return co
+
+
+def layer_from_rows(rows_at, row_offsets, radius, group_offsets=None, start_rows=None, max_steps=63):
+    """Prioritised deconfliction by offset layers, decided on SAMPLED rows -- the SPECIFICATION of `uavac_minsnap_layer_dev`
+    (csrc/minsnap_layer.hip), which is tested against it exactly.  NumPy on the host.
+    `rows_at(q)` -> the (N, >= 3) rows of the WHOLE batch with every mission on layer q, i.e. of the plan with fl(q * delta) added to
+    c0 of every segment (`Engine.sample_rows(Engine.shift(plan, q * delta))`); a callable, so that the caller can sample lazily and
+    memoise -- it is asked for the layers 0 .. max_steps at most, layer 0 first.  `row_offsets`, `radius`, `group_offsets` as
+    `stagger_from_rows` takes them, and the clock, the excluded missions (judged on layer 0) and the arithmetic are the same.
+    `start_rows` (B,) or None = all 0: FIXED starts S_b, clamped to 0 .. 2^29; nobody is delayed.
+
+    Per group the included missions in ascending batch index -- the priority: the lowest index is never moved.  Mission i examines
+    the layers q = 0, 1, ..., max_steps in that order; its candidate q reads rows_at(q), partner j reads rows_at(L_j), its GRANTED
+    layer.  A candidate is clear iff for every included mission j < i of the group and every clock row k in [0, max(S_i + N_i, S_j +
+    N_j)) the two are not inside the radius.  The first clear candidate is granted: L_i = steps = q; if none is clear the mission is
+    unresolved: steps = -1, L_i = 0, and it remains a partner for every later mission.  An excluded mission, and every mission of a
+    group of more than LAYER_MAX_GROUP, is not examined: layer 0, steps = -2, earlier = 0; nobody is checked against an excluded one.
+    -> ilayer (LAYER_ROWS, B) i32: the granted layer; steps; earlier (how many missions it was checked against)."""
+    ro = np.asarray(row_offsets.detach().cpu().numpy() if hasattr(row_offsets, "detach") else row_offsets, dtype=np.int64).reshape(-1)
+    B = len(ro) - 1
+    radius, max_steps = float(radius), int(max_steps)
+    if not callable(rows_at):
+        raise ValueError("rows_at must be a callable: layer -> rows")
+    if not (np.isfinite(radius) and radius >= 0.0):
+        raise ValueError("radius must be finite and >= 0")
+    if not (0 <= max_steps <= nat.LAYER_MAX_STEPS):
+        raise ValueError(f"max_steps must be in 0 .. {nat.LAYER_MAX_STEPS}")
+    go = np.array([0, B], dtype=np.int64) if group_offsets is None else np.asarray(
+        group_offsets.detach().cpu().numpy() if hasattr(group_offsets, "detach") else group_offsets, dtype=np.int64).reshape(-1)
+    if len(go) < 2 or go[0] != 0 or go[-1] != B or (np.diff(go) < 0).any():
+        raise ValueError("group_offsets must ascend from 0 to B")
+    S = np.zeros(B, dtype=np.int64) if start_rows is None else np.clip(np.asarray(
+        start_rows.detach().cpu().numpy() if hasattr(start_rows, "detach") else start_rows, dtype=np.int64).reshape(-1), 0, _MAX_CLOCK)
+    if len(S) != B:
+        raise ValueError("one start row per mission")
+    r2 = radius * radius
+    N = np.diff(ro)
+
+    def pos(q, b):
+        return _host(rows_at(q))[ro[b]:ro[b + 1], 0:3]
+
+    included = np.array([0 < N[b] <= _MAX_CLOCK and bool(np.isfinite(pos(0, b)).all()) for b in range(B)], dtype=bool)
+    ilayer = np.zeros((nat.LAYER_ROWS, B), dtype=np.int32)
+    ilayer[LAYER_STEPS] = -2
+    for g in range(len(go) - 1):
+        g0, g1 = int(go[g]), int(go[g + 1])
+        if g1 - g0 > nat.LAYER_MAX_GROUP:
+            continue
+        done = []                                                                     # the included missions decided so far
+        L = {}
+        for i in range(g0, g1):
+            if not included[i]:
+                continue
+            ilayer[LAYER_EARLIER, i] = len(done)
+            L[i], steps = 0, -1
+            if done:
+                H = max(max(int(S[j]) + int(N[j]) for j in done), int(S[i]) + int(N[i]))
+                k = np.arange(H)
+                others = np.stack([pos(L[j], j)[np.clip(k - S[j], 0, N[j] - 1)] for j in done])                # (n, H, 3)
+                at = np.clip(k - S[i], 0, N[i] - 1)
+            for q in range(max_steps + 1):
+                clear = True
+                if done:
+                    own = pos(q, i)[at]                                               # (H, 3): where the candidate stands at clock row k
+                    with np.errstate(invalid="ignore", over="ignore"):
+                        dx, dy, dz = (own[None, :, c] - others[:, :, c] for c in range(3))
+                        clear = not bool(((dx * dx + dy * dy) + dz * dz < r2).any())
+                if clear:
+                    L[i], steps = q, q
+                    break
+            ilayer[LAYER_LAYER, i], ilayer[LAYER_STEPS, i] = L[i], steps
+            done.append(i)
+    return ilayer
+
+
+def layer_ok(result) -> dict:
+    """A layer result (`Engine.layer` -> LayerResult, anything with `steps`, or the [LAYER_ROWS][B] block itself; tensors on any device
+    or arrays) -> dict of (B,) bool host arrays: `resolved` (steps >= 0: a layer was granted, layer 0 included) and `examined` (steps
+    != -2).  A mission that was not examined -- an excluded one, or one of an oversized group -- never looks resolved."""
+    if hasattr(result, "steps"):
+        steps = np.asarray(_host(result.steps)).reshape(-1)
+    else:
+        block = np.asarray(_host(result))
+        if block.ndim != 2 or block.shape[0] != nat.LAYER_ROWS:
+            raise ValueError(f"a layer block is [{nat.LAYER_ROWS}][B], got {block.shape}")
+        steps = block[LAYER_STEPS]
     return {"resolved": steps >= 0, "examined": steps != -2}
