@@ -895,10 +895,10 @@ int uavac_minsnap_delay_dev(uavac_ctx *ctx, const double *coeffs, const double *
                               out_seg_rows);
 }
 
-int uavac_minsnap_layer_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
-                            double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double delta_x,
-                            double delta_y, double delta_z, int max_steps, int32_t *ilayer, double *offsets) {
-    UAVAC_ENTER(ctx);
+// what uavac_minsnap_layer_dev and uavac_minsnap_layer_obs_dev refuse alike
+static int check_layer_args(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, int B, int m, double dt, const int64_t *group_offsets,
+                            int G, double radius, double delta_x, double delta_y, double delta_z, int max_steps, const int32_t *ilayer,
+                            const double *offsets) {
     if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
     if (!seg_rows || !ilayer || !offsets) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
     if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
@@ -908,8 +908,31 @@ int uavac_minsnap_layer_dev(uavac_ctx *ctx, const double *coeffs, const int32_t 
     if (max_steps < 0 || max_steps > UAVAC_LAYER_MAX_STEPS) return uavac_fail(ctx, UAVAC_EINVAL, "max_steps must be in [0, UAVAC_LAYER_MAX_STEPS]");
     if (!group_offsets && B > UAVAC_LAYER_MAX_GROUP)
         return uavac_fail(ctx, UAVAC_EINVAL, "one group of all B: B must not exceed UAVAC_LAYER_MAX_GROUP");
+    return UAVAC_OK;
+}
+
+int uavac_minsnap_layer_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                            double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double delta_x,
+                            double delta_y, double delta_z, int max_steps, int32_t *ilayer, double *offsets) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_layer_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, delta_x, delta_y, delta_z, max_steps, ilayer, offsets))
+        return rc;
     return uavac_launch_layer(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, delta_x, delta_y, delta_z,
                               max_steps, ilayer, offsets);
+}
+
+int uavac_minsnap_layer_obs_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double delta_x,
+                                double delta_y, double delta_z, int max_steps, const double *cuboids, int n_cuboids, int32_t *ilayer,
+                                double *offsets) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_layer_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, delta_x, delta_y, delta_z, max_steps, ilayer, offsets))
+        return rc;
+    if (n_cuboids < 0 || n_cuboids > UAVAC_AUDIT_MAX_CUBOIDS)
+        return uavac_fail(ctx, UAVAC_EINVAL, "n_cuboids must be in [0, UAVAC_AUDIT_MAX_CUBOIDS]");
+    if (n_cuboids > 0 && !cuboids) return uavac_fail(ctx, UAVAC_EINVAL, "cuboids must be given when n_cuboids > 0");
+    return uavac_launch_layer_obs(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, delta_x, delta_y, delta_z,
+                                  max_steps, cuboids, n_cuboids, ilayer, offsets);
 }
 
 int uavac_minsnap_shift_dev(uavac_ctx *ctx, const double *coeffs, const int64_t *seg_offsets, int B, int m, int64_t total_segments,

@@ -245,6 +245,11 @@ int uavac_launch_layer(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_
                        double delta_z, int max_steps, int32_t *ilayer, double *offsets);
 int uavac_launch_shift(uavac_ctx *ctx, const double *coeffs, const int64_t *seg_offsets, int B, int m, int64_t total_segments,
                        const double *offsets, double *out_coeffs);
+// the same search, refusing every layer on which a row of the mission's own lies inside a cuboid (minsnap_layer_obs.hip): cuboids
+// [n_cuboids][6] (may be NULL with n_cuboids = 0), ilayer [UAVAC_LAYER_OBS_ROWS][B]
+int uavac_launch_layer_obs(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
+                           const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double delta_x, double delta_y,
+                           double delta_z, int max_steps, const double *cuboids, int n_cuboids, int32_t *ilayer, double *offsets);
 // the separation the fleet flew (flown_separation.hip): the audit's outputs from the positions of a state log [K][13][pitch]
 int uavac_launch_flown_separation(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
                                   double radius, double *sep, int32_t *isep);

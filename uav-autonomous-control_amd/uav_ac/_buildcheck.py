@@ -218,15 +218,9 @@ def kernel_lds_bytes(obj: str, kernel: str):
     return [(n, int(v)) for v, n in found]
 
 
-def check_layer_kernels():
-    """The kernels of csrc/minsnap_layer.hip (offset layers that clear the separation audit, and the offset transform): all three must
-    be there, none may spill or use scratch memory at all (zero private-segment bytes: the coefficient sets of the decision kernel are
-    indexed by constants only).  The register limit of each follows from the LDS it ends up with: workgroups of four waves, so
-    min(8, 160 KiB // LDS) workgroups per CU are as many waves per SIMD, and the kernel must fit the allocation that still runs that
-    many (built: the decision kernel 50192 B of LDS -- the 48 KB tile, 1 KB of granted layers, two words -- hence three and <= 168,
-    at 139; the pre-pass and the transform no LDS, hence eight and <= 64, at 14 and 21).  Returns {kernel: VGPRs}, None when the
-    counts cannot be read."""
-    obj = os.path.join(PKG, "build", "minsnap_layer.o")
+def _check_layer_object(obj_name: str, kernels, what: str):
+    """The budget of the kernels of one object file of the layer search: see `check_layer_kernels`."""
+    obj = os.path.join(PKG, "build", obj_name)
     regs, priv, lds = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel"), kernel_lds_bytes(obj, "_kernel")
     if regs is None or priv is None or lds is None:
         return None
@@ -242,11 +236,33 @@ def check_layer_kernels():
             bad.append((n[:70], f"{lds[n]} bytes of LDS: fewer than three workgroups per CU", 0, 0))
         if v > limit or sp:
             bad.append((n[:70], v, sp, limit))
-    missing = [k for k in LAYER_KERNELS if not any(k in n for n, _, _ in regs)]
-    if bad or missing or len(regs) != len(LAYER_KERNELS) or len(priv) != len(regs):
-        raise RuntimeError(f"layer kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
+    missing = [k for k in kernels if not any(k in n for n, _, _ in regs)]
+    if bad or missing or len(regs) != len(kernels) or len(priv) != len(regs):
+        raise RuntimeError(f"{what} kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
                            f"{len(regs)} kernels found (compiler: {compiler_version()})")
     return {n: v for n, v, _ in regs}
+
+
+def check_layer_kernels():
+    """The kernels of csrc/minsnap_layer.hip (offset layers that clear the separation audit, and the offset transform): all three must
+    be there, none may spill or use scratch memory at all (zero private-segment bytes: the coefficient sets of the decision kernel are
+    indexed by constants only).  The register limit of each follows from the LDS it ends up with: workgroups of four waves, so
+    min(8, 160 KiB // LDS) workgroups per CU are as many waves per SIMD, and the kernel must fit the allocation that still runs that
+    many (built: the decision kernel 50192 B of LDS -- the 48 KB tile, 1 KB of granted layers, two words -- hence three and <= 168,
+    at 139; the pre-pass and the transform no LDS, hence eight and <= 64, at 14 and 21).  Returns {kernel: VGPRs}, None when the
+    counts cannot be read."""
+    return _check_layer_object("minsnap_layer.o", LAYER_KERNELS, "layer")
+
+
+LAYER_OBS_KERNELS = ("layer_prepass_kernel", "minsnap_layer_kernel")
+
+
+def check_layer_obs_kernels():
+    """The kernels of csrc/minsnap_layer_obs.hip (the same search, refusing layers that put a mission into a cuboid): the same check as
+    `check_layer_kernels` on the two instantiations with cuboids (built: the decision kernel 50976 B of LDS -- the search's 50192 B,
+    768 B of cuboids, two more words -- hence still three workgroups per CU and <= 168, at 142; the pre-pass no LDS, <= 64, at 14).
+    Returns {kernel: VGPRs}, None when the counts cannot be read."""
+    return _check_layer_object("minsnap_layer_obs.o", LAYER_OBS_KERNELS, "obstacle-aware layer")
 
 
 def check_rollout_registers(obj: str = None):
@@ -500,7 +516,9 @@ def run_all(verbose: bool = False, write_stamp: bool = True) -> dict:
              ("flown_separation_kernels", check_flown_separation_kernels,
               lambda r: f"{len(r)} flown-separation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("layer_kernels", check_layer_kernels,
-              lambda r: f"{len(r)} layer kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"))
+              lambda r: f"{len(r)} layer kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
+             ("layer_obs_kernels", check_layer_obs_kernels,
+              lambda r: f"{len(r)} obstacle-aware layer kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"))
     for key, fn, say in steps:
         r = fn()
         if r is None:

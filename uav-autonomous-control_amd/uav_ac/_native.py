@@ -26,6 +26,7 @@ SEP_ROWS, SEP_MAX_SPLIT = 5, 64             # separation audits (include/uavac.h
 STATE_LOG_ROWS = 13                         # rows of the rollout's state log per tick (positions: 0-2)
 STAGGER_ROWS, STAGGER_MAX_STEPS, STAGGER_MAX_GROUP = 3, 1023, 256      # start delays (include/uavac.h uavac_minsnap_stagger_dev)
 LAYER_ROWS, LAYER_MAX_STEPS, LAYER_MAX_GROUP = 3, 1023, 256            # offset layers (include/uavac.h uavac_minsnap_layer_dev)
+LAYER_OBS_ROWS = 4                                                     # ... that keep out of cuboids (uavac_minsnap_layer_obs_dev)
 VERSION = 310
 GROUND_IN_CONTACT, GROUND_TAKEN_OFF, GROUND_HIT_AFTER_TAKEOFF = 1, 2, 4       # istate row 3 (include/uavac.h)
 
@@ -99,6 +100,8 @@ _SIGNATURES = {
     "uavac_minsnap_delay_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P, _P]),
     "uavac_minsnap_layer_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, C.c_double, C.c_double, C.c_double,
                                           C.c_double, C.c_int, _P, _P]),
+    "uavac_minsnap_layer_obs_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, C.c_double, C.c_double, C.c_double,
+                                              C.c_double, C.c_int, _P, C.c_int, _P, _P]),
     "uavac_minsnap_shift_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int64, _P, _P]),
     "uavac_flown_separation_dev": (C.c_int,[_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, C.c_double, _P, _P]),
     "uavac_minsnap_row_counts_v_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P]),

@@ -210,8 +210,25 @@ class LayerResult:
     layers: "object"         # (B,) i32: the granted layer (0 for an unresolved or unexamined mission)
     steps: "object"          # (B,) i32: the candidate index granted (== layers); -1 unresolved; -2 not examined
     earlier: "object"        # (B,) i32: how many missions it was checked against (the included missions before it in its group)
-    block: "object" = None   # the [LAYER_ROWS][B] i32 block the three rows above are views of
+    block: "object" = None   # the [LAYER_ROWS][B] i32 block the three rows above are views of; [LAYER_OBS_ROWS][B] from a search with obstacles
     offsets: "object" = None  # (B, 3) f64: the granted layer * delta, what `Engine.shift` takes
+
+    @property
+    def blocked(self):
+        """(B,) i32 from a search with obstacles (`Engine.layer(..., obstacles=)`): how many of the candidates below the granted layer
+        (all of them for an unresolved mission) a cuboid refused -- row 3 of `block`; None from a search without obstacles."""
+        if self.block is None or self.block.shape[0] != nat.LAYER_OBS_ROWS:
+            return None
+        return self.block[nat.LAYER_OBS_ROWS - 1]
+
+
+@dataclass
+class DeconflictResult:
+    """What `Engine.deconflict` returns: the plan to fly and the two searches it was made from."""
+    plan: "object"           # rows-free RaggedBatch: delay(shift(plan, layer.offsets), stagger.start_rows)
+    stagger: StaggerResult   # the start delays (`Engine.stagger`)
+    layer: LayerResult       # the offset layers at those starts (`Engine.layer`, with the obstacles if any were given)
+    resolved: "object"       # (B,) bool, device: layer.steps >= 0
 
 
 @dataclass
@@ -784,7 +801,8 @@ class Engine:
                           True)
         return self.sample_rows(out) if rows else out
 
-    def layer(self, plan, radius: float, groups=None, start_rows=None, delta=(0.0, 0.0, -0.5), max_steps: int = 63) -> LayerResult:
+    def layer(self, plan, radius: float, groups=None, start_rows=None, delta=(0.0, 0.0, -0.5), max_steps: int = 63,
+              obstacles=None) -> LayerResult:
         """Prioritised deconfliction by offset (`uavac_minsnap_layer_dev`): the second lever on `Engine.separation`'s verdict, for the
         conflicts that waiting cannot resolve (a shared first or last waypoint, a crossing of a busy region).  `start_rows` are FIXED
         starts -- `StaggerResult.start_rows`, for instance; nobody is delayed by this call.  Within a group the missions are taken in
@@ -796,7 +814,15 @@ class Engine:
         `plan` and `groups` as `Engine.stagger` takes them, with the same limit of `LAYER_MAX_GROUP` missions per group.  Never reads
         `plan.traj`; stream-ordered, no sync.  Make the result part of the plan with `Engine.shift(plan, result.offsets)`;
         `Engine.separation(shifted, radius, groups, start_rows)` then finds no pair of resolved missions inside the radius.  The search
-        knows nothing about obstacles: run `Engine.audit(shifted, obstacles)` again, a layer can move a mission into a cuboid."""
+        knows nothing about obstacles unless obstacles are given: run `Engine.audit(shifted, obstacles)` again, a layer can move a
+        mission into a cuboid.
+        `obstacles` ((n, 6) array or tensor as `Engine.audit` takes it, n <= 16; zero rows are allowed): the search with obstacles
+        (`uavac_minsnap_layer_obs_dev`, `uav_ac.scoring.layer_obstacles_from_rows`).  A layer on which any sampled row of the mission's
+        own lies inside a cuboid is refused before it is compared with anybody; every included mission is examined, the first of its
+        group too, which is then moved only by a cuboid; `result.block` is (4, B) and `result.blocked` counts the refused layers below
+        the granted one (all of them for an unresolved mission).  `Engine.audit(shifted, obstacles).hit_rows` is then 0 for every
+        resolved mission.  steps = -1 with blocked = max_steps + 1 (`uav_ac.scoring.blocked_out`): every layer hits a cuboid, the
+        mission needs a new plan around the obstacle (`plan_collision_free`), not an offset."""
         torch = self._torch
         if isinstance(plan, RaggedPlan):
             batch = plan.batch
@@ -833,8 +859,22 @@ class Engine:
             start = self._dev(start_rows, torch.int32).reshape(-1)
             if start.numel() != B:
                 raise ValueError(f"one start row per mission: expected {B}, got {start.numel()}")
-        block = torch.empty((nat.LAYER_ROWS, B), dtype=torch.int32, device=self.device)
         offsets = torch.empty((B, 3), dtype=torch.float64, device=self.device)
+        if obstacles is not None:
+            cub = self._dev(obstacles, torch.float64)
+            if cub.numel() % 6 or (cub.dim() == 2 and cub.shape[1] != 6):
+                raise ValueError(f"obstacles must be (n, 6): xmin xmax ymin ymax zmin zmax, got {tuple(cub.shape)}")
+            cub = cub.reshape(-1, 6).contiguous()
+            n = int(cub.shape[0])
+            if n > nat.AUDIT_MAX_CUBOIDS:
+                raise ValueError(f"{n} cuboids; at most {nat.AUDIT_MAX_CUBOIDS} per search")
+            block = torch.empty((nat.LAYER_OBS_ROWS, B), dtype=torch.int32, device=self.device)
+            self._bind_stream()
+            self.ctx.call("uavac_minsnap_layer_obs_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
+                          B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(go), G, _ptr(start), float(radius), float(d[0]),
+                          float(d[1]), float(d[2]), max_steps, _ptr(cub) if n else None, n, _ptr(block), _ptr(offsets))
+            return LayerResult(*block[:nat.LAYER_ROWS].unbind(0), block, offsets)
+        block = torch.empty((nat.LAYER_ROWS, B), dtype=torch.int32, device=self.device)
         self._bind_stream()
         self.ctx.call("uavac_minsnap_layer_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
                       B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(go), G, _ptr(start), float(radius), float(d[0]), float(d[1]),
@@ -884,6 +924,29 @@ class Engine:
                           plan.row_offsets.clone(), co, torch.zeros((B,), dtype=torch.int32, **kw), None, int(plan.total_rows), first_yaw,
                           None, None, True)
         return self.sample_rows(out) if rows else out
+
+    def deconflict(self, plan, radius: float, groups=None, obstacles=None, start_rows=None, step: int = 1, max_delay_steps: int = 255,
+                   delta=(0.0, 0.0, -0.5), max_layers: int = 63) -> DeconflictResult:
+        """The fleet chain as one call: stagger -> layer -> shift -> delay.  `Engine.stagger(plan, radius, groups, start_rows, step,
+        max_delay_steps)` makes missions wait; `Engine.layer(plan, radius, groups, start_rows=stagger.start_rows, delta=delta,
+        max_steps=max_layers, obstacles=obstacles)` moves, at the granted starts, the ones that waiting cannot clear -- and, with
+        `obstacles`, every mission that a cuboid is in the way of; the plan to fly is `Engine.delay(Engine.shift(plan, layer.offsets),
+        stagger.start_rows)`.  A pure composition of those calls: every argument means what it means there, and the one host read is
+        `Engine.delay`'s.  `plan` is left as it is.
+        -> DeconflictResult: `plan` (a rows-free RaggedBatch; `eng.fleet(result.plan)` flies it), `stagger`, `layer`, and `resolved`
+        (B,) bool on the device = layer.steps >= 0.
+        GUARANTEES, among the RESOLVED missions of `result.plan`: `Engine.separation(result.plan, radius, groups)` finds no pair of them
+        inside the radius, and with `obstacles` `Engine.audit(result.plan, obstacles).hit_rows` is 0 for each of them (a hold row is the
+        mission's first row, which the search tested).  WHAT IT DOES NOT: it is greedy in priority order (ascending batch index), not a
+        minimum of the total delay or displacement; a mission that is not resolved keeps layer 0 and its granted start, wherever that
+        leaves it, and may be inside the radius of others or inside a cuboid -- look at `resolved`.  A mission whose every layer is
+        blocked (`uav_ac.scoring.blocked_out(result.layer, max_layers)`) needs a re-plan around the obstacle (`plan_collision_free`),
+        not an offset.  The start delays know nothing about obstacles: a delay does not move a path.  Without `obstacles` nothing is
+        known about cuboids at all."""
+        stag = self.stagger(plan, radius, groups=groups, start_rows=start_rows, step=step, max_steps=max_delay_steps)
+        lay = self.layer(plan, radius, groups=groups, start_rows=stag.start_rows, delta=delta, max_steps=max_layers, obstacles=obstacles)
+        flown = self.delay(self.shift(plan, lay.offsets), stag.start_rows)
+        return DeconflictResult(flown, stag, lay, lay.steps >= 0)
 
     def flown_separation(self, state_log, radius: float, groups=None) -> SeparationAudit:
         """The separation the fleet FLEW (`uavac_flown_separation_dev`): `Engine.separation` speaks about plans, this about the

@@ -19,7 +19,8 @@ bit for bit; `separation_ok` judges a separation audit.  `stagger_from_rows` sta
 `delay_rows` states on sampled rows what the delay transform (`Engine.delay`, uavac_minsnap_delay_dev) makes of a plan and its start
 rows, and `separation_from_log` is `separation_from_rows` for a FLIGHT: the rule of `Engine.flown_separation`
 (uavac_flown_separation_dev) on the positions of a rollout's state log.  `layer_from_rows` states the rule of the second lever on
-the audit (`Engine.layer`, uavac_minsnap_layer_dev: offset layers by priority at fixed starts), `layer_ok` judges its result, and
+the audit (`Engine.layer`, uavac_minsnap_layer_dev: offset layers by priority at fixed starts), `layer_obstacles_from_rows` the same
+search when it also refuses layers inside cuboids (uavac_minsnap_layer_obs_dev), `layer_ok` and `blocked_out` judge the result, and
 `shift_coeffs` states the transform that makes granted offsets part of the plan (`Engine.shift`, uavac_minsnap_shift_dev).
 """
 from __future__ import annotations
@@ -419,6 +420,7 @@ def stagger_ok(istag) -> dict:
 
 
 LAYER_LAYER, LAYER_STEPS, LAYER_EARLIER = range(nat.LAYER_ROWS)                                  # ilayer rows (include/uavac.h)
+LAYER_BLOCKED = nat.LAYER_OBS_ROWS - 1                                                           # ... and the row the search with obstacles adds
 
 
 def shift_coeffs(coeffs, seg_offsets_or_m, offsets):
@@ -523,15 +525,127 @@ def layer_from_rows(rows_at, row_offsets, radius, group_offsets=None, start_rows
     return ilayer
 
 
+def layer_obstacles_from_rows(rows_at, row_offsets, radius, cuboids, group_offsets=None, start_rows=None, max_steps=63):
+    """`layer_from_rows` with obstacles -- the SPECIFICATION of `uavac_minsnap_layer_obs_dev` (csrc/minsnap_layer_obs.hip), which is
+    tested against it exactly.  NumPy on the host.  `rows_at`, `row_offsets`, `radius`, `group_offsets`, `start_rows`, `max_steps` as
+    `layer_from_rows` takes them, and the clock, the excluded missions (judged on layer 0), the clamped starts, `LAYER_MAX_GROUP` and
+    the distance arithmetic are the same.  `cuboids` (n, 6): xmin xmax ymin ymax zmin zmax, 0 <= n <= AUDIT_MAX_CUBOIDS.
+
+    The differences, and only these.  Candidate q of mission i is BLOCKED when any of the mission's own rows
+    rows_at(q)[ro[i]:ro[i + 1], 0:3] lies inside any cuboid by the audit's inclusive test (x >= xmin and x <= xmax and ...: a NaN bound
+    or an inverted box contains nothing); those rows cover its whole shared clock, since before its start it holds row 0 and after its
+    end row N - 1.  The cuboid test comes first: a blocked candidate is never compared with partners.  EVERY included mission is
+    examined, the first of its group too (earlier = 0, no partners): it gets the lowest layer that no cuboid blocks, so "the lowest
+    index is never moved" becomes "is moved only by a cuboid".  A mission for which no layer 0 .. max_steps is both unblocked and clear
+    is unresolved: steps = -1, layer 0, and it remains a partner for later missions.
+    -> ilayer (LAYER_OBS_ROWS, B) i32: rows 0-2 as `layer_from_rows`; row 3 `blocked` = how many of the candidates q = 0 .. steps - 1
+    (0 .. max_steps when unresolved) a cuboid refused, 0 for a mission that was not examined.  With n = 0 rows 0-2 equal
+    `layer_from_rows` exactly and row 3 is zero."""
+    ro = np.asarray(row_offsets.detach().cpu().numpy() if hasattr(row_offsets, "detach") else row_offsets, dtype=np.int64).reshape(-1)
+    B = len(ro) - 1
+    radius, max_steps = float(radius), int(max_steps)
+    if not callable(rows_at):
+        raise ValueError("rows_at must be a callable: layer -> rows")
+    if not (np.isfinite(radius) and radius >= 0.0):
+        raise ValueError("radius must be finite and >= 0")
+    if not (0 <= max_steps <= nat.LAYER_MAX_STEPS):
+        raise ValueError(f"max_steps must be in 0 .. {nat.LAYER_MAX_STEPS}")
+    cub = np.asarray(_host(cuboids), dtype=np.float64)
+    if cub.size and (cub.ndim != 2 or cub.shape[1] != 6):
+        raise ValueError("cuboids must be (n, 6): xmin xmax ymin ymax zmin zmax")
+    cub = cub.reshape(-1, 6)
+    if len(cub) > nat.AUDIT_MAX_CUBOIDS:
+        raise ValueError(f"{len(cub)} cuboids; at most {nat.AUDIT_MAX_CUBOIDS}")
+    go = np.array([0, B], dtype=np.int64) if group_offsets is None else np.asarray(
+        group_offsets.detach().cpu().numpy() if hasattr(group_offsets, "detach") else group_offsets, dtype=np.int64).reshape(-1)
+    if len(go) < 2 or go[0] != 0 or go[-1] != B or (np.diff(go) < 0).any():
+        raise ValueError("group_offsets must ascend from 0 to B")
+    S = np.zeros(B, dtype=np.int64) if start_rows is None else np.clip(np.asarray(
+        start_rows.detach().cpu().numpy() if hasattr(start_rows, "detach") else start_rows, dtype=np.int64).reshape(-1), 0, _MAX_CLOCK)
+    if len(S) != B:
+        raise ValueError("one start row per mission")
+    r2 = radius * radius
+    N = np.diff(ro)
+
+    def pos(q, b):
+        return _host(rows_at(q))[ro[b]:ro[b + 1], 0:3]
+
+    def is_blocked(q, b):
+        p = pos(q, b)
+        with np.errstate(invalid="ignore"):
+            for x in cub:
+                if ((p[:, 0] >= x[0]) & (p[:, 0] <= x[1]) & (p[:, 1] >= x[2]) & (p[:, 1] <= x[3]) & (p[:, 2] >= x[4]) & (p[:, 2] <= x[5])).any():
+                    return True
+        return False
+
+    included = np.array([0 < N[b] <= _MAX_CLOCK and bool(np.isfinite(pos(0, b)).all()) for b in range(B)], dtype=bool)
+    ilayer = np.zeros((nat.LAYER_OBS_ROWS, B), dtype=np.int32)
+    ilayer[LAYER_STEPS] = -2
+    for g in range(len(go) - 1):
+        g0, g1 = int(go[g]), int(go[g + 1])
+        if g1 - g0 > nat.LAYER_MAX_GROUP:
+            continue
+        done = []                                                                     # the included missions decided so far
+        L = {}
+        for i in range(g0, g1):
+            if not included[i]:
+                continue
+            ilayer[LAYER_EARLIER, i] = len(done)
+            L[i], steps, blocked = 0, -1, 0
+            if done:
+                H = max(max(int(S[j]) + int(N[j]) for j in done), int(S[i]) + int(N[i]))
+                k = np.arange(H)
+                others = np.stack([pos(L[j], j)[np.clip(k - S[j], 0, N[j] - 1)] for j in done])                # (n, H, 3)
+                at = np.clip(k - S[i], 0, N[i] - 1)
+            for q in range(max_steps + 1):
+                if len(cub) and is_blocked(q, i):                                     # the cuboids first: never compared with partners
+                    blocked += 1
+                    continue
+                clear = True
+                if done:
+                    own = pos(q, i)[at]                                               # (H, 3): where the candidate stands at clock row k
+                    with np.errstate(invalid="ignore", over="ignore"):
+                        dx, dy, dz = (own[None, :, c] - others[:, :, c] for c in range(3))
+                        clear = not bool(((dx * dx + dy * dy) + dz * dz < r2).any())
+                if clear:
+                    L[i], steps = q, q
+                    break
+            ilayer[LAYER_LAYER, i], ilayer[LAYER_STEPS, i], ilayer[LAYER_BLOCKED, i] = L[i], steps, blocked
+            done.append(i)
+    return ilayer
+
+
+def _layer_block(result):
+    block = np.asarray(_host(result))
+    if block.ndim != 2 or block.shape[0] not in (nat.LAYER_ROWS, nat.LAYER_OBS_ROWS):
+        raise ValueError(f"a layer block is [{nat.LAYER_ROWS}][B] (with obstacles [{nat.LAYER_OBS_ROWS}][B]), got {block.shape}")
+    return block
+
+
 def layer_ok(result) -> dict:
-    """A layer result (`Engine.layer` -> LayerResult, anything with `steps`, or the [LAYER_ROWS][B] block itself; tensors on any device
-    or arrays) -> dict of (B,) bool host arrays: `resolved` (steps >= 0: a layer was granted, layer 0 included) and `examined` (steps
-    != -2).  A mission that was not examined -- an excluded one, or one of an oversized group -- never looks resolved."""
+    """A layer result (`Engine.layer` -> LayerResult, anything with `steps`, or the [LAYER_ROWS][B] block itself -- with obstacles the
+    [LAYER_OBS_ROWS][B] one; tensors on any device or arrays) -> dict of (B,) bool host arrays: `resolved` (steps >= 0: a layer was
+    granted, layer 0 included) and `examined` (steps != -2).  A mission that was not examined -- an excluded one, or one of an oversized
+    group -- never looks resolved."""
     if hasattr(result, "steps"):
         steps = np.asarray(_host(result.steps)).reshape(-1)
     else:
-        block = np.asarray(_host(result))
-        if block.ndim != 2 or block.shape[0] != nat.LAYER_ROWS:
-            raise ValueError(f"a layer block is [{nat.LAYER_ROWS}][B], got {block.shape}")
-        steps = block[LAYER_STEPS]
+        steps = _layer_block(result)[LAYER_STEPS]
     return {"resolved": steps >= 0, "examined": steps != -2}
+
+
+def blocked_out(result, max_steps: int):
+    """The missions for which EVERY layer 0 .. `max_steps` hits a cuboid: steps == -1 and blocked == max_steps + 1, from the result of
+    a layer search with obstacles (`Engine.layer(..., obstacles=)` -> LayerResult, anything with `steps` and `blocked`, or the
+    [LAYER_OBS_ROWS][B] block; `max_steps` as the search was given it) -> (B,) bool host array.  "Too crowded" (unresolved with fewer
+    blocked layers) may yield to more layers or another delta; a blocked-out mission needs a new plan around the obstacle."""
+    if hasattr(result, "steps"):
+        if getattr(result, "blocked", None) is None:
+            raise ValueError("a layer result without `blocked`: the search was run without obstacles")
+        steps, blocked = (np.asarray(_host(v)).reshape(-1) for v in (result.steps, result.blocked))
+    else:
+        block = _layer_block(result)
+        if block.shape[0] != nat.LAYER_OBS_ROWS:
+            raise ValueError(f"a layer block with obstacles is [{nat.LAYER_OBS_ROWS}][B], got {block.shape}")
+        steps, blocked = block[LAYER_STEPS], block[LAYER_BLOCKED]
+    return (steps == -1) & (blocked == int(max_steps) + 1)
