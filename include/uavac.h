@@ -306,7 +306,7 @@ int uavac_minsnap_audit_dev(uavac_ctx *ctx, const double *coeffs, const int32_t 
 
 /* SEPARATION AUDIT: the fleet's audit against itself.  For every mission of a GROUP of missions that share an airspace: the closest
  * approach to any other mission of the group, to which one and when; how many others come inside a protection radius and when the
- * first one does -- from coefficients and row counts alone (csrc/minsnap_separation.hip): no row is written, nothing is read back,
+ * first one does -- from coefficients and row counts alone (csrc/minsnap_separation.hip, csrc/fleet_clock.h): no row is written, nothing is read back,
  * everything is enqueued on the ctx stream.  coeffs / seg_rows / seg_offsets / B / m / dt as in uavac_minsnap_audit_dev (seg_offsets
  * NULL = uniform, otherwise ragged and clamped).
  * CLOCK.  The missions of a group share one row clock k = 0, 1, ....  Mission b has N_b rows -- exactly the rows the sampler writes,
@@ -349,7 +349,7 @@ int uavac_minsnap_separation_dev(uavac_ctx *ctx, const double *coeffs, const int
 /* STAGGER: the call that acts on the separation audit's verdict -- prioritised deconfliction by start delay.  Within a group the
  * missions are taken in ascending batch index, which is the priority (the lowest index is never delayed), and each one is granted the
  * smallest start delay that keeps it outside the protection radius of every mission decided before it -- from coefficients and row
- * counts alone (csrc/minsnap_stagger.hip): no row is written, nothing is read back, everything is enqueued on the ctx stream, scratch
+ * counts alone (csrc/minsnap_stagger.hip, csrc/fleet_search.h): no row is written, nothing is read back, everything is enqueued on the ctx stream, scratch
  * comes from the ctx arena.  coeffs / seg_rows / seg_offsets / B / m / dt / group_offsets / G / start_rows / radius exactly as in
  * uavac_minsnap_separation_dev, and CLOCK, GROUPS, EXCLUDED MISSIONS and ROUNDING are the ones stated there: mission b with start s
  * stands at its own row clamp(k - s, 0, N_b - 1); d^2 = (dx * dx + dy * dy) + dz * dz without contraction; r^2 = radius * radius
@@ -421,7 +421,7 @@ int uavac_minsnap_delay_dev(uavac_ctx *ctx, const double *coeffs, const double *
 
 /* LAYER: prioritised deconfliction by OFFSET -- the second lever on the separation audit's verdict.  uavac_minsnap_stagger_dev makes a
  * mission wait; this call moves it, by whole steps of `delta` (metres; NED, so delta_z < 0 is one flight level UP; any direction is
- * allowed, a lateral offset is the same code).  From coefficients and row counts alone (csrc/minsnap_layer.hip): no row is written,
+ * allowed, a lateral offset is the same code).  From coefficients and row counts alone (csrc/minsnap_layer.hip, csrc/fleet_search.h): no row is written,
  * nothing is read back, everything is enqueued on the ctx stream, scratch comes from the ctx arena.  coeffs / seg_rows / seg_offsets /
  * B / m / dt / group_offsets / G / start_rows / radius exactly as in uavac_minsnap_stagger_dev, and CLOCK, GROUPS, EXCLUDED MISSIONS,
  * the priority (ascending batch index; the lowest index is never moved) and the group limit are the ones stated there.  start_rows[b]

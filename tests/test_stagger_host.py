@@ -61,6 +61,30 @@ def test_the_build_keeps_the_stagger_kernels_in_registers():
     assert any("minsnap_stagger_kernel" in k for k in counts) and any("stagger_prepass_kernel" in k for k in counts)
 
 
+def test_groups_as_the_fleet_calls_take_them():
+    """`Engine._groups`, behind separation, stagger, layer and flown_separation: None, a group size, offsets; the refusals and their words."""
+    import torch
+    from uav_ac.engine import Engine
+    eng = object.__new__(Engine)                             # (no context: the helper needs the device and torch only)
+    eng._torch, eng.device = torch, torch.device("cpu")
+    assert eng._groups(None, 10) == (None, 0) and eng._groups(None, 256, 256) == (None, 0)
+    for groups, want in ((4, [0, 4, 8, 10]), (np.int64(5), [0, 5, 10]), (16, [0, 10]), ([0, 3, 10], [0, 3, 10]),
+                         (np.array([0, 10]), [0, 10]), (torch.tensor([0, 1, 10], dtype=torch.int32), [0, 1, 10])):
+        for limit in (None, 10):
+            go, G = eng._groups(groups, 10, limit)
+            assert go.dtype == torch.int64 and go.tolist() == want and G == len(want) - 1
+    for call, words in ((lambda: eng._groups(0, 10), "a group size must be >= 1"),
+                        (lambda: eng._groups(-3, 10, 256), "a group size must be >= 1"),
+                        (lambda: eng._groups([0], 10), "group offsets hold at least two entries"),
+                        (lambda: eng._groups(None, 257, 256), "one group of 257 missions; at most 256 per group"),
+                        (lambda: eng._groups(300, 600, 256), "a group of 300 missions; at most 256 per group"),
+                        (lambda: eng._groups(torch.tensor([0, 1, 300]), 300, 256), "a group of 299 missions; at most 256 per group")):
+        with pytest.raises(ValueError) as err:
+            call()
+        assert str(err.value) == words
+    assert eng._groups([0, 300], 300)[1] == 1                # (no limit: the separation audits take a group of any size)
+
+
 def test_two_crossing_paths_the_second_gets_the_smallest_clearing_delay():
     from uav_ac.scoring import separation_from_rows, stagger_from_rows
     rows, ro = rows_of(ALONG_X, ALONG_Y)

@@ -32,14 +32,14 @@
 // pitch, nor on what else is in the batch; each output has one writer and there are no atomics.  Every column index is below B (lanes
 // past the batch or the group read column B - 1 or the group's last one and are masked): columns B .. pitch - 1 are never read.
 
-#include "uavac_internal.h"
-#include "separation_reduce.h"
+#include "fleet_clock.h"
 
 #include <limits>
 
 namespace {
 
 using namespace sepred;                                     // the tile's shape and the reduction: shared with minsnap_separation.hip
+using fleet::group_range;                                   // (fleet_clock.h: the group clamp of every fleet kernel)
 
 constexpr int kLogRows = 13;                                // rows of the state log per tick (positions: 0-2)
 
@@ -69,9 +69,8 @@ __global__ void __launch_bounds__(kThreads, 3) flown_separation_kernel(const dou
         g = lo;
     }
     for (; g < G; ++g) {                                     // (uniform: every thread of the workgroup sees the same groups)
-        const long long a0 = group_offsets ? group_offsets[g] : 0, a1 = group_offsets ? group_offsets[g + 1] : B;
-        const int g0 = (int)(a0 < 0 ? 0 : (a0 > B ? B : a0));            // clamped: malformed offsets must not leave the batch
-        const int g1 = (int)(a1 < g0 ? g0 : (a1 > B ? B : a1));
+        int g0, g1;
+        group_range(group_offsets, g, B, g0, g1);
         if (g0 >= w1 || g0 >= B) break;
         if (g1 <= w0 || g1 == g0) continue;
         const bool act = live && b >= g0 && b < g1;

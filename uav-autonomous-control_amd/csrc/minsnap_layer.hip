@@ -7,36 +7,23 @@
 // uav_ac.scoring.layer_from_rows states the search in NumPy on sampled rows, uav_ac.scoring.shift_coeffs the transform.
 //
 // Three kernels, all on the ctx stream:
-//   layer_prepass_kernel   per mission (sixteen lanes each), the audit's and stagger's: its row total N, its start clamped to 0 ..
-//                          2^29, whether it is EXCLUDED (kept as N = 0 in ctx scratch); and the record of a mission that is never
-//                          examined -- layer 0 / -2 / 0 and the offset of layer 0 -- which the decision kernel overwrites for everybody
-//                          it decides
-//   minsnap_layer_kernel   the decisions.  Stagger's structure with another candidate axis: one workgroup of four wavefronts per group
-//                          walks the group's included missions in ascending order; for mission i THE 64 LANES ARE 64 CANDIDATE LAYERS
-//                          of that one mission, lane l stands on layer q0 + l.  The earlier missions come in j-tiles of 64, the clock
-//                          from 0 to the horizon in chunks of 32 rows, wave w taking rows 8 w .. 8 w + 7; for its rows a wave evaluates
-//                          the j-tile's positions ON THEIR GRANTED LAYERS into its own quarter of the LDS tile (lane = j), then each
-//                          lane evaluates its own candidate and reads the partners as LDS broadcasts.  All 64 candidates share the
-//                          start, hence the clock row, the segment and t: only c0 differs between the lanes, and of the Horner chain
-//                          only the last fma per axis sees it.  A lane keeps one bit: somebody was inside.  After the last tile the
-//                          four waves OR their bits through LDS and every thread takes the same decision: the lowest clear lane with
-//                          q <= max_steps is granted; if there is none the next 64 layers are examined; after the last one the mission
-//                          is unresolved and stays on layer 0.  The OR lives in one LDS word (`round_hit`) that every wave feeds after
-//                          each chunk in which a lane of its met somebody; once every live candidate is in it the round's answer is
-//                          "none" whatever else would be found, and every wave leaves the round at its next chunk: reading the word
-//                          early or late changes the time only.
+//   layer_prepass_kernel   per mission: fleet_clock.h's pre-pass -- row total N (0: EXCLUDED), start clamped to 0 .. 2^29, in ctx scratch
+//                          -- and the record of a mission that is never examined -- layer 0 / -2 / 0 and the offset of layer 0 --
+//                          which the decision kernel overwrites for everybody it decides (fleet_search.h: two object files need it)
+//   minsnap_layer_kernel   the decisions: fleet_search.h's search with the Layer policy.  THE 64 LANES ARE 64 CANDIDATE LAYERS of one
+//                          mission, lane l stands on layer q0 + l, the partners ON THEIR GRANTED LAYERS.  All 64 candidates share the
+//                          start, hence the clock row, the segment and t: only c0 differs between the lanes (the walk's after-load
+//                          hook, layer_c0), and of the Horner chain only the last fma per axis sees it.  A mission that is not
+//                          resolved stays on layer 0.
 //   minsnap_shift_kernel   the transform: out = coeffs with offsets[b] added to c0 of every segment of mission b.  One thread per 16
 //                          bytes of the coefficients, twelve per segment; c0 = (x, y, z) is piece 0 and the first half of piece 1.
-// The granted layers of the group live in LDS (256 int32: hence UAVAC_LAYER_MAX_GROUP).  A workgroup never waits for another one, and
-// nothing is spun on anywhere: round_hit is looked at once per chunk; the only atomic on global memory is the sticky flag.
 //
 // ROUNDING (part of the contract).  The offset of layer q on axis a is o = fl((double)q * delta_a), the candidate's coefficient
 // c0' = fl(c0 + o): two roundings, never one fma; layer 0 is the mission as it is (nothing is added).  Positions by the sampler's fma
 // chain on those coefficients (minsnap_eval_pos), the distance WITHOUT contraction: d^2 = (dx dx + dy dy) + dz dz.
-// The pre-pass and the decision kernel are templates (minsnap_layer_search.h) that the obstacle-aware search shares: this file
-// instantiates them without cuboids and holds the transform.
+// This file instantiates the search without cuboids and holds the transform.
 
-#include "minsnap_layer_search.h"
+#include "fleet_search.h"
 
 namespace {
 

@@ -2,12 +2,12 @@
 // refuse a candidate -- a row of the mission's OWN on that layer lies inside a cuboid.  The contract is in include/uavac.h
 // (uavac_minsnap_layer_obs_dev); uav_ac.scoring.layer_obstacles_from_rows states the search in NumPy on sampled rows.
 //
-// The kernels are the OBS = true instantiations of minsnap_layer_search.h; the pair search is the one copy there.  What OBS adds to the
-// decision kernel, per mission i and round of 64 candidates (the 64 lanes are the layers q0 .. q0 + 63 of mission i):
+// The kernels are the OBS = true instantiations of fleet_search.h (the LayerObs policy); the search is the one copy there.  What it adds to
+// the decision kernel, per mission i and round of 64 candidates (the 64 lanes are the layers q0 .. q0 + 63 of mission i):
 //   the cuboids    [n][6] in LDS, loaded once per workgroup: a read is one broadcast, the trip count is uniform
 //   the blocked    before the round's pair search the four wavefronts split the mission's own rows 0 .. N_i - 1 (they cover its whole
 //   mask           clock: before its start it holds row 0, after its end row N_i - 1); every lane evaluates its candidate's position --
-//                  minsnap_eval_pos on layer_c0(c0, q, delta): all lanes share the row, the segment and t, only the last fma per axis
+//                  the clock walk (fleet_clock.h) with layer_c0(c0, q, delta) as its hook: all lanes share the row, the segment and t, only the last fma per axis
 //                  sees c0 -- and tests it against the cuboids with the audit's inclusive comparison.  The bit is therefore what the
 //                  sampler writes, and the audit counts, for the plan shifted by q * delta, bit for bit
 //   the seed       the waves OR their ballots into a word of their own (`round_blocks`) and into the round's `round_hit`; behind a
@@ -21,7 +21,7 @@
 // LDS: the search's 50 192 B, 768 B of cuboids and two more words -- three workgroups per CU as before.  Plain C++ and vector stores;
 // the only atomic on global memory is the sticky flag.
 
-#include "minsnap_layer_search.h"
+#include "fleet_search.h"
 
 int uavac_launch_layer_obs(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
                            const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double delta_x, double delta_y,

@@ -5,15 +5,15 @@
 // (uavac_minsnap_separation_dev); uav_ac.scoring.separation_from_rows states it in NumPy on sampled rows, and the results are the same bits.
 //
 // Three launches on the ctx stream:
-//   separation_prepass_kernel   per mission (sixteen lanes each): its row total N, its start row clamped to >= 0, and whether it is
-//                               EXCLUDED (no rows, or a coefficient that is not finite) -- kept as N = 0 in ctx scratch
+//   separation_prepass_kernel   per mission: fleet_clock.h's pre-pass and nothing else -- the row total N (0: EXCLUDED) and the clamped
+//                               start row, in ctx scratch
 //   minsnap_separation_kernel   the pairs.  A workgroup owns the 64 consecutive missions [64 x, 64 x + 64) of the batch, one per lane (i),
 //                               and visits every group that reaches into this window, with the lanes of other groups idle.  Per group
 //                               it walks the group's missions in j-tiles of 64 and, per j-tile, the group's clock from 0 to its horizon
 //                               in chunks of 32 rows.  Its four wavefronts split each chunk: wave w takes rows 8 w .. 8 w + 7.  For its
 //                               rows a wave first evaluates the j-tile's positions into its own quarter of the LDS tile (lane = j: the
-//                               audit's forward segment walk, position-only Horner, the segment's coefficients fetched per chunk), then
-//                               each lane evaluates its OWN position once per row (its segment's coefficients stay in registers for the chunk) and
+//                               clock walk of fleet_clock.h -- forward segment walk, position-only Horner, the segment's coefficients
+//                               fetched per chunk), then each lane evaluates its OWN position once per row in the same way and
 //                               reads the 64 partners' positions as LDS broadcasts (every lane reads the same address).  A wave reads
 //                               only what it wrote itself: no workgroup barrier inside the clock loop.
 //                               Excluded partners and lanes past the group's end are NaN positions: a NaN distance is never below
@@ -30,86 +30,38 @@
 // of order, so the outputs depend neither on P, nor on the tile or chunk sizes, nor on what else is in the batch; each output has one
 // writer and there are no atomics but the sticky flag.  The price is the factor 2 of not using d(i, j) = d(j, i).
 // The reduction itself -- the pair loop of a row, the order, the meeting of the waves, the merge of the partial records -- is in
-// separation_reduce.h, shared with the audit of a FLIGHT (flown_separation.hip), which reads its positions from a state log.
+// separation_reduce.h, shared with the audit of a FLIGHT (flown_separation.hip), which reads its positions from a state log.  The clock
+// itself -- a mission's segments, the pre-pass, the walk, the group clamp -- is in fleet_clock.h, shared with the two searches that act
+// on this audit's verdict (fleet_search.h).
 //
 // ROUNDING (part of the contract): positions by the sampler's fma chain (minsnap_eval_pos), the distance WITHOUT contraction: dx = xi -
 // xj, ..., d^2 = (dx dx + dy dy) + dz dz, each product and sum rounded on its own.
 
-#include "uavac_internal.h"
-#include "minsnap_eval.h"
-#include "separation_reduce.h"
+#include "fleet_clock.h"
 
 #include <cmath>
 #include <limits>
 
 namespace {
 
-using namespace sepred;                                     // the tile's shape and the reduction: shared with flown_separation.hip
-
-constexpr int kMaxClock = 1 << 29;                          // start rows and row totals above this cannot be clocked with int
-constexpr int kPreLanes = 16;                               // lanes per mission of the pre-pass
-
-// First segment and segment count of mission b: uniform (so == NULL) or ragged, clamped to 1 .. m like every ragged kernel clamps it.
-struct Mission {
-    long long s0;
-    int m;
-};
-__device__ __forceinline__ Mission mission_of(const int64_t *__restrict__ so, int b, int m_uniform) {
-    Mission M;
-    if (so) {
-        M.s0 = so[b];
-        const long long n = so[b + 1] - M.s0;
-        M.m = (int)(n < 1 ? 1 : (n > m_uniform ? m_uniform : n));
-    } else {
-        M.s0 = (long long)b * m_uniform;
-        M.m = m_uniform;
-    }
-    return M;
-}
+using namespace fleet;                                      // the clock, the pre-pass and, through it, sepred's tile and reduction
 
 // ------------------------------------------------------------------------------------------------------------------ pre-pass
 __global__ void __launch_bounds__(kThreads) separation_prepass_kernel(const double *__restrict__ coeffs, const int32_t *__restrict__ seg_rows,
                                                                       const int64_t *__restrict__ seg_offsets, int B, int m,
                                                                       const int32_t *__restrict__ start_rows, int32_t *__restrict__ n_rows,
                                                                       int32_t *__restrict__ start, int32_t *__restrict__ flags) {
-    constexpr int kPerWave = 64 / kPreLanes;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int g = lane / kPreLanes, l = lane % kPreLanes;
-    const int b = (blockIdx.x * kWaves + w) * kPerWave + g;
-    const bool live = b < B;
-    const Mission M = mission_of(seg_offsets, live ? b : B - 1, m);
-    const int32_t *rows_of = seg_rows + M.s0;
-    const double *cm = coeffs + (size_t)M.s0 * 24;
-    long long total = 0;                                     // the mission's rows: what the sampler's row offsets give it
-    for (int s = 0; s < M.m; ++s) total += rows_of[s];
-    double z = 0.0;                                          // stays 0 while every coefficient is finite (0 * inf and 0 * NaN are NaN)
-    for (int k = l; k < M.m * 24; k += kPreLanes) z = fma(0.0, cm[k], z);
-#pragma unroll
-    for (int d = kPreLanes / 2; d >= 1; d >>= 1) z += __shfl_xor(z, d);
-    if (live && l == 0) {
-        int s = start_rows ? start_rows[b] : 0;
-        bool bad = s < 0 || s > kMaxClock;                   // cannot be refused by the host: clamped, and flag 0
-        s = s < 0 ? 0 : (s > kMaxClock ? kMaxClock : s);
-        const bool too_long = total > kMaxClock;
-        const bool excluded = !(z == 0.0) || total < 1 || too_long;
-        n_rows[b] = excluded ? 0 : (int)total;
-        start[b] = s;
-        if (bad || too_long) atomicOr(&flags[0], 1);
-    }
+    int b, s;                                                // (the audit keeps no record of its own for a mission)
+    prepass_mission(coeffs, seg_rows, seg_offsets, B, m, start_rows, n_rows, start, flags, b, s);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the pairs
-// the segment of a mission's row r, walked forward from where the lane stood (rows only grow): the audit's walk
-__device__ __forceinline__ void seek(const int32_t *__restrict__ rows_of, int mb, int r, int &s, int &base, int &cnt) {
-    while (s + 1 < mb && r >= base + cnt) { base += cnt; ++s; cnt = rows_of[s]; }
-}
-
 __global__ void __launch_bounds__(kThreads, 3) minsnap_separation_kernel(
     const double *__restrict__ coeffs, const int32_t *__restrict__ seg_rows, const int64_t *__restrict__ seg_offsets, int B, int m, double dt,
     const int64_t *__restrict__ group_offsets, int G, const int32_t *__restrict__ n_rows, const int32_t *__restrict__ start, double r2,
     double *__restrict__ part_d2, int32_t *__restrict__ part_i) {
     __shared__ double tile[kWaves * kRegion];
-    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    const double inf = std::numeric_limits<double>::infinity();
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int P = gridDim.y, p = blockIdx.y;
     const int w0 = blockIdx.x * kTile, w1 = w0 + kTile;      // the window of missions this workgroup owns
@@ -132,9 +84,8 @@ __global__ void __launch_bounds__(kThreads, 3) minsnap_separation_kernel(
         g = lo;
     }
     for (; g < G; ++g) {                                     // (uniform: every thread of the workgroup sees the same groups)
-        const long long a0 = group_offsets ? group_offsets[g] : 0, a1 = group_offsets ? group_offsets[g + 1] : B;
-        const int g0 = (int)(a0 < 0 ? 0 : (a0 > B ? B : a0));            // clamped: malformed offsets must not leave the batch
-        const int g1 = (int)(a1 < g0 ? g0 : (a1 > B ? B : a1));
+        int g0, g1;
+        group_range(group_offsets, g, B, g0, g1);
         if (g0 >= w1 || g0 >= B) break;
         if (g1 <= w0 || g1 == g0) continue;
         const bool act = live && b >= g0 && b < g1;
@@ -174,54 +125,18 @@ __global__ void __launch_bounds__(kThreads, 3) minsnap_separation_kernel(
             int tk = kNone, tj = kNone, tfirst = kNone;
             unsigned long long mask = 0;
             for (int k0 = w * kRows; k0 < H; k0 += kChunk) {
-                {                                            // the j-tile's positions at this wavefront's rows of the chunk
-                    // (the segment of the chunk's first row is fetched unconditionally: the 24 coefficients then live from here to
-                    // the end of this block only, not around the clock loop)
-                    double cj[24];
-                    seek(jrows, Mj.m, min(max(k0 - sj, 0), nj - 1), js, jbase, jcnt);
-                    int jloaded = js;
-#pragma unroll
-                    for (int q = 0; q < 24; ++q) cj[q] = jcm[js * 24 + q];
-#pragma nounroll
-                    for (int r = 0; r < kRows && k0 + r < H; ++r) {
-                        const int row = min(max(k0 + r - sj, 0), nj - 1);
-                        seek(jrows, Mj.m, row, js, jbase, jcnt);
-                        if (js != jloaded) {
-#pragma unroll
-                            for (int q = 0; q < 24; ++q) cj[q] = jcm[js * 24 + q];
-                            jloaded = js;
-                        }
-                        double x, y, z;
-                        minsnap_eval_pos<1>(cj, (double)(int)(row - jbase) * dt, x, y, z);
-                        double *o = mine + (r * kTile + lane) * 3;
-                        o[0] = nj > 0 ? x : nan; o[1] = nj > 0 ? y : nan; o[2] = nj > 0 ? z : nan;
-                    }
-                }
-                lds_wave_fence();                            // (a wavefront reads only its own quarter)
-                double c[24];                                // the lane's own segment, fetched per chunk in the same way
-                seek(irows, Mi.m, min(max(k0 - si, 0), ni - 1), is, ibase, icnt);
-                int iloaded = is;
-#pragma unroll
-                for (int q = 0; q < 24; ++q) c[q] = icm[is * 24 + q];
-#pragma nounroll
-                for (int r = 0; r < kRows && k0 + r < H; ++r) {
-                    const int k = k0 + r;
-                    const int row = min(max(k - si, 0), ni - 1);
-                    seek(irows, Mi.m, row, is, ibase, icnt);
-                    if (is != iloaded) {
-#pragma unroll
-                        for (int q = 0; q < 24; ++q) c[q] = icm[is * 24 + q];
-                        iloaded = is;
-                    }
-                    double xi, yi, zi;
-                    minsnap_eval_pos<1>(c, (double)(int)(row - ibase) * dt, xi, yi, zi);
+                // the j-tile's positions at this wavefront's rows of the chunk, then the lane's own against them (a wavefront reads only
+                // its own quarter)
+                clock_walk_to_tile<false>(mine, lane, jrows, jcm, Mj.m, nj, sj, k0, H, dt, js, jbase, jcnt, AsPlanned{});
+                lds_wave_fence();
+                clock_walk<false>(irows, icm, Mi.m, ni, si, k0, H, dt, is, ibase, icnt, AsPlanned{}, [&](int r, int k, double xi, double yi, double zi) {
                     double rm = inf;
                     int rkey = 0;
                     if (self_tile) pair_row<true>(mine + r * kTile * 3, xi, yi, zi, r2, selfjj, rm, rkey, mask);
                     else pair_row<false>(mine + r * kTile * 3, xi, yi, zi, r2, selfjj, rm, rkey, mask);
                     if (rm < tb) { tb = rm; tk = k; tj = j0 + rkey; }
                     if (rm < r2) tfirst = min(tfirst, k);
-                }
+                });
                 lds_wave_fence();
             }
             // the four wavefronts meet: 1 .. 3 leave their results in their quarters, wavefront 0 merges
@@ -283,8 +198,7 @@ int uavac_launch_separation(uavac_ctx *ctx, const double *coeffs, const int32_t 
     double *part_d2 = static_cast<double *>(uavac_arena_take(ctx, P * Bs * 8));
     int32_t *part_i = static_cast<int32_t *>(uavac_arena_take(ctx, P * 5 * Bs * 4));
     if (!n_rows || !start || !part_d2 || !part_i) return uavac_fail(ctx, UAVAC_ENOMEM, "separation audit: scratch arena too small");
-    const int per_wg = kWaves * (64 / kPreLanes);
-    hipLaunchKernelGGL(separation_prepass_kernel, dim3((B + per_wg - 1) / per_wg), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows,
+    hipLaunchKernelGGL(separation_prepass_kernel, dim3((B + kPreMissions - 1) / kPreMissions), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows,
                        seg_offsets, B, m, start_rows, n_rows, start, ctx->d_flags);
     hipLaunchKernelGGL(minsnap_separation_kernel, dim3(windows, P), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows, seg_offsets, B, m, dt,
                        group_offsets, group_offsets ? G : 1, n_rows, start, radius * radius, part_d2, part_i);

@@ -841,15 +841,22 @@ int uavac_minsnap_audit_dev(uavac_ctx *ctx, const double *coeffs, const int32_t 
     return uavac_launch_audit(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, cuboids, n_cuboids, audit, hit_rows, first_hit);
 }
 
+// what the fleet's pair calls (separation, stagger, layer) refuse alike, in this order; `outputs`: every output pointer of the call is there
+static int check_pair_args(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, int B, int m, double dt, const int64_t *group_offsets,
+                           int G, double radius, bool outputs) {
+    if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
+    if (!seg_rows || !outputs) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
+    if (!std::isfinite(radius) || radius < 0.0) return uavac_fail(ctx, UAVAC_EINVAL, "radius must be finite and >= 0");
+    if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
+    return UAVAC_OK;
+}
+
 int uavac_minsnap_separation_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                                  double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double *sep,
                                  int32_t *isep) {
     UAVAC_ENTER(ctx);
-    if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
-    if (!seg_rows || !sep || !isep) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
-    if (!std::isfinite(radius) || radius < 0.0) return uavac_fail(ctx, UAVAC_EINVAL, "radius must be finite and >= 0");
-    if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
+    if (int rc = check_pair_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, sep && isep)) return rc;
     return uavac_launch_separation(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, sep, isep);
 }
 
@@ -857,11 +864,7 @@ int uavac_minsnap_stagger_dev(uavac_ctx *ctx, const double *coeffs, const int32_
                               double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, int step,
                               int max_steps, int32_t *istag) {
     UAVAC_ENTER(ctx);
-    if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
-    if (!seg_rows || !istag) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
-    if (!std::isfinite(radius) || radius < 0.0) return uavac_fail(ctx, UAVAC_EINVAL, "radius must be finite and >= 0");
-    if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
+    if (int rc = check_pair_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, istag != nullptr)) return rc;
     if (step < 1) return uavac_fail(ctx, UAVAC_EINVAL, "step must be >= 1");
     if (max_steps < 0 || max_steps > UAVAC_STAGGER_MAX_STEPS) return uavac_fail(ctx, UAVAC_EINVAL, "max_steps must be in [0, UAVAC_STAGGER_MAX_STEPS]");
     if ((long long)step * max_steps > (1LL << 29)) return uavac_fail(ctx, UAVAC_EINVAL, "step * max_steps must not exceed 2^29 rows");
@@ -899,11 +902,7 @@ int uavac_minsnap_delay_dev(uavac_ctx *ctx, const double *coeffs, const double *
 static int check_layer_args(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, int B, int m, double dt, const int64_t *group_offsets,
                             int G, double radius, double delta_x, double delta_y, double delta_z, int max_steps, const int32_t *ilayer,
                             const double *offsets) {
-    if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
-    if (!seg_rows || !ilayer || !offsets) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
-    if (!std::isfinite(radius) || radius < 0.0) return uavac_fail(ctx, UAVAC_EINVAL, "radius must be finite and >= 0");
-    if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
+    if (int rc = check_pair_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, ilayer && offsets)) return rc;
     if (!std::isfinite(delta_x) || !std::isfinite(delta_y) || !std::isfinite(delta_z)) return uavac_fail(ctx, UAVAC_EINVAL, "delta must be finite");
     if (max_steps < 0 || max_steps > UAVAC_LAYER_MAX_STEPS) return uavac_fail(ctx, UAVAC_EINVAL, "max_steps must be in [0, UAVAC_LAYER_MAX_STEPS]");
     if (!group_offsets && B > UAVAC_LAYER_MAX_GROUP)

@@ -99,109 +99,6 @@ def check_planning_registers():
     return s + k + a + kb
 
 
-TIMEOPT_KERNELS = ("row_counts_t_kernel", "plan_t_commit_kernel", "minsnap_cost_kernel", "timeopt_expand_kernel", "timeopt_init_kernel",
-                   "timeopt_probe_kernel", "timeopt_direction_kernel", "timeopt_candidate_kernel", "timeopt_select_kernel")
-
-
-def check_timeopt_kernels():
-    """The kernels of csrc/minsnap_timeopt.hip (plans from given durations, the snap cost, the bookkeeping of the duration
-    optimisation): every one must be there, none may spill or use scratch memory at all (zero private-segment bytes: their loops over
-    a mission's segments keep no per-segment arrays), and all run at least four waves per SIMD (<= 128 vector registers; built: the
-    cost kernel 64, the others 10 .. 40).  Returns {kernel: VGPRs} (the two row-count variants under their mangled names), None when
-    the counts cannot be read."""
-    obj = os.path.join(PKG, "build", "minsnap_timeopt.o")
-    regs, priv = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel")
-    if regs is None or priv is None:
-        return None
-    bad = [(n[:70], v, sp, 128) for n, v, sp in regs if v > 128 or sp] + [(n[:70], f"{p} private-segment bytes", 0, 0) for n, p in priv if p]
-    missing = [k for k in TIMEOPT_KERNELS if not any(k in n for n, _, _ in regs)]
-    if bad or missing or len(regs) != len(TIMEOPT_KERNELS) + 1 or len(priv) != len(regs):
-        raise RuntimeError(f"time-optimisation kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
-                           f"{len(regs)} kernels found (compiler: {compiler_version()})")
-    return {n: v for n, v, _ in regs}
-
-
-SEPARATION_KERNELS = ("separation_prepass_kernel", "minsnap_separation_kernel", "separation_merge_kernel")
-
-
-def check_separation_kernels():
-    """The kernels of csrc/minsnap_separation.hip (the fleet's separation audit): all three must be there, none may spill or use
-    scratch memory at all (zero private-segment bytes: the two coefficient sets of the pair kernel are indexed by constants only), and
-    the pair kernel, whose 48 KB LDS tile admits three workgroups per CU, must run three waves per SIMD (<= 168 vector registers;
-    built: 168, the pre-pass 14, the merge 24).  Returns {kernel: VGPRs}, None when the counts cannot be read."""
-    obj = os.path.join(PKG, "build", "minsnap_separation.o")
-    regs, priv = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel")
-    if regs is None or priv is None:
-        return None
-    bad = [(n[:70], v, sp, 168) for n, v, sp in regs if v > 168 or sp] + [(n[:70], f"{p} private-segment bytes", 0, 0) for n, p in priv if p]
-    missing = [k for k in SEPARATION_KERNELS if not any(k in n for n, _, _ in regs)]
-    if bad or missing or len(regs) != len(SEPARATION_KERNELS) or len(priv) != len(regs):
-        raise RuntimeError(f"separation kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
-                           f"{len(regs)} kernels found (compiler: {compiler_version()})")
-    return {n: v for n, v, _ in regs}
-
-
-STAGGER_KERNELS = ("stagger_prepass_kernel", "minsnap_stagger_kernel")
-
-
-def check_stagger_kernels():
-    """The kernels of csrc/minsnap_stagger.hip (start delays that clear the separation audit): both must be there, none may spill or
-    use scratch memory at all (zero private-segment bytes: the two coefficient sets of the decision kernel are indexed by constants
-    only), and the decision kernel, whose 48 KB LDS tile plus 1 KB of granted starts admits three workgroups per CU, must run three
-    waves per SIMD (<= 168 vector registers; built: 129, the pre-pass 14).  Returns {kernel: VGPRs}, None when the counts cannot be
-    read."""
-    obj = os.path.join(PKG, "build", "minsnap_stagger.o")
-    regs, priv = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel")
-    if regs is None or priv is None:
-        return None
-    bad = [(n[:70], v, sp, 168) for n, v, sp in regs if v > 168 or sp] + [(n[:70], f"{p} private-segment bytes", 0, 0) for n, p in priv if p]
-    missing = [k for k in STAGGER_KERNELS if not any(k in n for n, _, _ in regs)]
-    if bad or missing or len(regs) != len(STAGGER_KERNELS) or len(priv) != len(regs):
-        raise RuntimeError(f"stagger kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
-                           f"{len(regs)} kernels found (compiler: {compiler_version()})")
-    return {n: v for n, v, _ in regs}
-
-
-FLOWN_SEPARATION_KERNELS = ("flown_separation_kernel", "flown_merge_kernel")
-
-
-def check_flown_separation_kernels():
-    """The kernels of csrc/flown_separation.hip (the separation the fleet flew, from a state log): both must be there, none may spill or
-    use scratch memory at all (zero private-segment bytes), and the pair kernel, whose 48 KB LDS tile admits three workgroups per CU
-    like the plan audit's, must run three waves per SIMD (<= 168 vector registers; built: 143, the merge 18).  Returns {kernel: VGPRs},
-    None when the counts cannot be read."""
-    obj = os.path.join(PKG, "build", "flown_separation.o")
-    regs, priv = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel")
-    if regs is None or priv is None:
-        return None
-    bad = [(n[:70], v, sp, 168) for n, v, sp in regs if v > 168 or sp] + [(n[:70], f"{p} private-segment bytes", 0, 0) for n, p in priv if p]
-    missing = [k for k in FLOWN_SEPARATION_KERNELS if not any(k in n for n, _, _ in regs)]
-    if bad or missing or len(regs) != len(FLOWN_SEPARATION_KERNELS) or len(priv) != len(regs):
-        raise RuntimeError(f"flown-separation kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
-                           f"{len(regs)} kernels found (compiler: {compiler_version()})")
-    return {n: v for n, v, _ in regs}
-
-
-DELAY_KERNELS = ("delay_counts_kernel", "minsnap_delay_kernel")
-
-
-def check_delay_kernels():
-    """The kernels of csrc/minsnap_delay.hip (start delays as a leading hold segment of the plan): both must be there, none may spill or
-    use scratch memory at all, and both are plain copies that run at least eight waves per SIMD (<= 64 vector registers; built: 24
-    each).  Returns {kernel: VGPRs}, None when the counts cannot be read."""
-    obj = os.path.join(PKG, "build", "minsnap_delay.o")
-    regs, priv = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel")
-    if regs is None or priv is None:
-        return None
-    bad = [(n[:70], v, sp, 64) for n, v, sp in regs if v > 64 or sp] + [(n[:70], f"{p} private-segment bytes", 0, 0) for n, p in priv if p]
-    missing = [k for k in DELAY_KERNELS if not any(k in n for n, _, _ in regs)]
-    if bad or missing or len(regs) != len(DELAY_KERNELS) or len(priv) != len(regs):
-        raise RuntimeError(f"delay kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
-                           f"{len(regs)} kernels found (compiler: {compiler_version()})")
-    return {n: v for n, v, _ in regs}
-
-
-LAYER_KERNELS = ("layer_prepass_kernel", "minsnap_layer_kernel", "minsnap_shift_kernel")
 LDS_BYTES_PER_CU = 160 * 1024
 VGPRS_AT_WAVES_PER_SIMD = {8: 64, 7: 72, 6: 80, 5: 96, 4: 128, 3: 168, 2: 256, 1: 512}     # the largest allocation that still runs that many
 
@@ -218,40 +115,103 @@ def kernel_lds_bytes(obj: str, kernel: str):
     return [(n, int(v)) for v, n in found]
 
 
-def _check_layer_object(obj_name: str, kernels, what: str):
-    """The budget of the kernels of one object file of the layer search: see `check_layer_kernels`."""
+def _check_object(obj_name: str, kernels, what: str, vgpr_limit=None, extra_kernels: int = 0):
+    """The budget of the kernels of one object file under build/: every kernel of `kernels` must be there and the object must hold
+    exactly len(kernels) + `extra_kernels` of them (further instantiations of a listed kernel), none may spill or use scratch memory at
+    all (zero private-segment bytes), and none may need more than `vgpr_limit` vector registers.  `vgpr_limit` None: the limit of each
+    kernel follows from the LDS it ends up with -- workgroups of four waves, so min(8, 160 KiB // LDS) workgroups per CU are as many
+    waves per SIMD, and the kernel must fit the allocation that still runs that many --, and a decision kernel of the layer search must
+    keep three workgroups per CU.  Returns {kernel: VGPRs}, None when the counts cannot be read."""
     obj = os.path.join(PKG, "build", obj_name)
-    regs, priv, lds = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel"), kernel_lds_bytes(obj, "_kernel")
+    regs, priv = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel")
+    lds = kernel_lds_bytes(obj, "_kernel") if vgpr_limit is None else []
     if regs is None or priv is None or lds is None:
         return None
     lds = dict(lds)
     bad = [(n[:70], f"{p} private-segment bytes", 0, 0) for n, p in priv if p]
     for n, v, sp in regs:
-        if n not in lds:
-            bad.append((n[:70], "no LDS size found", 0, 0))
-            continue
-        waves = min(8, LDS_BYTES_PER_CU // lds[n]) if lds[n] else 8
-        limit = VGPRS_AT_WAVES_PER_SIMD.get(waves, 0)          # (a workgroup that does not fit a CU at all: limit 0)
-        if "minsnap_layer_kernel" in n and waves < 3:
-            bad.append((n[:70], f"{lds[n]} bytes of LDS: fewer than three workgroups per CU", 0, 0))
+        limit = vgpr_limit
+        if limit is None:
+            if n not in lds:
+                bad.append((n[:70], "no LDS size found", 0, 0))
+                continue
+            waves = min(8, LDS_BYTES_PER_CU // lds[n]) if lds[n] else 8
+            limit = VGPRS_AT_WAVES_PER_SIMD.get(waves, 0)      # (a workgroup that does not fit a CU at all: limit 0)
+            if "minsnap_layer_kernel" in n and waves < 3:
+                bad.append((n[:70], f"{lds[n]} bytes of LDS: fewer than three workgroups per CU", 0, 0))
         if v > limit or sp:
             bad.append((n[:70], v, sp, limit))
     missing = [k for k in kernels if not any(k in n for n, _, _ in regs)]
-    if bad or missing or len(regs) != len(kernels) or len(priv) != len(regs):
+    if bad or missing or len(regs) != len(kernels) + extra_kernels or len(priv) != len(regs):
         raise RuntimeError(f"{what} kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
                            f"{len(regs)} kernels found (compiler: {compiler_version()})")
     return {n: v for n, v, _ in regs}
 
 
-def check_layer_kernels():
-    """The kernels of csrc/minsnap_layer.hip (offset layers that clear the separation audit, and the offset transform): all three must
-    be there, none may spill or use scratch memory at all (zero private-segment bytes: the coefficient sets of the decision kernel are
-    indexed by constants only).  The register limit of each follows from the LDS it ends up with: workgroups of four waves, so
-    min(8, 160 KiB // LDS) workgroups per CU are as many waves per SIMD, and the kernel must fit the allocation that still runs that
-    many (built: the decision kernel 50192 B of LDS -- the 48 KB tile, 1 KB of granted layers, two words -- hence three and <= 168,
-    at 139; the pre-pass and the transform no LDS, hence eight and <= 64, at 14 and 21).  Returns {kernel: VGPRs}, None when the
+TIMEOPT_KERNELS = ("row_counts_t_kernel", "plan_t_commit_kernel", "minsnap_cost_kernel", "timeopt_expand_kernel", "timeopt_init_kernel",
+                   "timeopt_probe_kernel", "timeopt_direction_kernel", "timeopt_candidate_kernel", "timeopt_select_kernel")
+
+
+def check_timeopt_kernels():
+    """The kernels of csrc/minsnap_timeopt.hip (plans from given durations, the snap cost, the bookkeeping of the duration
+    optimisation): `_check_object` -- their loops over a mission's segments keep no per-segment arrays -- with all of them at least
+    four waves per SIMD (<= 128 vector registers; built: the cost kernel 64, the others 10 .. 40).  Returns {kernel: VGPRs} (the two
+    row-count variants under their mangled names), None when the counts cannot be read."""
+    return _check_object("minsnap_timeopt.o", TIMEOPT_KERNELS, "time-optimisation", vgpr_limit=128, extra_kernels=1)
+
+
+SEPARATION_KERNELS = ("separation_prepass_kernel", "minsnap_separation_kernel", "separation_merge_kernel")
+
+
+def check_separation_kernels():
+    """The kernels of csrc/minsnap_separation.hip (the fleet's separation audit): `_check_object` -- the two coefficient sets of the pair
+    kernel are indexed by constants only --, and the pair kernel, whose 48 KB LDS tile admits three workgroups per CU, must run three
+    waves per SIMD (<= 168 vector registers; built: 164, the pre-pass 14, the merge 20).  Returns {kernel: VGPRs}, None when the
     counts cannot be read."""
-    return _check_layer_object("minsnap_layer.o", LAYER_KERNELS, "layer")
+    return _check_object("minsnap_separation.o", SEPARATION_KERNELS, "separation", vgpr_limit=168)
+
+
+STAGGER_KERNELS = ("stagger_prepass_kernel", "minsnap_stagger_kernel")
+
+
+def check_stagger_kernels():
+    """The kernels of csrc/minsnap_stagger.hip (start delays that clear the separation audit): `_check_object` -- the two coefficient
+    sets of the decision kernel are indexed by constants only --, and the decision kernel, whose 48 KB LDS tile plus 1 KB of granted
+    starts admits three workgroups per CU, must run three waves per SIMD (<= 168 vector registers; built: 145, the pre-pass 14).
+    Returns {kernel: VGPRs}, None when the counts cannot be read."""
+    return _check_object("minsnap_stagger.o", STAGGER_KERNELS, "stagger", vgpr_limit=168)
+
+
+FLOWN_SEPARATION_KERNELS = ("flown_separation_kernel", "flown_merge_kernel")
+
+
+def check_flown_separation_kernels():
+    """The kernels of csrc/flown_separation.hip (the separation the fleet flew, from a state log): `_check_object`, and the pair kernel,
+    whose 48 KB LDS tile admits three workgroups per CU like the plan audit's, must run three waves per SIMD (<= 168 vector registers;
+    built: 143, the merge 18).  Returns {kernel: VGPRs}, None when the counts cannot be read."""
+    return _check_object("flown_separation.o", FLOWN_SEPARATION_KERNELS, "flown-separation", vgpr_limit=168)
+
+
+DELAY_KERNELS = ("delay_counts_kernel", "minsnap_delay_kernel")
+
+
+def check_delay_kernels():
+    """The kernels of csrc/minsnap_delay.hip (start delays as a leading hold segment of the plan): `_check_object`; both are plain
+    copies that run at least eight waves per SIMD (<= 64 vector registers; built: 24 each).  Returns {kernel: VGPRs}, None when the
+    counts cannot be read."""
+    return _check_object("minsnap_delay.o", DELAY_KERNELS, "delay", vgpr_limit=64)
+
+
+LAYER_KERNELS = ("layer_prepass_kernel", "minsnap_layer_kernel", "minsnap_shift_kernel")
+
+
+def check_layer_kernels():
+    """The kernels of csrc/minsnap_layer.hip (offset layers that clear the separation audit, and the offset transform): `_check_object`
+    -- the coefficient sets of the decision kernel are indexed by constants only -- with the register limit of each from the LDS it
+    ends up with (built: the decision kernel 50192 B of LDS -- the 48 KB tile, 1 KB of granted layers, two words -- hence three
+    workgroups per CU and <= 168, at 137; the pre-pass and the transform no LDS, hence eight and <= 64, at 14 and 21).  Returns
+    {kernel: VGPRs}, None when the counts cannot be read."""
+    return _check_object("minsnap_layer.o", LAYER_KERNELS, "layer")
 
 
 LAYER_OBS_KERNELS = ("layer_prepass_kernel", "minsnap_layer_kernel")
@@ -262,7 +222,7 @@ def check_layer_obs_kernels():
     `check_layer_kernels` on the two instantiations with cuboids (built: the decision kernel 50976 B of LDS -- the search's 50192 B,
     768 B of cuboids, two more words -- hence still three workgroups per CU and <= 168, at 142; the pre-pass no LDS, <= 64, at 14).
     Returns {kernel: VGPRs}, None when the counts cannot be read."""
-    return _check_layer_object("minsnap_layer_obs.o", LAYER_OBS_KERNELS, "obstacle-aware layer")
+    return _check_object("minsnap_layer_obs.o", LAYER_OBS_KERNELS, "obstacle-aware layer")
 
 
 def check_rollout_registers(obj: str = None):

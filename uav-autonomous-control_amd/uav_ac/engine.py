@@ -608,15 +608,61 @@ class Engine:
             self.sample(plan)
         return plan
 
+    def _coeff_plan(self, plan):
+        """What the calls that read coefficients and row counts take, as the Plan or RaggedBatch that holds them: a RaggedPlan goes
+        through the batch it was sampled from; one without a batch -- `plan_collision_free(device_loop=False)` -- is re-planned
+        rows-free from its final waypoints, which gives the same coefficients bit for bit."""
+        if isinstance(plan, RaggedPlan):
+            batch = plan.batch
+            if batch is None:
+                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
+            plan = batch
+        return plan
+
+    @staticmethod
+    def _plan_args(plan):
+        """The leading arguments of those calls: coeffs, seg_rows, seg_offsets (NULL for a uniform Plan), B, m (the largest), dt."""
+        ragged = hasattr(plan, "seg_offsets")
+        return (_ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None, int(plan.B),
+                plan.max_m if ragged else plan.m, float(plan.dt))
+
+    def _groups(self, groups, B: int, max_group: int = None):
+        """`groups` as the fleet calls take it (None, a group size, or the offsets as array or tensor) -> (the offsets (G + 1,) i64 on the
+        device or None, G).  `max_group`: a larger group is refused where its size is known without a sync -- offsets that are a device
+        tensor go through."""
+        torch = self._torch
+        if groups is None:
+            if max_group is not None and B > max_group:
+                raise ValueError(f"one group of {B} missions; at most {max_group} per group")
+            return None, 0
+        if isinstance(groups, (int, np.integer)):
+            if groups < 1:
+                raise ValueError("a group size must be >= 1")
+            groups = list(range(0, B, int(groups))) + [B]
+        if max_group is not None and not (hasattr(groups, "is_cuda") and groups.is_cuda):
+            sizes = np.diff(np.asarray(groups.numpy() if hasattr(groups, "numpy") else groups, dtype=np.int64).reshape(-1))
+            if sizes.size and sizes.max() > max_group:
+                raise ValueError(f"a group of {int(sizes.max())} missions; at most {max_group} per group")
+        go = self._dev(groups, torch.int64).reshape(-1)
+        G = int(go.numel()) - 1
+        if G < 1:
+            raise ValueError("group offsets hold at least two entries")
+        return go, G
+
+    def _start_rows(self, start_rows, B: int):
+        """One start row per mission -> (B,) i32 on the device."""
+        start = self._dev(start_rows, self._torch.int32).reshape(-1)
+        if start.numel() != B:
+            raise ValueError(f"one start row per mission: expected {B}, got {start.numel()}")
+        return start
+
     def first_yaw(self, plan):
         """The missions' first headings from coefficients and row counts alone (`uavac_minsnap_first_yaw_dev`; a Plan or a
         RaggedBatch) -> (B,) f64: bit for bit what the sampler writes into `plan.first_yaw`."""
         torch = self._torch
         out = torch.empty((plan.B,), dtype=torch.float64, device=self.device)
-        ragged = hasattr(plan, "seg_offsets")
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_first_yaw_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
-                      plan.B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(out))
+        self.ctx.call("uavac_minsnap_first_yaw_dev", *self._plan_args(plan), _ptr(out))
         return out
 
     def audit(self, plan, obstacles=None) -> PlanAudit:
@@ -628,12 +674,7 @@ class Engine:
         waypoints, which gives the same coefficients bit for bit).  Reads coefficients and row counts only, never `plan.traj`;
         stream-ordered like the other _dev calls, no sync.  `uav_ac.scoring.plan_feasibility` turns the result into verdicts."""
         torch = self._torch
-        if isinstance(plan, RaggedPlan):
-            batch = plan.batch
-            if batch is None:
-                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
-            plan = batch
-        ragged = hasattr(plan, "seg_offsets")
+        plan = self._coeff_plan(plan)
         B = int(plan.B)
         kw = dict(device=self.device)
         cub = None
@@ -647,8 +688,7 @@ class Engine:
         hit_rows = torch.empty((n, B), dtype=torch.int32, **kw)
         first_hit = torch.empty((n, B), dtype=torch.int32, **kw)
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_audit_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
-                      B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(cub) if n else None, n, _ptr(block),
+        self.ctx.call("uavac_minsnap_audit_dev", *self._plan_args(plan), _ptr(cub) if n else None, n, _ptr(block),
                       _ptr(hit_rows) if n else None, _ptr(first_hit) if n else None)
         return PlanAudit(*block.unbind(0), hit_rows, first_hit, block)
 
@@ -662,33 +702,14 @@ class Engine:
         (B,) i32: the clock row at which each mission starts (None: all 0); before it a mission waits on its first row, after its end
         it holds its last.  Never reads `plan.traj`; stream-ordered like the other _dev calls, no sync."""
         torch = self._torch
-        if isinstance(plan, RaggedPlan):
-            batch = plan.batch
-            if batch is None:
-                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
-            plan = batch
-        ragged = hasattr(plan, "seg_offsets")
+        plan = self._coeff_plan(plan)
         B = int(plan.B)
-        go, G = None, 0
-        if groups is not None:
-            if isinstance(groups, (int, np.integer)):
-                if groups < 1:
-                    raise ValueError("a group size must be >= 1")
-                groups = list(range(0, B, int(groups))) + [B]
-            go = self._dev(groups, torch.int64).reshape(-1)
-            G = int(go.numel()) - 1
-            if G < 1:
-                raise ValueError("group offsets hold at least two entries")
-        start = None
-        if start_rows is not None:
-            start = self._dev(start_rows, torch.int32).reshape(-1)
-            if start.numel() != B:
-                raise ValueError(f"one start row per mission: expected {B}, got {start.numel()}")
+        go, G = self._groups(groups, B)
+        start = None if start_rows is None else self._start_rows(start_rows, B)
         sep = torch.empty((B,), dtype=torch.float64, device=self.device)
         block = torch.empty((nat.SEP_ROWS, B), dtype=torch.int32, device=self.device)
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_separation_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
-                      B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(go), G, _ptr(start), float(radius), _ptr(sep), _ptr(block))
+        self.ctx.call("uavac_minsnap_separation_dev", *self._plan_args(plan), _ptr(go), G, _ptr(start), float(radius), _ptr(sep), _ptr(block))
         return SeparationAudit(sep, *block.unbind(0), block)
 
     def stagger(self, plan, radius: float, groups=None, start_rows=None, step: int = 1, max_steps: int = 255) -> StaggerResult:
@@ -705,12 +726,7 @@ class Engine:
         no pair of resolved missions is inside the radius.  To fly the granted starts make them part of the plan:
         `Engine.delay(plan, result.start_rows)` (the rollout's cursor has no start row and needs none)."""
         torch = self._torch
-        if isinstance(plan, RaggedPlan):
-            batch = plan.batch
-            if batch is None:
-                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
-            plan = batch
-        ragged = hasattr(plan, "seg_offsets")
+        plan = self._coeff_plan(plan)
         B = int(plan.B)
         step, max_steps = int(step), int(max_steps)
         if step < 1:
@@ -719,32 +735,11 @@ class Engine:
             raise ValueError(f"max_steps must be in 0 .. {nat.STAGGER_MAX_STEPS}")
         if step * max_steps > 2 ** 29:
             raise ValueError("step * max_steps must not exceed 2^29 rows")
-        go, G = None, 0
-        if groups is None:
-            if B > nat.STAGGER_MAX_GROUP:
-                raise ValueError(f"one group of {B} missions; at most {nat.STAGGER_MAX_GROUP} per group")
-        else:
-            if isinstance(groups, (int, np.integer)):
-                if groups < 1:
-                    raise ValueError("a group size must be >= 1")
-                groups = list(range(0, B, int(groups))) + [B]
-            if not (hasattr(groups, "is_cuda") and groups.is_cuda):
-                sizes = np.diff(np.asarray(groups.numpy() if hasattr(groups, "numpy") else groups, dtype=np.int64).reshape(-1))
-                if sizes.size and sizes.max() > nat.STAGGER_MAX_GROUP:
-                    raise ValueError(f"a group of {int(sizes.max())} missions; at most {nat.STAGGER_MAX_GROUP} per group")
-            go = self._dev(groups, torch.int64).reshape(-1)
-            G = int(go.numel()) - 1
-            if G < 1:
-                raise ValueError("group offsets hold at least two entries")
-        start = None
-        if start_rows is not None:
-            start = self._dev(start_rows, torch.int32).reshape(-1)
-            if start.numel() != B:
-                raise ValueError(f"one start row per mission: expected {B}, got {start.numel()}")
+        go, G = self._groups(groups, B, nat.STAGGER_MAX_GROUP)
+        start = None if start_rows is None else self._start_rows(start_rows, B)
         block = torch.empty((nat.STAGGER_ROWS, B), dtype=torch.int32, device=self.device)
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_stagger_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
-                      B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(go), G, _ptr(start), float(radius), step, max_steps,
+        self.ctx.call("uavac_minsnap_stagger_dev", *self._plan_args(plan), _ptr(go), G, _ptr(start), float(radius), step, max_steps,
                       _ptr(block))
         return StaggerResult(*block.unbind(0), block)
 
@@ -765,18 +760,12 @@ class Engine:
         hold rows like any others.  ONE host sync: the read of the (B + 1,) segment offsets (with the row total), which a RaggedBatch
         carries on the host.  A plan whose missions already have UAVAC_MAX_SEGMENTS segments is a ValueError."""
         torch = self._torch
-        if isinstance(plan, RaggedPlan):
-            batch = plan.batch
-            if batch is None:
-                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
-            plan = batch
+        plan = self._coeff_plan(plan)
         ragged = hasattr(plan, "seg_offsets")
         B, m = int(plan.B), int(plan.max_m if ragged else plan.m)
         if m >= nat.MAX_SEGMENTS:
             raise ValueError(f"a mission of {m} segments cannot take a hold segment: at most {nat.MAX_SEGMENTS} per mission")
-        start = self._dev(start_rows, torch.int32).reshape(-1)
-        if start.numel() != B:
-            raise ValueError(f"one start row per mission: expected {B}, got {start.numel()}")
+        start = self._start_rows(start_rows, B)
         kw = dict(device=self.device)
         S_in = int(plan.seg_offsets_host[-1]) if ragged else B * m
         so_in = _ptr(plan.seg_offsets) if ragged else None
@@ -824,12 +813,7 @@ class Engine:
         resolved mission.  steps = -1 with blocked = max_steps + 1 (`uav_ac.scoring.blocked_out`): every layer hits a cuboid, the
         mission needs a new plan around the obstacle (`plan_collision_free`), not an offset."""
         torch = self._torch
-        if isinstance(plan, RaggedPlan):
-            batch = plan.batch
-            if batch is None:
-                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
-            plan = batch
-        ragged = hasattr(plan, "seg_offsets")
+        plan = self._coeff_plan(plan)
         B = int(plan.B)
         max_steps = int(max_steps)
         if not (0 <= max_steps <= nat.LAYER_MAX_STEPS):
@@ -837,28 +821,8 @@ class Engine:
         d = np.asarray(delta.detach().cpu().numpy() if hasattr(delta, "detach") else delta, dtype=np.float64).reshape(-1)
         if d.size != 3 or not np.isfinite(d).all():
             raise ValueError("delta must be three finite numbers")
-        go, G = None, 0
-        if groups is None:
-            if B > nat.LAYER_MAX_GROUP:
-                raise ValueError(f"one group of {B} missions; at most {nat.LAYER_MAX_GROUP} per group")
-        else:
-            if isinstance(groups, (int, np.integer)):
-                if groups < 1:
-                    raise ValueError("a group size must be >= 1")
-                groups = list(range(0, B, int(groups))) + [B]
-            if not (hasattr(groups, "is_cuda") and groups.is_cuda):
-                sizes = np.diff(np.asarray(groups.numpy() if hasattr(groups, "numpy") else groups, dtype=np.int64).reshape(-1))
-                if sizes.size and sizes.max() > nat.LAYER_MAX_GROUP:
-                    raise ValueError(f"a group of {int(sizes.max())} missions; at most {nat.LAYER_MAX_GROUP} per group")
-            go = self._dev(groups, torch.int64).reshape(-1)
-            G = int(go.numel()) - 1
-            if G < 1:
-                raise ValueError("group offsets hold at least two entries")
-        start = None
-        if start_rows is not None:
-            start = self._dev(start_rows, torch.int32).reshape(-1)
-            if start.numel() != B:
-                raise ValueError(f"one start row per mission: expected {B}, got {start.numel()}")
+        go, G = self._groups(groups, B, nat.LAYER_MAX_GROUP)
+        start = None if start_rows is None else self._start_rows(start_rows, B)
         offsets = torch.empty((B, 3), dtype=torch.float64, device=self.device)
         if obstacles is not None:
             cub = self._dev(obstacles, torch.float64)
@@ -870,14 +834,12 @@ class Engine:
                 raise ValueError(f"{n} cuboids; at most {nat.AUDIT_MAX_CUBOIDS} per search")
             block = torch.empty((nat.LAYER_OBS_ROWS, B), dtype=torch.int32, device=self.device)
             self._bind_stream()
-            self.ctx.call("uavac_minsnap_layer_obs_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
-                          B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(go), G, _ptr(start), float(radius), float(d[0]),
+            self.ctx.call("uavac_minsnap_layer_obs_dev", *self._plan_args(plan), _ptr(go), G, _ptr(start), float(radius), float(d[0]),
                           float(d[1]), float(d[2]), max_steps, _ptr(cub) if n else None, n, _ptr(block), _ptr(offsets))
             return LayerResult(*block[:nat.LAYER_ROWS].unbind(0), block, offsets)
         block = torch.empty((nat.LAYER_ROWS, B), dtype=torch.int32, device=self.device)
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_layer_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None,
-                      B, plan.max_m if ragged else plan.m, float(plan.dt), _ptr(go), G, _ptr(start), float(radius), float(d[0]), float(d[1]),
+        self.ctx.call("uavac_minsnap_layer_dev", *self._plan_args(plan), _ptr(go), G, _ptr(start), float(radius), float(d[0]), float(d[1]),
                       float(d[2]), max_steps, _ptr(block), _ptr(offsets))
         return LayerResult(*block.unbind(0), block, offsets)
 
@@ -895,11 +857,7 @@ class Engine:
         are on the host already.  The OBSTACLE AUDIT has to be re-run on the result (`Engine.audit(shifted, obstacles)`): an offset
         can move a mission into a cuboid that the original plan avoided."""
         torch = self._torch
-        if isinstance(plan, RaggedPlan):
-            batch = plan.batch
-            if batch is None:
-                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
-            plan = batch
+        plan = self._coeff_plan(plan)
         ragged = hasattr(plan, "seg_offsets")
         B, m = int(plan.B), int(plan.max_m if ragged else plan.m)
         off = self._dev(offsets, torch.float64).reshape(-1)
@@ -970,16 +928,7 @@ class Engine:
         pitch = int(state_log.stride(1))
         if state_log.stride(2) != 1 or pitch < B or (K > 1 and state_log.stride(0) != nat.STATE_LOG_ROWS * pitch):
             raise ValueError("state_log must be laid out [K][13][pitch]: stride(2) == 1, stride(1) = pitch >= B, stride(0) == 13 * pitch")
-        go, G = None, 0
-        if groups is not None:
-            if isinstance(groups, (int, np.integer)):
-                if groups < 1:
-                    raise ValueError("a group size must be >= 1")
-                groups = list(range(0, B, int(groups))) + [B]
-            go = self._dev(groups, torch.int64).reshape(-1)
-            G = int(go.numel()) - 1
-            if G < 1:
-                raise ValueError("group offsets hold at least two entries")
+        go, G = self._groups(groups, B)
         sep = torch.empty((B,), dtype=torch.float64, device=self.device)
         block = torch.empty((nat.SEP_ROWS, B), dtype=torch.int32, device=self.device)
         self._bind_stream()
