@@ -1,14 +1,14 @@
 // What the fleet's pair kernels share ahead of the reduction (gfx950): the separation audit (minsnap_separation.hip), the start delays
 // (minsnap_stagger.hip) and the offset layers (fleet_search.h) all put missions on one group clock and evaluate "the audit's" rows with
 // "the audit's" rounding.  That is stated once, here:
-//   Mission / mission_of   a mission's first segment and segment count, uniform or ragged
-//   seek                   the segment of a clock row, walked forward
 //   group_range            a group's missions from its offsets, clamped to the batch (flown_separation.hip uses it too)
 //   prepass_mission        the pre-pass of a mission: its row total, its clamped start, whether it is EXCLUDED, flag 0
 //   clock_walk             a wavefront's 8 rows of a chunk for one mission: seek, 24 coefficients, position-only Horner
 //   inside_row             one position against a j-tile's positions at the same clock row: is anybody inside the radius?
 //   inside_cuboids         one position against the cuboids
-// The tile's shape is sepred's (separation_reduce.h), which also holds what happens to the positions in the audits.
+// The tile's shape is sepred's (separation_reduce.h), which also holds what happens to the positions in the audits; a mission's segments,
+// the forward walk over its row counts, the lanes of a group and the clock's bound are mission_walk.h's, which every kernel that walks a
+// mission shares.
 // ROUNDING (part of every contract, include/uavac.h): positions by the sampler's fma chain (minsnap_eval_pos) on the coefficients as
 // the caller's hook leaves them -- untouched without one --, the distance WITHOUT contraction: dx = xi - xj, ..., d^2 = (dx dx + dy dy)
 // + dz dz, each product and sum rounded on its own.
@@ -16,38 +16,19 @@
 
 #include "uavac_internal.h"
 #include "minsnap_eval.h"
+#include "mission_walk.h"
 #include "separation_reduce.h"
 
 namespace fleet {
 
 using namespace sepred;                                     // the tile's shape
+using mission_walk::Mission;
+using mission_walk::mission_of;
+using mission_walk::seek;
+using mission_walk::kMaxClock;
 
-constexpr int kMaxClock = 1 << 29;                          // start rows and row totals above this cannot be clocked with int
 constexpr int kPreLanes = 16;                               // lanes per mission of the pre-pass
 constexpr int kPreMissions = kWaves * (64 / kPreLanes);     // missions per workgroup of the pre-pass
-
-// First segment and segment count of mission b: uniform (so == NULL) or ragged, clamped to 1 .. m like every ragged kernel clamps it.
-struct Mission {
-    long long s0;
-    int m;
-};
-__device__ __forceinline__ Mission mission_of(const int64_t *__restrict__ so, int b, int m_uniform) {
-    Mission M;
-    if (so) {
-        M.s0 = so[b];
-        const long long n = so[b + 1] - M.s0;
-        M.m = (int)(n < 1 ? 1 : (n > m_uniform ? m_uniform : n));
-    } else {
-        M.s0 = (long long)b * m_uniform;
-        M.m = m_uniform;
-    }
-    return M;
-}
-
-// the segment of a mission's row r, walked forward from where the lane stood (rows only grow)
-__device__ __forceinline__ void seek(const int32_t *__restrict__ rows_of, int mb, int r, int &s, int &base, int &cnt) {
-    while (s + 1 < mb && r >= base + cnt) { base += cnt; ++s; cnt = rows_of[s]; }
-}
 
 // The missions [g0, g1) of group g (group_offsets == NULL: all B in one), clamped: malformed offsets must not leave the batch.
 __device__ __forceinline__ void group_range(const int64_t *__restrict__ group_offsets, int g, int B, int &g0, int &g1) {
@@ -63,25 +44,21 @@ __device__ __forceinline__ bool prepass_mission(const double *__restrict__ coeff
                                                 const int64_t *__restrict__ seg_offsets, int B, int m,
                                                 const int32_t *__restrict__ start_rows, int32_t *__restrict__ n_rows,
                                                 int32_t *__restrict__ start, int32_t *__restrict__ flags, int &b, int &s) {
-    constexpr int kPerWave = 64 / kPreLanes;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int g = lane / kPreLanes, l = lane % kPreLanes;
-    b = (blockIdx.x * kWaves + w) * kPerWave + g;
-    const bool live = b < B;
-    const Mission M = mission_of(seg_offsets, live ? b : B - 1, m);
+    const mission_walk::LaneGroup<kPreLanes, kWaves> G(B);
+    b = G.b;
+    const Mission M = mission_of(seg_offsets, G.shadow, m);
     const int32_t *rows_of = seg_rows + M.s0;
     const double *cm = coeffs + (size_t)M.s0 * 24;
     long long total = 0;                                     // the mission's rows: what the sampler's row offsets give it
     for (int q = 0; q < M.m; ++q) total += rows_of[q];
     double z = 0.0;                                          // stays 0 while every coefficient is finite (0 * inf and 0 * NaN are NaN)
-    for (int k = l; k < M.m * 24; k += kPreLanes) z = fma(0.0, cm[k], z);
-#pragma unroll
-    for (int d = kPreLanes / 2; d >= 1; d >>= 1) z += __shfl_xor(z, d);
+    for (int k = G.l; k < M.m * 24; k += kPreLanes) z = fma(0.0, cm[k], z);
+    z = mission_walk::group_reduce<kPreLanes>(z, mission_walk::Add());
     s = 0;
-    if (!(live && l == 0)) return false;
+    if (!(G.live && G.l == 0)) return false;
     s = start_rows ? start_rows[b] : 0;
     const bool bad = s < 0 || s > kMaxClock;                 // cannot be refused by the host: clamped, and flag 0
-    s = s < 0 ? 0 : (s > kMaxClock ? kMaxClock : s);
+    s = mission_walk::clamped_start(s);
     const bool too_long = total > kMaxClock;
     const bool excluded = !(z == 0.0) || total < 1 || too_long;
     n_rows[b] = excluded ? 0 : (int)total;

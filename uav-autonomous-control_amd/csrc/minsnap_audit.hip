@@ -24,12 +24,14 @@
 
 #include "uavac_internal.h"
 #include "minsnap_eval.h"
+#include "mission_walk.h"
 
 #include <cmath>
 #include <limits>
 
 namespace {
 
+using namespace mission_walk;
 constexpr int kWaves = 4;                                   // wavefronts per workgroup
 constexpr int kNoHit = 0x7fffffff;                          // "no sample inside" while the minimum is being formed
 
@@ -70,7 +72,7 @@ __global__ void __launch_bounds__(64 * kWaves) minsnap_audit_kernel(
     const double *__restrict__ coeffs, const int32_t *__restrict__ seg_rows, const int64_t *__restrict__ seg_offsets, int B, int m,
     double dt, const double *__restrict__ cuboids, int n_cuboids, double *__restrict__ audit, int32_t *__restrict__ hit_rows,
     int32_t *__restrict__ first_hit) {
-    constexpr int kPerWave = 64 / kLanes, kThreads = 64 * kWaves;
+    constexpr int kThreads = 64 * kWaves;
     extern __shared__ double lds[];
     const double *box = lds;                                                      // [n_cuboids][6]
     int *count = reinterpret_cast<int *>(lds + 6 * n_cuboids) + threadIdx.x;      // [n_cuboids][kThreads], this lane's column
@@ -80,20 +82,13 @@ __global__ void __launch_bounds__(64 * kWaves) minsnap_audit_kernel(
         for (int q = 0; q < n_cuboids; ++q) { count[q * kThreads] = 0; first[q * kThreads] = kNoHit; }
         __syncthreads();
     }
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int g = lane / kLanes, l = lane % kLanes;
-    const int b = (blockIdx.x * kWaves + w) * kPerWave + g;
-    const bool live = b < B;
-    const int bb = live ? b : B - 1;                         // (dead groups shadow the last mission, walk nothing and write nothing)
-    long long sb = (long long)bb * m;                        // first segment of the mission in the batch
-    int mb = m;
-    if (seg_offsets) {                                       // ragged batch: clamped like the sampler clamps it
-        sb = seg_offsets[bb];
-        const long long n = seg_offsets[bb + 1] - sb;
-        mb = (int)(n < 1 ? 1 : (n > m ? m : n));
-    }
-    const int32_t *rows_of = seg_rows + sb;
-    const double *cm = coeffs + (size_t)sb * 24;
+    const LaneGroup<kLanes, kWaves> G(B);                    // (dead groups shadow the last mission, walk nothing and write nothing)
+    const int b = G.b, l = G.l;
+    const bool live = G.live;
+    const Mission M = mission_of(seg_offsets, G.shadow, m);
+    const int mb = M.m;
+    const int32_t *rows_of = seg_rows + M.s0;
+    const double *cm = coeffs + (size_t)M.s0 * 24;
 
     long long total = 0;                                     // the mission's rows: what the sampler's row offsets give it
     for (int s = 0; s < mb; ++s) total += rows_of[s];
@@ -107,7 +102,7 @@ __global__ void __launch_bounds__(64 * kWaves) minsnap_audit_kernel(
     int s = 0, loaded = -1, cnt = rows_of[0];                // this lane's segment, the one in `c`, its row count
     long long base = 0;                                      // ... and its first row
     for (long long r = l; r < n_rows; r += kLanes) {
-        while (s + 1 < mb && r >= base + cnt) { base += cnt; ++s; cnt = rows_of[s]; }     // first segment whose rows reach past r
+        seek(rows_of, mb, r, s, base, cnt);
         if (s != loaded) {
 #pragma unroll
             for (int k = 0; k < 24; ++k) c[k] = cm[s * 24 + k];
@@ -135,24 +130,18 @@ __global__ void __launch_bounds__(64 * kWaves) minsnap_audit_kernel(
         }
     }
 
-    // across the group: max, integer add, min -- exact whatever the order (xor distances below kLanes stay inside the group)
-#pragma unroll
-    for (int d = kLanes / 2; d >= 1; d >>= 1) {
-        m_vxy2 = fmax(m_vxy2, __shfl_xor(m_vxy2, d)); m_climb = fmax(m_climb, __shfl_xor(m_climb, d));
-        m_descent = fmax(m_descent, __shfl_xor(m_descent, d)); m_axy2 = fmax(m_axy2, __shfl_xor(m_axy2, d));
-        m_up = fmax(m_up, __shfl_xor(m_up, d)); m_down = fmax(m_down, __shfl_xor(m_down, d));
-        m_v2 = fmax(m_v2, __shfl_xor(m_v2, d));
-        bad += __shfl_xor(bad, d);                           // (0 + 0 or NaN: order-free as well)
-    }
+    // across the group: max, integer add, min -- exact whatever the order
+    const auto peak = [](double a, double o) { return fmax(a, o); };
+    m_vxy2 = group_reduce<kLanes>(m_vxy2, peak); m_climb = group_reduce<kLanes>(m_climb, peak);
+    m_descent = group_reduce<kLanes>(m_descent, peak); m_axy2 = group_reduce<kLanes>(m_axy2, peak);
+    m_up = group_reduce<kLanes>(m_up, peak); m_down = group_reduce<kLanes>(m_down, peak);
+    m_v2 = group_reduce<kLanes>(m_v2, peak);
+    bad = group_reduce<kLanes>(bad, Add());                  // (0 + 0 or NaN: order-free as well)
     const bool finite = bad == 0.0 && n_rows > 0;            // a mission without rows has no peaks either: NaN
     if (HITS) {
         for (int q = 0; q < n_cuboids; ++q) {
-            int n = count[q * kThreads], f = first[q * kThreads];
-#pragma unroll
-            for (int d = kLanes / 2; d >= 1; d >>= 1) {
-                n += __shfl_xor(n, d);
-                f = min(f, __shfl_xor(f, d));
-            }
+            const int n = group_reduce<kLanes>(count[q * kThreads], Add());
+            const int f = group_reduce<kLanes>(first[q * kThreads], [](int a, int o) { return min(a, o); });
             if (live && l == 0) {
                 hit_rows[(size_t)q * B + b] = finite ? n : 0;
                 first_hit[(size_t)q * B + b] = (finite && f != kNoHit) ? f : -1;

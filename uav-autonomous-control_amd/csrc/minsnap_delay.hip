@@ -15,48 +15,13 @@
 // Every output has one writer; no atomics but the flag.
 
 #include "uavac_internal.h"
+#include "mission_walk.h"
 
 namespace {
 
+using namespace mission_walk;                               // Mission, the clock's bound and the clamped start, the workgroup scan
 constexpr int kThreads = 256;
-constexpr int kMaxClock = 1 << 29;                          // the separation audit's bound on a start row
 constexpr int kPairs = 12;                                  // 16-byte pieces of a segment's 24 coefficients
-
-// First segment and segment count of mission b: uniform (so == NULL) or ragged, clamped to 1 .. m like every ragged kernel clamps it.
-struct Mission {
-    long long s0;
-    int m;
-};
-__device__ __forceinline__ Mission mission_of(const int64_t *__restrict__ so, int b, int m_uniform) {
-    Mission M;
-    if (so) {
-        M.s0 = so[b];
-        const long long n = so[b + 1] - M.s0;
-        M.m = (int)(n < 1 ? 1 : (n > m_uniform ? m_uniform : n));
-    } else {
-        M.s0 = (long long)b * m_uniform;
-        M.m = m_uniform;
-    }
-    return M;
-}
-
-__device__ __forceinline__ int clamped_start(int s) { return s < 0 ? 0 : (s > kMaxClock ? kMaxClock : s); }
-
-// (minsnap_solve.hip and minsnap_timeopt.hip keep their copies in anonymous namespaces; the scan kernel behind
-// uavac_launch_totals_scan is shared)
-__device__ __forceinline__ int64_t block_inclusive_scan_256(int64_t v, int64_t *wsum /* [4] shared */) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    if (lane == 63) wsum[wv] = v;
-    __syncthreads();
-    int64_t base = 0;
-    for (int w = 0; w < wv; ++w) base += wsum[w];
-    return v + base;
-}
 
 __global__ void __launch_bounds__(kThreads) delay_counts_kernel(const int64_t *__restrict__ seg_offsets, int B, int m,
                                                                 const int32_t *__restrict__ start_rows, int32_t *__restrict__ totals,

@@ -7,8 +7,11 @@
 // ~260 rounds when a few missions run the bounded loop to its end.
 
 #include "uavac_internal.h"
+#include "mission_walk.h"
 
 namespace {
+
+using namespace mission_walk;
 
 // Collision scan: one wavefront per active mission, lanes over its rows.  Positions by the sampler's own Horner chain
 // (minsnap_eval.h: px = fma(px, t, c_i), i = 6 .. 0 -- the position does not depend on the derivative chains it is
@@ -23,9 +26,9 @@ __global__ void __launch_bounds__(64) obstacle_hits_kernel(const double *__restr
     const int lane = threadIdx.x;
     const int b = blockIdx.x;
     if (!active[b]) return;
-    const size_t seg0 = (size_t)seg_offsets[b];
-    const int64_t n = seg_offsets[b + 1] - seg_offsets[b];
-    const int mb = (int)(n < 1 ? 1 : (n > max_m ? max_m : n));
+    const Mission M = mission_of(seg_offsets, b, max_m);
+    const size_t seg0 = (size_t)M.s0;
+    const int mb = M.m;
     for (int i = lane; i < 24 * mb; i += 64) cl[i] = coeffs[seg0 * 24 + i];
     {
         const int v = (lane < mb) ? seg_rows[seg0 + lane] : 0;
@@ -52,20 +55,6 @@ __global__ void __launch_bounds__(64) obstacle_hits_kernel(const double *__restr
         const bool in = (px >= x0) & (px <= x1) & (py >= y0) & (py <= y1) & (pz >= z0) & (pz <= z1);    // inclusive
         if (in) hit[seg0 + s] = 1;                        // after the zeroing above in program order (one wave)
     }
-}
-
-__device__ __forceinline__ int64_t block_scan_256(int64_t v, int64_t *wsum) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    if (lane == 63) wsum[wv] = v;
-    __syncthreads();
-    int64_t base = 0;
-    for (int w = 0; w < wv; ++w) base += wsum[w];
-    return v + base;
 }
 
 // Per mission: how many segments will it have after this round?  Active missions without a hit are clean for this cuboid
@@ -103,7 +92,7 @@ __global__ void __launch_bounds__(256) insert_count_kernel(const int64_t *__rest
         totals[b] = (int32_t)new_m;
         atomicMax(&counters[2], (int32_t)new_m);
     }
-    const int64_t inc = block_scan_256(new_m, wsum);
+    const int64_t inc = block_inclusive_scan_256(new_m, wsum);
     if (threadIdx.x == 255) tile_sum[blockIdx.x] = inc;
 }
 

@@ -17,6 +17,7 @@
 // block-Thomas forms.
 
 #include "minsnap_kkt.h"
+#include "mission_walk.h"
 
 #include <type_traits>
 
@@ -26,6 +27,7 @@
 
 namespace {
 
+using mission_walk::block_inclusive_scan_256;
 constexpr int KL = 7;             // sub-diagonals of the knot-ordered KKT matrix
 constexpr int BW = 22;            // stored band per row: columns [i-7, i+14] (fill-in of partial pivoting)
 constexpr int RS = 25;            // row stride in doubles: band + 3 right-hand sides (odd: spreads LDS banks)
@@ -54,20 +56,6 @@ __constant__ Flat<32> kW = flat(Wc);
 // committed reference times are reproduced bit for bit by this form only (the plain sum of squares differs in the
 // last bit for ~8 % of the segments, which moves ceil(T/dt) by one row whenever T/dt sits on an integer).  No other
 // contraction: the division, the factor and ceil(T/dt) are the plain IEEE sequence of len(np.arange(0, T, dt)).
-__device__ __forceinline__ int64_t block_inclusive_scan_256(int64_t v, int64_t *wsum /* [4] shared */) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    if (lane == 63) wsum[wv] = v;
-    __syncthreads();
-    int64_t base = 0;
-    for (int w = 0; w < wv; ++w) base += wsum[w];
-    return v + base;
-}
-
 // The cruise speed of mission b: the batch's one value, or the mission's own out of velocities [B].
 __device__ __forceinline__ double velocity_of(double v, int) { return v; }
 __device__ __forceinline__ double velocity_of(const double *v, int b) { return v[b]; }

@@ -18,6 +18,7 @@
 // Contraction is off in every kernel of this file: each step is one rounded IEEE operation.
 
 #include "uavac_internal.h"
+#include "mission_walk.h"
 
 #include <cmath>
 #include <limits>
@@ -26,38 +27,7 @@ namespace {
 
 constexpr int kThreads = 256;
 
-// (minsnap_solve.hip keeps its copy in an anonymous namespace; the scan kernel behind uavac_launch_totals_scan is shared)
-__device__ __forceinline__ int64_t block_inclusive_scan_256(int64_t v, int64_t *wsum /* [4] shared */) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    if (lane == 63) wsum[wv] = v;
-    __syncthreads();
-    int64_t base = 0;
-    for (int w = 0; w < wv; ++w) base += wsum[w];
-    return v + base;
-}
-
-// First segment and segment count of mission b: uniform (so == NULL) or ragged, clamped to 1 .. m like every ragged kernel clamps it.
-struct Mission {
-    long long s0;
-    int m;
-};
-__device__ __forceinline__ Mission mission_of(const int64_t *__restrict__ so, int b, int m_uniform) {
-    Mission M;
-    if (so) {
-        M.s0 = so[b];
-        const long long n = so[b + 1] - M.s0;
-        M.m = (int)(n < 1 ? 1 : (n > m_uniform ? m_uniform : n));
-    } else {
-        M.s0 = (long long)b * m_uniform;
-        M.m = m_uniform;
-    }
-    return M;
-}
+using namespace mission_walk;                               // Mission and the workgroup scan
 
 // ------------------------------------------------------------------------------------------ rows from given durations
 // One thread per mission, 256 missions per workgroup, which also leaves the tile's row total (as row_counts_kernel does).  A duration

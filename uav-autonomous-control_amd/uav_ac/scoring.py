@@ -103,8 +103,13 @@ def plan_feasibility(audit, vehicle=None, slack: float = 0.0) -> dict:
 DEFAULT_RETIME_MARGIN = 1e-3     # see `retime_factors`; the default of `Engine.retime`
 
 
-def _host(x) -> np.ndarray:
-    return np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, dtype=np.float64)
+def _host(x, dtype=np.float64) -> np.ndarray:
+    return np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, dtype=dtype)
+
+
+def _host_i64(x) -> np.ndarray:
+    """offsets and start rows: flat int64"""
+    return _host(x, np.int64).reshape(-1)
 
 
 def retime_factors(audit, vehicle=None, margin: float = DEFAULT_RETIME_MARGIN, velocities=None) -> dict:
@@ -160,6 +165,84 @@ SEP_PARTNER, SEP_ROW, SEP_CONFLICTS, SEP_FIRST_CONFLICT, SEP_COMPARED = range(na
 _MAX_CLOCK = 1 << 29                                                                           # the largest start row the shared clock takes
 
 
+def _radius(radius) -> float:
+    radius = float(radius)
+    if not (np.isfinite(radius) and radius >= 0.0):
+        raise ValueError("radius must be finite and >= 0")
+    return radius
+
+
+def _group_offsets(group_offsets, B) -> np.ndarray:
+    """(G + 1,) offsets that ascend from 0 to B; None = one group of all B"""
+    go = np.array([0, B], dtype=np.int64) if group_offsets is None else _host_i64(group_offsets)
+    if len(go) < 2 or go[0] != 0 or go[-1] != B or (np.diff(go) < 0).any():
+        raise ValueError("group_offsets must ascend from 0 to B")
+    return go
+
+
+def _start_rows(start_rows, B, upper=_MAX_CLOCK) -> np.ndarray:
+    """(B,) start rows clamped to 0 .. `upper` (the searches; None: from below only, the separation audit); None = all 0"""
+    S = np.zeros(B, dtype=np.int64) if start_rows is None else np.clip(_host_i64(start_rows), 0, upper)
+    if len(S) != B:
+        raise ValueError("one start row per mission")
+    return S
+
+
+def _included(pos, N, longest=_MAX_CLOCK) -> np.ndarray:
+    """(B,) bool: mission b has rows -- at most `longest` (the searches; None: no such term, the separation audit) -- and every
+    position pos(b) (N_b, 3) is finite.  Everybody else is EXCLUDED."""
+    return np.array([N[b] > 0 and (longest is None or N[b] <= longest) and bool(np.isfinite(pos(b)).all()) for b in range(len(N))],
+                    dtype=bool)
+
+
+def _at(pos, k, s):
+    """where a mission with positions `pos` (N, 3) and start row s stands at the clock rows k: it waits on its first row, holds its last"""
+    return pos[np.clip(k - s, 0, len(pos) - 1)]
+
+
+def _inside_any(own, partners, r2) -> bool:
+    """is the candidate `own` (H, 3) inside the radius of any decided partner (n, H, 3) at any clock row?"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        dx, dy, dz = (own[None, :, c] - partners[:, :, c] for c in range(3))
+        return bool(((dx * dx + dy * dy) + dz * dz < r2).any())
+
+
+def _prioritised_search(N, included, go, max_group, max_steps, pos, start, r2, blocked=None):
+    """The search the stagger and the layer rules share.  Candidate q of mission i stands at the positions pos(i, q) (N_i, 3) from
+    start row start(i, q) on; per group the included missions in ascending index examine q = 0 .. max_steps against the GRANTED
+    candidates of the missions decided before them (candidate 0 for an unresolved one), up to the horizon max(every partner's end,
+    the candidate's own end).  `blocked(i, q)`: refused before anybody is compared -- and then the first of a group is examined too.
+    pos is only called for a candidate that is compared with somebody, and for a partner's granted one.
+    -> steps (-2: not examined, -1: unresolved), earlier, refused candidates: (B,) each."""
+    B = len(N)
+    steps, earlier, refused = np.full(B, -2), np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+    for g in range(len(go) - 1):
+        g0, g1 = int(go[g]), int(go[g + 1])
+        if g1 - g0 > max_group:
+            continue
+        done = []                                                                     # (mission, granted candidate) of the included missions decided so far
+        for i in range(g0, g1):
+            if not included[i]:
+                continue
+            n, earlier[i], steps[i] = int(N[i]), len(done), -1
+            if done:
+                h_prev = max(start(j, c) + int(N[j]) for j, c in done)
+                k = np.arange(max(h_prev, start(i, max_steps) + n))
+                partners = np.stack([_at(pos(j, c), k, start(j, c)) for j, c in done])                # (n, h_max, 3)
+            for q in range(max_steps + 1):
+                if blocked is not None and blocked(i, q):
+                    refused[i] += 1
+                    continue
+                if done:
+                    H = max(h_prev, start(i, q) + n)
+                    if _inside_any(_at(pos(i, q), k[:H], start(i, q)), partners[:, :H], r2):
+                        continue
+                steps[i] = q
+                break
+            done.append((i, max(int(steps[i]), 0)))
+    return steps, earlier, refused
+
+
 def separation_from_rows(rows, row_offsets, radius, group_offsets=None, start_rows=None):
     """The separation audit recomputed from SAMPLED rows -- the SPECIFICATION of `uavac_minsnap_separation_dev`
     (csrc/minsnap_separation.hip), which is tested against it bit for bit.  NumPy on the host.
@@ -175,23 +258,15 @@ def separation_from_rows(rows, row_offsets, radius, group_offsets=None, start_ro
     -> (sep (B,) f64, isep (SEP_ROWS, B) i32): minimum distance (+inf: nobody to compare with); partner, clock row of the minimum (-1
     with +inf / NaN), conflicts (partners that come inside the radius), first clock row with a partner inside (-1: none), compared."""
     rows = _host(rows)
-    ro = np.asarray(row_offsets.detach().cpu().numpy() if hasattr(row_offsets, "detach") else row_offsets, dtype=np.int64).reshape(-1)
+    ro = _host_i64(row_offsets)
     B = len(ro) - 1
-    radius = float(radius)
-    if not (np.isfinite(radius) and radius >= 0.0):
-        raise ValueError("radius must be finite and >= 0")
-    go = np.array([0, B], dtype=np.int64) if group_offsets is None else np.asarray(
-        group_offsets.detach().cpu().numpy() if hasattr(group_offsets, "detach") else group_offsets, dtype=np.int64).reshape(-1)
-    if len(go) < 2 or go[0] != 0 or go[-1] != B or (np.diff(go) < 0).any():
-        raise ValueError("group_offsets must ascend from 0 to B")
-    S = np.zeros(B, dtype=np.int64) if start_rows is None else np.maximum(0, np.asarray(
-        start_rows.detach().cpu().numpy() if hasattr(start_rows, "detach") else start_rows, dtype=np.int64).reshape(-1))
-    if len(S) != B:
-        raise ValueError("one start row per mission")
+    radius = _radius(radius)
+    go = _group_offsets(group_offsets, B)
+    S = _start_rows(start_rows, B, upper=None)
     r2 = radius * radius
     N = np.diff(ro)
     pos = [rows[ro[b]:ro[b + 1], 0:3] for b in range(B)]
-    included = np.array([N[b] > 0 and bool(np.isfinite(pos[b]).all()) for b in range(B)], dtype=bool)
+    included = _included(pos.__getitem__, N, longest=None)
     sep = np.full(B, np.nan)
     isep = np.zeros((nat.SEP_ROWS, B), dtype=np.int32)
     isep[[SEP_PARTNER, SEP_ROW, SEP_FIRST_CONFLICT]] = -1
@@ -199,9 +274,8 @@ def separation_from_rows(rows, row_offsets, radius, group_offsets=None, start_ro
         members = [b for b in range(int(go[g]), int(go[g + 1])) if included[b]]
         if not members:
             continue
-        H = int(max(S[b] + N[b] for b in members))
-        k = np.arange(H)
-        P = np.stack([pos[b][np.clip(k - S[b], 0, N[b] - 1)] for b in members])          # (n, H, 3): where everybody stands at clock row k
+        k = np.arange(int(max(S[b] + N[b] for b in members)))
+        P = np.stack([_at(pos[b], k, S[b]) for b in members])                            # (n, H, 3): where everybody stands at clock row k
         idx = np.asarray(members)
         for a, b in enumerate(members):
             isep[SEP_COMPARED, b] = len(members) - 1
@@ -229,15 +303,15 @@ def separation_ok(sep, group_sizes=None) -> dict:
     mission's group, (B,) or one number -- without it `complete` is all False) and `ok` (both).  A mission whose minimum distance is NaN
     -- an excluded one: no rows, or a singular plan -- fails all three: a plan that was not checked never looks clear."""
     dist = _host(sep.min_distance).reshape(-1)
-    conflicts = np.asarray(_host(sep.conflicts)).reshape(-1)
-    compared = np.asarray(_host(sep.compared)).reshape(-1)
+    conflicts = _host(sep.conflicts).reshape(-1)
+    compared = _host(sep.compared).reshape(-1)
     finite = ~np.isnan(dist)
     clear = finite & (conflicts == 0)
     if group_sizes is None:
         complete = np.zeros(len(dist), dtype=bool)
     else:
-        sizes = np.broadcast_to(np.asarray(_host(group_sizes)).reshape(-1), dist.shape) if np.size(group_sizes) == 1 else \
-            np.asarray(_host(group_sizes)).reshape(-1)
+        sizes = np.broadcast_to(_host(group_sizes).reshape(-1), dist.shape) if np.size(group_sizes) == 1 else \
+            _host(group_sizes).reshape(-1)
         if len(sizes) != len(dist):
             raise ValueError("one group size per mission (or one number)")
         complete = finite & (compared == sizes - 1)
@@ -260,13 +334,8 @@ def separation_from_log(log, radius, group_offsets=None):
     if log.ndim != 3 or log.shape[0] < 1 or log.shape[1] < 3 or log.shape[2] < 1:
         raise ValueError("log must have shape (K, >= 3, B) with K >= 1 and B >= 1")
     K, B = log.shape[0], log.shape[2]
-    radius = float(radius)
-    if not (np.isfinite(radius) and radius >= 0.0):
-        raise ValueError("radius must be finite and >= 0")
-    go = np.array([0, B], dtype=np.int64) if group_offsets is None else np.asarray(
-        group_offsets.detach().cpu().numpy() if hasattr(group_offsets, "detach") else group_offsets, dtype=np.int64).reshape(-1)
-    if len(go) < 2 or go[0] != 0 or go[-1] != B or (np.diff(go) < 0).any():
-        raise ValueError("group_offsets must ascend from 0 to B")
+    radius = _radius(radius)
+    go = _group_offsets(group_offsets, B)
     r2 = radius * radius
     sep = np.full(B, np.inf)
     isep = np.zeros((nat.SEP_ROWS, B), dtype=np.int32)
@@ -309,10 +378,10 @@ def delay_rows(rows, row_offsets, start_rows, first_yaw):
     by one.  A mission without rows cannot be delayed from rows (ValueError).
     -> (rows' (N + sum S, 11) f64, row_offsets' (B + 1,) i64)."""
     rows = _host(rows)
-    ro = np.asarray(_host(row_offsets), dtype=np.int64).reshape(-1)
+    ro = _host_i64(row_offsets)
     B = len(ro) - 1
-    S = np.clip(np.asarray(_host(start_rows), dtype=np.int64).reshape(-1), 0, _MAX_CLOCK)
-    fy = np.asarray(_host(first_yaw), dtype=np.float64).reshape(-1)
+    S = np.clip(_host_i64(start_rows), 0, _MAX_CLOCK)
+    fy = _host(first_yaw).reshape(-1)
     if len(S) != B or len(fy) != B:
         raise ValueError("one start row and one first heading per mission")
     out_ro = np.zeros(B + 1, dtype=np.int64)
@@ -352,56 +421,21 @@ def stagger_from_rows(rows, row_offsets, radius, group_offsets=None, start_rows=
     examined: its clamped base start, steps = -2, earlier = 0; nobody is checked against an excluded mission.
     -> istag (STAGGER_ROWS, B) i32: the granted start row; steps; earlier (how many missions it was checked against)."""
     rows = _host(rows)
-    ro = np.asarray(row_offsets.detach().cpu().numpy() if hasattr(row_offsets, "detach") else row_offsets, dtype=np.int64).reshape(-1)
+    ro = _host_i64(row_offsets)
     B = len(ro) - 1
     radius, step, max_steps = float(radius), int(step), int(max_steps)
-    if not (np.isfinite(radius) and radius >= 0.0):
-        raise ValueError("radius must be finite and >= 0")
+    radius = _radius(radius)
     if step < 1 or not (0 <= max_steps <= nat.STAGGER_MAX_STEPS) or step * max_steps > _MAX_CLOCK:
         raise ValueError(f"step must be >= 1, max_steps in 0 .. {nat.STAGGER_MAX_STEPS}, step * max_steps at most 2^29")
-    go = np.array([0, B], dtype=np.int64) if group_offsets is None else np.asarray(
-        group_offsets.detach().cpu().numpy() if hasattr(group_offsets, "detach") else group_offsets, dtype=np.int64).reshape(-1)
-    if len(go) < 2 or go[0] != 0 or go[-1] != B or (np.diff(go) < 0).any():
-        raise ValueError("group_offsets must ascend from 0 to B")
-    S = np.zeros(B, dtype=np.int64) if start_rows is None else np.clip(np.asarray(
-        start_rows.detach().cpu().numpy() if hasattr(start_rows, "detach") else start_rows, dtype=np.int64).reshape(-1), 0, _MAX_CLOCK)
-    if len(S) != B:
-        raise ValueError("one start row per mission")
-    r2 = radius * radius
+    go = _group_offsets(group_offsets, B)
+    S = _start_rows(start_rows, B)
     N = np.diff(ro)
     pos = [rows[ro[b]:ro[b + 1], 0:3] for b in range(B)]
-    included = np.array([0 < N[b] <= _MAX_CLOCK and bool(np.isfinite(pos[b]).all()) for b in range(B)], dtype=bool)
+    # the candidate is a start row: the mission's own rows from S_i + q * step on, up to the horizon of that candidate
+    steps, earlier, _ = _prioritised_search(N, _included(pos.__getitem__, N), go, nat.STAGGER_MAX_GROUP, max_steps, lambda i, q: pos[i],
+                                            lambda i, q: int(S[i]) + q * step, radius * radius)
     istag = np.zeros((nat.STAGGER_ROWS, B), dtype=np.int32)
-    istag[STAG_START], istag[STAG_STEPS] = S, -2
-    for g in range(len(go) - 1):
-        g0, g1 = int(go[g]), int(go[g + 1])
-        if g1 - g0 > nat.STAGGER_MAX_GROUP:
-            continue
-        done = []                                                                     # the included missions decided so far
-        T = {}
-        for i in range(g0, g1):
-            if not included[i]:
-                continue
-            istag[STAG_EARLIER, i] = len(done)
-            T[i], steps = int(S[i]), -1
-            if done:
-                h_prev = max(T[j] + int(N[j]) for j in done)
-                h_max = max(h_prev, int(S[i]) + max_steps * step + int(N[i]))
-                k = np.arange(h_max)
-                others = np.stack([pos[j][np.clip(k - T[j], 0, N[j] - 1)] for j in done])                 # (n, h_max, 3)
-            for q in range(max_steps + 1):
-                s = int(S[i]) + q * step
-                clear = True
-                if done:
-                    H = max(h_prev, s + int(N[i]))
-                    own = pos[i][np.clip(k[:H] - s, 0, N[i] - 1)]                     # (H, 3): where the candidate stands at clock row k
-                    dx, dy, dz = (own[None, :, c] - others[:, :H, c] for c in range(3))
-                    clear = not bool(((dx * dx + dy * dy) + dz * dz < r2).any())
-                if clear:
-                    T[i], steps = s, q
-                    break
-            istag[STAG_START, i], istag[STAG_STEPS, i] = T[i], steps
-            done.append(i)
+    istag[STAG_START], istag[STAG_STEPS], istag[STAG_EARLIER] = S + np.maximum(steps, 0) * step, steps, earlier
     return istag
 
 
@@ -410,9 +444,9 @@ def stagger_ok(istag) -> dict:
     any device or arrays) -> dict of (B,) bool host arrays: `resolved` (steps >= 0: a start was granted) and `examined` (steps !=
     -2).  A mission that was not examined -- an excluded one, or one of an oversized group -- never looks resolved."""
     if hasattr(istag, "steps"):
-        steps = np.asarray(_host(istag.steps)).reshape(-1)
+        steps = _host(istag.steps).reshape(-1)
     else:
-        block = np.asarray(_host(istag))
+        block = _host(istag)
         if block.ndim != 2 or block.shape[0] != nat.STAGGER_ROWS:
             raise ValueError(f"a stagger block is [{nat.STAGGER_ROWS}][B], got {block.shape}")
         steps = block[STAG_STEPS]
@@ -431,9 +465,9 @@ def shift_coeffs(coeffs, seg_offsets_or_m, offsets):
     Every segment of mission b gets c0'[a] = c0[a] + offsets[b][a] (one rounded sum); c1 .. c7 keep every bit, and a mission whose three
     offsets are all +-0 is not touched at all (a -0.0 stays -0.0).  Non-finite offsets pass through.
     -> a new array of the shape of `coeffs`."""
-    co = np.array(_host(coeffs), dtype=np.float64)
+    co = np.array(_host(coeffs))
     out = co.reshape(-1, 8, 3)
-    off = np.asarray(_host(offsets), dtype=np.float64).reshape(-1, 3)
+    off = _host(offsets).reshape(-1, 3)
     B = len(off)
     if np.ndim(seg_offsets_or_m) == 0:
         m = int(seg_offsets_or_m)
@@ -441,7 +475,7 @@ def shift_coeffs(coeffs, seg_offsets_or_m, offsets):
             raise ValueError(f"{len(out)} segments are not {B} missions of {m}")
         so = np.arange(B + 1, dtype=np.int64) * m
     else:
-        so = np.asarray(_host(seg_offsets_or_m), dtype=np.int64).reshape(-1)
+        so = _host_i64(seg_offsets_or_m)
         if len(so) != B + 1 or so[0] != 0 or so[-1] != len(out) or (np.diff(so) < 0).any():
             raise ValueError("seg_offsets must ascend from 0 to the number of segments, one entry per mission and one more")
     for b in range(B):
@@ -468,61 +502,7 @@ def layer_from_rows(rows_at, row_offsets, radius, group_offsets=None, start_rows
     unresolved: steps = -1, L_i = 0, and it remains a partner for every later mission.  An excluded mission, and every mission of a
     group of more than LAYER_MAX_GROUP, is not examined: layer 0, steps = -2, earlier = 0; nobody is checked against an excluded one.
     -> ilayer (LAYER_ROWS, B) i32: the granted layer; steps; earlier (how many missions it was checked against)."""
-    ro = np.asarray(row_offsets.detach().cpu().numpy() if hasattr(row_offsets, "detach") else row_offsets, dtype=np.int64).reshape(-1)
-    B = len(ro) - 1
-    radius, max_steps = float(radius), int(max_steps)
-    if not callable(rows_at):
-        raise ValueError("rows_at must be a callable: layer -> rows")
-    if not (np.isfinite(radius) and radius >= 0.0):
-        raise ValueError("radius must be finite and >= 0")
-    if not (0 <= max_steps <= nat.LAYER_MAX_STEPS):
-        raise ValueError(f"max_steps must be in 0 .. {nat.LAYER_MAX_STEPS}")
-    go = np.array([0, B], dtype=np.int64) if group_offsets is None else np.asarray(
-        group_offsets.detach().cpu().numpy() if hasattr(group_offsets, "detach") else group_offsets, dtype=np.int64).reshape(-1)
-    if len(go) < 2 or go[0] != 0 or go[-1] != B or (np.diff(go) < 0).any():
-        raise ValueError("group_offsets must ascend from 0 to B")
-    S = np.zeros(B, dtype=np.int64) if start_rows is None else np.clip(np.asarray(
-        start_rows.detach().cpu().numpy() if hasattr(start_rows, "detach") else start_rows, dtype=np.int64).reshape(-1), 0, _MAX_CLOCK)
-    if len(S) != B:
-        raise ValueError("one start row per mission")
-    r2 = radius * radius
-    N = np.diff(ro)
-
-    def pos(q, b):
-        return _host(rows_at(q))[ro[b]:ro[b + 1], 0:3]
-
-    included = np.array([0 < N[b] <= _MAX_CLOCK and bool(np.isfinite(pos(0, b)).all()) for b in range(B)], dtype=bool)
-    ilayer = np.zeros((nat.LAYER_ROWS, B), dtype=np.int32)
-    ilayer[LAYER_STEPS] = -2
-    for g in range(len(go) - 1):
-        g0, g1 = int(go[g]), int(go[g + 1])
-        if g1 - g0 > nat.LAYER_MAX_GROUP:
-            continue
-        done = []                                                                     # the included missions decided so far
-        L = {}
-        for i in range(g0, g1):
-            if not included[i]:
-                continue
-            ilayer[LAYER_EARLIER, i] = len(done)
-            L[i], steps = 0, -1
-            if done:
-                H = max(max(int(S[j]) + int(N[j]) for j in done), int(S[i]) + int(N[i]))
-                k = np.arange(H)
-                others = np.stack([pos(L[j], j)[np.clip(k - S[j], 0, N[j] - 1)] for j in done])                # (n, H, 3)
-                at = np.clip(k - S[i], 0, N[i] - 1)
-            for q in range(max_steps + 1):
-                clear = True
-                if done:
-                    own = pos(q, i)[at]                                               # (H, 3): where the candidate stands at clock row k
-                    with np.errstate(invalid="ignore", over="ignore"):
-                        dx, dy, dz = (own[None, :, c] - others[:, :, c] for c in range(3))
-                        clear = not bool(((dx * dx + dy * dy) + dz * dz < r2).any())
-                if clear:
-                    L[i], steps = q, q
-                    break
-            ilayer[LAYER_LAYER, i], ilayer[LAYER_STEPS, i] = L[i], steps
-            done.append(i)
-    return ilayer
+    return _layer_search(rows_at, row_offsets, radius, (), group_offsets, start_rows, max_steps)[:nat.LAYER_ROWS]
 
 
 def layer_obstacles_from_rows(rows_at, row_offsets, radius, cuboids, group_offsets=None, start_rows=None, max_steps=63):
@@ -541,82 +521,49 @@ def layer_obstacles_from_rows(rows_at, row_offsets, radius, cuboids, group_offse
     -> ilayer (LAYER_OBS_ROWS, B) i32: rows 0-2 as `layer_from_rows`; row 3 `blocked` = how many of the candidates q = 0 .. steps - 1
     (0 .. max_steps when unresolved) a cuboid refused, 0 for a mission that was not examined.  With n = 0 rows 0-2 equal
     `layer_from_rows` exactly and row 3 is zero."""
-    ro = np.asarray(row_offsets.detach().cpu().numpy() if hasattr(row_offsets, "detach") else row_offsets, dtype=np.int64).reshape(-1)
+    return _layer_search(rows_at, row_offsets, radius, cuboids, group_offsets, start_rows, max_steps)
+
+
+def _layer_search(rows_at, row_offsets, radius, cuboids, group_offsets, start_rows, max_steps):
+    """Both layer rules -> ilayer (LAYER_OBS_ROWS, B) i32.  Without cuboids nothing is ever blocked and rows 0-2 are `layer_from_rows`."""
+    ro = _host_i64(row_offsets)
     B = len(ro) - 1
     radius, max_steps = float(radius), int(max_steps)
     if not callable(rows_at):
         raise ValueError("rows_at must be a callable: layer -> rows")
-    if not (np.isfinite(radius) and radius >= 0.0):
-        raise ValueError("radius must be finite and >= 0")
+    radius = _radius(radius)
     if not (0 <= max_steps <= nat.LAYER_MAX_STEPS):
         raise ValueError(f"max_steps must be in 0 .. {nat.LAYER_MAX_STEPS}")
-    cub = np.asarray(_host(cuboids), dtype=np.float64)
+    cub = _host(cuboids)
     if cub.size and (cub.ndim != 2 or cub.shape[1] != 6):
         raise ValueError("cuboids must be (n, 6): xmin xmax ymin ymax zmin zmax")
     cub = cub.reshape(-1, 6)
     if len(cub) > nat.AUDIT_MAX_CUBOIDS:
         raise ValueError(f"{len(cub)} cuboids; at most {nat.AUDIT_MAX_CUBOIDS}")
-    go = np.array([0, B], dtype=np.int64) if group_offsets is None else np.asarray(
-        group_offsets.detach().cpu().numpy() if hasattr(group_offsets, "detach") else group_offsets, dtype=np.int64).reshape(-1)
-    if len(go) < 2 or go[0] != 0 or go[-1] != B or (np.diff(go) < 0).any():
-        raise ValueError("group_offsets must ascend from 0 to B")
-    S = np.zeros(B, dtype=np.int64) if start_rows is None else np.clip(np.asarray(
-        start_rows.detach().cpu().numpy() if hasattr(start_rows, "detach") else start_rows, dtype=np.int64).reshape(-1), 0, _MAX_CLOCK)
-    if len(S) != B:
-        raise ValueError("one start row per mission")
-    r2 = radius * radius
+    go = _group_offsets(group_offsets, B)
+    S = _start_rows(start_rows, B)
     N = np.diff(ro)
 
-    def pos(q, b):
+    def pos(b, q):                                                                    # the candidate is a layer: the mission's rows of rows_at(q)
         return _host(rows_at(q))[ro[b]:ro[b + 1], 0:3]
 
-    def is_blocked(q, b):
-        p = pos(q, b)
+    def is_blocked(b, q):
+        p = pos(b, q)
         with np.errstate(invalid="ignore"):
             for x in cub:
                 if ((p[:, 0] >= x[0]) & (p[:, 0] <= x[1]) & (p[:, 1] >= x[2]) & (p[:, 1] <= x[3]) & (p[:, 2] >= x[4]) & (p[:, 2] <= x[5])).any():
                     return True
         return False
 
-    included = np.array([0 < N[b] <= _MAX_CLOCK and bool(np.isfinite(pos(0, b)).all()) for b in range(B)], dtype=bool)
+    steps, earlier, blocked = _prioritised_search(N, _included(lambda b: pos(b, 0), N), go, nat.LAYER_MAX_GROUP, max_steps, pos,
+                                                  lambda b, q: int(S[b]), radius * radius, is_blocked if len(cub) else None)
     ilayer = np.zeros((nat.LAYER_OBS_ROWS, B), dtype=np.int32)
-    ilayer[LAYER_STEPS] = -2
-    for g in range(len(go) - 1):
-        g0, g1 = int(go[g]), int(go[g + 1])
-        if g1 - g0 > nat.LAYER_MAX_GROUP:
-            continue
-        done = []                                                                     # the included missions decided so far
-        L = {}
-        for i in range(g0, g1):
-            if not included[i]:
-                continue
-            ilayer[LAYER_EARLIER, i] = len(done)
-            L[i], steps, blocked = 0, -1, 0
-            if done:
-                H = max(max(int(S[j]) + int(N[j]) for j in done), int(S[i]) + int(N[i]))
-                k = np.arange(H)
-                others = np.stack([pos(L[j], j)[np.clip(k - S[j], 0, N[j] - 1)] for j in done])                # (n, H, 3)
-                at = np.clip(k - S[i], 0, N[i] - 1)
-            for q in range(max_steps + 1):
-                if len(cub) and is_blocked(q, i):                                     # the cuboids first: never compared with partners
-                    blocked += 1
-                    continue
-                clear = True
-                if done:
-                    own = pos(q, i)[at]                                               # (H, 3): where the candidate stands at clock row k
-                    with np.errstate(invalid="ignore", over="ignore"):
-                        dx, dy, dz = (own[None, :, c] - others[:, :, c] for c in range(3))
-                        clear = not bool(((dx * dx + dy * dy) + dz * dz < r2).any())
-                if clear:
-                    L[i], steps = q, q
-                    break
-            ilayer[LAYER_LAYER, i], ilayer[LAYER_STEPS, i], ilayer[LAYER_BLOCKED, i] = L[i], steps, blocked
-            done.append(i)
+    ilayer[LAYER_LAYER], ilayer[LAYER_STEPS], ilayer[LAYER_EARLIER], ilayer[LAYER_BLOCKED] = np.maximum(steps, 0), steps, earlier, blocked
     return ilayer
 
 
 def _layer_block(result):
-    block = np.asarray(_host(result))
+    block = _host(result)
     if block.ndim != 2 or block.shape[0] not in (nat.LAYER_ROWS, nat.LAYER_OBS_ROWS):
         raise ValueError(f"a layer block is [{nat.LAYER_ROWS}][B] (with obstacles [{nat.LAYER_OBS_ROWS}][B]), got {block.shape}")
     return block
@@ -628,7 +575,7 @@ def layer_ok(result) -> dict:
     granted, layer 0 included) and `examined` (steps != -2).  A mission that was not examined -- an excluded one, or one of an oversized
     group -- never looks resolved."""
     if hasattr(result, "steps"):
-        steps = np.asarray(_host(result.steps)).reshape(-1)
+        steps = _host(result.steps).reshape(-1)
     else:
         steps = _layer_block(result)[LAYER_STEPS]
     return {"resolved": steps >= 0, "examined": steps != -2}
@@ -642,7 +589,7 @@ def blocked_out(result, max_steps: int):
     if hasattr(result, "steps"):
         if getattr(result, "blocked", None) is None:
             raise ValueError("a layer result without `blocked`: the search was run without obstacles")
-        steps, blocked = (np.asarray(_host(v)).reshape(-1) for v in (result.steps, result.blocked))
+        steps, blocked = (_host(v).reshape(-1) for v in (result.steps, result.blocked))
     else:
         block = _layer_block(result)
         if block.shape[0] != nat.LAYER_OBS_ROWS:
