@@ -170,7 +170,9 @@ int uavac_clock_probe_dev(uavac_ctx *ctx, int window_us, int64_t *stamps);
  * buffers, slower into most: DESIGN K2).  "audit_lanes": 16 (default) or 64 = lanes per mission of uavac_minsnap_audit_dev.
  * "timeopt_chunk": 0 (default: sized from UAVAC_TIMEOPT_SCRATCH_BYTES) or the missions per chunk of uavac_minsnap_optimize_times_dev
  * (same results).  "separation_split": 0 (default: sized from B and G) or 1 .. UAVAC_SEP_MAX_SPLIT = workgroups that share the partners
- * of one window of 64 missions in uavac_minsnap_separation_dev and uavac_flown_separation_dev (same results).
+ * of one window of 64 missions in uavac_minsnap_separation_dev and uavac_flown_separation_dev (same results).  "flown_audit_split": 0
+ * (default: sized from B and K) or 1 .. UAVAC_FLOWN_AUDIT_MAX_SPLIT = workgroups that share the ticks of one window of 64 vehicles in
+ * uavac_flown_audit_dev (same results).
  * Defaults from the environment (UAVAC_ROLLOUT_ALIGN, UAVAC_YAW_GROUP, UAVAC_SAMPLER_WAVES, UAVAC_SAMPLER_GROUP) at uavac_create.
  * ONE option is not a tuning knob but part of the log layout: "log_pitch" = P doubles per log row,
  * 0 (default) = B.  With P >= B the rollouts write state_log [K][13][P] and cmd_log [K][12][P]
@@ -526,6 +528,51 @@ int uavac_minsnap_shift_dev(uavac_ctx *ctx, const double *coeffs, const int64_t 
  * finite, G < 1 when group_offsets != NULL. */
 int uavac_flown_separation_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
                                double radius, double *sep, int32_t *isep);
+
+/* FLOWN AUDIT: the plan audit of a FLIGHT.  uavac_minsnap_audit_dev says what a plan's rows would show against the flight limits and the
+ * cuboids; the vehicles track the plan with an error, and uavac_minsnap_layer_obs_dev deliberately puts missions next to cuboids.  This
+ * call reads a rollout's state log once and reports, per vehicle, what it DID (csrc/flown_audit.hip): nothing is read back, everything is
+ * enqueued on the ctx stream, scratch from the arena.
+ *   state_log [K][13][pitch] f64 (device) as the rollouts write it and as uavac_flown_separation_dev takes it; its rows are
+ *             x y z | q0 q1 q2 q3 | vx vy vz | p q r (NED; the quaternion scalar first: row 3 is 1 at identity, uavac_state_init_dev);
+ *             columns B .. pitch - 1 are never read.  The clock is the tick k = 0 .. K - 1.
+ *   cuboids   [n_cuboids][6] f64 (device): xmin xmax ymin ymax zmin zmax, 0 <= n_cuboids <= UAVAC_AUDIT_MAX_CUBOIDS.
+ *             n_cuboids == 0: cuboids, hit_ticks, first_hit, clearance and clearance_tick must all be NULL.
+ * VALID TICK.  Tick k of vehicle b is valid iff all 13 logged values are finite.  Peaks, hits and clearances are taken over the valid
+ * ticks only.
+ *   audit [UAVAC_FLOWN_AUDIT_ROWS][B] f64 (SoA like the plan audit's block):
+ *     0 the number of valid ticks (exact as a double)     4 peak speed sqrt(max((vx * vx + vy * vy) + vz * vz))
+ *     1 peak horizontal speed sqrt(max(vx * vx + vy * vy))    5 max |2 * (q1 * q3 + q0 * q2)|
+ *     2 peak climb rate   max(-vz)   (NED)                6 max |2 * (q2 * q3 - q0 * q1)|
+ *     3 peak descent rate max(vz)                         7 peak body rate sqrt(max((p * p + q * q) + r * r))
+ *     Rows 5 and 6 are the rotation-matrix elements R13 and R23 the control law clips its attitude COMMAND to with max_tilt
+ *     (csrc/control_law.h); the flown attitude may exceed the command.
+ *   first_bad [B] i32: the first invalid tick, -1 when every tick is valid.
+ *   hit_ticks [n_cuboids][B] i32: the number of valid ticks whose position lies inside cuboid c -- the inclusive test px >= xmin && px <=
+ *             xmax && ... of the rollouts' `collided` and of uavac_minsnap_audit_dev;  first_hit [n_cuboids][B] i32: the first such tick, -1
+ *             when there is none.
+ *   clearance [n_cuboids][B] f64, clearance_tick [n_cuboids][B] i32: the closest approach to cuboid c and its tick.  Per valid tick
+ *             ex = px < xmin ? xmin - px : (px > xmax ? px - xmax : 0.0), ey and ez likewise -- selects, so a NaN bound gives 0 on its
+ *             axis and an inverted one whatever the two comparisons give, exactly as np.where does --, d2 = (ex * ex + ey * ey) + ez * ez;
+ *             reported is the lexicographic minimum of (d2, tick) over the valid ticks: clearance = sqrt(d2), clearance_tick = that tick.
+ *             For a proper box (xmin <= xmax, ...) clearance == 0 iff hit_ticks > 0.
+ * ROUNDING is part of the contract, as for the plan audit: every product and every sum is separately rounded (no fused multiply-add), a
+ * maximum is taken of the squares, and one correctly rounded sqrt comes last.  The maximum of -0.0 and +0.0 is +0.0 (rows 2 and 3 of a
+ * vehicle that never climbs or never sinks).
+ * NO VALID TICK (a vehicle whose log is NaN throughout): row 0 is 0, rows 1-7 are NaN, first_bad 0, hit_ticks 0, first_hit -1, clearance
+ * NaN, clearance_tick -1 -- such a vehicle never looks clean (uav_ac.scoring.flight_feasibility).
+ * Every reduction is a maximum, an integer sum, an integer minimum or a lexicographic minimum, so every output is bit for bit what
+ * NumPy gives on the log (uav_ac.scoring.audit_from_log) whatever the launch shape, the pitch, or what else is in the batch.  (Option
+ * "flown_audit_split": 0 = automatic (default), 1 .. UAVAC_FLOWN_AUDIT_MAX_SPLIT = workgroups that share the ticks of one window of 64
+ * vehicles; a tuning knob, same results.)  Cost: one read of the log, K x 13 x B x 8 bytes, and about 30 fp64 operations per cuboid and tick.
+ * UAVAC_EINVAL before anything is enqueued: no context, NULL state_log, audit or first_bad, K < 1, B < 1, pitch < B, n_cuboids outside
+ * 0 .. UAVAC_AUDIT_MAX_CUBOIDS, a NULL among cuboids / hit_ticks / first_hit / clearance / clearance_tick with n_cuboids > 0 or a
+ * pointer among them with n_cuboids == 0. */
+#define UAVAC_FLOWN_AUDIT_ROWS 8
+#define UAVAC_FLOWN_AUDIT_MAX_SPLIT 64
+int uavac_flown_audit_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const double *cuboids, int n_cuboids,
+                          double *audit, int32_t *first_bad, int32_t *hit_ticks, int32_t *first_hit, double *clearance,
+                          int32_t *clearance_tick);
 
 /* ONE CRUISE SPEED PER MISSION: the _v twins of uavac_minsnap_row_counts_dev, uavac_minsnap_row_counts_ragged_dev and
  * uavac_minsnap_plan_dev (both of its forms: rows with a capacity and flag 2 and the same all-or-nothing commit, and rows-free with

@@ -398,6 +398,9 @@ int uavac_set_option(uavac_ctx *ctx, const char *name, int value) {
     } else if (n == "separation_split") {
         if (value < 0 || value > UAVAC_SEP_MAX_SPLIT) return uavac_fail(ctx, UAVAC_EINVAL, "separation_split is 0 (automatic) or 1 .. UAVAC_SEP_MAX_SPLIT");
         ctx->separation_split = value;
+    } else if (n == "flown_audit_split") {
+        if (value < 0 || value > UAVAC_FLOWN_AUDIT_MAX_SPLIT) return uavac_fail(ctx, UAVAC_EINVAL, "flown_audit_split is 0 (automatic) or 1 .. UAVAC_FLOWN_AUDIT_MAX_SPLIT");
+        ctx->flown_audit_split = value;
     } else if (n == "timeopt_chunk") {
         if (value < 0) return uavac_fail(ctx, UAVAC_EINVAL, "timeopt_chunk is 0 (automatic) or a number of missions");
         ctx->timeopt_chunk = value;
@@ -954,6 +957,23 @@ int uavac_flown_separation_dev(uavac_ctx *ctx, const double *state_log, int K, i
     if (!std::isfinite(radius) || radius < 0.0) return uavac_fail(ctx, UAVAC_EINVAL, "radius must be finite and >= 0");
     if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
     return uavac_launch_flown_separation(ctx, state_log, K, B, pitch, group_offsets, G, radius, sep, isep);
+}
+
+int uavac_flown_audit_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const double *cuboids, int n_cuboids,
+                          double *audit, int32_t *first_bad, int32_t *hit_ticks, int32_t *first_hit, double *clearance,
+                          int32_t *clearance_tick) {
+    UAVAC_ENTER(ctx);
+    if (!state_log || !audit || !first_bad) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (K < 1) return uavac_fail(ctx, UAVAC_EINVAL, "K must be >= 1");
+    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
+    if (pitch < B) return uavac_fail(ctx, UAVAC_EINVAL, "pitch must be >= B");
+    if (n_cuboids < 0 || n_cuboids > UAVAC_AUDIT_MAX_CUBOIDS)
+        return uavac_fail(ctx, UAVAC_EINVAL, "n_cuboids must be in [0, UAVAC_AUDIT_MAX_CUBOIDS]");
+    if (n_cuboids == 0 ? (cuboids || hit_ticks || first_hit || clearance || clearance_tick)
+                       : (!cuboids || !hit_ticks || !first_hit || !clearance || !clearance_tick))
+        return uavac_fail(ctx, UAVAC_EINVAL, "cuboids, hit_ticks, first_hit, clearance and clearance_tick go with n_cuboids > 0: all five or none");
+    return uavac_launch_flown_audit(ctx, state_log, K, B, pitch, cuboids, n_cuboids, audit, first_bad, hit_ticks, first_hit, clearance,
+                                    clearance_tick);
 }
 
 int uavac_minsnap_row_offsets_dev(uavac_ctx *ctx, const int32_t *seg_rows, int B, int m, int64_t *row_offsets) {

@@ -35,7 +35,8 @@ struct uavac_ctx {
     int yaw_group = 8;               // tuning: chunks of the sampler's dense yaw column that leave together (1, 4, 8, 16)
     int audit_lanes = 16;            // tuning: lanes of a wavefront that walk one mission in the plan audit: 16 or 64 (minsnap_audit.hip; same results)
     int separation_split = 0;        // tuning: workgroups that share the j-tiles of one window of the separation audits (minsnap_separation.hip, flown_separation.hip; same results); 0 = sized from the batch
-    int timeopt_chunk = 0;           // tuning: missions per chunk of the duration optimisation (minsnap_timeopt.hip; same results); 0 = sized from UAVAC_TIMEOPT_SCRATCH_BYTES
+    int flown_audit_split = 0;       // tuning: workgroups that share the ticks of one window of the flown audit (flown_audit.hip; same results); 0 = sized from the batch
+    int timeopt_chunk = 0;          // tuning: missions per chunk of the duration optimisation (minsnap_timeopt.hip; same results); 0 = sized from UAVAC_TIMEOPT_SCRATCH_BYTES
     int rollout_align = 1;          // tuning: launch the 2-wave aligner kernel before a logged launch of shape 1
     int late_handover = -1;          // tuning: -1 = the launcher picks per launch; 0 / 1 = slab handed over at the end of the tick / a third of a tick later
     int coeff_dma = -1;              // tuning: -1 = the launcher picks per launch; 0 / 1 / 2 = the plan-fed rollout's PMODE (control_rollout.hip)
@@ -253,6 +254,11 @@ int uavac_launch_layer_obs(uavac_ctx *ctx, const double *coeffs, const int32_t *
 // the separation the fleet flew (flown_separation.hip): the audit's outputs from the positions of a state log [K][13][pitch]
 int uavac_launch_flown_separation(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
                                   double radius, double *sep, int32_t *isep);
+// what the vehicles did against the flight limits and the cuboids (flown_audit.hip): audit [UAVAC_FLOWN_AUDIT_ROWS][B], first_bad [B],
+// and per cuboid hit_ticks / first_hit / clearance / clearance_tick [n_cuboids][B], from a state log [K][13][pitch]; scratch from the arena
+int uavac_launch_flown_audit(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const double *cuboids, int n_cuboids,
+                             double *audit, int32_t *first_bad, int32_t *hit_ticks, int32_t *first_hit, double *clearance,
+                             int32_t *clearance_tick);
 // Retiming factors from an audit block (minsnap_retime.hip): factors [B], counters [2] += {missions slowed down, missions with a
 // NaN peak}; apply != 0 divides the velocities of the missions over a limit by their factor.  The loop's extras (each may be NULL):
 // factors_total [B] *= the factor applied (NaN for a NaN mission), converged [B] = 1 where the factor is 1.0, else 0.

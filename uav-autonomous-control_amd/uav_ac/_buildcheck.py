@@ -192,6 +192,17 @@ def check_flown_separation_kernels():
     return _check_object("flown_separation.o", FLOWN_SEPARATION_KERNELS, "flown-separation", vgpr_limit=168)
 
 
+FLOWN_AUDIT_KERNELS = ("flown_audit_kernel", "flown_audit_merge_kernel")
+
+
+def check_flown_audit_kernels():
+    """The kernels of csrc/flown_audit.hip (the plan audit of a flight, from a state log): `_check_object`, and the streaming kernel,
+    which is launched for four waves per SIMD (`__launch_bounds__(256, 4)`: one workgroup per SIMD keeps 26 row loads per wavefront
+    in flight), must fit that (<= 128 vector registers; built: 82, the merge 44).  Returns {kernel: VGPRs}, None when the counts
+    cannot be read."""
+    return _check_object("flown_audit.o", FLOWN_AUDIT_KERNELS, "flown-audit", vgpr_limit=128)
+
+
 DELAY_KERNELS = ("delay_counts_kernel", "minsnap_delay_kernel")
 
 
@@ -475,6 +486,8 @@ def run_all(verbose: bool = False, write_stamp: bool = True) -> dict:
               lambda r: f"{len(r)} delay kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("flown_separation_kernels", check_flown_separation_kernels,
               lambda r: f"{len(r)} flown-separation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
+             ("flown_audit_kernels", check_flown_audit_kernels,
+              lambda r: f"{len(r)} flown-audit kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("layer_kernels", check_layer_kernels,
               lambda r: f"{len(r)} layer kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("layer_obs_kernels", check_layer_obs_kernels,

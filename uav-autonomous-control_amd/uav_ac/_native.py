@@ -24,6 +24,7 @@ SCORE_ROWS = 11                  # tracking scores of the scored rollouts (inclu
 AUDIT_ROWS, AUDIT_MAX_CUBOIDS = 8, 16       # plan audit (include/uavac.h uavac_minsnap_audit_dev)
 SEP_ROWS, SEP_MAX_SPLIT = 5, 64             # separation audits (include/uavac.h uavac_minsnap_separation_dev, uavac_flown_separation_dev)
 STATE_LOG_ROWS = 13                         # rows of the rollout's state log per tick (positions: 0-2)
+FLOWN_AUDIT_ROWS, FLOWN_AUDIT_MAX_SPLIT = 8, 64      # the plan audit of a flight (include/uavac.h uavac_flown_audit_dev)
 STAGGER_ROWS, STAGGER_MAX_STEPS, STAGGER_MAX_GROUP = 3, 1023, 256      # start delays (include/uavac.h uavac_minsnap_stagger_dev)
 LAYER_ROWS, LAYER_MAX_STEPS, LAYER_MAX_GROUP = 3, 1023, 256            # offset layers (include/uavac.h uavac_minsnap_layer_dev)
 LAYER_OBS_ROWS = 4                                                     # ... that keep out of cuboids (uavac_minsnap_layer_obs_dev)
@@ -104,6 +105,7 @@ _SIGNATURES = {
                                               C.c_double, C.c_int, _P, C.c_int, _P, _P]),
     "uavac_minsnap_shift_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int64, _P, _P]),
     "uavac_flown_separation_dev": (C.c_int,[_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, C.c_double, _P, _P]),
+    "uavac_flown_audit_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "uavac_minsnap_row_counts_v_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P]),
     "uavac_minsnap_row_counts_ragged_v_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P]),
     "uavac_minsnap_plan_v_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),

@@ -192,6 +192,28 @@ class SeparationAudit:
 
 
 @dataclass
+class FlightAudit:
+    """What the vehicles DID, per vehicle, from a rollout's state log (`Engine.flown_audit`, include/uavac.h uavac_flown_audit_dev):
+    device tensors.  A tick counts iff all 13 logged values are finite; the peaks (B,) f64 are maxima over those ticks (NaN when there
+    is none), and per cuboid (n, B) the ticks spent inside it, the first of them, and the closest approach with its tick.
+    `uav_ac.scoring.flight_feasibility` judges it against a vehicle's flight limits."""
+    ticks: "object"          # (B,) f64: the number of valid ticks
+    speed_xy: "object"       # peak sqrt(vx^2 + vy^2)
+    ascent: "object"         # peak climb rate max(-vz) (NED)
+    descent: "object"        # peak descent rate max(vz)
+    speed: "object"          # peak sqrt(vx^2 + vy^2 + vz^2)
+    bank_x: "object"         # peak |2 (q1 q3 + q0 q2)|: the rotation-matrix element R13 that max_tilt clips in the command
+    bank_y: "object"         # peak |2 (q2 q3 - q0 q1)|: R23
+    body_rate: "object"      # peak sqrt(p^2 + q^2 + r^2)
+    first_bad: "object"      # (B,) i32: the first tick with a value that is not finite (-1: none)
+    hit_ticks: "object"      # (n, B) i32: valid ticks inside cuboid c
+    first_hit: "object"      # (n, B) i32: the first of them (-1: none)
+    clearance: "object"      # (n, B) f64: closest approach to cuboid c (0 inside or on a face; NaN without a valid tick)
+    clearance_tick: "object"  # (n, B) i32: its tick (the first such tick; -1 without a valid tick)
+    block: "object" = None   # the [FLOWN_AUDIT_ROWS][B] block the eight rows above are views of
+
+
+@dataclass
 class StaggerResult:
     """Start delays that clear the separation audit (`Engine.stagger`, include/uavac.h uavac_minsnap_stagger_dev): device tensors, per
     mission.  `Engine.separation(plan, radius, groups, start_rows=result.start_rows)` confirms it; `uav_ac.scoring.stagger_ok` turns
@@ -825,13 +847,7 @@ class Engine:
         start = None if start_rows is None else self._start_rows(start_rows, B)
         offsets = torch.empty((B, 3), dtype=torch.float64, device=self.device)
         if obstacles is not None:
-            cub = self._dev(obstacles, torch.float64)
-            if cub.numel() % 6 or (cub.dim() == 2 and cub.shape[1] != 6):
-                raise ValueError(f"obstacles must be (n, 6): xmin xmax ymin ymax zmin zmax, got {tuple(cub.shape)}")
-            cub = cub.reshape(-1, 6).contiguous()
-            n = int(cub.shape[0])
-            if n > nat.AUDIT_MAX_CUBOIDS:
-                raise ValueError(f"{n} cuboids; at most {nat.AUDIT_MAX_CUBOIDS} per search")
+            cub, n = self._cuboids(obstacles, "search")
             block = torch.empty((nat.LAYER_OBS_ROWS, B), dtype=torch.int32, device=self.device)
             self._bind_stream()
             self.ctx.call("uavac_minsnap_layer_obs_dev", *self._plan_args(plan), _ptr(go), G, _ptr(start), float(radius), float(d[0]),
@@ -906,6 +922,34 @@ class Engine:
         flown = self.delay(self.shift(plan, lay.offsets), stag.start_rows)
         return DeconflictResult(flown, stag, lay, lay.steps >= 0)
 
+    def _cuboids(self, obstacles, per: str):
+        """(the cuboids as a contiguous (n, 6) float64 device tensor, n) of `obstacles` ((n, 6) array or tensor: xmin xmax ymin ymax zmin
+        zmax); another shape, or more than `AUDIT_MAX_CUBOIDS` of them, is a ValueError."""
+        cub = self._dev(obstacles, self._torch.float64)
+        if cub.numel() % 6 or (cub.dim() == 2 and cub.shape[1] != 6):
+            raise ValueError(f"obstacles must be (n, 6): xmin xmax ymin ymax zmin zmax, got {tuple(cub.shape)}")
+        cub = cub.reshape(-1, 6).contiguous()
+        n = int(cub.shape[0])
+        if n > nat.AUDIT_MAX_CUBOIDS:
+            raise ValueError(f"{n} cuboids; at most {nat.AUDIT_MAX_CUBOIDS} per {per}")
+        return cub, n
+
+    def _log_view(self, state_log):
+        """(K, B, pitch) of a state log the flown audits can read in place -- the (K, 13, B) view a logged rollout returns (at whatever
+        log pitch) or a dense caller tensor: float64 on the engine's device with stride(2) == 1 and stride(0) == 13 * stride(1) (the
+        pitch is stride(1)); anything else is a ValueError."""
+        torch = self._torch
+        if not isinstance(state_log, torch.Tensor) or state_log.dim() != 3 or state_log.dtype != torch.float64 \
+                or state_log.device != self.device:
+            raise ValueError("state_log must be a float64 tensor (K, 13, B) on the engine's device")
+        K, R, B = (int(v) for v in state_log.shape)
+        if R != nat.STATE_LOG_ROWS or K < 1 or B < 1:
+            raise ValueError(f"state_log must have shape (K >= 1, {nat.STATE_LOG_ROWS}, B >= 1), got {tuple(state_log.shape)}")
+        pitch = int(state_log.stride(1))
+        if state_log.stride(2) != 1 or pitch < B or (K > 1 and state_log.stride(0) != nat.STATE_LOG_ROWS * pitch):
+            raise ValueError("state_log must be laid out [K][13][pitch]: stride(2) == 1, stride(1) = pitch >= B, stride(0) == 13 * pitch")
+        return K, B, pitch
+
     def flown_separation(self, state_log, radius: float, groups=None) -> SeparationAudit:
         """The separation the fleet FLEW (`uavac_flown_separation_dev`): `Engine.separation` speaks about plans, this about the
         vehicles, which track them with an error -- from the positions in a rollout's state log, on the device, without pulling the
@@ -919,21 +963,40 @@ class Engine:
         whose log holds NaN is visible.  A vehicle with nobody to compare with reports +inf / -1 / -1 / 0 / -1 / 0.
         `uav_ac.scoring.separation_ok` applies unchanged.  Stream-ordered like the other _dev calls, no sync."""
         torch = self._torch
-        if not isinstance(state_log, torch.Tensor) or state_log.dim() != 3 or state_log.dtype != torch.float64 \
-                or state_log.device != self.device:
-            raise ValueError("state_log must be a float64 tensor (K, 13, B) on the engine's device")
-        K, R, B = (int(v) for v in state_log.shape)
-        if R != nat.STATE_LOG_ROWS or K < 1 or B < 1:
-            raise ValueError(f"state_log must have shape (K >= 1, {nat.STATE_LOG_ROWS}, B >= 1), got {tuple(state_log.shape)}")
-        pitch = int(state_log.stride(1))
-        if state_log.stride(2) != 1 or pitch < B or (K > 1 and state_log.stride(0) != nat.STATE_LOG_ROWS * pitch):
-            raise ValueError("state_log must be laid out [K][13][pitch]: stride(2) == 1, stride(1) = pitch >= B, stride(0) == 13 * pitch")
+        K, B, pitch = self._log_view(state_log)
         go, G = self._groups(groups, B)
         sep = torch.empty((B,), dtype=torch.float64, device=self.device)
         block = torch.empty((nat.SEP_ROWS, B), dtype=torch.int32, device=self.device)
         self._bind_stream()
         self.ctx.call("uavac_flown_separation_dev", _ptr(state_log), K, B, pitch, _ptr(go), G, float(radius), _ptr(sep), _ptr(block))
         return SeparationAudit(sep, *block.unbind(0), block)
+
+    def flown_audit(self, state_log, obstacles=None) -> FlightAudit:
+        """The plan audit of a FLIGHT (`uavac_flown_audit_dev`): `Engine.audit` says what a plan's rows would show, this what the
+        vehicles DID, which track the plan with an error -- one pass over a rollout's state log on the device, without pulling the log
+        to the host.  `state_log` as `Engine.flown_separation` takes it (the view a logged rollout returns, at whatever pitch, or a
+        dense tensor; anything else is a ValueError); `obstacles` as `Engine.audit` takes them ((n, 6), n <= 16).
+        -> FlightAudit, bit for bit what NumPy gives on the log (`uav_ac.scoring.audit_from_log`).  A tick counts iff its 13 logged
+        values are finite: `ticks` says how many did and `first_bad` which was the first that did not (-1: none); the peaks of
+        horizontal speed, climb, descent and speed, of the two rotation-matrix elements the control law clips its attitude command to
+        with max_tilt (`bank_x`, `bank_y`) and of the body rate are over those ticks, NaN when there is none.  Per cuboid:
+        `hit_ticks` -- how many valid ticks the vehicle spent inside it (the inclusive test of the rollout's `collided` bit) --,
+        `first_hit` (a tick, -1: none), and `clearance` with `clearance_tick`: the closest approach to the cuboid and when (0 exactly
+        where there are hits).  `uav_ac.scoring.flight_feasibility` turns it into verdicts.  Stream-ordered like the other _dev calls,
+        no sync."""
+        torch = self._torch
+        K, B, pitch = self._log_view(state_log)
+        kw = dict(device=self.device)
+        cub, n = (None, 0) if obstacles is None else self._cuboids(obstacles, "audit")
+        block = torch.empty((nat.FLOWN_AUDIT_ROWS, B), dtype=torch.float64, **kw)
+        first_bad = torch.empty((B,), dtype=torch.int32, **kw)
+        hit_ticks, first_hit, clearance_tick = (torch.empty((n, B), dtype=torch.int32, **kw) for _ in range(3))
+        clearance = torch.empty((n, B), dtype=torch.float64, **kw)
+        self._bind_stream()
+        per_cuboid = [_ptr(t) if n else None for t in (hit_ticks, first_hit, clearance, clearance_tick)]
+        self.ctx.call("uavac_flown_audit_dev", _ptr(state_log), K, B, pitch, _ptr(cub) if n else None, n, _ptr(block), _ptr(first_bad),
+                      *per_cuboid)
+        return FlightAudit(*block.unbind(0), first_bad, hit_ticks, first_hit, clearance, clearance_tick, block)
 
     DEFAULT_RETIME_MARGIN = 1e-3
 

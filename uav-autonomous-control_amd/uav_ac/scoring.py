@@ -22,6 +22,8 @@ rows, and `separation_from_log` is `separation_from_rows` for a FLIGHT: the rule
 the audit (`Engine.layer`, uavac_minsnap_layer_dev: offset layers by priority at fixed starts), `layer_obstacles_from_rows` the same
 search when it also refuses layers inside cuboids (uavac_minsnap_layer_obs_dev), `layer_ok` and `blocked_out` judge the result, and
 `shift_coeffs` states the transform that makes granted offsets part of the plan (`Engine.shift`, uavac_minsnap_shift_dev).
+`audit_from_log` is the plan audit of a FLIGHT: the rule of `Engine.flown_audit` (uavac_flown_audit_dev) on a rollout's state log --
+valid ticks, flown peaks, and per cuboid hits and closest approach --, and `flight_feasibility` judges it as `plan_feasibility` judges a plan.
 """
 from __future__ import annotations
 
@@ -365,6 +367,97 @@ def separation_from_log(log, radius, group_offsets=None):
             isep[SEP_FIRST_CONFLICT, b] = hit[0] if len(hit) else -1
             isep[SEP_COMPARED, b] = int(valid.any(axis=0).sum())
     return sep, isep
+
+
+def audit_from_log(log, cuboids=None):
+    """What the vehicles DID against the flight limits and the cuboids, recomputed from a state log -- the SPECIFICATION of
+    `uavac_flown_audit_dev` (csrc/flown_audit.hip), which is tested against it bit for bit.  NumPy on the host.
+    `log` (K, 13, B): x y z | q0 q1 q2 q3 | vx vy vz | p q r per tick, as `Fleet.rollout(K, state_log=True)` returns it (a view at
+    another pitch is fine: only columns 0 .. B - 1 exist here); `cuboids` (n, 6) xmin xmax ymin ymax zmin zmax, or None = none.
+
+    A tick of a vehicle is VALID iff its 13 values are finite; everything below is over a vehicle's valid ticks.  Products and sums are
+    separately rounded, a maximum is taken of the squares, one sqrt comes last.
+    -> dict of host arrays: `audit` (FLOWN_AUDIT_ROWS, B) f64 -- 0 the valid ticks, 1 sqrt(max(vx vx + vy vy)), 2 max(-vz), 3 max(vz),
+    4 sqrt(max((vx vx + vy vy) + vz vz)), 5 max |2 (q1 q3 + q0 q2)|, 6 max |2 (q2 q3 - q0 q1)|, 7 sqrt(max((p p + q q) + r r)) --,
+    `first_bad` (B,) i32 the first invalid tick (-1: none), and per cuboid (n, B): `hit_ticks` i32 the valid ticks inside it (inclusive
+    test), `first_hit` i32 the first of them (-1: none), `clearance` f64 = sqrt of the smallest d2 = (ex ex + ey ey) + ez ez with
+    ex = where(px < xmin, xmin - px, where(px > xmax, px - xmax, 0)), ..., and `clearance_tick` i32 the FIRST tick at which it is
+    attained.  A vehicle without a valid tick: 0 ticks, NaN peaks, first_bad 0, no hits, first_hit -1, clearance NaN, tick -1."""
+    log = _host(log)
+    if log.ndim != 3 or log.shape[0] < 1 or log.shape[1] != nat.STATE_LOG_ROWS or log.shape[2] < 1:
+        raise ValueError(f"log must have shape (K, {nat.STATE_LOG_ROWS}, B) with K >= 1 and B >= 1")
+    K, B = log.shape[0], log.shape[2]
+    cub = np.zeros((0, 6)) if cuboids is None else _host(cuboids)
+    if cub.size % 6 or (cub.ndim == 2 and cub.shape[1] != 6):
+        raise ValueError("cuboids must be (n, 6): xmin xmax ymin ymax zmin zmax")
+    cub = cub.reshape(-1, 6)
+    n = len(cub)
+    if n > nat.AUDIT_MAX_CUBOIDS:
+        raise ValueError(f"{n} cuboids; at most {nat.AUDIT_MAX_CUBOIDS} per audit")
+    valid = np.isfinite(log).all(axis=1)                                                   # (K, B)
+    px, py, pz, q0, q1, q2, q3, vx, vy, vz, p, q, r = (log[:, i, :] for i in range(nat.STATE_LOG_ROWS))
+    with np.errstate(invalid="ignore", over="ignore"):
+        vxy2 = vx * vx + vy * vy
+        per_tick = (vxy2, -vz, vz, vxy2 + vz * vz, np.abs(2.0 * (q1 * q3 + q0 * q2)), np.abs(2.0 * (q2 * q3 - q0 * q1)),
+                    (p * p + q * q) + r * r)
+    any_valid = valid.any(axis=0)
+    audit = np.full((nat.FLOWN_AUDIT_ROWS, B), np.nan)
+    audit[0] = valid.sum(axis=0)
+    for row, (values, root) in enumerate(zip(per_tick, (True, False, False, True, False, False, True)), start=1):
+        peak = np.where(valid, values, -np.inf).max(axis=0)
+        plus_zero = (valid & (values == 0.0) & ~np.signbit(values)).any(axis=0)            # the maximum of -0.0 and +0.0 is +0.0
+        peak = np.where((peak == 0.0) & plus_zero, 0.0, peak)
+        with np.errstate(invalid="ignore"):
+            audit[row] = np.where(any_valid, np.sqrt(peak) if root else peak, np.nan)
+    bad = ~valid
+    first_bad = np.where(bad.any(axis=0), bad.argmax(axis=0), -1).astype(np.int32)
+    hit_ticks = np.zeros((n, B), dtype=np.int32)
+    first_hit = np.full((n, B), -1, dtype=np.int32)
+    clearance = np.full((n, B), np.nan)
+    clearance_tick = np.full((n, B), -1, dtype=np.int32)
+    for c, (x0, x1, y0, y1, z0, z1) in enumerate(cub):
+        with np.errstate(invalid="ignore", over="ignore"):
+            inside = valid & (px >= x0) & (px <= x1) & (py >= y0) & (py <= y1) & (pz >= z0) & (pz <= z1)
+            ex = np.where(px < x0, x0 - px, np.where(px > x1, px - x1, 0.0))
+            ey = np.where(py < y0, y0 - py, np.where(py > y1, py - y1, 0.0))
+            ez = np.where(pz < z0, z0 - pz, np.where(pz > z1, pz - z1, 0.0))
+            d2 = (ex * ex + ey * ey) + ez * ez
+        hit_ticks[c] = inside.sum(axis=0)
+        first_hit[c] = np.where(inside.any(axis=0), inside.argmax(axis=0), -1)
+        for b in np.flatnonzero(any_valid):
+            ticks = np.flatnonzero(valid[:, b])
+            at = ticks[int(np.argmin(d2[ticks, b]))]                                       # the first minimum: the lowest tick
+            clearance[c, b], clearance_tick[c, b] = np.sqrt(d2[at, b]), at
+    return {"audit": audit, "first_bad": first_bad, "hit_ticks": hit_ticks, "first_hit": first_hit, "clearance": clearance,
+            "clearance_tick": clearance_tick}
+
+
+def flight_feasibility(audit, K, vehicle=None, slack: float = 0.0) -> dict:
+    """A flight audit (`Engine.flown_audit` -> FlightAudit, or anything with its fields; tensors on any device or arrays) of a log of
+    `K` ticks against the limits `plan_feasibility` judges a plan by -> dict of (B,) bool host arrays:
+    complete (every tick is valid: ticks == K), speed_ok (speed_xy <= max_speed_xy + slack), ascent_ok (ascent <= max_ascent + slack),
+    descent_ok (descent <= max_descent + slack), tilt_ok (bank_x and bank_y <= max_tilt + slack), clear (no valid tick inside any
+    cuboid; all true when none was given), flown_ok (complete, the three limits and clear).  `tilt_ok` is reported but is not part of
+    `flown_ok`: the control law clips the attitude COMMAND, not the attitude.  A NaN peak -- a vehicle without a valid tick -- fails
+    every test, `clear` included.  `vehicle`: a `Vehicle` (or anything with the four limits); None = `uavac_vehicle_default`."""
+    V = nat.Vehicle.default() if vehicle is None else vehicle
+    slack = float(slack)
+    ticks, speed_xy, ascent, descent = (_host(getattr(audit, f)).reshape(-1) for f in ("ticks", "speed_xy", "ascent", "descent"))
+    bank_x, bank_y = _host(audit.bank_x).reshape(-1), _host(audit.bank_y).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        complete = ticks == float(int(K))
+        speed_ok = speed_xy <= float(V.max_speed_xy) + slack
+        ascent_ok = ascent <= float(V.max_ascent) + slack
+        descent_ok = descent <= float(V.max_descent) + slack
+        tilt_ok = (bank_x <= float(V.max_tilt) + slack) & (bank_y <= float(V.max_tilt) + slack)
+    clear = ~(np.isnan(speed_xy) | np.isnan(ascent) | np.isnan(descent))
+    hits = getattr(audit, "hit_ticks", None)
+    if hits is not None:
+        hits = _host(hits, np.int64)
+        if hits.size:
+            clear = clear & (hits.reshape(-1, len(ticks)) == 0).all(axis=0)
+    return {"complete": complete, "speed_ok": speed_ok, "ascent_ok": ascent_ok, "descent_ok": descent_ok, "tilt_ok": tilt_ok,
+            "clear": clear, "flown_ok": complete & speed_ok & ascent_ok & descent_ok & clear}
 
 
 def delay_rows(rows, row_offsets, start_rows, first_yaw):
