@@ -172,7 +172,8 @@ int uavac_clock_probe_dev(uavac_ctx *ctx, int window_us, int64_t *stamps);
  * (same results).  "separation_split": 0 (default: sized from B and G) or 1 .. UAVAC_SEP_MAX_SPLIT = workgroups that share the partners
  * of one window of 64 missions in uavac_minsnap_separation_dev and uavac_flown_separation_dev (same results).  "flown_audit_split": 0
  * (default: sized from B and K) or 1 .. UAVAC_FLOWN_AUDIT_MAX_SPLIT = workgroups that share the ticks of one window of 64 vehicles in
- * uavac_flown_audit_dev (same results).
+ * uavac_flown_audit_dev (same results).  "conflict_slots": 0 (default: 64) or 1 .. 64 = j-tile slots per mission and discovery round
+ * of the conflict list (uavac_minsnap_conflict_offsets_dev, uavac_minsnap_conflicts_dev; same results, less scratch, more rounds).
  * Defaults from the environment (UAVAC_ROLLOUT_ALIGN, UAVAC_YAW_GROUP, UAVAC_SAMPLER_WAVES, UAVAC_SAMPLER_GROUP) at uavac_create.
  * ONE option is not a tuning knob but part of the log layout: "log_pitch" = P doubles per log row,
  * 0 (default) = B.  With P >= B the rollouts write state_log [K][13][P] and cmd_log [K][12][P]
@@ -347,6 +348,45 @@ int uavac_minsnap_audit_dev(uavac_ctx *ctx, const double *coeffs, const int32_t 
 int uavac_minsnap_separation_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                                  double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double *sep,
                                  int32_t *isep);
+
+/* CONFLICT LIST: the separation audit's conflict graph in CSR form -- not one partner and a count per mission, but every pair inside
+ * the radius, with when and how near (csrc/minsnap_conflicts.hip).  From coefficients and row counts alone: no row is written, nothing
+ * is read back, everything is enqueued on the ctx stream, scratch comes from the ctx arena (UAVAC_ENOMEM with a message when it cannot
+ * be had).  coeffs / seg_rows / seg_offsets / B / m / dt / group_offsets / G / start_rows / radius exactly as in
+ * uavac_minsnap_separation_dev, and CLOCK, GROUPS, EXCLUDED MISSIONS, ROUNDING and BAD INPUTS are the ones stated there.
+ * THE LIST.  Mission i lists every partner j of its group with d^2(i, j, k) < r^2 -- strictly -- at some clock row k in [0, H_g).  An
+ * excluded mission is nobody's partner and lists nothing.  The entries of mission i are [pair_offsets[i], pair_offsets[i + 1]), its
+ * partners in ascending batch index; pair_offsets [B + 1] i64 is the exclusive prefix sum of the audit's `conflicts`.  Per entry e:
+ *   pair_d [E] f64: the pair's minimum distance over [0, H_g): the minimum of the squares, then one correctly rounded sqrt
+ *   pair_i [UAVAC_CONF_ROWS][capacity] i32:  0 the partner j      1 the first clock row inside      2 the last clock row inside
+ *        3 the number of clock rows inside (less than last - first + 1 when the pair parts and meets again)      4 the clock row of the
+ *        pair's minimum, the lowest one on a tie
+ * Two calls, in the order counts -> offsets -> allocate -> fill that uavac_minsnap_delay_offsets_dev / uavac_minsnap_delay_dev have:
+ *   uavac_minsnap_conflict_offsets_dev  pair_offsets [B + 1].  The caller reads pair_offsets[B], the number of entries E, to size the
+ *                                       buffers.
+ *   uavac_minsnap_conflicts_dev         pair_d and pair_i for buffers of `capacity` entries (the row stride of pair_i).  It repeats the
+ *                                       discovery and relies on nothing the first call left behind.
+ * WHAT THE RESULT GUARANTEES, on the same inputs:  diff(pair_offsets) == isep[2] of the audit.  The minimum of row 1 over a mission's
+ * entries == isep[3].  For a mission with conflicts > 0 the audit's (sep, row, partner) is the lexicographic minimum of (pair_d, row 4,
+ * partner) over its entries.  d^2 is bit-symmetric -- (xi - xj)^2 == (xj - xi)^2 --, so the entries (i -> j) and (j -> i) agree in
+ * pair_d and in rows 1 .. 4.  Every output is bit for bit what NumPy gives on the sampled rows (uav_ac.scoring.conflicts_from_rows),
+ * whatever the launch shape (options "separation_split" and "conflict_slots") or what else is in the batch: a group listed alone gives
+ * the same records with the partner indices shifted.
+ * BOUNDS are part of the contract.  Mission i writes nothing outside its slice, and nothing is written at or beyond `capacity` (or below
+ * 0).  Entries of a slice that lie at or beyond `capacity` are dropped and raise sticky flag 2 (a buffer that is too small).  The plan
+ * may have changed between the two calls: a mission that now has more or fewer partners than its slice holds fills what fits in
+ * ascending partner order -- entries of the slice beyond its partners are left as they were -- and raises sticky flag 0.  capacity == 0
+ * with pair_d == pair_i == NULL is allowed (pair_offsets[B] == 0: nothing to fill).
+ * UAVAC_EINVAL before anything is enqueued: everything uavac_minsnap_separation_dev refuses (required pointers: coeffs, seg_rows,
+ * pair_offsets), capacity < 0, pair_d or pair_i NULL with capacity > 0.
+ * Cost: each call about one audit (pairs x horizon); the fill adds entries x horizon. */
+#define UAVAC_CONF_ROWS 5
+int uavac_minsnap_conflict_offsets_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B,
+                                       int m, double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius,
+                                       int64_t *pair_offsets);
+int uavac_minsnap_conflicts_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius,
+                                const int64_t *pair_offsets, int64_t capacity, double *pair_d, int32_t *pair_i);
 
 /* STAGGER: the call that acts on the separation audit's verdict -- prioritised deconfliction by start delay.  Within a group the
  * missions are taken in ascending batch index, which is the priority (the lowest index is never delayed), and each one is granted the

@@ -1,0 +1,161 @@
+"""The conflict list (`uavac_minsnap_conflict_offsets_dev` + `uavac_minsnap_conflicts_dev`, `Engine.conflicts`) against its yardstick,
+the separation audit on the same input (`Engine.separation`), and against the only route to the same answers that existed before it:
+sample the rows, build every mission's clamped positions on its group's clock, compare all pairs of a group in torch on the GPU and list
+the pairs that come inside the radius.  Eight segments (the bench's generator), velocity 3, dt 0.01, radius 0.5, no start rows, the
+audit's two shapes:
+
+    65 536 missions in groups of 64        4 096 missions in one group
+
+    conflicts_rate.py [OUT.jsonl] [rounds]
+
+The two routes must give the SAME answers (offsets and every record, bit for bit) before anything is timed.  hipEvents around each arm,
+warm-up first, the arms interleaved over rounds in one process; median, minimum and maximum per arm, one JSON line per arm with the
+device's identity, and one line per shape with the two RATIOS this tool is for -- both calls over the audit, the torch route over both
+calls -- each formed per round from that round's times, with the median and the spread over the rounds.  `Engine.conflicts` includes its
+one host read (the number of entries) between the two calls; the arm "offsets call only" shows the first call alone.
+
+The torch route, per call: `Engine.sample` into the plan's row buffer (allocated once, outside the timing); the gather of the clamped
+positions (G, n, H, 3) on the common horizon H (a group's own horizon H_g masks the rows past it); then, in chunks that keep a
+temporary under 1 GiB, d^2 = (dx dx + dy dy) + dz dz for all pairs of a group as (chunk, i, j, k), per pair `any`, the first and the
+last row inside, their number, and the first minimum over k; the listed pairs in (mission, partner) order.  Eager torch rounds every product and sum on its own, so the bits are the kernel's."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "uav-autonomous-control_amd")]
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from bench import missions  # noqa: E402
+from uav_ac.fleet import Engine  # noqa: E402
+
+M, VEL, DT, RADIUS = 8, 3.0, 0.01, 0.5
+SHAPES = ((65536, 64), (4096, 4096))                     # (missions, group size)
+TEMP_BYTES = 1 << 30
+
+
+def timed(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def rows_route(eng, plan, n, H, radius):
+    """-> (offsets (B + 1,), pair_d (E,), pair_i (5, E)) from sampled rows, groups of n consecutive missions, common horizon H."""
+    dev = plan.row_offsets.device
+    B, G = plan.B, plan.B // n
+    eng.sample(plan)
+    ro = plan.row_offsets
+    N = ro[1:] - ro[:-1]
+    k = torch.arange(H, device=dev)
+    idx = ro[:-1, None] + torch.minimum(k[None, :], (N - 1)[:, None])                     # start rows are 0: clamp(k, 0, N - 1)
+    P = plan.traj[:, 0:3][idx].reshape(G, n, H, 3)
+    Hg = N.reshape(G, n).max(dim=1).values                                               # every group's own horizon: rows past it do not count
+    r2 = radius * radius
+    per_i = n * H * 8
+    ci = max(1, min(n, TEMP_BYTES // per_i))
+    cg = max(1, min(G, TEMP_BYTES // (per_i * ci))) if ci == n else 1
+    eye = torch.eye(n, dtype=torch.bool, device=dev)
+    counts = torch.zeros((B,), dtype=torch.int64, device=dev)
+    found = []
+    for g0 in range(0, G, cg):
+        Pg = P[g0:g0 + cg]
+        for i0 in range(0, n, ci):
+            d2 = None
+            for c in range(3):
+                d = Pg[:, i0:i0 + ci, None, :, c] - Pg[:, None, :, :, c]                  # (cg, ci, n, H): own minus partner
+                d = d * d
+                d2 = d if d2 is None else d2 + d          # (dx dx + dy dy) + dz dz, left to right
+            inside = d2 < r2
+            inside &= ~eye[i0:i0 + ci][None, :, :, None]
+            inside &= (k[None, :] < Hg[g0:g0 + cg, None])[:, None, None, :]
+            g, i, j = inside.any(dim=3).nonzero(as_tuple=True)                            # ascending mission, then ascending partner
+            hit, dd = inside[g, i, j], d2[g, i, j]                                        # (e, H)
+            low = dd.argmin(dim=1)                                                        # the first minimum: the lowest row
+            own = (g0 + g) * n + i0 + i
+            counts += torch.bincount(own, minlength=B)
+            found.append((torch.sqrt(dd.gather(1, low[:, None])[:, 0]),
+                          torch.stack([(g0 + g) * n + j, hit.to(torch.int8).argmax(dim=1), H - 1 - hit.flip(1).to(torch.int8).argmax(dim=1),
+                                       hit.sum(dim=1), low]).to(torch.int32)))
+    offsets = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+    offsets[1:] = counts.cumsum(0)
+    return offsets, torch.cat([f[0] for f in found]), torch.cat([f[1] for f in found], dim=1)
+
+
+def spread(values):
+    return {"median": round(float(np.median(values)), 3), "min": round(float(min(values)), 3), "max": round(float(max(values)), 3)}
+
+
+def main():
+    out_path = sys.argv[1] if len(sys.argv) > 1 else None
+    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    eng = Engine("cuda:0")
+    box = eng.ctx.device_identity()
+    lines = []
+    for B, n in SHAPES:
+        wps = missions(B, M, 0, B)
+        plan = eng.plan(wps, VEL, DT)
+        groups = None if n == B else n
+        lengths = (plan.row_offsets[1:] - plan.row_offsets[:-1]).cpu().numpy().reshape(B // n, n)
+        H = int(lengths.max())
+        pair_rows = int((lengths.max(axis=1).astype(np.int64) * n * (n - 1)).sum())
+        offsets_only = torch.empty((B + 1,), dtype=torch.int64, device=eng.device)
+        go, G = eng._groups(groups, B)
+
+        def offsets_call():
+            eng._bind_stream()
+            eng.ctx.call("uavac_minsnap_conflict_offsets_dev", *eng._plan_args(plan), go.data_ptr() if go is not None else None, G, None,
+                         RADIUS, offsets_only.data_ptr())
+
+        # the two routes agree before anything is timed: offsets and every record, bit for bit; and the list agrees with the audit
+        cl = eng.conflicts(plan, RADIUS, groups=groups)
+        a = eng.separation(plan, RADIUS, groups=groups)
+        want_off, want_d, want_i = rows_route(eng, plan, n, H, RADIUS)
+        offsets_call()
+        torch.cuda.synchronize()
+        differ = {"offsets": int((cl.offsets != want_off).sum()), "offsets call": int((offsets_only != want_off).sum()),
+                  "entries": abs(cl.total - int(want_off[-1]))}
+        if not differ["entries"]:
+            differ.update({"pair_d": int((cl.min_distance != want_d).sum()), "pair_i": int((cl.block != want_i).sum())})
+        differ["counts against the audit"] = int((cl.offsets[1:] - cl.offsets[:-1] != a.conflicts).sum())
+        print(json.dumps({"B": B, "group": n, "entries": cl.total, "most partners of one mission": int(a.conflicts.max()),
+                          "outputs that differ between the two routes": differ}), flush=True)
+        assert not any(differ.values()), differ
+
+        arms = {"conflict list, both calls": (lambda: eng.conflicts(plan, RADIUS, groups=groups), 5),
+                "conflict list, offsets call only": (offsets_call, 5),
+                "separation audit": (lambda: eng.separation(plan, RADIUS, groups=groups), 5),
+                "rows route: sample + clamped positions + pairwise torch + list": (lambda: rows_route(eng, plan, n, H, RADIUS), 1)}
+        for fn, _ in arms.values():                      # warm-up of every arm
+            fn()
+        torch.cuda.synchronize()
+        times = {name: [] for name in arms}
+        for _ in range(rounds):
+            for name, (fn, reps) in arms.items():
+                times[name].append(timed(fn, reps))
+        for name, ts in times.items():
+            med = float(np.median(ts))
+            lines.append(json.dumps({"arm": name, "B": B, "group": n, "m": M, "horizon_rows": H, "pair_rows": pair_rows, "entries": cl.total,
+                                     "median_ms": round(med, 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4), "rounds": rounds,
+                                     "box": box}))
+            print(lines[-1], flush=True)
+        both, first, audit, torch_route = (np.array(times[name]) for name in arms)
+        lines.append(json.dumps({"ratios": True, "B": B, "group": n, "rounds": rounds, "entries": cl.total,
+                                 "both calls / separation audit": spread(both / audit),
+                                 "offsets call / separation audit": spread(first / audit),
+                                 "rows route / both calls": spread(torch_route / both), "box": box}))
+        print(lines[-1], flush=True)
+        del plan, cl, a, want_off, want_d, want_i
+        torch.cuda.empty_cache()
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

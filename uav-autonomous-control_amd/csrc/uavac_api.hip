@@ -398,6 +398,9 @@ int uavac_set_option(uavac_ctx *ctx, const char *name, int value) {
     } else if (n == "separation_split") {
         if (value < 0 || value > UAVAC_SEP_MAX_SPLIT) return uavac_fail(ctx, UAVAC_EINVAL, "separation_split is 0 (automatic) or 1 .. UAVAC_SEP_MAX_SPLIT");
         ctx->separation_split = value;
+    } else if (n == "conflict_slots") {
+        if (value < 0 || value > 64) return uavac_fail(ctx, UAVAC_EINVAL, "conflict_slots is 0 (automatic) or 1 .. 64");
+        ctx->conflict_slots = value;
     } else if (n == "flown_audit_split") {
         if (value < 0 || value > UAVAC_FLOWN_AUDIT_MAX_SPLIT) return uavac_fail(ctx, UAVAC_EINVAL, "flown_audit_split is 0 (automatic) or 1 .. UAVAC_FLOWN_AUDIT_MAX_SPLIT");
         ctx->flown_audit_split = value;
@@ -861,6 +864,25 @@ int uavac_minsnap_separation_dev(uavac_ctx *ctx, const double *coeffs, const int
     UAVAC_ENTER(ctx);
     if (int rc = check_pair_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, sep && isep)) return rc;
     return uavac_launch_separation(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, sep, isep);
+}
+
+int uavac_minsnap_conflict_offsets_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B,
+                                       int m, double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius,
+                                       int64_t *pair_offsets) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_pair_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, pair_offsets != nullptr)) return rc;
+    return uavac_launch_conflict_offsets(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, pair_offsets);
+}
+
+int uavac_minsnap_conflicts_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius,
+                                const int64_t *pair_offsets, int64_t capacity, double *pair_d, int32_t *pair_i) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_pair_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, pair_offsets != nullptr)) return rc;
+    if (capacity < 0) return uavac_fail(ctx, UAVAC_EINVAL, "capacity must be >= 0");
+    if (capacity > 0 && (!pair_d || !pair_i)) return uavac_fail(ctx, UAVAC_EINVAL, "pair_d and pair_i are required when capacity > 0");
+    return uavac_launch_conflicts(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, pair_offsets, capacity,
+                                  pair_d, pair_i);
 }
 
 int uavac_minsnap_stagger_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,

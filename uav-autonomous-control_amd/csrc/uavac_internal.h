@@ -35,6 +35,7 @@ struct uavac_ctx {
     int yaw_group = 8;               // tuning: chunks of the sampler's dense yaw column that leave together (1, 4, 8, 16)
     int audit_lanes = 16;            // tuning: lanes of a wavefront that walk one mission in the plan audit: 16 or 64 (minsnap_audit.hip; same results)
     int separation_split = 0;        // tuning: workgroups that share the j-tiles of one window of the separation audits (minsnap_separation.hip, flown_separation.hip; same results); 0 = sized from the batch
+    int conflict_slots = 0;          // tuning: j-tile slots per mission and round of the conflict list's discovery (minsnap_conflicts.hip; same results); 0 = 64
     int flown_audit_split = 0;       // tuning: workgroups that share the ticks of one window of the flown audit (flown_audit.hip; same results); 0 = sized from the batch
     int timeopt_chunk = 0;          // tuning: missions per chunk of the duration optimisation (minsnap_timeopt.hip; same results); 0 = sized from UAVAC_TIMEOPT_SCRATCH_BYTES
     int rollout_align = 1;          // tuning: launch the 2-wave aligner kernel before a logged launch of shape 1
@@ -229,6 +230,14 @@ int uavac_launch_audit(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_
 // the fleet's audit against itself (minsnap_separation.hip): sep [B], isep [UAVAC_SEP_ROWS][B]; scratch from the ctx arena
 int uavac_launch_separation(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
                             const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double *sep, int32_t *isep);
+// the audit's conflict graph in CSR form (minsnap_conflicts.hip): pair_offsets [B + 1], then pair_d [capacity] and pair_i
+// [UAVAC_CONF_ROWS][capacity]; scratch from the ctx arena
+int uavac_launch_conflict_offsets(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                  double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius,
+                                  int64_t *pair_offsets);
+int uavac_launch_conflicts(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
+                           const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, const int64_t *pair_offsets,
+                           int64_t capacity, double *pair_d, int32_t *pair_i);
 // the call that acts on it (minsnap_stagger.hip): start delays by priority, istag [UAVAC_STAGGER_ROWS][B]; scratch from the ctx arena
 int uavac_launch_stagger(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
                          const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, int step, int max_steps,

@@ -171,6 +171,18 @@ def check_separation_kernels():
     return _check_object("minsnap_separation.o", SEPARATION_KERNELS, "separation", vgpr_limit=168)
 
 
+CONFLICT_KERNELS = ("conflict_prepass_kernel", "conflict_discover_kernel", "conflict_count_kernel", "conflict_list_kernel",
+                    "conflict_measure_kernel")
+
+
+def check_conflict_kernels():
+    """The kernels of csrc/minsnap_conflicts.hip (the separation audit's conflict list): `_check_object` -- the coefficient sets of the
+    discovery and of the measure are indexed by constants only -- with the register limit of each from the LDS it ends up with: the
+    discovery and the measure keep the audit's 48 KB tile, hence three workgroups per CU and <= 168; the pre-pass, the counts (32 B for
+    its scan) and the list run eight waves per SIMD and <= 64.  Returns {kernel: VGPRs}, None when the counts cannot be read."""
+    return _check_object("minsnap_conflicts.o", CONFLICT_KERNELS, "conflict-list")
+
+
 STAGGER_KERNELS = ("stagger_prepass_kernel", "minsnap_stagger_kernel")
 
 
@@ -480,6 +492,8 @@ def run_all(verbose: bool = False, write_stamp: bool = True) -> dict:
               lambda r: f"{len(r)} time-optimisation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("separation_kernels", check_separation_kernels,
               lambda r: f"{len(r)} separation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
+             ("conflict_kernels", check_conflict_kernels,
+              lambda r: f"{len(r)} conflict-list kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("stagger_kernels", check_stagger_kernels,
               lambda r: f"{len(r)} stagger kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("delay_kernels", check_delay_kernels,

@@ -192,6 +192,23 @@ class SeparationAudit:
 
 
 @dataclass
+class ConflictList:
+    """The separation audit's conflict graph in CSR form (`Engine.conflicts`, include/uavac.h uavac_minsnap_conflicts_dev): device
+    tensors.  Mission i lists its partners -- every mission of its group that comes inside the radius at some row of the shared clock
+    -- in the entries [offsets[i], offsets[i + 1]), in ascending batch index; a pair shows in both directions, with the same record.
+    `uav_ac.scoring.conflict_pairs` gives the unique pairs on the host."""
+    offsets: "object"        # (B + 1,) i64: exclusive prefix sum of the audit's `conflicts`
+    partner: "object"        # (E,) i32: batch index of the partner
+    first_row: "object"      # (E,) i32: first clock row at which the pair is inside the radius
+    last_row: "object"       # (E,) i32: last such row
+    rows_inside: "object"    # (E,) i32: how many rows (less than last - first + 1 when the pair parts and meets again)
+    min_row: "object"        # (E,) i32: clock row of the pair's closest approach, the lowest one on a tie
+    min_distance: "object"   # (E,) f64: the pair's closest approach over the group's clock
+    total: int = 0           # E, the number of entries (twice the number of pairs)
+    block: "object" = None   # the [CONF_ROWS][E] i32 block the five rows above are views of
+
+
+@dataclass
 class FlightAudit:
     """What the vehicles DID, per vehicle, from a rollout's state log (`Engine.flown_audit`, include/uavac.h uavac_flown_audit_dev):
     device tensors.  A tick counts iff all 13 logged values are finite; the peaks (B,) f64 are maxima over those ticks (NaN when there
@@ -724,15 +741,43 @@ class Engine:
         (B,) i32: the clock row at which each mission starts (None: all 0); before it a mission waits on its first row, after its end
         it holds its last.  Never reads `plan.traj`; stream-ordered like the other _dev calls, no sync."""
         torch = self._torch
+        B, held, pair_args = self._pair_args(plan, radius, groups, start_rows)      # (`held` keeps the pointers' tensors alive)
+        sep = torch.empty((B,), dtype=torch.float64, device=self.device)
+        block = torch.empty((nat.SEP_ROWS, B), dtype=torch.int32, device=self.device)
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_separation_dev", *pair_args, _ptr(sep), _ptr(block))
+        return SeparationAudit(sep, *block.unbind(0), block)
+
+    def _pair_args(self, plan, radius, groups, start_rows):
+        """What `separation` and `conflicts` take, checked once -> (B, the tensors behind the pointers, the arguments of the C call up
+        to and with the radius)."""
         plan = self._coeff_plan(plan)
         B = int(plan.B)
         go, G = self._groups(groups, B)
         start = None if start_rows is None else self._start_rows(start_rows, B)
-        sep = torch.empty((B,), dtype=torch.float64, device=self.device)
-        block = torch.empty((nat.SEP_ROWS, B), dtype=torch.int32, device=self.device)
+        return B, (plan, go, start), (*self._plan_args(plan), _ptr(go), G, _ptr(start), float(radius))
+
+    def conflicts(self, plan, radius: float, groups=None, start_rows=None) -> ConflictList:
+        """Every pair of the plan's missions that `Engine.separation` counts as a conflict, with when and how near
+        (`uavac_minsnap_conflict_offsets_dev`, `uavac_minsnap_conflicts_dev`): mission i lists each mission of its group that comes
+        inside `radius` at some row of the shared clock, in ascending batch index, with the first and the last row inside, the number
+        of rows inside, and the pair's closest approach and its row -- computed from coefficients and row counts, bit for bit what
+        NumPy gives on the sampled rows (`uav_ac.scoring.conflicts_from_rows`).  `plan`, `groups` and `start_rows` as
+        `Engine.separation` takes them, and on the same inputs diff(offsets) is its `conflicts`, the least `first_row` of a mission
+        its `first_conflict`, and its (min_distance, row, partner) the least (min_distance, min_row, partner) of the mission's
+        entries.  The two directions of a pair carry the same record (`uav_ac.scoring.conflict_pairs`).  Never reads `plan.traj`.
+        ONE small host read: the number of entries, to size the result; without entries the second launch is skipped."""
+        torch = self._torch
+        B, held, pair_args = self._pair_args(plan, radius, groups, start_rows)      # (`held` keeps the pointers' tensors alive)
+        offsets = torch.empty((B + 1,), dtype=torch.int64, device=self.device)
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_separation_dev", *self._plan_args(plan), _ptr(go), G, _ptr(start), float(radius), _ptr(sep), _ptr(block))
-        return SeparationAudit(sep, *block.unbind(0), block)
+        self.ctx.call("uavac_minsnap_conflict_offsets_dev", *pair_args, _ptr(offsets))
+        E = int(offsets[B].item())                                       # the one sync
+        dist = torch.empty((E,), dtype=torch.float64, device=self.device)
+        block = torch.empty((nat.CONF_ROWS, E), dtype=torch.int32, device=self.device)
+        if E:
+            self.ctx.call("uavac_minsnap_conflicts_dev", *pair_args, _ptr(offsets), E, _ptr(dist), _ptr(block))
+        return ConflictList(offsets, *block.unbind(0), dist, E, block)
 
     def stagger(self, plan, radius: float, groups=None, start_rows=None, step: int = 1, max_steps: int = 255) -> StaggerResult:
         """Prioritised deconfliction by start delay (`uavac_minsnap_stagger_dev`): the call that acts on `Engine.separation`'s

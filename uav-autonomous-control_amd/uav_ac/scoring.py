@@ -14,7 +14,9 @@ uavac_minsnap_retime_factors_dev), NumPy on the host, bit for bit.
 
 `separation_from_rows` is the same kind of statement for the fleet's audit against itself (`Engine.separation`, include/uavac.h
 uavac_minsnap_separation_dev): closest approach, partner, clock row, conflicts inside a radius, recomputed from sampled rows in NumPy,
-bit for bit; `separation_ok` judges a separation audit.  `stagger_from_rows` states the rule of the call that acts on that audit
+bit for bit; `separation_ok` judges a separation audit.  `conflicts_from_rows` states the audit's conflict LIST the same way
+(`Engine.conflicts`, uavac_minsnap_conflicts_dev: every pair inside the radius, from when to when and how near), and `conflict_pairs`
+turns such a list into its unique pairs.  `stagger_from_rows` states the rule of the call that acts on that audit
 (`Engine.stagger`, uavac_minsnap_stagger_dev: start delays by priority) on sampled rows, and `stagger_ok` judges its result.
 `delay_rows` states on sampled rows what the delay transform (`Engine.delay`, uavac_minsnap_delay_dev) makes of a plan and its start
 rows, and `separation_from_log` is `separation_from_rows` for a FLIGHT: the rule of `Engine.flown_separation`
@@ -296,6 +298,73 @@ def separation_from_rows(rows, row_offsets, radius, group_offsets=None, start_ro
             hit_rows = np.flatnonzero(inside.any(axis=1))
             isep[SEP_FIRST_CONFLICT, b] = hit_rows[0] if len(hit_rows) else -1
     return sep, isep
+
+
+def conflicts_from_rows(rows, row_offsets, radius, group_offsets=None, start_rows=None):
+    """The conflict list recomputed from SAMPLED rows -- the SPECIFICATION of `uavac_minsnap_conflict_offsets_dev` and
+    `uavac_minsnap_conflicts_dev` (csrc/minsnap_conflicts.hip), which are tested against it bit for bit.  NumPy on the host; inputs,
+    clock, groups, excluded missions and rounding exactly as in `separation_from_rows`.
+    Mission i lists every included mission j of its group with d^2(i, j, k) < r^2, strictly, at some clock row k below the group's
+    horizon, in ascending j; an excluded mission lists nothing and is listed by nobody.
+    -> (offsets (B + 1,) i64, pair_d (E,) f64, pair_i (CONF_ROWS, E) i32): the entries of mission i are [offsets[i], offsets[i + 1]);
+    per entry the pair's minimum distance over the clock (the minimum of the squares, one sqrt), and the partner, the first and the
+    last clock row inside, the number of rows inside, the clock row of the minimum (the lowest one on a tie)."""
+    rows = _host(rows)
+    ro = _host_i64(row_offsets)
+    B = len(ro) - 1
+    radius = _radius(radius)
+    go = _group_offsets(group_offsets, B)
+    S = _start_rows(start_rows, B, upper=None)
+    r2 = radius * radius
+    N = np.diff(ro)
+    pos = [rows[ro[b]:ro[b + 1], 0:3] for b in range(B)]
+    included = _included(pos.__getitem__, N, longest=None)
+    per_mission = [[] for _ in range(B)]                                                  # (partner, first, last, inside, row of the minimum, d^2)
+    for g in range(len(go) - 1):
+        members = [b for b in range(int(go[g]), int(go[g + 1])) if included[b]]
+        if len(members) < 2:
+            continue
+        k = np.arange(int(max(S[b] + N[b] for b in members)))
+        P = np.stack([_at(pos[b], k, S[b]) for b in members])                            # (n, H, 3): where everybody stands at clock row k
+        for a, i in enumerate(members):
+            dx, dy, dz = (P[a, :, c][None, :] - P[:, :, c] for c in range(3))            # (n, H): partners first, rows ascending
+            d2 = (dx * dx + dy * dy) + dz * dz
+            inside = d2 < r2
+            inside[a] = False                                                             # nobody is their own partner
+            for c in np.flatnonzero(inside.any(axis=1)):
+                hit = np.flatnonzero(inside[c])
+                low = int(np.argmin(d2[c]))                                               # the first minimum: the lowest row
+                per_mission[i].append((members[c], hit[0], hit[-1], len(hit), low, d2[c, low]))
+    offsets = np.concatenate([[0], np.cumsum([len(p) for p in per_mission])]).astype(np.int64)
+    flat = [e for p in per_mission for e in p]
+    pair_i = np.array([e[:5] for e in flat], dtype=np.int32).reshape(-1, nat.CONF_ROWS).T.copy()
+    pair_d = np.sqrt(np.array([e[5] for e in flat], dtype=np.float64))
+    return offsets, pair_d, pair_i
+
+
+def conflict_pairs(cl) -> dict:
+    """A conflict list (`Engine.conflicts` -> ConflictList, or anything with its fields; tensors on any device or arrays) -> the unique
+    pairs i < j on the host, in ascending (i, j): dict of (n,) arrays `i`, `j`, `first_row`, `last_row`, `rows_inside`, `min_row`,
+    `min_distance`.  The distance is bit-symmetric, so both directions of a pair must be listed and carry the same record: a list
+    in which they do not is a ValueError."""
+    off = _host_i64(cl.offsets)
+    owner = np.repeat(np.arange(len(off) - 1, dtype=np.int64), np.diff(off))
+    partner = _host_i64(cl.partner)
+    fields = {"first_row": _host_i64(cl.first_row), "last_row": _host_i64(cl.last_row), "rows_inside": _host_i64(cl.rows_inside),
+              "min_row": _host_i64(cl.min_row), "min_distance": _host(cl.min_distance).reshape(-1)}
+    if len(partner) != len(owner) or any(len(v) != len(owner) for v in fields.values()):
+        raise ValueError("a conflict list holds offsets[-1] entries in every field")
+    fwd, bwd = np.flatnonzero(owner < partner), np.flatnonzero(owner > partner)
+    if len(fwd) + len(bwd) != len(owner):
+        raise ValueError("a mission lists itself")
+    fwd = fwd[np.lexsort((partner[fwd], owner[fwd]))]
+    bwd = bwd[np.lexsort((owner[bwd], partner[bwd]))]
+    if len(fwd) != len(bwd) or not (np.array_equal(owner[fwd], partner[bwd]) and np.array_equal(partner[fwd], owner[bwd])):
+        raise ValueError("a pair is listed in one direction only")
+    for name, v in fields.items():
+        if not np.array_equal(v[fwd], v[bwd]):
+            raise ValueError(f"the two directions of a pair disagree in {name}")
+    return {"i": owner[fwd], "j": partner[fwd], **{name: v[fwd] for name, v in fields.items()}}
 
 
 def separation_ok(sep, group_sizes=None) -> dict:
