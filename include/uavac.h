@@ -545,6 +545,54 @@ int uavac_minsnap_layer_obs_dev(uavac_ctx *ctx, const double *coeffs, const int3
 int uavac_minsnap_shift_dev(uavac_ctx *ctx, const double *coeffs, const int64_t *seg_offsets, int B, int m, int64_t total_segments,
                             const double *offsets, double *out_coeffs);
 
+/* TAKE: a gather of missions -- how missions of a plan are selected, reordered and merged on the device (csrc/minsnap_take.hip).  The
+ * input is a plan as uavac_minsnap_delay_dev takes it (coeffs / times / seg_rows / seg_offsets / B / m: seg_offsets NULL = uniform,
+ * otherwise ragged with segment counts clamped to 1 .. m; times may be NULL), optionally first_yaw [B] f64, and index [n] i32 (device,
+ * required): duplicates and any order are allowed, n may exceed B.  The output is a RAGGED plan of n missions: mission i of the result
+ * is mission index[i] of the input, every bit of it -- its m_index[i] segments' 24 coefficients, row counts and (iff times != NULL)
+ * durations, and (iff first_yaw != NULL) its first heading.  Nothing is computed, so the sampled rows of output mission i are the rows
+ * of input mission index[i] bit for bit, and so is everything that is computed per mission (uavac_minsnap_audit_dev, a plan-fed
+ * rollout's lane); what is computed per group (uavac_minsnap_separation_dev, stagger, layer) of a taken group is the group's with the
+ * partners renumbered, whatever else was in the batch.  uav_ac.scoring.take_parts is the construction in NumPy.
+ * Two calls, in the order offsets -> allocate -> fill that uavac_minsnap_delay_dev has; everything is enqueued on the ctx stream and
+ * the library reads nothing back:
+ *   uavac_minsnap_take_offsets_dev  out_seg_offsets [n+1] i64 = exclusive prefix sum of m_index[i].  The caller reads out_seg_offsets[n],
+ *                                   the result's segment total (at most n * m), to size the buffers.
+ *   uavac_minsnap_take_dev          out_coeffs [S'][8][3], out_seg_rows [S'], -- iff times != NULL -- out_times [S'], S' = that total, and
+ *                                   -- iff first_yaw != NULL -- out_first_yaw [n].
+ * Row offsets of the result: uavac_minsnap_row_offsets_ragged_dev(out_seg_rows, out_seg_offsets, n, m).  The outputs must not overlap
+ * the inputs.
+ * BAD INPUTS.  An index[i] outside 0 .. B - 1 cannot be refused without a read-back: it is clamped into that range and raises sticky
+ * flag 0 (uavac_take_flags), like a bad start row.  UAVAC_EINVAL before anything is enqueued: no context, a NULL required pointer (index
+ * and out_seg_offsets; for the second call also coeffs, seg_rows, out_coeffs, out_seg_rows), B < 1, n < 1, m outside 1 ..
+ * UAVAC_MAX_SEGMENTS, times == NULL xor out_times == NULL, first_yaw == NULL xor out_first_yaw == NULL.
+ * Cost: one read and one write of what is taken -- 200 bytes per segment with durations -- by one thread per 16 bytes of coefficients. */
+int uavac_minsnap_take_offsets_dev(uavac_ctx *ctx, const int64_t *seg_offsets, int B, int m, const int32_t *index, int n,
+                                   int64_t *out_seg_offsets);
+int uavac_minsnap_take_dev(uavac_ctx *ctx, const double *coeffs, const double *times, const int32_t *seg_rows, const int64_t *seg_offsets,
+                           int B, int m, const double *first_yaw, const int32_t *index, int n, const int64_t *out_seg_offsets,
+                           double *out_coeffs, double *out_times, int32_t *out_seg_rows, double *out_first_yaw);
+
+/* ORDER: priorities into a within-group order -- what a priority other than the batch index needs.  The searches
+ * (uavac_minsnap_stagger_dev, uavac_minsnap_layer_dev, uavac_minsnap_layer_obs_dev) take the missions of a group in ascending batch
+ * index; with this call the plan is reordered within its groups (uavac_minsnap_take_dev with index = order), the search runs on it
+ * unchanged, and its per-mission answers are gathered back with rank.  priority [B] f64 (device); group_offsets [G + 1] i64 / G as in
+ * uavac_minsnap_separation_dev, clamped to the batch in the same way (NULL: one group of all B); order, rank [B] i32 (device).
+ * THE RULE.  Within each group the missions are sorted by the total order "a before b" iff  p_a is a number and p_b is NaN,  or
+ * p_a < p_b,  or  (p_a == p_b or both are NaN) and a < b.  So a LOWER priority goes first, -0.0 ties with +0.0, NaN comes after +inf,
+ * and ties go to the lower batch index: priority[b] = b is the identity.
+ * OUTPUTS.  order[g0 + k] = the mission in slot k of its group [g0, g1); rank is the inverse permutation, rank[order[s]] = s.  A mission
+ * that no group holds keeps its place: order[b] = rank[b] = b.  With offsets that follow the contract (ascending from 0 to B) order is
+ * a permutation of 0 .. B - 1 that maps every group onto itself, so the same group_offsets describe the reordered batch.  No write
+ * leaves [B], whatever the offsets hold; with offsets that do not ascend the contents of order and rank are unspecified.
+ * Every comparison is exact, so there is no rounding and the result does not depend on the launch shape: it is what NumPy gives
+ * (uav_ac.scoring.priority_order).  Any group size is accepted -- the limits of the searches are theirs.
+ * Cost: a counting rank, a mission's slot is the number of missions of its group that come before it: the sum of g^2 comparisons over
+ * the groups, one thread per mission, the priorities through LDS tiles.  One kernel on the ctx stream; nothing is read back.
+ * UAVAC_EINVAL before anything is enqueued: no context, a NULL priority / order / rank, B < 1, G < 1 when group_offsets != NULL. */
+int uavac_fleet_order_dev(uavac_ctx *ctx, const double *priority, const int64_t *group_offsets, int G, int B, int32_t *order,
+                          int32_t *rank);
+
 /* FLOWN SEPARATION: the separation audit of a FLIGHT.  uavac_minsnap_separation_dev speaks about plans; the vehicles track them with an
  * error.  This call reads the positions in a rollout's state log and reports, in the same terms and with the same exactness, how close
  * the vehicles came (csrc/flown_separation.hip): nothing is read back, everything is enqueued on the ctx stream, scratch from the arena.

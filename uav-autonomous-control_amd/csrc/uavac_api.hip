@@ -969,6 +969,40 @@ int uavac_minsnap_shift_dev(uavac_ctx *ctx, const double *coeffs, const int64_t 
     return uavac_launch_shift(ctx, coeffs, seg_offsets, B, m, total_segments, offsets, out_coeffs);
 }
 
+int uavac_minsnap_take_offsets_dev(uavac_ctx *ctx, const int64_t *seg_offsets, int B, int m, const int32_t *index, int n,
+                                   int64_t *out_seg_offsets) {
+    UAVAC_ENTER(ctx);
+    if (!index || !out_seg_offsets) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
+    if (n < 1) return uavac_fail(ctx, UAVAC_EINVAL, "n must be >= 1");
+    if (m < 1 || m > UAVAC_MAX_SEGMENTS) return uavac_fail(ctx, UAVAC_EINVAL, "m must be in [1, UAVAC_MAX_SEGMENTS]");
+    return uavac_launch_take_offsets(ctx, seg_offsets, B, m, index, n, out_seg_offsets);
+}
+
+int uavac_minsnap_take_dev(uavac_ctx *ctx, const double *coeffs, const double *times, const int32_t *seg_rows, const int64_t *seg_offsets,
+                           int B, int m, const double *first_yaw, const int32_t *index, int n, const int64_t *out_seg_offsets,
+                           double *out_coeffs, double *out_times, int32_t *out_seg_rows, double *out_first_yaw) {
+    UAVAC_ENTER(ctx);
+    if (!coeffs || !seg_rows || !index || !out_seg_offsets || !out_coeffs || !out_seg_rows)
+        return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
+    if (n < 1) return uavac_fail(ctx, UAVAC_EINVAL, "n must be >= 1");
+    if (m < 1 || m > UAVAC_MAX_SEGMENTS) return uavac_fail(ctx, UAVAC_EINVAL, "m must be in [1, UAVAC_MAX_SEGMENTS]");
+    if (!times != !out_times) return uavac_fail(ctx, UAVAC_EINVAL, "times and out_times go together: both or none");
+    if (!first_yaw != !out_first_yaw) return uavac_fail(ctx, UAVAC_EINVAL, "first_yaw and out_first_yaw go together: both or none");
+    return uavac_launch_take(ctx, coeffs, times, seg_rows, seg_offsets, B, m, first_yaw, index, n, out_seg_offsets, out_coeffs, out_times,
+                             out_seg_rows, out_first_yaw);
+}
+
+int uavac_fleet_order_dev(uavac_ctx *ctx, const double *priority, const int64_t *group_offsets, int G, int B, int32_t *order,
+                          int32_t *rank) {
+    UAVAC_ENTER(ctx);
+    if (!priority || !order || !rank) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
+    if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
+    return uavac_launch_fleet_order(ctx, priority, group_offsets, G, B, order, rank);
+}
+
 int uavac_flown_separation_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
                                double radius, double *sep, int32_t *isep) {
     UAVAC_ENTER(ctx);

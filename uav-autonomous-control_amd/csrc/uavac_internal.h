@@ -307,3 +307,13 @@ struct PlanRef {
 int uavac_launch_rollout(uavac_ctx *ctx, const VehK &V, const double *traj, const int64_t *row_offsets, double *state,
                          int32_t *istate, int B, int K, double *state_log, double *cmd_log, const double *aabbs,
                          int n_obs, const PlanRef *plan = nullptr, double *score = nullptr);
+// missions of a plan selected, reordered and merged (minsnap_take.hip): out_seg_offsets [n+1] = prefix sum of the segment counts of
+// the missions index[i] (clamped into 0 .. B - 1, flag 0); then their coefficients, durations (times / out_times may both be NULL), row
+// counts and first headings (first_yaw / out_first_yaw may both be NULL), output mission i = input mission index[i]
+int uavac_launch_take_offsets(uavac_ctx *ctx, const int64_t *seg_offsets, int B, int m, const int32_t *index, int n, int64_t *out_seg_offsets);
+int uavac_launch_take(uavac_ctx *ctx, const double *coeffs, const double *times, const int32_t *seg_rows, const int64_t *seg_offsets, int B,
+                      int m, const double *first_yaw, const int32_t *index, int n, const int64_t *out_seg_offsets, double *out_coeffs,
+                      double *out_times, int32_t *out_seg_rows, double *out_first_yaw);
+// priorities into a within-group order (minsnap_take.hip): order [B] = the mission in every slot, rank [B] its inverse
+int uavac_launch_fleet_order(uavac_ctx *ctx, const double *priority, const int64_t *group_offsets, int G, int B, int32_t *order,
+                             int32_t *rank);

@@ -225,6 +225,17 @@ def check_delay_kernels():
     return _check_object("minsnap_delay.o", DELAY_KERNELS, "delay", vgpr_limit=64)
 
 
+TAKE_KERNELS = ("take_counts_kernel", "minsnap_take_kernel", "fleet_order_kernel")
+
+
+def check_take_kernels():
+    """The kernels of csrc/minsnap_take.hip (missions of a plan selected and reordered, priorities into a within-group order):
+    `_check_object`; the first two are plain copies like the delay kernels, the third counts over 2 KB LDS tiles of keys, and all run at
+    least eight waves per SIMD (<= 64 vector registers; built: 24, 28 and 18).  Returns {kernel: VGPRs}, None when the counts cannot
+    be read."""
+    return _check_object("minsnap_take.o", TAKE_KERNELS, "take", vgpr_limit=64)
+
+
 LAYER_KERNELS = ("layer_prepass_kernel", "minsnap_layer_kernel", "minsnap_shift_kernel")
 
 
@@ -498,6 +509,8 @@ def run_all(verbose: bool = False, write_stamp: bool = True) -> dict:
               lambda r: f"{len(r)} stagger kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("delay_kernels", check_delay_kernels,
               lambda r: f"{len(r)} delay kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
+             ("take_kernels", check_take_kernels,
+              lambda r: f"{len(r)} take kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("flown_separation_kernels", check_flown_separation_kernels,
               lambda r: f"{len(r)} flown-separation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("flown_audit_kernels", check_flown_audit_kernels,

@@ -108,6 +108,9 @@ _SIGNATURES = {
     "uavac_minsnap_layer_obs_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, C.c_double, C.c_double, C.c_double,
                                               C.c_double, C.c_int, _P, C.c_int, _P, _P]),
     "uavac_minsnap_shift_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int64, _P, _P]),
+    "uavac_minsnap_take_offsets_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "uavac_minsnap_take_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "uavac_fleet_order_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "uavac_flown_separation_dev": (C.c_int,[_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, C.c_double, _P, _P]),
     "uavac_flown_audit_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "uavac_minsnap_row_counts_v_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P]),

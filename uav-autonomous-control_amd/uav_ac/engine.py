@@ -779,7 +779,8 @@ class Engine:
             self.ctx.call("uavac_minsnap_conflicts_dev", *pair_args, _ptr(offsets), E, _ptr(dist), _ptr(block))
         return ConflictList(offsets, *block.unbind(0), dist, E, block)
 
-    def stagger(self, plan, radius: float, groups=None, start_rows=None, step: int = 1, max_steps: int = 255) -> StaggerResult:
+    def stagger(self, plan, radius: float, groups=None, start_rows=None, step: int = 1, max_steps: int = 255,
+                priority=None) -> StaggerResult:
         """Prioritised deconfliction by start delay (`uavac_minsnap_stagger_dev`): the call that acts on `Engine.separation`'s
         verdict.  Within a group the missions are taken in ascending batch index -- the lowest index is never delayed --, and each
         gets the smallest start `start_rows[b] + q * step`, q = 0 .. `max_steps`, that keeps it outside `radius` of every mission
@@ -791,7 +792,17 @@ class Engine:
         tensor go through, the missions of such a group report steps = -2 and sticky flag 0 is raised (`take_flags`).  Never reads
         `plan.traj`; stream-ordered, no sync.  Confirm with `Engine.separation(plan, radius, groups, start_rows=result.start_rows)`:
         no pair of resolved missions is inside the radius.  To fly the granted starts make them part of the plan:
-        `Engine.delay(plan, result.start_rows)` (the rollout's cursor has no start row and needs none)."""
+        `Engine.delay(plan, result.start_rows)` (the rollout's cursor has no start row and needs none).
+        `priority` (B,) array or tensor, or None: an order other than the batch index.  Within a group the missions are then taken in
+        ascending priority -- a LOWER number goes first, -0.0 ties with +0.0, NaN comes after +inf, ties go to the lower batch index
+        (`uavac_fleet_order_dev`, `uav_ac.scoring.priority_order`) --, and "the lowest index is never delayed" becomes "the first of its
+        group's order".  A composition: the search runs unchanged on `Engine.take(plan, order)` with `start_rows[order]`, and its answers
+        are gathered back, so the result is in the caller's batch order and is exactly `stagger_from_rows` on `take_rows(rows,
+        row_offsets, order)` mapped back with `rank`; the one host read is `Engine.take`'s.  None: the call as it always was."""
+        if priority is not None:
+            B = int(self._coeff_plan(plan).B)
+            order, rank, start = self._priority_order(priority, groups, B, nat.STAGGER_MAX_GROUP, start_rows)
+            return self._stagger_back(self.stagger(self.take(plan, order), radius, groups, start, step, max_steps), rank)
         torch = self._torch
         plan = self._coeff_plan(plan)
         B = int(plan.B)
@@ -858,7 +869,7 @@ class Engine:
         return self.sample_rows(out) if rows else out
 
     def layer(self, plan, radius: float, groups=None, start_rows=None, delta=(0.0, 0.0, -0.5), max_steps: int = 63,
-              obstacles=None) -> LayerResult:
+              obstacles=None, priority=None) -> LayerResult:
         """Prioritised deconfliction by offset (`uavac_minsnap_layer_dev`): the second lever on `Engine.separation`'s verdict, for the
         conflicts that waiting cannot resolve (a shared first or last waypoint, a crossing of a busy region).  `start_rows` are FIXED
         starts -- `StaggerResult.start_rows`, for instance; nobody is delayed by this call.  Within a group the missions are taken in
@@ -878,7 +889,17 @@ class Engine:
         group too, which is then moved only by a cuboid; `result.block` is (4, B) and `result.blocked` counts the refused layers below
         the granted one (all of them for an unresolved mission).  `Engine.audit(shifted, obstacles).hit_rows` is then 0 for every
         resolved mission.  steps = -1 with blocked = max_steps + 1 (`uav_ac.scoring.blocked_out`): every layer hits a cuboid, the
-        mission needs a new plan around the obstacle (`plan_collision_free`), not an offset."""
+        mission needs a new plan around the obstacle (`plan_collision_free`), not an offset.
+        `priority` (B,) array or tensor, or None: an order other than the batch index, by the rule and the composition of
+        `Engine.stagger` -- a lower number goes first, ties to the lower batch index; "the lowest index is never moved" becomes "the
+        first of its group's order"; the search runs unchanged on `Engine.take(plan, order)` with `start_rows[order]`, and `block`
+        (column-wise) and `offsets` (row-wise) are gathered back into the caller's batch order.  Exactly `layer_from_rows` /
+        `layer_obstacles_from_rows` on `take_rows(...)` of the shifted plans' rows, mapped back with `rank`.  The one host read is
+        `Engine.take`'s.  None: the call as it always was."""
+        if priority is not None:
+            B = int(self._coeff_plan(plan).B)
+            order, rank, start = self._priority_order(priority, groups, B, nat.LAYER_MAX_GROUP, start_rows)
+            return self._layer_back(self.layer(self.take(plan, order), radius, groups, start, delta, max_steps, obstacles), rank)
         torch = self._torch
         plan = self._coeff_plan(plan)
         B = int(plan.B)
@@ -944,8 +965,182 @@ class Engine:
                           None, None, True)
         return self.sample_rows(out) if rows else out
 
+    def _take_index(self, index, B: int):
+        """What `Engine.take` selects -> (n,) i32 on the device.  `index`: integers (array, list or tensor), or a boolean mask of one
+        entry per mission, which is turned into the indices of its True entries (a mask on the device costs one small read: their
+        number).  Checked where it is on the host: an empty selection, a mask of another length, numbers that are not integers and an
+        index outside 0 .. B - 1 are ValueErrors; the indices of a device tensor go through unread."""
+        torch = self._torch
+        t = index if isinstance(index, torch.Tensor) else torch.as_tensor(np.asarray(index))
+        t = t.reshape(-1)
+        if t.numel() < 1:
+            raise ValueError("an empty selection: take needs at least one mission")
+        if t.dtype == torch.bool:
+            if t.numel() != B:
+                raise ValueError(f"a mask holds one entry per mission: expected {B}, got {t.numel()}")
+            t = torch.nonzero(t).reshape(-1)
+        elif t.is_floating_point() or t.is_complex():
+            raise ValueError("index must hold integers or be a boolean mask")
+        if t.numel() < 1:
+            raise ValueError("an empty selection: take needs at least one mission")
+        if not t.is_cuda and (int(t.min()) < 0 or int(t.max()) >= B):
+            raise ValueError(f"index must be in 0 .. {B - 1}")
+        return t.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def take(self, plan, index, rows: bool = False) -> RaggedBatch:
+        """Missions of a plan selected on the device (`uavac_minsnap_take_dev`): mission i of the result is mission `index[i]` of `plan`,
+        every bit of it -- coefficients, durations, row counts, first heading (`uav_ac.scoring.take_parts`), so its sampled rows are
+        that mission's rows bit for bit (`uav_ac.scoring.take_rows`), `Engine.audit` of the result is the audit's columns `index`,
+        and a group taken whole is audited, staggered and layered as it was inside its batch.  `index` (n,) integers, array or tensor:
+        any order, duplicates allowed, n may exceed B; or a boolean (B,) mask, e.g. `~result.resolved`, which selects its True entries
+        in ascending order.  An index outside 0 .. B - 1 is a ValueError where the index is on the host; in a device tensor it is
+        clamped into range and raises sticky flag 0 (`take_flags`).  An empty selection is a ValueError.  `plan`: what `Engine.delay`
+        takes (a Plan with rows or rows-free, a RaggedBatch, a RaggedPlan through its batch); it is left as it is.
+        -> a rows-free RaggedBatch (`rows=True`: with rows, through `sample_rows`) of n missions, assembled like `Engine.delay`'s:
+        `waypoints` None (`start_positions` falls back to c0), `free_times` True, `max_m` the input's, velocity and dt carried over,
+        `first_yaw` gathered (from `Engine.first_yaw(plan)` if the input carries none), `status` and `velocities` gathered when
+        present.  ONE host sync: the read of the (n + 1,) segment offsets with the row total, as in `Engine.delay` (a mask on the
+        device adds the read of its count)."""
+        torch = self._torch
+        plan = self._coeff_plan(plan)
+        ragged = hasattr(plan, "seg_offsets")
+        B, m = int(plan.B), int(plan.max_m if ragged else plan.m)
+        idx = self._take_index(index, B)
+        n = int(idx.numel())
+        kw = dict(device=self.device)
+        so_in = _ptr(plan.seg_offsets) if ragged else None
+        cap = n * m                                                      # (buffers for the largest result, narrowed once the offsets are known)
+        tail = torch.empty((n + 2,), dtype=torch.int64, **kw)            # the segment offsets (n + 1,) and, behind them, the row total
+        co = torch.empty((cap, 8, 3), dtype=torch.float64, **kw)
+        sr = torch.empty((cap,), dtype=torch.int32, **kw)
+        tm = None if plan.times is None else torch.empty((cap,), dtype=torch.float64, **kw)
+        row_offsets = torch.empty((n + 1,), dtype=torch.int64, **kw)
+        fy_in = plan.first_yaw if getattr(plan, "first_yaw", None) is not None else self.first_yaw(plan)
+        first_yaw = torch.empty((n,), dtype=torch.float64, **kw)
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_take_offsets_dev", so_in, B, m, _ptr(idx), n, _ptr(tail))
+        self.ctx.call("uavac_minsnap_take_dev", _ptr(plan.coeffs), _ptr(plan.times), _ptr(plan.seg_rows), so_in, B, m, _ptr(fy_in),
+                      _ptr(idx), n, _ptr(tail), _ptr(co), _ptr(tm), _ptr(sr), _ptr(first_yaw))
+        self.ctx.call("uavac_minsnap_row_offsets_ragged_dev", _ptr(sr), _ptr(tail), n, m, _ptr(row_offsets))
+        tail[n + 1:].copy_(row_offsets[n:])
+        at = idx.clamp(0, B - 1).long()                                  # (as the kernel clamps it)
+        status = plan.status[at] if getattr(plan, "status", None) is not None else torch.zeros((n,), dtype=torch.int32, **kw)
+        velocities = plan.velocities[at] if getattr(plan, "velocities", None) is not None else None
+        host = tail.cpu().numpy()                                        # the one sync
+        so_host, total = host[:n + 1].copy(), int(host[n + 1])
+        S = int(so_host[-1])
+        out = RaggedBatch(n, m, float(plan.velocity), float(plan.dt), tail[:n + 1], so_host, None, None if tm is None else tm[:S], sr[:S],
+                          row_offsets, co[:S], status, None, total, first_yaw, None, velocities, True)
+        return self.sample_rows(out) if rows else out
+
+    def concat(self, plans) -> RaggedBatch:
+        """The missions of several plans back to back in one batch -- plumbing (`torch.cat` of the per-segment arrays with the offsets
+        moved up; a uniform Plan contributes offsets of arange * m), no kernel, no host sync.  `plans`: a sequence of what
+        `Engine.delay` takes; every part is left as it is.  All parts must have the same `dt`, otherwise ValueError.
+        -> a rows-free RaggedBatch assembled like `Engine.delay`'s (`waypoints` None, `free_times` True): `max_m` the largest of the
+        parts', `times` kept iff every part has them, `first_yaw` and `status` joined (`Engine.first_yaw(part)` / zeros for a part
+        that carries none), `velocity` the common value -- or NaN with `velocities` filled in, when the parts differ or one of them
+        has a speed per mission."""
+        torch = self._torch
+        parts = [self._coeff_plan(p) for p in plans]
+        if not parts:
+            raise ValueError("concat needs at least one plan")
+        dts = {float(p.dt) for p in parts}
+        if len(dts) != 1:
+            raise ValueError(f"the plans differ in dt ({sorted(dts)}): their rows would not share a clock")
+        kw = dict(device=self.device)
+        B = sum(int(p.B) for p in parts)
+        so, so_host, counts, base = [], [], [], 0
+        for p in parts:
+            if hasattr(p, "seg_offsets"):
+                part, host = p.seg_offsets.to(dtype=torch.int64, **kw), np.asarray(p.seg_offsets_host, dtype=np.int64)
+            else:
+                part, host = torch.arange(p.B + 1, dtype=torch.int64, **kw) * p.m, np.arange(p.B + 1, dtype=np.int64) * p.m
+            so.append(part[:-1] + base), so_host.append(host[:-1] + base)
+            base += int(host[-1])
+            counts.append(p.row_offsets[1:] - p.row_offsets[:-1])
+        so = torch.cat(so + [torch.full((1,), base, dtype=torch.int64, **kw)])
+        so_host = np.concatenate(so_host + [np.array([base], dtype=np.int64)])
+        row_offsets = torch.cat([torch.zeros((1,), dtype=torch.int64, **kw), torch.cumsum(torch.cat(counts), 0)])
+        times = torch.cat([p.times.reshape(-1) for p in parts]) if all(p.times is not None for p in parts) else None
+        first_yaw = torch.cat([p.first_yaw if getattr(p, "first_yaw", None) is not None else self.first_yaw(p) for p in parts])
+        status = torch.cat([p.status.to(torch.int32) if getattr(p, "status", None) is not None else torch.zeros((p.B,), dtype=torch.int32, **kw)
+                            for p in parts])
+        speeds = {float(p.velocity) for p in parts}
+        velocity, velocities = float(parts[0].velocity), None
+        per_mission = any(getattr(p, "velocities", None) is not None for p in parts)
+        if per_mission or (len(speeds) != 1 and not all(np.isnan(v) for v in speeds)):
+            velocity = float("nan")
+            velocities = torch.cat([p.velocities if getattr(p, "velocities", None) is not None
+                                    else torch.full((p.B,), float(p.velocity), dtype=torch.float64, **kw) for p in parts])
+        return RaggedBatch(B, max(int(p.max_m if hasattr(p, "seg_offsets") else p.m) for p in parts), velocity, float(parts[0].dt), so, so_host,
+                           None, times, torch.cat([p.seg_rows.reshape(-1) for p in parts]), row_offsets,
+                           torch.cat([p.coeffs.reshape(-1, 8, 3) for p in parts]), status, None, sum(int(p.total_rows) for p in parts),
+                           first_yaw, None, velocities, True)
+
+    def _put_index(self, index, B: int, n: int) -> np.ndarray:
+        """Where `Engine.put` puts the n missions of `other` -> (n,) i64 on the host, checked: integers (or a boolean (B,) mask with n
+        True entries), one per mission of `other`, in 0 .. B - 1, no index twice.  A device tensor costs one small read."""
+        a = np.asarray(index.detach().cpu().numpy() if hasattr(index, "detach") else index).reshape(-1)
+        if a.dtype == np.bool_:
+            if a.size != B:
+                raise ValueError(f"a mask holds one entry per mission: expected {B}, got {a.size}")
+            a = np.flatnonzero(a)
+        elif not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("index must hold integers or be a boolean mask")
+        a = a.astype(np.int64)
+        if a.size != n:
+            raise ValueError(f"one index per mission of `other`: expected {n}, got {a.size}")
+        if a.size and (a.min() < 0 or a.max() >= B):
+            raise ValueError(f"index must be in 0 .. {B - 1}")
+        if np.unique(a).size != a.size:
+            raise ValueError("index must not name a mission twice")
+        return a
+
+    def put(self, plan, index, other, rows: bool = False) -> RaggedBatch:
+        """`plan` with mission `index[i]` replaced by mission i of `other` -- how re-planned missions go back into a fleet's plan:
+        `take(concat([plan, other]), sel)` with sel = arange(B), sel[index] = B + arange(n).  Every mission of the result is, bit for
+        bit, `other`'s at `index` and `plan`'s elsewhere.  `index` (n,) unique integers in 0 .. B - 1, n = other.B, array or tensor
+        (or a boolean (B,) mask with n True entries, e.g. `~result.resolved`): checked on the host, with one small read when it is a
+        device tensor; anything else is a ValueError.  `plan` and `other`: what `Engine.delay` takes, with the same `dt`; both are
+        left as they are.  -> a rows-free RaggedBatch as `Engine.take` returns it (`rows=True`: with rows); the host sync is `take`'s."""
+        plan, other = self._coeff_plan(plan), self._coeff_plan(other)
+        B, n = int(plan.B), int(other.B)
+        at = self._put_index(index, B, n)
+        sel = np.arange(B, dtype=np.int64)
+        sel[at] = B + np.arange(n, dtype=np.int64)
+        return self.take(self.concat([plan, other]), sel, rows=rows)
+
+    def _priority_order(self, priority, groups, B: int, max_group: int, start_rows):
+        """The front of the `priority=` forms: the within-group order of `priority` (`uavac_fleet_order_dev`) -> (order, rank, the start
+        rows in slot order or None), device tensors.  The groups are checked against `max_group` here, before anything is copied."""
+        torch = self._torch
+        pr = self._dev(priority, torch.float64).reshape(-1)
+        if pr.numel() != B:
+            raise ValueError(f"one priority per mission: expected {B}, got {pr.numel()}")
+        go, G = self._groups(groups, B, max_group)
+        order = torch.empty((B,), dtype=torch.int32, device=self.device)
+        rank = torch.empty((B,), dtype=torch.int32, device=self.device)
+        self._bind_stream()
+        self.ctx.call("uavac_fleet_order_dev", _ptr(pr), _ptr(go), G, B, _ptr(order), _ptr(rank))
+        start = None if start_rows is None else self._start_rows(start_rows, B)[order.long()]
+        return order, rank, start
+
+    @staticmethod
+    def _stagger_back(res: StaggerResult, rank) -> StaggerResult:
+        """A stagger result in slot order -> the caller's batch order (no row of it holds a batch index)."""
+        block = res.block[:, rank.long()].contiguous()
+        return StaggerResult(*block.unbind(0), block)
+
+    @staticmethod
+    def _layer_back(res: LayerResult, rank) -> LayerResult:
+        """A layer result in slot order -> the caller's batch order: the block column-wise, the offsets row-wise."""
+        at = rank.long()
+        block = res.block[:, at].contiguous()
+        return LayerResult(*block[:nat.LAYER_ROWS].unbind(0), block, res.offsets[at].contiguous())
+
     def deconflict(self, plan, radius: float, groups=None, obstacles=None, start_rows=None, step: int = 1, max_delay_steps: int = 255,
-                   delta=(0.0, 0.0, -0.5), max_layers: int = 63) -> DeconflictResult:
+                   delta=(0.0, 0.0, -0.5), max_layers: int = 63, priority=None) -> DeconflictResult:
         """The fleet chain as one call: stagger -> layer -> shift -> delay.  `Engine.stagger(plan, radius, groups, start_rows, step,
         max_delay_steps)` makes missions wait; `Engine.layer(plan, radius, groups, start_rows=stagger.start_rows, delta=delta,
         max_steps=max_layers, obstacles=obstacles)` moves, at the granted starts, the ones that waiting cannot clear -- and, with
@@ -961,7 +1156,26 @@ class Engine:
         leaves it, and may be inside the radius of others or inside a cuboid -- look at `resolved`.  A mission whose every layer is
         blocked (`uav_ac.scoring.blocked_out(result.layer, max_layers)`) needs a re-plan around the obstacle (`plan_collision_free`),
         not an offset.  The start delays know nothing about obstacles: a delay does not move a path.  Without `obstacles` nothing is
-        known about cuboids at all."""
+        known about cuboids at all.
+        `priority` (B,) array or tensor, or None: the order of both searches, by the rule of `Engine.stagger` (a lower number goes
+        first, ties to the lower batch index; "ascending batch index" above becomes "ascending priority": the first of its group's
+        order is never delayed, and is moved only by a cuboid).  Both searches run on ONE `Engine.take(plan, order)` -- the layer search
+        takes the stagger's granted starts as they come, in slot order -- and their answers are gathered back: `stagger`, `layer`,
+        `resolved` and `plan`, which is built from the original `plan`, are all in the caller's batch order.  One host read more,
+        `Engine.take`'s.  None: the calls as they always were.
+        WHAT STAYS UNRESOLVED: `eng.take(plan, ~result.resolved)` takes those missions out to look at them; re-plan them from your own
+        waypoints (`plan_ragged` / `plan_collision_free`: `waypoints` is None after a transform, so the caller keeps them),
+        `eng.put(plan, ~result.resolved, replanned)` puts them back, and `deconflict` runs again -- with a priority that takes them
+        first if they are to win this time."""
+        if priority is not None:
+            B = int(self._coeff_plan(plan).B)
+            order, rank, start = self._priority_order(priority, groups, B, min(nat.STAGGER_MAX_GROUP, nat.LAYER_MAX_GROUP), start_rows)
+            taken = self.take(plan, order)
+            stag = self.stagger(taken, radius, groups=groups, start_rows=start, step=step, max_steps=max_delay_steps)
+            lay = self.layer(taken, radius, groups=groups, start_rows=stag.start_rows, delta=delta, max_steps=max_layers, obstacles=obstacles)
+            stag, lay = self._stagger_back(stag, rank), self._layer_back(lay, rank)
+            flown = self.delay(self.shift(plan, lay.offsets), stag.start_rows)
+            return DeconflictResult(flown, stag, lay, lay.steps >= 0)
         stag = self.stagger(plan, radius, groups=groups, start_rows=start_rows, step=step, max_steps=max_delay_steps)
         lay = self.layer(plan, radius, groups=groups, start_rows=stag.start_rows, delta=delta, max_steps=max_layers, obstacles=obstacles)
         flown = self.delay(self.shift(plan, lay.offsets), stag.start_rows)

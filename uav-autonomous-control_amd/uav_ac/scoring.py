@@ -758,3 +758,82 @@ def blocked_out(result, max_steps: int):
             raise ValueError(f"a layer block with obstacles is [{nat.LAYER_OBS_ROWS}][B], got {block.shape}")
         steps, blocked = block[LAYER_STEPS], block[LAYER_BLOCKED]
     return (steps == -1) & (blocked == int(max_steps) + 1)
+
+
+def take_parts(coeffs, times, seg_rows, seg_offsets_or_m, index):
+    """A gather of missions on a plan's parts -- the construction `uavac_minsnap_take_dev` (csrc/minsnap_take.hip) is tested against bit
+    for bit.  NumPy on the host; nothing is computed.
+    `coeffs`: anything that reshapes to (S, 8, 3); `times` (S values, or None) and `seg_rows` (S values) per segment back to back;
+    `seg_offsets_or_m`: the ragged batch's segment offsets (B + 1,), or an int m = segments per mission of a uniform batch.  `index`
+    (n,) integers in 0 .. B - 1: duplicates and any order are allowed, n may exceed B.
+    Mission i of the result is mission index[i] of the input, every bit of it.
+    -> (coeffs (S', 8, 3), times (S',) or None, seg_rows (S',) i32, seg_offsets (n + 1,) i64)."""
+    co = _host(coeffs).reshape(-1, 8, 3)
+    sr = _host(seg_rows, np.int32).reshape(-1)
+    tm = None if times is None else _host(times).reshape(-1)
+    if np.ndim(seg_offsets_or_m) == 0:
+        m = int(seg_offsets_or_m)
+        if m < 1 or len(co) % m:
+            raise ValueError(f"{len(co)} segments are not missions of {m}")
+        so = np.arange(len(co) // m + 1, dtype=np.int64) * m
+    else:
+        so = _host_i64(seg_offsets_or_m)
+        if len(so) < 2 or so[0] != 0 or so[-1] != len(co) or (np.diff(so) < 0).any():
+            raise ValueError("seg_offsets must ascend from 0 to the number of segments, one entry per mission and one more")
+    B = len(so) - 1
+    if len(sr) != len(co) or (tm is not None and len(tm) != len(co)):
+        raise ValueError("one row count (and one duration) per segment")
+    idx = _host_i64(index)
+    if len(idx) < 1:
+        raise ValueError("an empty selection")
+    if (idx < 0).any() or (idx >= B).any():
+        raise ValueError(f"index must be in 0 .. {B - 1}")
+    seg = np.concatenate([np.arange(so[b], so[b + 1], dtype=np.int64) for b in idx])
+    out_so = np.concatenate([[0], np.cumsum(np.diff(so)[idx])]).astype(np.int64)
+    return co[seg].copy(), None if tm is None else tm[seg].copy(), sr[seg].copy(), out_so
+
+
+def take_rows(rows, row_offsets, index):
+    """The sampled rows of selected missions back to back: what the sampler writes for `Engine.take(plan, index)` when `rows` are the
+    plan's -- every row keeps all of its columns, the spline ids included.  `index` as `take_parts` takes it.
+    -> (rows (N', cols), row_offsets (n + 1,) i64)."""
+    rows = _host(rows)
+    ro = _host_i64(row_offsets)
+    B = len(ro) - 1
+    idx = _host_i64(index)
+    if len(idx) < 1:
+        raise ValueError("an empty selection")
+    if (idx < 0).any() or (idx >= B).any():
+        raise ValueError(f"index must be in 0 .. {B - 1}")
+    out = np.concatenate([rows[ro[b]:ro[b + 1]] for b in idx])
+    return out, np.concatenate([[0], np.cumsum(np.diff(ro)[idx])]).astype(np.int64)
+
+
+def priority_order(priority, group_offsets=None):
+    """Priorities into a within-group order -- the SPECIFICATION of `uavac_fleet_order_dev` (csrc/minsnap_take.hip), which is tested
+    against it exactly.  NumPy on the host.
+    `priority` (B,) f64.  `group_offsets` (G + 1,) or None = one group of all B; every entry is clamped as the fleet's kernels clamp
+    it -- group g holds [g0, g1) with g0 = clamp(go[g], 0, B) and g1 = clamp(go[g + 1], g0, B) -- so offsets that do not reach from 0
+    to B leave a head or a tail that no group holds.
+    Within each group the missions are sorted by the total order "a before b" iff p_a is a number and p_b is NaN, or p_a < p_b, or
+    (p_a == p_b or both are NaN) and a < b: a LOWER priority goes first, -0.0 ties with +0.0, NaN comes after +inf, ties go to the lower
+    batch index.
+    -> (order, rank), (B,) i32 each: order[g0 + k] is the mission in slot k of its group, rank its inverse (rank[order[s]] = s); a
+    mission that no group holds keeps its place, order[b] = rank[b] = b."""
+    p = _host(priority).reshape(-1)
+    B = len(p)
+    go = np.array([0, B], dtype=np.int64) if group_offsets is None else _host_i64(group_offsets)
+    if len(go) < 2:
+        raise ValueError("group offsets hold at least two entries")
+    order = np.arange(B, dtype=np.int32)
+    nan = np.isnan(p)
+    key = np.where(nan, np.inf, p)                                                    # (a NaN sorts behind +inf through the second key)
+    for g in range(len(go) - 1):
+        g0 = int(min(max(go[g], 0), B))
+        g1 = int(min(max(go[g + 1], g0), B))
+        ids = np.arange(g0, g1)
+        # lexsort: the last key is the primary one; -0.0 == +0.0 for it, and it is stable, so ties go to the lower index
+        order[g0:g1] = ids[np.lexsort((ids, nan[ids], key[ids]))]
+    rank = np.empty(B, dtype=np.int32)
+    rank[order] = np.arange(B, dtype=np.int32)
+    return order, rank
