@@ -173,7 +173,8 @@ int uavac_clock_probe_dev(uavac_ctx *ctx, int window_us, int64_t *stamps);
  * of one window of 64 missions in uavac_minsnap_separation_dev and uavac_flown_separation_dev (same results).  "flown_audit_split": 0
  * (default: sized from B and K) or 1 .. UAVAC_FLOWN_AUDIT_MAX_SPLIT = workgroups that share the ticks of one window of 64 vehicles in
  * uavac_flown_audit_dev (same results).  "conflict_slots": 0 (default: 64) or 1 .. 64 = j-tile slots per mission and discovery round
- * of the conflict list (uavac_minsnap_conflict_offsets_dev, uavac_minsnap_conflicts_dev; same results, less scratch, more rounds).
+ * of the conflict lists (uavac_minsnap_conflict_offsets_dev, uavac_minsnap_conflicts_dev, uavac_flown_conflict_offsets_dev,
+ * uavac_flown_conflicts_dev; same results, less scratch, more rounds).
  * Defaults from the environment (UAVAC_ROLLOUT_ALIGN, UAVAC_YAW_GROUP, UAVAC_SAMPLER_WAVES, UAVAC_SAMPLER_GROUP) at uavac_create.
  * ONE option is not a tuning knob but part of the log layout: "log_pitch" = P doubles per log row,
  * 0 (default) = B.  With P >= B the rollouts write state_log [K][13][P] and cmd_log [K][12][P]
@@ -616,6 +617,47 @@ int uavac_fleet_order_dev(uavac_ctx *ctx, const double *priority, const int64_t 
  * finite, G < 1 when group_offsets != NULL. */
 int uavac_flown_separation_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
                                double radius, double *sep, int32_t *isep);
+
+/* FLOWN CONFLICT LIST: the flown separation audit's conflict graph in CSR form -- not one partner and a count per vehicle, but every
+ * pair a flight brought inside the radius, with when and how near (csrc/flown_conflicts.hip).  What uavac_minsnap_conflicts_dev is to
+ * uavac_minsnap_separation_dev, this is to uavac_flown_separation_dev: nothing is read back, no log leaves the device, everything is
+ * enqueued on the ctx stream, scratch comes from the ctx arena (UAVAC_ENOMEM with a message when it cannot be had).
+ * state_log / K / B / pitch / group_offsets / G / radius exactly as in uavac_flown_separation_dev, and so are the log's layout
+ * [K][13][pitch], the CLOCK (the tick k = 0 .. K - 1), the columns B .. pitch - 1 that are never read, d^2 = (dx * dx + dy * dy) + dz * dz
+ * without contraction, r^2 = radius * radius rounded once, inside meaning d^2 < r^2, strictly, and a pair-tick being VALID iff its d^2
+ * is not NaN.
+ * THE LIST.  Vehicle i lists every partner j != i of its group that has a valid pair-tick inside the radius.  The entries of vehicle i
+ * are [pair_offsets[i], pair_offsets[i + 1]), its partners in ascending batch index; pair_offsets [B + 1] i64 is the exclusive prefix
+ * sum of the flown audit's `conflicts`.  Per entry e:
+ *   pair_d [E] f64: one correctly rounded sqrt of the minimum d^2 over the pair's valid pair-ticks
+ *   pair_i [UAVAC_CONF_ROWS][capacity] i32:  0 the partner j      1 the first tick inside      2 the last tick inside
+ *        3 the number of ticks inside (less than last - first + 1 when the pair parts and meets again; a NaN tick in the middle of an
+ *        incursion is not inside and is not counted)      4 the tick of the pair's minimum, the lowest one on a tie
+ * UAVAC_CONF_ROWS and the rows are those of the plan's list, with ticks where it has clock rows (clock row of the plan = tick /
+ * inner_per_outer).  Two calls, in the order counts -> offsets -> allocate -> fill that the plan's list has:
+ *   uavac_flown_conflict_offsets_dev  pair_offsets [B + 1].  The caller reads pair_offsets[B], the number of entries E, to size the
+ *                                     buffers.
+ *   uavac_flown_conflicts_dev         pair_d and pair_i for buffers of `capacity` entries (the row stride of pair_i).  It repeats the
+ *                                     discovery and relies on nothing the first call left in the arena.
+ * WHAT THE RESULT GUARANTEES, on the same inputs as uavac_flown_separation_dev:  diff(pair_offsets) == isep[2].  The minimum of row 1
+ * over a vehicle's entries == isep[3].  For a vehicle with conflicts > 0 the audit's (sep, tick, partner) is the lexicographic minimum
+ * of (pair_d, row 4, partner) over its entries.  d^2 is bit-symmetric, so the entries (i -> j) and (j -> i) agree in pair_d and in rows
+ * 1 .. 4.  Every output is bit for bit what NumPy gives on the log (uav_ac.scoring.conflicts_from_log), whatever the pitch, the launch
+ * shape (options "separation_split" and "conflict_slots") or what else is in the batch: a group listed alone gives the same records
+ * with the partner indices shifted.
+ * BOUNDS are part of the contract, and they are those of uavac_minsnap_conflicts_dev.  Vehicle i writes nothing outside its slice, and
+ * nothing is written at or beyond `capacity` (or below 0).  Entries of a slice that lie at or beyond `capacity` are dropped and raise
+ * sticky flag 2.  The log or the radius may have changed between the two calls: a vehicle that now has more or fewer partners than its
+ * slice holds fills what fits in ascending partner order -- entries of the slice beyond its partners are left as they were -- and
+ * raises sticky flag 0.  capacity == 0 with pair_d == pair_i == NULL is allowed (pair_offsets[B] == 0: nothing to fill).
+ * UAVAC_EINVAL before anything is enqueued: everything uavac_flown_separation_dev refuses (required pointers: state_log,
+ * pair_offsets), capacity < 0, pair_d or pair_i NULL with capacity > 0.
+ * Cost: each call about one flown audit (pairs x ticks); the fill adds entries x ticks, each entry reading its two columns of the log
+ * (lanes across consecutive entries, which share their owner's column and their group's span of a log row). */
+int uavac_flown_conflict_offsets_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets,
+                                     int G, double radius, int64_t *pair_offsets);
+int uavac_flown_conflicts_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
+                              double radius, const int64_t *pair_offsets, int64_t capacity, double *pair_d, int32_t *pair_i);
 
 /* FLOWN AUDIT: the plan audit of a FLIGHT.  uavac_minsnap_audit_dev says what a plan's rows would show against the flight limits and the
  * cuboids; the vehicles track the plan with an error, and uavac_minsnap_layer_obs_dev deliberately puts missions next to cuboids.  This

@@ -13,18 +13,11 @@
 //                              scratch, words [slot][B], slot = the j-tile's index within the mission's group: ONE writer per word --
 //                              the share that owns the tile --, no atomics decide a position.  The first share also leaves, per mission,
 //                              its group's first mission, horizon and number of j-tiles.
-//                              The host knows the groups' sizes only on average (the offsets are on the device), so it cannot size the
-//                              words for the largest group: it hands out `slots` (<= 64) tile slots per mission and repeats discovery in
-//                              ROUNDS over the slots [T0, T0 + slots) until ceil(B / 64), the most a group can have, is covered.  A batch
-//                              of up to 4 096 missions is one round whatever its groups; in a later round a workgroup whose groups
-//                              have no tile that far finds that out from the group's size and leaves.
-//   conflict_count_kernel      (the offsets call) per mission: the popcounts of the round's words added up; the last round leaves the
-//                              counts as the totals of the scan behind every offset table here (uavac_launch_totals_scan)
-//   conflict_list_kernel       (the fill call) per mission: its words of the round in tile order, bit by bit -- ascending partners,
-//                              ascending entry indices -- into row 0 of its slice, and who owns the entry into scratch.  Bounded: an
-//                              entry is written iff it lies inside [pair_offsets[b], pair_offsets[b + 1]), at or above 0 and below
-//                              `capacity`; what does not fit raises flag 2 (capacity) or, the last round, flag 0 (the slice holds another
-//                              number of entries than the mission has partners: the plan changed between the two calls).
+//                              Discovery is repeated in ROUNDS over the slots [T0, T0 + slots) (conflict_csr.h); in a later round a
+//                              workgroup whose groups have no tile that far finds that out from the group's size and leaves.
+//   conflict_count_kernel,     (conflict_csr.h, one copy for this list and the flown one, flown_conflicts.hip) the popcounts of the
+//   conflict_list_kernel       round's words into the totals of the offsets' scan; the words bit by bit into row 0 of the mission's
+//                              slice, bounded, with flags 2 and 0
 //   conflict_measure_kernel    per listed entry, sixteen lanes each: both missions walked over the group's clock [0, H_g) with
 //                              clock_walk's arithmetic -- lane l takes the rows 8 (16 c + l) .. + 7 of every c --, the partner's eight
 //                              positions parked in the lane's own slots of the LDS tile; first row inside (min), last row inside (max),
@@ -38,6 +31,7 @@
 // xj, ..., d^2 = (dx dx + dy dy) + dz dz, each product and sum rounded on its own -- (xi - xj)^2 == (xj - xi)^2 bit for bit, so the two
 // directions of a pair agree in everything but the partner.
 
+#include "conflict_csr.h"
 #include "fleet_clock.h"
 
 #include <cmath>
@@ -46,9 +40,7 @@
 namespace {
 
 using namespace fleet;                                      // the clock, the pre-pass and, through it, sepred's tile and reduction
-using mission_walk::block_inclusive_scan_256;
 
-constexpr int kMaxSlots = 64;                               // tile slots per mission and round: 512 bytes of words per mission at most
 constexpr int kPairLanes = 16;                              // lanes per entry of the measure
 constexpr int kPairsPerWave = 64 / kPairLanes;
 constexpr int kPairsPerGroup = kWaves * kPairsPerWave;      // entries per workgroup of the measure
@@ -158,65 +150,6 @@ __global__ void __launch_bounds__(kThreads, 3) conflict_discover_kernel(
     }
 }
 
-// a mission's words of the round: the slots [0, n) hold the tiles T0 .. T0 + n - 1 of its group; none for an excluded mission, whose
-// lanes walked garbage
-__device__ __forceinline__ int round_slots(const int32_t *__restrict__ n_rows, const int32_t *__restrict__ info, int b, int B, int T0, int slots) {
-    if (n_rows[b] == 0) return 0;
-    const int n = info[2 * (size_t)B + b] - T0;
-    return n < 0 ? 0 : (n > slots ? slots : n);
-}
-
-// ------------------------------------------------------------------------------------------------------------------ the counts
-__global__ void __launch_bounds__(256) conflict_count_kernel(const int32_t *__restrict__ n_rows, const int32_t *__restrict__ info,
-                                                             const unsigned long long *__restrict__ words, int B, int T0, int slots, int last,
-                                                             int32_t *__restrict__ count, int32_t *__restrict__ totals,
-                                                             int64_t *__restrict__ tile_sum) {
-    __shared__ int64_t wsum[4];
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    int c = 0;
-    if (b < B) {
-        c = T0 == 0 ? 0 : count[b];
-        const int n = round_slots(n_rows, info, b, B, T0, slots);
-        for (int s = 0; s < n; ++s) c += __popcll(words[(size_t)s * B + b]);
-        count[b] = c;
-    }
-    if (last) {                                              // (uniform) the totals and the workgroup sums of uavac_launch_totals_scan
-        if (b < B) totals[b] = c;
-        const int64_t inc = block_inclusive_scan_256(c, wsum);
-        if (threadIdx.x == 255) tile_sum[blockIdx.x] = inc;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------------ the list
-__global__ void __launch_bounds__(256) conflict_list_kernel(const int32_t *__restrict__ n_rows, const int32_t *__restrict__ info,
-                                                            const unsigned long long *__restrict__ words, int B, int T0, int slots, int last,
-                                                            const int64_t *__restrict__ pair_offsets, long long capacity,
-                                                            int32_t *__restrict__ found, int32_t *__restrict__ owner,
-                                                            int32_t *__restrict__ pair_i, int32_t *__restrict__ flags) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    const long long lo = pair_offsets[b], hi = pair_offsets[b + 1];
-    int f = T0 == 0 ? 0 : found[b];
-    const int n = round_slots(n_rows, info, b, B, T0, slots), g0 = info[b];
-    bool full = false;
-    for (int s = 0; s < n; ++s) {
-        unsigned long long word = words[(size_t)s * B + b];
-        while (word) {
-            const int j = g0 + (T0 + s) * kTile + __builtin_ctzll(word);
-            word &= word - 1;
-            const long long at = lo + f;
-            ++f;
-            if (at < 0 || at >= hi) continue;                // not in the mission's slice: flag 0 below
-            if (at >= capacity) { full = true; continue; }   // the buffers end inside the slice
-            pair_i[at] = j;
-            owner[at] = b;
-        }
-    }
-    found[b] = f;
-    if (full) atomicOr(&flags[2], 1);
-    if (last && (long long)f != hi - lo) atomicOr(&flags[0], 1);
-}
-
 // ------------------------------------------------------------------------------------------------------------------ the measure
 __device__ __forceinline__ double pair_d2(double xi, double yi, double zi, const double *o) {
 #pragma clang fp contract(off)
@@ -280,40 +213,20 @@ __global__ void __launch_bounds__(kThreads, 3) conflict_measure_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the host side
-// What the two calls share: the shares per window (the audit's rule), the tile slots per round and the rounds, the scratch.
-struct Shape {
-    int windows, P, slots, rounds;
-    int32_t *n_rows, *start, *info, *count;
-    unsigned long long *words;
-    int32_t *owner;
+// What the two calls share: csr's shape (shares, slots, rounds; counts, words, owners) and the pre-pass's and the discovery's records.
+struct Shape : csr::Shape {
+    int32_t *n_rows, *start, *info;
 };
 
 int shape_of(uavac_ctx *ctx, int B, const int64_t *group_offsets, int G, long long capacity, Shape &s) {
-    s.windows = (B + kTile - 1) / kTile;
-    int P = ctx->separation_split;                           // (as uavac_launch_separation sizes it; the results do not depend on it)
-    if (P <= 0) {
-        const int groups = group_offsets ? G : 1;
-        const int tiles = (B / groups + kTile - 1) / kTile;
-        const int wanted = ctx->n_simds * 4;
-        P = (wanted + s.windows - 1) / s.windows;
-        P = P > tiles ? tiles : P;
-    }
-    s.P = P < 1 ? 1 : (P > UAVAC_SEP_MAX_SPLIT ? UAVAC_SEP_MAX_SPLIT : P);
-    const int most = s.windows;                              // j-tiles of the largest group there can be
-    s.slots = ctx->conflict_slots > 0 ? ctx->conflict_slots : kMaxSlots;
-    s.slots = s.slots > most ? most : s.slots;
-    s.rounds = (most + s.slots - 1) / s.slots;
-    const size_t Bs = (size_t)B, cap = (size_t)capacity;
-    if (int rc = uavac_arena_reserve(ctx, 3 * uavac_arena_size(Bs * 4) + uavac_arena_size(3 * Bs * 4) + uavac_arena_size(s.slots * Bs * 8) +
-                                              uavac_arena_size(cap ? cap * 4 : 8)))
+    csr::shape_of(ctx, B, group_offsets, G, s);
+    const size_t Bs = (size_t)B;
+    if (int rc = uavac_arena_reserve(ctx, 2 * uavac_arena_size(Bs * 4) + uavac_arena_size(3 * Bs * 4) + csr::shape_bytes(s, B, capacity)))
         return rc;
     s.n_rows = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4));
     s.start = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4));
-    s.count = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4));
     s.info = static_cast<int32_t *>(uavac_arena_take(ctx, 3 * Bs * 4));
-    s.words = static_cast<unsigned long long *>(uavac_arena_take(ctx, s.slots * Bs * 8));
-    s.owner = static_cast<int32_t *>(uavac_arena_take(ctx, cap * 4));
-    if (!s.n_rows || !s.start || !s.count || !s.info || !s.words || !s.owner)
+    if (!s.n_rows || !s.start || !s.info || !csr::shape_take(ctx, s, B, capacity))
         return uavac_fail(ctx, UAVAC_ENOMEM, "conflict list: scratch arena too small");
     return UAVAC_OK;
 }
@@ -327,10 +240,13 @@ int launch_prepass(uavac_ctx *ctx, const Shape &s, const double *coeffs, const i
     return UAVAC_OK;
 }
 
-void launch_discover(uavac_ctx *ctx, const Shape &s, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
-                     double dt, const int64_t *group_offsets, int G, double radius, int round) {
-    hipLaunchKernelGGL(conflict_discover_kernel, dim3(s.windows, s.P), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows, seg_offsets, B, m, dt,
-                       group_offsets, group_offsets ? G : 1, s.n_rows, s.start, radius * radius, round * s.slots, s.slots, s.words, s.info);
+// one round of the discovery, from its first j-tile T0 (csr_offsets / csr_list call it once per round)
+auto discovery(uavac_ctx *ctx, const Shape &s, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+               double dt, const int64_t *group_offsets, int G, double radius) {
+    return [=](int T0) {
+        hipLaunchKernelGGL(conflict_discover_kernel, dim3(s.windows, s.P), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows, seg_offsets, B, m,
+                           dt, group_offsets, group_offsets ? G : 1, s.n_rows, s.start, radius * radius, T0, s.slots, s.words, s.info);
+    };
 }
 
 }  // namespace
@@ -338,18 +254,11 @@ void launch_discover(uavac_ctx *ctx, const Shape &s, const double *coeffs, const
 int uavac_launch_conflict_offsets(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                                   double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius,
                                   int64_t *pair_offsets) {
-    int32_t *totals = nullptr;
-    int64_t *tiles = nullptr;
-    if (int rc = uavac_ensure_totals(ctx, B, &totals, &tiles)) return rc;
     Shape s;
     if (int rc = shape_of(ctx, B, group_offsets, G, 0, s)) return rc;
     if (int rc = launch_prepass(ctx, s, coeffs, seg_rows, seg_offsets, B, m, start_rows)) return rc;
-    for (int r = 0; r < s.rounds; ++r) {
-        launch_discover(ctx, s, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, radius, r);
-        hipLaunchKernelGGL(conflict_count_kernel, dim3((B + 255) / 256), dim3(256), 0, ctx->stream, s.n_rows, s.info, s.words, B, r * s.slots,
-                           s.slots, r == s.rounds - 1 ? 1 : 0, s.count, totals, tiles);
-    }
-    return uavac_launch_totals_scan(ctx, B, pair_offsets);
+    const auto discover = discovery(ctx, s, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, radius);
+    return csr::csr_offsets(ctx, s, B, s.n_rows, s.info + 2 * (size_t)B, discover, pair_offsets);
 }
 
 int uavac_launch_conflicts(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
@@ -358,12 +267,9 @@ int uavac_launch_conflicts(uavac_ctx *ctx, const double *coeffs, const int32_t *
     Shape s;
     if (int rc = shape_of(ctx, B, group_offsets, G, capacity, s)) return rc;
     if (int rc = launch_prepass(ctx, s, coeffs, seg_rows, seg_offsets, B, m, start_rows)) return rc;
-    if (capacity > 0) UAVAC_HIP(ctx, hipMemsetAsync(s.owner, 0xff, (size_t)capacity * 4, ctx->stream));      // -1: nobody listed the entry
-    for (int r = 0; r < s.rounds; ++r) {
-        launch_discover(ctx, s, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, radius, r);
-        hipLaunchKernelGGL(conflict_list_kernel, dim3((B + 255) / 256), dim3(256), 0, ctx->stream, s.n_rows, s.info, s.words, B, r * s.slots,
-                           s.slots, r == s.rounds - 1 ? 1 : 0, pair_offsets, (long long)capacity, s.count, s.owner, pair_i, ctx->d_flags);
-    }
+    const auto discover = discovery(ctx, s, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, radius);
+    if (int rc = csr::csr_list(ctx, s, B, s.n_rows, s.info, s.info + 2 * (size_t)B, discover, pair_offsets, (long long)capacity, pair_i))
+        return rc;
     if (capacity > 0) {
         const long long groups = (capacity + kPairsPerGroup - 1) / kPairsPerGroup;
         hipLaunchKernelGGL(conflict_measure_kernel, dim3((unsigned)groups), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows, seg_offsets, B, m,

@@ -1003,16 +1003,39 @@ int uavac_fleet_order_dev(uavac_ctx *ctx, const double *priority, const int64_t 
     return uavac_launch_fleet_order(ctx, priority, group_offsets, G, B, order, rank);
 }
 
-int uavac_flown_separation_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
-                               double radius, double *sep, int32_t *isep) {
-    UAVAC_ENTER(ctx);
-    if (!state_log || !sep || !isep) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+// what the flown separation audit and the flown conflict list refuse alike; `outputs`: the call's required output pointers are there
+static int check_flown_pair_args(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
+                                 double radius, bool outputs) {
+    if (!state_log || !outputs) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
     if (K < 1) return uavac_fail(ctx, UAVAC_EINVAL, "K must be >= 1");
     if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
     if (pitch < B) return uavac_fail(ctx, UAVAC_EINVAL, "pitch must be >= B");
     if (!std::isfinite(radius) || radius < 0.0) return uavac_fail(ctx, UAVAC_EINVAL, "radius must be finite and >= 0");
     if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
+    return UAVAC_OK;
+}
+
+int uavac_flown_separation_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
+                               double radius, double *sep, int32_t *isep) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_flown_pair_args(ctx, state_log, K, B, pitch, group_offsets, G, radius, sep && isep)) return rc;
     return uavac_launch_flown_separation(ctx, state_log, K, B, pitch, group_offsets, G, radius, sep, isep);
+}
+
+int uavac_flown_conflict_offsets_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets,
+                                     int G, double radius, int64_t *pair_offsets) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_flown_pair_args(ctx, state_log, K, B, pitch, group_offsets, G, radius, pair_offsets != nullptr)) return rc;
+    return uavac_launch_flown_conflict_offsets(ctx, state_log, K, B, pitch, group_offsets, G, radius, pair_offsets);
+}
+
+int uavac_flown_conflicts_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
+                              double radius, const int64_t *pair_offsets, int64_t capacity, double *pair_d, int32_t *pair_i) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_flown_pair_args(ctx, state_log, K, B, pitch, group_offsets, G, radius, pair_offsets != nullptr)) return rc;
+    if (capacity < 0) return uavac_fail(ctx, UAVAC_EINVAL, "capacity must be >= 0");
+    if (capacity > 0 && (!pair_d || !pair_i)) return uavac_fail(ctx, UAVAC_EINVAL, "pair_d and pair_i are required when capacity > 0");
+    return uavac_launch_flown_conflicts(ctx, state_log, K, B, pitch, group_offsets, G, radius, pair_offsets, capacity, pair_d, pair_i);
 }
 
 int uavac_flown_audit_dev(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const double *cuboids, int n_cuboids,

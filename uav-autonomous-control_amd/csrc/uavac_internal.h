@@ -263,6 +263,12 @@ int uavac_launch_layer_obs(uavac_ctx *ctx, const double *coeffs, const int32_t *
 // the separation the fleet flew (flown_separation.hip): the audit's outputs from the positions of a state log [K][13][pitch]
 int uavac_launch_flown_separation(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
                                   double radius, double *sep, int32_t *isep);
+// that audit's conflict graph in CSR form (flown_conflicts.hip): pair_offsets [B + 1], then pair_d [capacity] and pair_i
+// [UAVAC_CONF_ROWS][capacity] with ticks where the plan's list has clock rows; scratch from the ctx arena
+int uavac_launch_flown_conflict_offsets(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets,
+                                        int G, double radius, int64_t *pair_offsets);
+int uavac_launch_flown_conflicts(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
+                                 double radius, const int64_t *pair_offsets, int64_t capacity, double *pair_d, int32_t *pair_i);
 // what the vehicles did against the flight limits and the cuboids (flown_audit.hip): audit [UAVAC_FLOWN_AUDIT_ROWS][B], first_bad [B],
 // and per cuboid hit_ticks / first_hit / clearance / clearance_tick [n_cuboids][B], from a state log [K][13][pitch]; scratch from the arena
 int uavac_launch_flown_audit(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const double *cuboids, int n_cuboids,

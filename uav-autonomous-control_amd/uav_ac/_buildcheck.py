@@ -204,6 +204,25 @@ def check_flown_separation_kernels():
     return _check_object("flown_separation.o", FLOWN_SEPARATION_KERNELS, "flown-separation", vgpr_limit=168)
 
 
+FLOWN_CONFLICT_KERNELS = ("flown_discover_kernel", "conflict_count_kernel", "conflict_list_kernel", "flown_measure_kernel")
+FLOWN_CONFLICT_LIMITS = {"flown_discover_kernel": 168, "conflict_count_kernel": 64, "conflict_list_kernel": 64, "flown_measure_kernel": 128}
+
+
+def check_flown_conflict_kernels():
+    """The kernels of csrc/flown_conflicts.hip (the conflict list of a flight, from a state log): `_check_object`, and each kernel
+    inside its own limit: the discovery, whose 48 KB LDS tile admits three workgroups per CU like `flown_separation_kernel`'s, must
+    run three waves per SIMD (<= 168 vector registers; built: 114); the measure keeps 48 log values per lane in flight and is
+    launched for four waves per SIMD (`__launch_bounds__(256, 4)`: <= 128; built: 112); the counts and the list of conflict_csr.h run
+    eight (<= 64; built: 24 each, as in minsnap_conflicts.o).  Returns {kernel: VGPRs}, None when the counts cannot be read."""
+    regs = _check_object("flown_conflicts.o", FLOWN_CONFLICT_KERNELS, "flown-conflict-list", vgpr_limit=168)
+    if regs is None:
+        return None
+    over = [(n[:70], v, limit) for k, limit in FLOWN_CONFLICT_LIMITS.items() for n, v in regs.items() if k in n and v > limit]
+    if over:
+        raise RuntimeError(f"flown-conflict-list kernels outside their budgets (name, VGPRs, limit): {over} (compiler: {compiler_version()})")
+    return regs
+
+
 FLOWN_AUDIT_KERNELS = ("flown_audit_kernel", "flown_audit_merge_kernel")
 
 
@@ -513,6 +532,8 @@ def run_all(verbose: bool = False, write_stamp: bool = True) -> dict:
               lambda r: f"{len(r)} take kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("flown_separation_kernels", check_flown_separation_kernels,
               lambda r: f"{len(r)} flown-separation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
+             ("flown_conflict_kernels", check_flown_conflict_kernels,
+              lambda r: f"{len(r)} flown-conflict-list kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("flown_audit_kernels", check_flown_audit_kernels,
               lambda r: f"{len(r)} flown-audit kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
              ("layer_kernels", check_layer_kernels,

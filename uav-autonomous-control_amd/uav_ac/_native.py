@@ -112,6 +112,8 @@ _SIGNATURES = {
     "uavac_minsnap_take_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "uavac_fleet_order_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "uavac_flown_separation_dev": (C.c_int,[_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, C.c_double, _P, _P]),
+    "uavac_flown_conflict_offsets_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, C.c_double, _P]),
+    "uavac_flown_conflicts_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, C.c_double, _P, C.c_int64, _P, _P]),
     "uavac_flown_audit_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "uavac_minsnap_row_counts_v_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P]),
     "uavac_minsnap_row_counts_ragged_v_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P]),

@@ -196,7 +196,8 @@ class ConflictList:
     """The separation audit's conflict graph in CSR form (`Engine.conflicts`, include/uavac.h uavac_minsnap_conflicts_dev): device
     tensors.  Mission i lists its partners -- every mission of its group that comes inside the radius at some row of the shared clock
     -- in the entries [offsets[i], offsets[i + 1]), in ascending batch index; a pair shows in both directions, with the same record.
-    `uav_ac.scoring.conflict_pairs` gives the unique pairs on the host."""
+    `uav_ac.scoring.conflict_pairs` gives the unique pairs on the host.  From `Engine.flown_conflicts` (uavac_flown_conflicts_dev) the
+    same record of a FLIGHT: vehicles for missions, and TICKS of the state log in the `*_row` fields."""
     offsets: "object"        # (B + 1,) i64: exclusive prefix sum of the audit's `conflicts`
     partner: "object"        # (E,) i32: batch index of the partner
     first_row: "object"      # (E,) i32: first clock row at which the pair is inside the radius
@@ -1229,6 +1230,33 @@ class Engine:
         self._bind_stream()
         self.ctx.call("uavac_flown_separation_dev", _ptr(state_log), K, B, pitch, _ptr(go), G, float(radius), _ptr(sep), _ptr(block))
         return SeparationAudit(sep, *block.unbind(0), block)
+
+    def flown_conflicts(self, state_log, radius: float, groups=None) -> ConflictList:
+        """Every pair of vehicles that `Engine.flown_separation` counts as a conflict, with when and how near
+        (`uavac_flown_conflict_offsets_dev`, `uavac_flown_conflicts_dev`): vehicle i lists each vehicle of its group that the flight
+        brought inside `radius` at some tick, in ascending batch index -- from the positions in a rollout's state log, on the device,
+        bit for bit what NumPy gives on the log (`uav_ac.scoring.conflicts_from_log`).  `state_log`, `radius` and `groups` as
+        `Engine.flown_separation` takes them (a log in another layout is a ValueError).
+        -> ConflictList whose `*_row` fields hold TICKS here: `first_row` and `last_row` the first and the last tick inside,
+        `rows_inside` the number of ticks inside (a tick at which either position is NaN is not inside), `min_row` the tick of the pair's
+        closest approach (clock row of the plan = tick // F, with F the vehicle's `inner_per_outer`).  On the same log diff(offsets)
+        is the flown audit's `conflicts`, the least `first_row` of a vehicle its `first_conflict`, and its (min_distance, row, partner)
+        the least (min_distance, min_row, partner) of the vehicle's entries; the two directions of a pair carry the same record
+        (`uav_ac.scoring.conflict_pairs`; `scoring.conflict_diff` compares the list with `Engine.conflicts` of the plan).
+        ONE small host read: the number of entries, to size the result; without entries the second launch is skipped."""
+        torch = self._torch
+        K, B, pitch = self._log_view(state_log)
+        go, G = self._groups(groups, B)
+        log_args = (_ptr(state_log), K, B, pitch, _ptr(go), G, float(radius))
+        offsets = torch.empty((B + 1,), dtype=torch.int64, device=self.device)
+        self._bind_stream()
+        self.ctx.call("uavac_flown_conflict_offsets_dev", *log_args, _ptr(offsets))
+        E = int(offsets[B].item())                                       # the one sync
+        dist = torch.empty((E,), dtype=torch.float64, device=self.device)
+        block = torch.empty((nat.CONF_ROWS, E), dtype=torch.int32, device=self.device)
+        if E:
+            self.ctx.call("uavac_flown_conflicts_dev", *log_args, _ptr(offsets), E, _ptr(dist), _ptr(block))
+        return ConflictList(offsets, *block.unbind(0), dist, E, block)
 
     def flown_audit(self, state_log, obstacles=None) -> FlightAudit:
         """The plan audit of a FLIGHT (`uavac_flown_audit_dev`): `Engine.audit` says what a plan's rows would show, this what the

@@ -20,7 +20,9 @@ turns such a list into its unique pairs.  `stagger_from_rows` states the rule of
 (`Engine.stagger`, uavac_minsnap_stagger_dev: start delays by priority) on sampled rows, and `stagger_ok` judges its result.
 `delay_rows` states on sampled rows what the delay transform (`Engine.delay`, uavac_minsnap_delay_dev) makes of a plan and its start
 rows, and `separation_from_log` is `separation_from_rows` for a FLIGHT: the rule of `Engine.flown_separation`
-(uavac_flown_separation_dev) on the positions of a rollout's state log.  `layer_from_rows` states the rule of the second lever on
+(uavac_flown_separation_dev) on the positions of a rollout's state log, `conflicts_from_log` likewise the rule of
+`Engine.flown_conflicts` (uavac_flown_conflicts_dev: every pair the flight brought inside the radius), and `conflict_diff` sets a planned
+and a flown list side by side: the pairs in both, only planned, only flown.  `layer_from_rows` states the rule of the second lever on
 the audit (`Engine.layer`, uavac_minsnap_layer_dev: offset layers by priority at fixed starts), `layer_obstacles_from_rows` the same
 search when it also refuses layers inside cuboids (uavac_minsnap_layer_obs_dev), `layer_ok` and `blocked_out` judge the result, and
 `shift_coeffs` states the transform that makes granted offsets part of the plan (`Engine.shift`, uavac_minsnap_shift_dev).
@@ -436,6 +438,75 @@ def separation_from_log(log, radius, group_offsets=None):
             isep[SEP_FIRST_CONFLICT, b] = hit[0] if len(hit) else -1
             isep[SEP_COMPARED, b] = int(valid.any(axis=0).sum())
     return sep, isep
+
+
+def conflicts_from_log(log, radius, group_offsets=None):
+    """The conflict list of a FLIGHT, recomputed from a state log -- the SPECIFICATION of `uavac_flown_conflict_offsets_dev` and
+    `uavac_flown_conflicts_dev` (csrc/flown_conflicts.hip), which are tested against it bit for bit.  NumPy on the host; the log, the
+    clock (the tick), the groups, the rounding and the validity rule exactly as in `separation_from_log`: d^2 = (dx * dx + dy * dy) +
+    dz * dz with separately rounded products and sums, inside means d^2 < r^2 strictly, a pair-tick is VALID iff its d^2 is not NaN.
+    Vehicle i lists every vehicle j != i of its group that has a valid pair-tick inside the radius, in ascending j; a vehicle whose log
+    is NaN throughout lists nothing and is listed by nobody, and a NaN tick in the middle of an incursion is not inside.
+    -> (offsets (B + 1,) i64, pair_d (E,) f64, pair_i (CONF_ROWS, E) i32), the shape of `conflicts_from_rows`: the entries of vehicle i
+    are [offsets[i], offsets[i + 1]); per entry the pair's minimum distance over its valid pair-ticks (the minimum of the squares, one
+    sqrt), and the partner, the first and the last tick inside, the number of ticks inside, the tick of the minimum (the lowest one on
+    a tie)."""
+    log = _host(log)
+    if log.ndim != 3 or log.shape[0] < 1 or log.shape[1] < 3 or log.shape[2] < 1:
+        raise ValueError("log must have shape (K, >= 3, B) with K >= 1 and B >= 1")
+    B = log.shape[2]
+    radius = _radius(radius)
+    go = _group_offsets(group_offsets, B)
+    r2 = radius * radius
+    per_vehicle = [[] for _ in range(B)]                                                  # (partner, first, last, inside, tick of the minimum, d^2)
+    for g in range(len(go) - 1):
+        g0, g1 = int(go[g]), int(go[g + 1])
+        if g1 - g0 < 2:
+            continue
+        P = np.ascontiguousarray(log[:, 0:3, g0:g1])                                       # (K, 3, n): ticks first, partners ascending
+        for a in range(g1 - g0):
+            with np.errstate(invalid="ignore", over="ignore"):
+                dx, dy, dz = (P[:, c, a][:, None] - P[:, c, :] for c in range(3))          # (K, n)
+                d2 = (dx * dx + dy * dy) + dz * dz
+                inside = d2 < r2                                                           # (a NaN is never below anything)
+            inside[:, a] = False                                                           # nobody is their own partner
+            for c in np.flatnonzero(inside.any(axis=0)):
+                hit = np.flatnonzero(inside[:, c])
+                low = int(np.argmin(np.where(np.isnan(d2[:, c]), np.inf, d2[:, c])))       # the first minimum over the valid ticks
+                per_vehicle[g0 + a].append((g0 + c, hit[0], hit[-1], len(hit), low, d2[low, c]))
+    offsets = np.concatenate([[0], np.cumsum([len(p) for p in per_vehicle])]).astype(np.int64)
+    flat = [e for p in per_vehicle for e in p]
+    pair_i = np.array([e[:5] for e in flat], dtype=np.int32).reshape(-1, nat.CONF_ROWS).T.copy()
+    pair_d = np.sqrt(np.array([e[5] for e in flat], dtype=np.float64))
+    return offsets, pair_d, pair_i
+
+
+def _pairs_of(cl) -> dict:
+    """a conflict list or the dict `conflict_pairs` made of one -> that dict"""
+    return cl if isinstance(cl, dict) else conflict_pairs(cl)
+
+
+def conflict_diff(planned, flown, inner_per_outer: int = 1) -> dict:
+    """Did tracking error create this conflict?  Two conflict lists over the same batch -- `planned` from `Engine.conflicts` (clock rows),
+    `flown` from `Engine.flown_conflicts` (ticks); each a ConflictList or the dict `conflict_pairs` gives -- compared by their unique
+    pairs i < j on the host.  -> dict of
+      `both`          (n, 2) i64: the pairs in both lists, ascending, with `flown_first_tick` (n,) the flown list's first tick inside and
+                      `planned_first_tick` (n,) the planned list's first row x `inner_per_outer` (the tick at which that row is due),
+      `only_planned`  (n, 2): planned conflicts the flight did not have,
+      `only_flown`    (n, 2): conflicts the plan did not have -- tracking error (or a plan other than the one flown) produced them."""
+    F = int(inner_per_outer)
+    if F < 1:
+        raise ValueError("inner_per_outer must be >= 1")
+    p, f = _pairs_of(planned), _pairs_of(flown)
+    pk = {(int(i), int(j)): int(r) for i, j, r in zip(p["i"], p["j"], p["first_row"])}
+    fk = {(int(i), int(j)): int(r) for i, j, r in zip(f["i"], f["j"], f["first_row"])}
+    both = sorted(set(pk) & set(fk))
+
+    def pairs(keys):
+        return np.array(sorted(keys), dtype=np.int64).reshape(-1, 2)
+    return {"both": pairs(both), "flown_first_tick": np.array([fk[k] for k in both], dtype=np.int64),
+            "planned_first_tick": np.array([pk[k] * F for k in both], dtype=np.int64),
+            "only_planned": pairs(set(pk) - set(fk)), "only_flown": pairs(set(fk) - set(pk))}
 
 
 def audit_from_log(log, cuboids=None):
