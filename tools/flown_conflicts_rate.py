@@ -7,6 +7,7 @@ radius 0.5; the flown audit's two shapes:
     65 536 vehicles in groups of 64        4 096 vehicles in one group
 
     flown_conflicts_rate.py [OUT.jsonl] [rounds]
+    flown_conflicts_rate.py [OUT.jsonl] [rounds] --against OTHER.so    both calls of this build against another build's (tools/against.py), appended
 
 The two routes must give the SAME answers (offsets and every record, bit for bit) before anything is timed.  hipEvents around each arm,
 warm-up first, the arms interleaved over rounds in one process; median, minimum and maximum per arm, one JSON line per arm with the
@@ -86,9 +87,46 @@ def spread(values):
     return {"median": round(float(np.median(values)), 3), "min": round(float(min(values)), 3), "max": round(float(max(values)), 3)}
 
 
+def main_against(out_path, rounds, other):
+    """Both calls through this build and through another one (tools/against.py), on the same log (flown once, through the Engine)."""
+    import ctypes as C
+    import against
+    from against import P, ptr as p
+    log_args = [P, P, C.c_int, C.c_int, C.c_int64, P, C.c_int, C.c_double]
+    builds = against.Builds(other, {"uavac_flown_conflict_offsets_dev": log_args + [P],
+                                    "uavac_flown_conflicts_dev": log_args + [P, C.c_int64, P, P]})
+    eng = Engine("cuda:0")
+    kw = dict(device="cuda:0")
+    for B, n in SHAPES:
+        plan = eng.plan(missions(B, M, 0, B), VEL, DT, rows=False)
+        log, _ = eng.fleet(plan).rollout(K, state_log=True)
+        ticks, _, pitch = eng._log_view(log)
+        go = torch.arange(0, B + 1, n, dtype=torch.int64, **kw)
+        torch.cuda.synchronize()
+
+        def both_calls(lib, ctx):
+            """what `Engine.flown_conflicts` does: the offsets, the host read of the entry count, the buffers, the fill"""
+            off = torch.empty((B + 1,), dtype=torch.int64, **kw)
+            args = (ctx, p(log), ticks, B, pitch, p(go), B // n, RADIUS)
+            assert lib.uavac_flown_conflict_offsets_dev(*args, p(off)) == 0
+            E = int(off[B].item())
+            d, i = torch.empty((E,), dtype=torch.float64, **kw), torch.empty((5, E), dtype=torch.int32, **kw)
+            if E:
+                assert lib.uavac_flown_conflicts_dev(*args, p(off), E, p(d), p(i)) == 0
+            return off, d, i
+        builds.alternate("flown conflict list, both calls", both_calls, rounds, B=B, group=n, ticks=ticks)
+        del plan, log, go
+        torch.cuda.empty_cache()
+    builds.write(out_path)
+
+
 def main():
-    out_path = sys.argv[1] if len(sys.argv) > 1 else None
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    from against import split_argv
+    argv, other = split_argv(sys.argv[1:])
+    out_path = argv[0] if len(argv) > 0 else None
+    rounds = int(argv[1]) if len(argv) > 1 else 5
+    if other:
+        return main_against(out_path, rounds, other)
     eng = Engine("cuda:0")
     box = eng.ctx.device_identity()
     lines = []

@@ -5,6 +5,7 @@ that keeps the log on the device: chunked pairwise distances from the same state
     65 536 vehicles in groups of 64        4 096 vehicles in one group
 
     flown_separation_rate.py [OUT.jsonl] [rounds]
+    flown_separation_rate.py [OUT.jsonl] [rounds] --against OTHER.so    the audit of this build against another build's (tools/against.py), appended
 
 The two routes must give the SAME answers (every output, bit for bit) before anything is timed.  hipEvents around each arm, warm-up
 first, the arms interleaved over rounds in one process; median, minimum and maximum per arm, one JSON line per arm with the device's
@@ -91,9 +92,38 @@ def torch_route(log, n, radius):
     return sep, isep
 
 
+def main_against(out_path, rounds, other):
+    """The flown audit through this build and through another one (tools/against.py), on the same log (flown once, through the Engine)."""
+    import ctypes as C
+    import against
+    from against import P, ptr as p
+    builds = against.Builds(other, {"uavac_flown_separation_dev": [P, P, C.c_int, C.c_int, C.c_int64, P, C.c_int, C.c_double, P, P]})
+    eng = Engine("cuda:0")
+    kw = dict(device="cuda:0")
+    for B, n in SHAPES:
+        plan = eng.plan(missions(B, M, 0, B), VEL, DT, rows=False)
+        log, _ = eng.fleet(plan).rollout(K, state_log=True)
+        ticks, _, pitch = eng._log_view(log)
+        go = torch.arange(0, B + 1, n, dtype=torch.int64, **kw)
+        torch.cuda.synchronize()
+
+        def audit(lib, ctx):
+            sep, isep = torch.empty((B,), dtype=torch.float64, **kw), torch.empty((5, B), dtype=torch.int32, **kw)
+            assert lib.uavac_flown_separation_dev(ctx, p(log), ticks, B, pitch, p(go), B // n, RADIUS, p(sep), p(isep)) == 0
+            return sep, isep
+        builds.alternate("flown separation audit", audit, rounds, B=B, group=n, ticks=ticks)
+        del plan, log, go
+        torch.cuda.empty_cache()
+    builds.write(out_path)
+
+
 def main():
-    out_path = sys.argv[1] if len(sys.argv) > 1 else None
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    from against import split_argv
+    argv, other = split_argv(sys.argv[1:])
+    out_path = argv[0] if len(argv) > 0 else None
+    rounds = int(argv[1]) if len(argv) > 1 else 5
+    if other:
+        return main_against(out_path, rounds, other)
     eng = Engine("cuda:0")
     box = eng.ctx.device_identity()
     lines = []

@@ -5,6 +5,7 @@ GPU.  Eight segments (the bench's generator), velocity 3, dt 0.01, radius 0.5, n
     65 536 missions in groups of 64        4 096 missions in one group
 
     separation_rate.py [OUT.jsonl] [rounds]
+    separation_rate.py [OUT.jsonl] [rounds] --against OTHER.so    the audit of this build against another build's (tools/against.py), appended
 
 The two routes must give the SAME answers (every output, bit for bit) before anything is timed.  hipEvents around each arm, warm-up
 first, the arms interleaved over rounds in one process; median, minimum and maximum per arm, one JSON line per arm with the device's
@@ -89,9 +90,43 @@ def rows_route(eng, plan, n, H, radius):
     return sep, isep
 
 
+def main_against(out_path, rounds, other):
+    """The audit through this build and through another one (tools/against.py), on the same plan."""
+    import ctypes as C
+    import against
+    from against import P, ptr as p
+    builds = against.Builds(other, {"uavac_minsnap_row_counts_dev": [P, P, C.c_int, C.c_int, C.c_double, C.c_double, P, P, P],
+                                    "uavac_minsnap_solve_dev": [P, P, P, C.c_int, C.c_int, P, P],
+                                    "uavac_minsnap_separation_dev": [P, P, P, P, C.c_int, C.c_int, C.c_double, P, C.c_int, P, C.c_double, P, P]})
+    kw = dict(device="cuda:0")
+    for B, n in SHAPES:
+        wp = torch.as_tensor(missions(B, M, 0, B), dtype=torch.float64).to("cuda:0").contiguous()
+        times = torch.empty((B, M), dtype=torch.float64, **kw)
+        seg_rows = torch.empty((B, M), dtype=torch.int32, **kw)
+        row_offsets = torch.empty((B + 1,), dtype=torch.int64, **kw)
+        coeffs = torch.empty((B, 8 * M, 3), dtype=torch.float64, **kw)
+        L, H = builds.lib[against.THIS], builds.ctx[against.THIS]                      # planned once, by this build
+        assert L.uavac_minsnap_row_counts_dev(H, p(wp), B, M, VEL, DT, p(times), p(seg_rows), p(row_offsets)) == 0
+        assert L.uavac_minsnap_solve_dev(H, p(wp), p(times), B, M, p(coeffs), None) == 0
+        go = torch.arange(0, B + 1, n, dtype=torch.int64, **kw)
+
+        def audit(lib, ctx):
+            sep, isep = torch.empty((B,), dtype=torch.float64, **kw), torch.empty((5, B), dtype=torch.int32, **kw)
+            assert lib.uavac_minsnap_separation_dev(ctx, p(coeffs), p(seg_rows), None, B, M, DT, p(go), B // n, None, RADIUS, p(sep), p(isep)) == 0
+            return sep, isep
+        builds.alternate("separation audit", audit, rounds, B=B, group=n, m=M)
+        del wp, times, seg_rows, row_offsets, coeffs, go
+        torch.cuda.empty_cache()
+    builds.write(out_path)
+
+
 def main():
-    out_path = sys.argv[1] if len(sys.argv) > 1 else None
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    from against import split_argv
+    argv, other = split_argv(sys.argv[1:])
+    out_path = argv[0] if len(argv) > 0 else None
+    rounds = int(argv[1]) if len(argv) > 1 else 5
+    if other:
+        return main_against(out_path, rounds, other)
     eng = Engine("cuda:0")
     box = eng.ctx.device_identity()
     lines = []

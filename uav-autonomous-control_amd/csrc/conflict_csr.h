@@ -18,6 +18,8 @@
 //                          `capacity`; what does not fit raises flag 2 (capacity) or, the last round, flag 0 (the slice holds another
 //                          number of entries than the vehicle has partners: the input changed between the two calls).
 //   csr_offsets / csr_list the round drivers of the two calls; `discover(T0)` enqueues the caller's discovery of one round.
+//   pair_d2, Measure       the ends the two measure kernels share, whichever way they lay their lanes out: a pair-row's d^2, the
+//                          result of a listed pair (update per row, merge of two partial results, the write with the sentinels)
 // `takes_part` [B] (may be NULL: everybody does): 0 for a vehicle whose lanes walked garbage in the discovery -- a plan's EXCLUDED
 // mission --, which lists nothing whatever its words hold.
 #pragma once
@@ -94,6 +96,43 @@ __global__ void __launch_bounds__(256) conflict_list_kernel(const int32_t *__res
     if (last && (long long)f != hi - lo) atomicOr(&flags[0], 1);
 }
 
+// ------------------------------------------------------------------------------------------------------------------ the measure
+// What the two measure kernels do with a listed pair's positions, whichever way their lanes are laid out.  The distance WITHOUT
+// contraction, as everywhere (ROUNDING, separation_reduce.h).
+__device__ __forceinline__ double pair_d2(double xi, double yi, double zi, double xj, double yj, double zj) {
+#pragma clang fp contract(off)
+    const double dx = xi - xj, dy = yi - yj, dz = zi - zj;
+    const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    return (xx + yy) + zz;
+}
+
+// One entry's result, whole or partial: the minimum (d^2, row), the first and the last row inside the radius, the rows inside.  Exact
+// reductions that do not depend on order: a lexicographic minimum, a min, a max, a sum; a NaN d^2 is neither below the minimum nor inside.
+struct Measure {
+    double bd = std::numeric_limits<double>::infinity();
+    int bk = sepred::kNone, first = sepred::kNone, last_in = -1, inside = 0;
+
+    __device__ __forceinline__ void row(double d2, int k, double r2) {
+        if (d2 < bd) { bd = d2; bk = k; }                    // (strict: the caller's rows ascend, the lowest row of a tie stays)
+        if (d2 < r2) { first = min(first, k); last_in = max(last_in, k); ++inside; }
+    }
+    __device__ __forceinline__ void merge(double od, int ok, int ofirst, int olast, int oinside) {
+        if (od < bd || (od == bd && ok < bk)) { bd = od; bk = ok; }
+        first = min(first, ofirst);
+        last_in = max(last_in, olast);
+        inside += oinside;
+    }
+    // rows 1 .. 4 of entry e (row 0 is the partner, the list's): one correctly rounded sqrt and the sentinels
+    __device__ __forceinline__ void write(double *__restrict__ pair_d, int32_t *__restrict__ pair_i, long long e, long long capacity) const {
+        const size_t cap = (size_t)capacity;
+        pair_d[e] = sqrt(bd);
+        pair_i[cap + e] = first == sepred::kNone ? -1 : first;
+        pair_i[2 * cap + e] = last_in;
+        pair_i[3 * cap + e] = inside;
+        pair_i[4 * cap + e] = bk == sepred::kNone ? -1 : bk;
+    }
+};
+
 // ------------------------------------------------------------------------------------------------------------------ the host side
 // What the two calls of a list share: the shares per window (the audits' rule), the tile slots per round and the rounds, the scratch.
 struct Shape {
@@ -103,16 +142,7 @@ struct Shape {
 };
 
 inline void shape_of(const uavac_ctx *ctx, int B, const int64_t *group_offsets, int G, Shape &s) {
-    s.windows = (B + kTile - 1) / kTile;
-    int P = ctx->separation_split;                           // (as the separation audits size it; the results do not depend on it)
-    if (P <= 0) {
-        const int groups = group_offsets ? G : 1;
-        const int tiles = (B / groups + kTile - 1) / kTile;
-        const int wanted = ctx->n_simds * 4;
-        P = (wanted + s.windows - 1) / s.windows;
-        P = P > tiles ? tiles : P;
-    }
-    s.P = P < 1 ? 1 : (P > UAVAC_SEP_MAX_SPLIT ? UAVAC_SEP_MAX_SPLIT : P);
+    sepred::sep_shares(ctx, B, group_offsets, G, s.windows, s.P);
     const int most = s.windows;                              // j-tiles of the largest group there can be
     s.slots = ctx->conflict_slots > 0 ? ctx->conflict_slots : kMaxSlots;
     s.slots = s.slots > most ? most : s.slots;

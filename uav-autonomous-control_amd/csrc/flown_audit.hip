@@ -33,7 +33,6 @@
 
 namespace {
 
-constexpr int kLogRows = 13;                                // rows of the state log per tick
 constexpr int kTile = 64;                                   // vehicles per workgroup: one per lane
 constexpr int kWaves = 4;                                   // wavefronts per workgroup: they split the workgroup's ticks
 constexpr int kThreads = kTile * kWaves;

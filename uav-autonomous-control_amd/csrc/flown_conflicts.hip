@@ -5,13 +5,11 @@
 // uavac_flown_conflicts_dev); uav_ac.scoring.conflicts_from_log states it in NumPy, and the results are the same bits.
 //
 // Launches on the ctx stream:
-//   flown_discover_kernel     the pairs: flown_separation_kernel's loop (64-vehicle windows x j-tiles x P shares, four wavefronts that
-//                             split each chunk of 32 ticks, a j-tile's x, y and z at one tick as three coalesced 512-byte loads into the
-//                             wave's own quarter of the LDS tile, the partners as LDS broadcasts) with nothing kept but the bit per
-//                             partner that came inside the radius.  A NaN d^2 is never below r^2: validity costs nothing here.  The
-//                             merged 64-bit word of (vehicle, j-tile) goes to scratch, words [slot][B] (conflict_csr.h): ONE writer per
-//                             word, the share that owns the tile.  The first share of the first round also leaves, per vehicle, its
-//                             group's first vehicle and number of j-tiles (0 for a group of one).
+//   flown_discover_kernel     the pairs: the sweep of pair_sweep.h, which describes it, with positions READ from the log (`Flown`) and
+//                             nothing kept but the bit per partner that came inside the radius (`Bits`).  A NaN d^2 is never below
+//                             r^2: validity costs nothing here.  The merged 64-bit word of (vehicle, j-tile) goes to scratch, words
+//                             [slot][B] (conflict_csr.h): ONE writer per word.  The first share of the first round also leaves, per
+//                             vehicle, its group's first vehicle and number of j-tiles (0 for a group of one).
 //   conflict_count_kernel,    conflict_csr.h: the CSR machinery the plan's list (minsnap_conflicts.hip) uses, one copy -- the popcounts
 //   conflict_list_kernel      into the offsets' scan; the words bit by bit into row 0 of the vehicle's slice, bounded, flags 2 and 0;
 //                             the rounds over "conflict_slots"
@@ -21,10 +19,8 @@
 //                             pitch doubles apart from tick to tick: nothing coalesces ALONG the clock, so the lanes are laid ACROSS
 //                             the entries instead.  Consecutive entries have the same owner or the next one, and ascending partners of
 //                             one group: at one tick the 64 lanes of a load read columns of one group's span of a log row -- 512 bytes
-//                             in groups of 64, four cache lines per load instead of 64.  The reductions -- first tick inside (min), last
-//                             (max), ticks inside (sum), the lexicographic minimum of (d^2, tick) -- are exact and independent of
-//                             order: over the ticks of a wave in ascending order, then over the four waves through LDS; a NaN d^2 is
-//                             neither below the minimum nor inside.  One correctly rounded sqrt comes last.  Every entry is measured by
+//                             in groups of 64, four cache lines per load instead of 64.  The result of a wave's ticks, the merge of the
+//                             four waves (through LDS) and the write are csr::Measure (conflict_csr.h).  Every entry is measured by
 //                             its own lane (both directions of a pair: twice the arithmetic, one writer per entry and no search for the
 //                             reverse entry); workgroups that are neighbours in the list are placed on the same XCD (xcd_contiguous), so
 //                             that a group's columns, which they re-read, are found in that XCD's L2.
@@ -36,17 +32,15 @@
 // its own -- (xi - xj)^2 == (xj - xi)^2 bit for bit, so the two directions of a pair agree in everything but the partner.
 
 #include "conflict_csr.h"
-#include "fleet_clock.h"
+#include "pair_sweep.h"
 
 #include <cmath>
 #include <limits>
 
 namespace {
 
-using namespace sepred;                                     // the tile's shape and pair_row: shared with the audits
-using fleet::group_range;
+using namespace pair_sweep;                                 // the sweep and, through it, sepred's tile
 
-constexpr int kLogRows = 13;                                // rows of the state log per tick (positions: 0-2)
 constexpr int kPairsPerGroup = 64;                          // entries per workgroup of the measure: one per lane
 
 // ------------------------------------------------------------------------------------------------------------------ discovery
@@ -56,89 +50,12 @@ __global__ void __launch_bounds__(kThreads, 3) flown_discover_kernel(const doubl
                                                                      int slots, unsigned long long *__restrict__ words,
                                                                      int32_t *__restrict__ first, int32_t *__restrict__ tiles) {
     __shared__ double tile[kWaves * kRegion];
-    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int P = gridDim.y, p = blockIdx.y;
-    const int w0 = blockIdx.x * kTile, w1 = w0 + kTile;      // the window of vehicles this workgroup owns
-    const int b = w0 + lane;
-    const bool live = b < B;
-    const double *own = slog + (live ? b : B - 1);           // the lane's own column (a lane past the batch shadows the last vehicle)
-    const long long tick = kLogRows * pitch;                 // doubles from one tick of the log to the next
-    double *mine = tile + w * kRegion;                       // this wavefront's quarter of the tile
-    const size_t Bs = (size_t)B;
-
-    int g = 0;                                               // the group that holds vehicle w0: the last one that starts at or before it
-    if (group_offsets) {
-        int lo = 0, hi = G;
-        while (hi - lo > 1) {
-            const int mid = lo + (hi - lo) / 2;
-            if (group_offsets[mid] <= w0) lo = mid; else hi = mid;
-        }
-        g = lo;
-    }
-    for (; g < G; ++g) {                                     // (uniform: every thread of the workgroup sees the same groups)
-        int g0, g1;
-        group_range(group_offsets, g, B, g0, g1);
-        if (g0 >= w1 || g0 >= B) break;
-        if (g1 <= w0 || g1 == g0) continue;
-        const bool act = live && b >= g0 && b < g1;
-        const int n_tiles = (g1 - g0 + kTile - 1) / kTile;
-        const int live_tiles = g1 - g0 >= 2 ? n_tiles : 0;
-        if (w == 0 && act && p == 0 && T0 == 0) { first[b] = g0; tiles[b] = live_tiles; }
-        const int t_end = min(live_tiles, T0 + slots);
-        for (int t = T0 + ((p - T0) % P + P) % P; t < t_end; t += P) {      // this share's tiles of the round: t = p (mod P)
-            const int j0 = g0 + t * kTile;
-            const bool jvalid = j0 + lane < g1;
-            const double *theirs = slog + (jvalid ? j0 + lane : g1 - 1);
-            const int selfjj = b - j0;
-            const bool self_tile = j0 < w1 && j0 + kTile > w0;
-            unsigned long long mask = 0;                     // partners that came inside the radius
-            for (int k0 = w * kRows; k0 < K; k0 += kChunk) {
-                const int n = min(kRows, K - k0);            // this wavefront's ticks of the chunk
-#pragma unroll
-                for (int r = 0; r < kRows; ++r) {            // the j-tile's positions (the ticks past the log's end repeat its last one: unused)
-                    const double *at = theirs + (long long)min(k0 + r, K - 1) * tick;
-                    const double x = at[0], y = at[pitch], z = at[2 * pitch];
-                    double *o = mine + (r * kTile + lane) * 3;
-                    o[0] = jvalid ? x : nan; o[1] = jvalid ? y : nan; o[2] = jvalid ? z : nan;
-                }
-                lds_wave_fence();                            // (a wavefront reads only its own quarter)
-                const double *at = own + (long long)k0 * tick;
-                double nx = at[0], ny = at[pitch], nz = at[2 * pitch];      // the lane's own position, one tick ahead
-#pragma nounroll
-                for (int r = 0; r < n; ++r) {
-                    const double xi = nx, yi = ny, zi = nz;
-                    if (r + 1 < n) {
-                        at = own + (long long)(k0 + r + 1) * tick;
-                        nx = at[0]; ny = at[pitch]; nz = at[2 * pitch];
-                    }
-                    double rm = inf;                         // (of pair_row's results only the bits are kept)
-                    int rkey = 0;
-                    if (self_tile) pair_row<true>(mine + r * kTile * 3, xi, yi, zi, r2, selfjj, rm, rkey, mask);
-                    else pair_row<false>(mine + r * kTile * 3, xi, yi, zi, r2, selfjj, rm, rkey, mask);
-                }
-                lds_wave_fence();
-            }
-            // the four wavefronts meet: 1 .. 3 leave their bits in their quarters, wavefront 0 merges them and writes the word
-            if (w != 0) sep_waves_leave_bits(mine, lane, mask);
-            __syncthreads();
-            if (w == 0) {
-                sep_waves_meet_bits(tile, lane, mask);
-                if (act) words[(size_t)(t - T0) * Bs + b] = mask;
-            }
-            __syncthreads();
-        }
-    }
+    Flown src{slog, K, pitch};
+    Bits<false> keep{T0, slots, words, first, nullptr, tiles};
+    sweep(tile, src, keep, B, group_offsets, G, r2);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the measure
-__device__ __forceinline__ double pair_d2(double xi, double yi, double zi, double xj, double yj, double zj) {
-#pragma clang fp contract(off)
-    const double dx = xi - xj, dy = yi - yj, dz = zi - zj;
-    const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
-    return (xx + yy) + zz;
-}
-
 __global__ void __launch_bounds__(kThreads, 4) flown_measure_kernel(const double *__restrict__ slog, int K, int B, long long pitch, double r2,
                                                                     const int32_t *__restrict__ owner, long long capacity,
                                                                     double *__restrict__ pair_d, int32_t *__restrict__ pair_i) {
@@ -156,8 +73,7 @@ __global__ void __launch_bounds__(kThreads, 4) flown_measure_kernel(const double
     const long long tick = kLogRows * pitch;
     const int Kl = live ? K : 0;
 
-    double bd = std::numeric_limits<double>::infinity();
-    int bk = kNone, first = kNone, last_in = -1, inside = 0;
+    csr::Measure res;
     for (int k0 = w * kRows; k0 < Kl; k0 += kChunk) {
         double pi[kRows][3], pj[kRows][3];
 #pragma unroll
@@ -169,34 +85,22 @@ __global__ void __launch_bounds__(kThreads, 4) flown_measure_kernel(const double
 #pragma unroll
         for (int r = 0; r < kRows; ++r) {
             const int k = k0 + r;
-            const double d2 = k < K ? pair_d2(pi[r][0], pi[r][1], pi[r][2], pj[r][0], pj[r][1], pj[r][2])
-                                    : std::numeric_limits<double>::quiet_NaN();
-            if (d2 < bd) { bd = d2; bk = k; }                // (strict: the wave's ticks ascend, the lowest tick of a tie stays)
-            if (d2 < r2) { first = min(first, k); last_in = max(last_in, k); ++inside; }
+            res.row(k < K ? csr::pair_d2(pi[r][0], pi[r][1], pi[r][2], pj[r][0], pj[r][1], pj[r][2]) : std::numeric_limits<double>::quiet_NaN(),
+                    k, r2);
         }
     }
-    // the four wavefronts of the entry: the minimum by (d^2, tick), the first tick by min, the last by max, the ticks inside by sum
+    // the four wavefronts of the entry
     if (w != 0) {
-        meet_d[w - 1][lane] = bd;
-        meet_i[w - 1][0][lane] = bk; meet_i[w - 1][1][lane] = first; meet_i[w - 1][2][lane] = last_in; meet_i[w - 1][3][lane] = inside;
+        meet_d[w - 1][lane] = res.bd;
+        meet_i[w - 1][0][lane] = res.bk; meet_i[w - 1][1][lane] = res.first; meet_i[w - 1][2][lane] = res.last_in;
+        meet_i[w - 1][3][lane] = res.inside;
     }
     __syncthreads();
     if (w == 0 && live) {
 #pragma unroll
-        for (int v = 0; v < kWaves - 1; ++v) {
-            const double od = meet_d[v][lane];
-            const int ok = meet_i[v][0][lane];
-            if (od < bd || (od == bd && ok < bk)) { bd = od; bk = ok; }
-            first = min(first, meet_i[v][1][lane]);
-            last_in = max(last_in, meet_i[v][2][lane]);
-            inside += meet_i[v][3][lane];
-        }
-        const size_t cap = (size_t)capacity;
-        pair_d[e] = sqrt(bd);
-        pair_i[cap + e] = first == kNone ? -1 : first;
-        pair_i[2 * cap + e] = last_in;
-        pair_i[3 * cap + e] = inside;
-        pair_i[4 * cap + e] = bk == kNone ? -1 : bk;
+        for (int v = 0; v < kWaves - 1; ++v)
+            res.merge(meet_d[v][lane], meet_i[v][0][lane], meet_i[v][1][lane], meet_i[v][2][lane], meet_i[v][3][lane]);
+        res.write(pair_d, pair_i, e, capacity);
     }
 }
 

@@ -7,44 +7,32 @@
 // Three launches on the ctx stream:
 //   separation_prepass_kernel   per mission: fleet_clock.h's pre-pass and nothing else -- the row total N (0: EXCLUDED) and the clamped
 //                               start row, in ctx scratch
-//   minsnap_separation_kernel   the pairs.  A workgroup owns the 64 consecutive missions [64 x, 64 x + 64) of the batch, one per lane (i),
-//                               and visits every group that reaches into this window, with the lanes of other groups idle.  Per group
-//                               it walks the group's missions in j-tiles of 64 and, per j-tile, the group's clock from 0 to its horizon
-//                               in chunks of 32 rows.  Its four wavefronts split each chunk: wave w takes rows 8 w .. 8 w + 7.  For its
-//                               rows a wave first evaluates the j-tile's positions into its own quarter of the LDS tile (lane = j: the
-//                               clock walk of fleet_clock.h -- forward segment walk, position-only Horner, the segment's coefficients
-//                               fetched per chunk), then each lane evaluates its OWN position once per row in the same way and
-//                               reads the 64 partners' positions as LDS broadcasts (every lane reads the same address).  A wave reads
-//                               only what it wrote itself: no workgroup barrier inside the clock loop.
-//                               Excluded partners and lanes past the group's end are NaN positions: a NaN distance is never below
-//                               anything, so they cost no instruction; the lane's own entry is turned into +inf in the one tile that
-//                               holds it.  Per row the lane keeps the row's minimum and its partner (strict <, partners ascending), per
-//                               j-tile the minimum and its row (strict <, rows ascending), one bit per partner that came inside the
-//                               radius, and the first row with anybody inside.  At the end of a j-tile the four waves meet (through the
-//                               LDS tile, which is dead by then): the minima merge by the full lexicographic order (d^2, row, partner),
-//                               the bits by OR -- their popcount is the tile's share of `conflicts` --, the first rows by min.
-//                               gridDim.y = P workgroups share a window: workgroup p takes j-tiles p, p + P, ... and leaves one
-//                               partial record per mission in scratch
+//   minsnap_separation_kernel   the pairs: the sweep that pair_sweep.h describes, with positions walked from the coefficients and the
+//                               full record kept -- WRITTEN OUT here, the one pair kernel that is not an instantiation of that
+//                               template: as `sweep<Planned, Record>` the compiler scheduled its pair loop differently and the audit
+//                               of 4 096 missions in one group took 1.003 x the time.  A change to the sweep's group loop,
+//                               tile loop or barriers belongs in both places.  Per mission and share of its window one partial record
+//                               in scratch: minimum (d^2, row, partner), conflicts, first row with anybody inside, and the partners
+//                               compared: everybody else of the group who takes part
 //   separation_merge_kernel     per mission: the P partial records merged the same way, one correctly rounded sqrt, the sentinels
 // Every reduction is a lexicographic minimum, an integer sum over disjoint partners, an OR or an integer minimum: exact and independent
 // of order, so the outputs depend neither on P, nor on the tile or chunk sizes, nor on what else is in the batch; each output has one
 // writer and there are no atomics but the sticky flag.  The price is the factor 2 of not using d(i, j) = d(j, i).
-// The reduction itself -- the pair loop of a row, the order, the meeting of the waves, the merge of the partial records -- is in
-// separation_reduce.h, shared with the audit of a FLIGHT (flown_separation.hip), which reads its positions from a state log.  The clock
-// itself -- a mission's segments, the pre-pass, the walk, the group clamp -- is in fleet_clock.h, shared with the two searches that act
-// on this audit's verdict (fleet_search.h).
+// The reduction itself -- the pair loop of a row, the order, the meeting of the waves, the merge of the partial records, the shares per
+// window -- is in separation_reduce.h; the clock -- a mission's segments, the pre-pass, the walk, the group clamp -- in fleet_clock.h,
+// shared with the two searches that act on this audit's verdict (fleet_search.h).
 //
 // ROUNDING (part of the contract): positions by the sampler's fma chain (minsnap_eval_pos), the distance WITHOUT contraction: dx = xi -
 // xj, ..., d^2 = (dx dx + dy dy) + dz dz, each product and sum rounded on its own.
 
-#include "fleet_clock.h"
+#include "pair_sweep.h"
 
 #include <cmath>
 #include <limits>
 
 namespace {
 
-using namespace fleet;                                      // the clock, the pre-pass and, through it, sepred's tile and reduction
+using namespace pair_sweep;                                 // the sweep and, through it, the clock, the pre-pass and sepred's tile and reduction
 
 // ------------------------------------------------------------------------------------------------------------------ pre-pass
 __global__ void __launch_bounds__(kThreads) separation_prepass_kernel(const double *__restrict__ coeffs, const int32_t *__restrict__ seg_rows,
@@ -177,20 +165,8 @@ __global__ void __launch_bounds__(kThreads) separation_merge_kernel(const int32_
 
 int uavac_launch_separation(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
                             const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double *sep, int32_t *isep) {
-    const int windows = (B + kTile - 1) / kTile;
-    // Shares per window: a window's workgroups split the j-tiles of its group.  The host knows the groups' sizes only on average (B / G:
-    // the offsets are on the device), which is enough to see whether the windows alone give the chip enough workgroups to balance --
-    // about four per SIMD -- or whether a few large groups have to be spread.  Measured at 4 096 missions in one group (64 windows):
-    // 1 / 8 / 12 / 24 / 64 shares take 85.7 / 13.0 / 10.9 / 10.2 / 9.8 ms.  The results do not depend on it (option "separation_split").
-    int P = ctx->separation_split;
-    if (P <= 0) {
-        const int groups = group_offsets ? G : 1;
-        const int tiles = (B / groups + kTile - 1) / kTile;
-        const int wanted = ctx->n_simds * 4;
-        P = (wanted + windows - 1) / windows;
-        P = P > tiles ? tiles : P;
-    }
-    P = P < 1 ? 1 : (P > UAVAC_SEP_MAX_SPLIT ? UAVAC_SEP_MAX_SPLIT : P);
+    int windows, P;
+    sep_shares(ctx, B, group_offsets, G, windows, P);
     const size_t Bs = (size_t)B;
     if (int rc = uavac_arena_reserve(ctx, 2 * uavac_arena_size(Bs * 4) + uavac_arena_size(P * Bs * 8) + uavac_arena_size(P * 5 * Bs * 4)))
         return rc;

@@ -7,10 +7,13 @@
 //   sep_waves_leave/meet  the four wavefronts of a workgroup merge their results of a j-tile through the tile, which is dead by then
 //   sep_merge_partials    the P partial records of a mission (one per workgroup that shared its window) merged the same way
 //   sep_write             one correctly rounded sqrt and the sentinels
+//   sep_shares            (host) the windows and the shares per window of a launch
 // Every reduction is a lexicographic minimum, an integer sum over disjoint partners, an OR or an integer minimum: exact and independent
 // of order.  ROUNDING (part of both contracts, include/uavac.h): the distance WITHOUT contraction, dx = xi - xj, ..., d^2 = (dx dx + dy
 // dy) + dz dz, each product and sum rounded on its own.
 #pragma once
+
+#include "uavac_internal.h"
 
 #include <cmath>
 #include <limits>
@@ -120,6 +123,24 @@ __device__ __forceinline__ void sep_write(double *__restrict__ sep, int32_t *__r
     isep[2 * Bs + b] = conf;
     isep[3 * Bs + b] = first == kNone ? -1 : first;
     isep[4 * Bs + b] = compared;
+}
+
+// The launch shape of every kernel that sweeps the pairs (pair_sweep.h): the 64-vehicle windows of the batch, and the shares P per
+// window -- a window's workgroups split the j-tiles of its group.  The host knows the groups' sizes only on average (B / G: the offsets
+// are on the device), which is enough to see whether the windows alone give the chip enough workgroups to balance -- about four per
+// SIMD -- or whether a few large groups have to be spread.  Measured at 4 096 missions in one group (64 windows): 1 / 8 / 12 / 24 / 64
+// shares take 85.7 / 13.0 / 10.9 / 10.2 / 9.8 ms.  The results do not depend on it (option "separation_split").
+inline void sep_shares(const uavac_ctx *ctx, int B, const int64_t *group_offsets, int G, int &windows, int &P) {
+    windows = (B + kTile - 1) / kTile;
+    P = ctx->separation_split;
+    if (P <= 0) {
+        const int groups = group_offsets ? G : 1;
+        const int tiles = (B / groups + kTile - 1) / kTile;
+        const int wanted = ctx->n_simds * 4;
+        P = (wanted + windows - 1) / windows;
+        P = P > tiles ? tiles : P;
+    }
+    P = P < 1 ? 1 : (P > UAVAC_SEP_MAX_SPLIT ? UAVAC_SEP_MAX_SPLIT : P);
 }
 
 }  // namespace sepred

@@ -91,6 +91,8 @@ static inline int uavac_fail(uavac_ctx *ctx, int code, const char *msg) {
     return code;
 }
 
+constexpr int kLogRows = 13;   // rows of the rollout's state log per tick ([K][13][pitch] f64; positions: rows 0-2), for every kernel that reads one
+
 // blockIdx -> tile such that the blocks of one XCD own a contiguous range of tiles; a bijection on [0, n) for every
 // n.  Workgroups go to the chip's 8 XCDs round-robin (blockIdx % 8); when consecutive tiles are consecutive in memory,
 // this gives every XCD's L2 one contiguous span to stream to HBM instead of every eighth piece.  Store-only probes:
