@@ -7,311 +7,19 @@ happens in the hand-written HIP kernels behind the C ABI (include/uavac.h).  No 
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
 
 from . import _native as nat
-
-_P = C.c_void_p
+from .plans import (ConflictList, DeconflictResult, FlightAudit, LayerResult, Plan, PlanAudit, RaggedBatch, RaggedPlan,  # noqa: F401
+                    RetimeResult, RRTDeviceBatch, Segments, SeparationAudit, StaggerResult, TimeOptResult, _ptr, segments,
+                    uniform_offsets)  # (the plans and result records live in uav_ac/plans.py; every name is re-exported here)
 
 
 def _torch():
     import torch
     return torch
-
-
-def _ptr(t) -> _P:
-    return _P(0 if t is None else t.data_ptr())
-
-
-@dataclass
-class Plan:
-    """Device-resident result of planning B missions of m segments."""
-    B: int
-    m: int
-    velocity: float
-    dt: float
-    waypoints: "object"      # (B, m+1, 3) f64
-    times: "object"          # (B, m) f64
-    seg_rows: "object"       # (B, m) i32
-    row_offsets: "object"    # (B+1,) i64
-    coeffs: "object"         # (B, 8m, 3) f64
-    status: "object"         # (B,) i32: 0 ok, 1 singular
-    traj: "object"           # (N, 11) f64, missions back to back; None for a rows-free plan (Engine.plan(..., rows=False))
-    total_rows: int          # N (known for a rows-free plan too: what the root of a plan gather will sample; after
-                             # `Engine.replan` it is re-read from the device on first use, see _plan_total_rows)
-    yaw: "object" = None     # (N,) f64 or None: the yaw column on its own (== traj[:, 9]); one way to feed the plan-fed rollout
-    first_yaw: "object" = None   # (B,) f64: heading of each mission's first row that has one; lets the rollout scan the yaw itself
-    placement_ms: "object" = None    # sampler times of the candidate row buffers when plan(..., placement_trials > 1) chose one
-    pooled: bool = False             # the rows live in the Engine's pooled buffer (shared with every other pooled plan of that Engine)
-    epoch: int = 0                   # bumped whenever the plan is re-solved / re-sampled in place (Engine.replan / solve / sample):
-                                     # an attached Fleet then rebuilds the yaw scan it carries instead of trusting a stale one
-    velocities: "object" = None      # (B,) f64, device: one cruise speed per mission (`velocity` is then NaN); None = the one `velocity`
-    boundary: "object" = None        # (B, 6, 3) f64, device: (v, a, j) at the first waypoint (rows 0-2) and at the last (rows 3-5); None =
-                                     # rest to rest.  Read again at every replan / solve.  Such a plan always has `velocities` (a scalar
-                                     # `velocity` is kept and broadcast)
-    free_times: bool = False         # the durations were GIVEN (`Engine.plan(..., times=...)`, `Engine.optimize_times`), not derived from a
-                                     # speed: `velocity` is NaN, `velocities` None; replan / solve re-run the chain from `times` as they stand
-
-    def mission(self, b: int) -> np.ndarray:
-        """Rows of mission b as a fresh host array (N_b, 11) -- the reference's `full_trajectory`."""
-        if self.traj is None:
-            raise ValueError("a rows-free plan holds no rows: Engine.sample_rows(plan) samples them")
-        ro = self.row_offsets[b:b + 2].cpu().numpy()
-        return self.traj[int(ro[0]):int(ro[1])].cpu().numpy().copy()
-
-    @property
-    def algorithmic_bytes(self) -> int:
-        """24(m+1) in + 192 m coefficients out + 88 N rows out, per mission, summed (a rows-free plan: the
-        first heading, 8 B per mission, instead of the rows)."""
-        rows = 88 * self.total_rows if self.traj is not None else 8 * self.B
-        return self.B * (24 * (self.m + 1) + 192 * self.m) + rows
-
-
-def _plan_total_rows(self) -> int:
-    # `Engine.replan` leaves the new row count on the device only (replan does not synchronise): the first reader after it --
-    # `RcclComm.plan_counts`, whose all-gather sizes the root's row buffer, among them -- takes it from there.
-    if self.__dict__.get("_rows_stale"):
-        self.__dict__["_total_rows"] = int(self.row_offsets[-1].item())
-        self.__dict__["_rows_stale"] = False
-    return self.__dict__["_total_rows"]
-
-
-def _set_plan_total_rows(self, value):
-    self.__dict__["_total_rows"] = int(value)
-    self.__dict__["_rows_stale"] = False
-
-
-Plan.total_rows = property(_plan_total_rows, _set_plan_total_rows)
-
-
-@dataclass
-class RaggedPlan:
-    """Trajectories of B missions whose segment counts differ (after obstacle-driven midpoint insertion).
-    Has what `Fleet` needs from a Plan: traj, row_offsets, start positions."""
-    B: int
-    velocity: float
-    dt: float
-    final_waypoints: list            # B host arrays (m_b + 1, 3): the waypoint lists after insertion
-    row_offsets: "object"            # (B+1,) i64
-    traj: "object"                   # (N, 11) f64
-    total_rows: int
-    start_positions: "object"        # (B, 3) f64
-    converged: "object" = None       # (B,) bool, host: False where the bounded obstacle loop gave up
-    batch: "object" = None           # the RaggedBatch the rows were sampled from (coefficients, rows per spline, first headings):
-                                     # lets a Fleet fly the plan from its coefficients and RcclComm.gather_plan ship it
-
-    def mission(self, b: int) -> np.ndarray:
-        ro = self.row_offsets[b:b + 2].cpu().numpy()
-        return self.traj[int(ro[0]):int(ro[1])].cpu().numpy().copy()
-
-    def __getattr__(self, name):     # coeffs, seg_rows, seg_offsets, first_yaw, max_m, times ...: the batch's, when there is one
-        batch = self.__dict__.get("batch")
-        if batch is not None and name in ("coeffs", "seg_rows", "seg_offsets", "seg_offsets_host", "first_yaw", "max_m", "times",
-                                          "waypoints", "status"):
-            return getattr(batch, name)
-        raise AttributeError(name)
-
-
-@dataclass
-class RaggedBatch:
-    """One ragged planning call (`Engine.plan_ragged`): B missions with m_b segments each, everything per-segment back to
-    back in mission order (include/uavac.h, "Ragged batches")."""
-    B: int
-    max_m: int
-    velocity: float
-    dt: float
-    seg_offsets: "object"            # (B+1,) i64, device
-    seg_offsets_host: np.ndarray     # the same on the host
-    waypoints: "object"              # (S + B, 3) f64
-    times: "object"                  # (S,) f64
-    seg_rows: "object"               # (S,) i32
-    row_offsets: "object"            # (B+1,) i64
-    coeffs: "object"                 # (S, 8, 3) f64
-    status: "object"                 # (B,) i32, 0 = ok
-    traj: "object"                   # (N, 11) f64; None for a rows-free batch
-    total_rows: int
-    first_yaw: "object"              # (B,) f64
-    hit: "object" = None             # (S,) i32 when a cuboid was given
-    velocities: "object" = None      # (B,) f64, device: one cruise speed per mission (`velocity` is then NaN); None = the one `velocity`
-    free_times: bool = False         # the durations were given (`Engine.plan_ragged(..., times=...)`, `Engine.optimize_times`): see Plan
-
-    def mission(self, b: int) -> np.ndarray:
-        if self.traj is None:
-            raise ValueError("a rows-free batch (plan_ragged(..., rows=False)) holds no rows")
-        ro = self.row_offsets[b:b + 2].cpu().numpy()
-        return self.traj[int(ro[0]):int(ro[1])].cpu().numpy().copy()
-
-    @property
-    def start_positions(self):
-        """(B, 3): first waypoint of every mission (what `Fleet` starts its vehicles from)."""
-        import torch
-        if self.waypoints is None:                  # assembled from gathered parts: c0 of a mission's first spline IS its first waypoint
-            return self.coeffs[self.seg_offsets[:-1], 0, :]
-        first = self.seg_offsets[:-1] + torch.arange(self.B, dtype=self.seg_offsets.dtype, device=self.seg_offsets.device)
-        return self.waypoints[first]
-
-    def mission_coeffs(self, b: int) -> np.ndarray:
-        s0, s1 = int(self.seg_offsets_host[b]), int(self.seg_offsets_host[b + 1])
-        return self.coeffs[s0:s1].reshape(-1, 3).cpu().numpy().copy()
-
-
-@dataclass
-class PlanAudit:
-    """What the sampled rows of a plan would show, per mission (`Engine.audit`, include/uavac.h uavac_minsnap_audit_dev): device
-    tensors, the peaks (B,) f64 -- maxima over exactly the rows the sampler writes, NaN for a mission with a non-finite sample --
-    and per cuboid (n, B) i32 how many samples lie inside it and the mission-local index of the first one (-1: none).
-    `uav_ac.scoring.plan_feasibility` judges it against a vehicle's flight limits."""
-    rows: "object"           # (B,) f64: the mission's row total
-    speed_xy: "object"       # peak sqrt(vx^2 + vy^2)
-    ascent: "object"         # peak climb rate max(-vz) (NED)
-    descent: "object"        # peak descent rate max(vz)
-    accel_xy: "object"       # peak sqrt(ax^2 + ay^2)
-    accel_up: "object"       # peak max(-az)
-    accel_down: "object"     # peak max(az)
-    speed: "object"          # peak sqrt(vx^2 + vy^2 + vz^2)
-    hit_rows: "object"       # (n, B) i32
-    first_hit: "object"      # (n, B) i32
-    block: "object" = None   # the [AUDIT_ROWS][B] block the eight rows above are views of
-
-
-@dataclass
-class SeparationAudit:
-    """The fleet's audit against itself (`Engine.separation`, include/uavac.h uavac_minsnap_separation_dev): device tensors, per
-    mission over the shared row clock of its group.  An excluded mission (no rows, or a coefficient that is not finite) reports NaN /
-    -1 / -1 / 0 / -1 / 0.  `uav_ac.scoring.separation_ok` turns it into verdicts."""
-    min_distance: "object"   # (B,) f64: closest approach to any other mission of the group; +inf when there was nobody to compare with
-    partner: "object"        # (B,) i32: batch index of that mission (-1 with +inf / NaN)
-    row: "object"            # (B,) i32: clock row of the closest approach (-1 with +inf / NaN); from `Engine.flown_separation`: the tick
-    conflicts: "object"      # (B,) i32: how many other missions come inside the radius
-    first_conflict: "object"  # (B,) i32: first clock row with anybody inside the radius (-1: none)
-    compared: "object"       # (B,) i32: how many partners the mission was compared with (group size - 1 unless some are excluded)
-    block: "object" = None   # the [SEP_ROWS][B] i32 block the five rows above are views of
-
-
-@dataclass
-class ConflictList:
-    """The separation audit's conflict graph in CSR form (`Engine.conflicts`, include/uavac.h uavac_minsnap_conflicts_dev): device
-    tensors.  Mission i lists its partners -- every mission of its group that comes inside the radius at some row of the shared clock
-    -- in the entries [offsets[i], offsets[i + 1]), in ascending batch index; a pair shows in both directions, with the same record.
-    `uav_ac.scoring.conflict_pairs` gives the unique pairs on the host.  From `Engine.flown_conflicts` (uavac_flown_conflicts_dev) the
-    same record of a FLIGHT: vehicles for missions, and TICKS of the state log in the `*_row` fields."""
-    offsets: "object"        # (B + 1,) i64: exclusive prefix sum of the audit's `conflicts`
-    partner: "object"        # (E,) i32: batch index of the partner
-    first_row: "object"      # (E,) i32: first clock row at which the pair is inside the radius
-    last_row: "object"       # (E,) i32: last such row
-    rows_inside: "object"    # (E,) i32: how many rows (less than last - first + 1 when the pair parts and meets again)
-    min_row: "object"        # (E,) i32: clock row of the pair's closest approach, the lowest one on a tie
-    min_distance: "object"   # (E,) f64: the pair's closest approach over the group's clock
-    total: int = 0           # E, the number of entries (twice the number of pairs)
-    block: "object" = None   # the [CONF_ROWS][E] i32 block the five rows above are views of
-
-
-@dataclass
-class FlightAudit:
-    """What the vehicles DID, per vehicle, from a rollout's state log (`Engine.flown_audit`, include/uavac.h uavac_flown_audit_dev):
-    device tensors.  A tick counts iff all 13 logged values are finite; the peaks (B,) f64 are maxima over those ticks (NaN when there
-    is none), and per cuboid (n, B) the ticks spent inside it, the first of them, and the closest approach with its tick.
-    `uav_ac.scoring.flight_feasibility` judges it against a vehicle's flight limits."""
-    ticks: "object"          # (B,) f64: the number of valid ticks
-    speed_xy: "object"       # peak sqrt(vx^2 + vy^2)
-    ascent: "object"         # peak climb rate max(-vz) (NED)
-    descent: "object"        # peak descent rate max(vz)
-    speed: "object"          # peak sqrt(vx^2 + vy^2 + vz^2)
-    bank_x: "object"         # peak |2 (q1 q3 + q0 q2)|: the rotation-matrix element R13 that max_tilt clips in the command
-    bank_y: "object"         # peak |2 (q2 q3 - q0 q1)|: R23
-    body_rate: "object"      # peak sqrt(p^2 + q^2 + r^2)
-    first_bad: "object"      # (B,) i32: the first tick with a value that is not finite (-1: none)
-    hit_ticks: "object"      # (n, B) i32: valid ticks inside cuboid c
-    first_hit: "object"      # (n, B) i32: the first of them (-1: none)
-    clearance: "object"      # (n, B) f64: closest approach to cuboid c (0 inside or on a face; NaN without a valid tick)
-    clearance_tick: "object"  # (n, B) i32: its tick (the first such tick; -1 without a valid tick)
-    block: "object" = None   # the [FLOWN_AUDIT_ROWS][B] block the eight rows above are views of
-
-
-@dataclass
-class StaggerResult:
-    """Start delays that clear the separation audit (`Engine.stagger`, include/uavac.h uavac_minsnap_stagger_dev): device tensors, per
-    mission.  `Engine.separation(plan, radius, groups, start_rows=result.start_rows)` confirms it; `uav_ac.scoring.stagger_ok` turns
-    it into verdicts."""
-    start_rows: "object"     # (B,) i32: the granted start row (the base start for an unresolved or unexamined mission)
-    steps: "object"          # (B,) i32: the candidate index granted (delay = steps * step rows); -1 unresolved; -2 not examined
-    earlier: "object"        # (B,) i32: how many missions it was checked against (the included missions before it in its group)
-    block: "object" = None   # the [STAGGER_ROWS][B] i32 block the three rows above are views of
-
-
-@dataclass
-class LayerResult:
-    """Offset layers that clear the separation audit at fixed starts (`Engine.layer`, include/uavac.h uavac_minsnap_layer_dev): device
-    tensors, per mission.  `Engine.separation(Engine.shift(plan, result.offsets), radius, groups, start_rows)` confirms it;
-    `uav_ac.scoring.layer_ok` turns it into verdicts."""
-    layers: "object"         # (B,) i32: the granted layer (0 for an unresolved or unexamined mission)
-    steps: "object"          # (B,) i32: the candidate index granted (== layers); -1 unresolved; -2 not examined
-    earlier: "object"        # (B,) i32: how many missions it was checked against (the included missions before it in its group)
-    block: "object" = None   # the [LAYER_ROWS][B] i32 block the three rows above are views of; [LAYER_OBS_ROWS][B] from a search with obstacles
-    offsets: "object" = None  # (B, 3) f64: the granted layer * delta, what `Engine.shift` takes
-
-    @property
-    def blocked(self):
-        """(B,) i32 from a search with obstacles (`Engine.layer(..., obstacles=)`): how many of the candidates below the granted layer
-        (all of them for an unresolved mission) a cuboid refused -- row 3 of `block`; None from a search without obstacles."""
-        if self.block is None or self.block.shape[0] != nat.LAYER_OBS_ROWS:
-            return None
-        return self.block[nat.LAYER_OBS_ROWS - 1]
-
-
-@dataclass
-class DeconflictResult:
-    """What `Engine.deconflict` returns: the plan to fly and the two searches it was made from."""
-    plan: "object"           # rows-free RaggedBatch: delay(shift(plan, layer.offsets), stagger.start_rows)
-    stagger: StaggerResult   # the start delays (`Engine.stagger`)
-    layer: LayerResult       # the offset layers at those starts (`Engine.layer`, with the obstacles if any were given)
-    resolved: "object"       # (B,) bool, device: layer.steps >= 0
-
-
-@dataclass
-class RetimeResult:
-    """What `Engine.retime` returns: the plan at speeds that keep every converged mission inside the flight limits."""
-    plan: "object"           # of the kind that was given (Plan / RaggedBatch / RaggedPlan), planned at `velocities`; with rows if it had rows
-    velocities: "object"     # (B,) f64, device: the cruise speed of every mission after retiming (== plan.velocities)
-    factors: "object"        # (B,) f64: product of the mission's slow-down factors (1.0: never touched; NaN: a NaN peak, e.g. singular)
-    passes: int              # retimings done (0: every mission was inside the limits, or max_passes = 0)
-    converged: "object"      # (B,) bool: the mission's last audit asked for no retiming
-    audit: PlanAudit         # the audit of `plan` (no cuboids)
-
-
-@dataclass
-class TimeOptResult:
-    """What `Engine.optimize_times` returns."""
-    plan: "object"           # a NEW free_times plan of the kind that was given (Plan / RaggedBatch) on the same waypoints, planned from the
-                             # optimised durations
-    cost_before: "object"    # (B,) f64, device: snap cost of the input's durations
-    cost_after: "object"     # (B,) f64: snap cost of `plan` (== Engine.cost(plan), bit for bit); <= cost_before
-    accepted: "object"       # (B,) i32: steps the mission took (0: its durations are the input's, bit for bit)
-
-
-@dataclass
-class RRTDeviceBatch:
-    """Device-resident results of `Engine.rrt_star` (torch tensors; layouts of include/uavac.h).
-    counts[:, k]: 0 n_nodes, 1 iterations begun, 2 status, 3 entries when best_tree was stored, 4 best_path rows,
-    5 dynamic_it_counter."""
-    nodes: "object"
-    canon: "object"
-    parent: "object"
-    best_parent: "object"
-    best_path: "object"
-    counts: "object"
-    best_cost: "object"
-
-    def to_host(self):
-        """-> uav_ac.planning.rrt.RRTBatch (NumPy)."""
-        from .planning.rrt import RRTBatch
-        c = self.counts.cpu().numpy()
-        return RRTBatch(self.nodes.cpu().numpy(), self.canon.cpu().numpy(), self.parent.cpu().numpy(),
-                        self.best_parent.cpu().numpy(), self.best_path.cpu().numpy(), c[:, 0].copy(), c[:, 1].copy(),
-                        c[:, 2].copy(), c[:, 3].copy(), c[:, 4].copy(), c[:, 5].copy(), self.best_cost.cpu().numpy())
 
 
 class Engine:
@@ -444,29 +152,24 @@ class Engine:
         if not rows:
             if dense_yaw or pool or int(placement_trials) > 1:
                 raise ValueError("dense_yaw, pool and placement_trials are about the rows: not with rows=False")
-            first_yaw = torch.empty((B,), dtype=torch.float64, **kw)
-            plan = Plan(B, m, float(velocity), float(dt), wp, times, seg_rows, row_offsets, coeffs, status, None, 0, None, first_yaw,
-                        velocities=speeds, boundary=boundary)
+            plan = Plan(B, m, float(velocity), float(dt), waypoints=wp, times=times, seg_rows=seg_rows, row_offsets=row_offsets, coeffs=coeffs,
+                        status=status, traj=None, total_rows=0, first_yaw=torch.empty((B,), dtype=torch.float64, **kw), velocities=speeds,
+                        boundary=boundary)
             self.replan(plan)
             plan.epoch = 0
             plan.total_rows = int(row_offsets[-1].item())       # (the one host sync; the rows would have needed it to be allocated)
             if strict:
                 self.check(plan)
             return plan
-        if speeds is None:
-            self.ctx.call("uavac_minsnap_row_counts_dev", _ptr(wp), B, m, float(velocity), float(dt), _ptr(times),
-                          _ptr(seg_rows), _ptr(row_offsets))
-        else:
-            self.ctx.call("uavac_minsnap_row_counts_v_dev", _ptr(wp), B, m, _ptr(speeds), float(dt), _ptr(times),
-                          _ptr(seg_rows), _ptr(row_offsets))
+        self._row_counts(wp, None, B, m, velocity, speeds, dt, times, seg_rows, row_offsets)
         if boundary is None:
             self.ctx.call("uavac_minsnap_solve_dev", _ptr(wp), _ptr(times), B, m, _ptr(coeffs), _ptr(status))
         total = int(row_offsets[-1].item())                 # the one host sync: sizes the trajectory buffer
         pooled = pool and self._row_pool is not None and self._row_pool.shape[0] >= total
         traj = self._row_pool[:total] if pooled else torch.empty((total, nat.TRAJ_COLS), dtype=torch.float64, **kw)
         yaw = torch.empty((total,), dtype=torch.float64, **kw) if dense_yaw else None
-        first_yaw = torch.empty((B,), dtype=torch.float64, **kw)
-        plan = Plan(B, m, float(velocity), float(dt), wp, times, seg_rows, row_offsets, coeffs, status, traj, total, yaw, first_yaw,
+        plan = Plan(B, m, float(velocity), float(dt), waypoints=wp, times=times, seg_rows=seg_rows, row_offsets=row_offsets, coeffs=coeffs,
+                    status=status, traj=traj, total_rows=total, yaw=yaw, first_yaw=torch.empty((B,), dtype=torch.float64, **kw),
                     velocities=speeds, boundary=boundary)
         del traj                                                 # (place_rows may release the first draw: no second reference to it)
         if boundary is None:
@@ -511,7 +214,7 @@ class Engine:
         if strict and not bool(((times > 0) & torch.isfinite(times)).all()):      # (without strict: device flag 0, no rows)
             raise ValueError("times must be positive and finite")
         if rows:
-            self.ctx.call("uavac_minsnap_row_counts_t_dev", _ptr(times), _ptr(so), B, m, float(dt), _ptr(seg_rows), _ptr(row_offsets))
+            self._row_counts(wp, so, B, m, None, None, dt, times, seg_rows, row_offsets, free_times=True)
             total = int(row_offsets[-1].item())
             traj = torch.empty((total, nat.TRAJ_COLS), dtype=torch.float64, **kw)
             yaw = torch.empty((total,), dtype=torch.float64, **kw) if dense_yaw else None
@@ -519,13 +222,12 @@ class Engine:
             raise ValueError("dense_yaw is about the rows: not with rows=False")
         self.ctx.call("uavac_minsnap_plan_t_dev", _ptr(wp), _ptr(so), B, m, _ptr(times), float(dt), _ptr(seg_rows), _ptr(row_offsets),
                       _ptr(coeffs), _ptr(status), _ptr(traj), 0 if traj is None else int(traj.shape[0]), _ptr(yaw), _ptr(first_yaw))
-        total = int(row_offsets[-1].item())
+        parts = dict(waypoints=wp, times=times, seg_rows=seg_rows, row_offsets=row_offsets, coeffs=coeffs, status=status, traj=traj,
+                     total_rows=int(row_offsets[-1].item()), first_yaw=first_yaw, free_times=True)
         if ragged:
-            plan = RaggedBatch(B, m, float("nan"), float(dt), so, so_host, wp, times, seg_rows, row_offsets, coeffs, status, traj, total,
-                               first_yaw, None, None, True)
+            plan = RaggedBatch(B, m, float("nan"), float(dt), seg_offsets=so, seg_offsets_host=so_host, **parts)
         else:
-            plan = Plan(B, m, float("nan"), float(dt), wp, times, seg_rows, row_offsets, coeffs, status, traj, total, yaw, first_yaw,
-                        free_times=True)
+            plan = Plan(B, m, float("nan"), float(dt), yaw=yaw, **parts)
         if strict:
             self.check(plan)
         return plan
@@ -537,9 +239,10 @@ class Engine:
         kw = dict(device=self.device)
         m = int(m)
         z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, **kw)      # noqa: E731
-        return Plan(0, m, float(velocity), float(dt), z((0, m + 1, 3), torch.float64), z((0, m), torch.float64), z((0, m), torch.int32),
-                    z((1,), torch.int64), z((0, 8 * m, 3), torch.float64), z((0,), torch.int32),
-                    z((0, nat.TRAJ_COLS), torch.float64) if rows else None, 0, None, z((0,), torch.float64))
+        return Plan(0, m, float(velocity), float(dt), waypoints=z((0, m + 1, 3), torch.float64), times=z((0, m), torch.float64),
+                    seg_rows=z((0, m), torch.int32), row_offsets=z((1,), torch.int64), coeffs=z((0, 8 * m, 3), torch.float64),
+                    status=z((0,), torch.int32), traj=z((0, nat.TRAJ_COLS), torch.float64) if rows else None, total_rows=0,
+                    first_yaw=z((0,), torch.float64))
 
     def hbm_peak_bytes_per_s(self) -> float:
         """The device's HBM peak from its own properties (memory clock x bus width x 2, DDR): 8.0e12 on MI355X."""
@@ -609,23 +312,18 @@ class Engine:
         if plan.B == 0:
             return                                               # (`empty_plan`: nothing to plan)
         self._bind_stream()
-        cap = 0 if plan.traj is None else int(plan.traj.shape[0])
+        # the chain's entry point from (free_times, boundary, velocities): the four take the same buffers behind what they plan from
+        head = (_ptr(plan.waypoints), plan.B, plan.m)
+        out = (_ptr(plan.seg_rows), _ptr(plan.row_offsets), _ptr(plan.coeffs), _ptr(plan.status), _ptr(plan.traj),
+               0 if plan.traj is None else int(plan.traj.shape[0]), _ptr(plan.yaw), _ptr(plan.first_yaw))
         if getattr(plan, "free_times", False):                   # given durations: the chain from plan.times as they stand, never from a speed
-            self.ctx.call("uavac_minsnap_plan_t_dev", _ptr(plan.waypoints), None, plan.B, plan.m, _ptr(plan.times), plan.dt,
-                          _ptr(plan.seg_rows), _ptr(plan.row_offsets), _ptr(plan.coeffs), _ptr(plan.status), _ptr(plan.traj), cap,
-                          _ptr(plan.yaw), _ptr(plan.first_yaw))
+            self.ctx.call("uavac_minsnap_plan_t_dev", _ptr(plan.waypoints), None, plan.B, plan.m, _ptr(plan.times), plan.dt, *out)
         elif getattr(plan, "boundary", None) is not None:        # start / end in motion (read from the device at every replan, like the speeds)
-            self.ctx.call("uavac_minsnap_plan_bc_dev", _ptr(plan.waypoints), plan.B, plan.m, _ptr(plan.velocities), plan.dt,
-                          _ptr(plan.boundary), _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets), _ptr(plan.coeffs),
-                          _ptr(plan.status), _ptr(plan.traj), cap, _ptr(plan.yaw), _ptr(plan.first_yaw))
+            self.ctx.call("uavac_minsnap_plan_bc_dev", *head, _ptr(plan.velocities), plan.dt, _ptr(plan.boundary), _ptr(plan.times), *out)
         elif getattr(plan, "velocities", None) is None:
-            self.ctx.call("uavac_minsnap_plan_dev", _ptr(plan.waypoints), plan.B, plan.m, plan.velocity, plan.dt,
-                          _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets), _ptr(plan.coeffs), _ptr(plan.status),
-                          _ptr(plan.traj), cap, _ptr(plan.yaw), _ptr(plan.first_yaw))
+            self.ctx.call("uavac_minsnap_plan_dev", *head, plan.velocity, plan.dt, _ptr(plan.times), *out)
         else:                                                    # one cruise speed per mission (read from the device at every replan)
-            self.ctx.call("uavac_minsnap_plan_v_dev", _ptr(plan.waypoints), plan.B, plan.m, _ptr(plan.velocities), plan.dt,
-                          _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets), _ptr(plan.coeffs), _ptr(plan.status),
-                          _ptr(plan.traj), cap, _ptr(plan.yaw), _ptr(plan.first_yaw))
+            self.ctx.call("uavac_minsnap_plan_v_dev", *head, _ptr(plan.velocities), plan.dt, _ptr(plan.times), *out)
         plan.__dict__["_rows_stale"] = True                      # (no sync here: Plan.total_rows reads it when asked)
         plan.epoch += 1
 
@@ -639,32 +337,49 @@ class Engine:
         elif traj.shape[0] < total or traj.dtype != torch.float64 or not traj.is_contiguous():
             raise ValueError("traj must be a contiguous float64 tensor with at least total_rows rows")
         plan.traj, plan.total_rows = traj[:total], total
-        if hasattr(plan, "seg_offsets"):                         # a ragged batch: its own sampler entry, segments back to back
+        s = segments(plan)
+        if s.ragged:                                             # a ragged batch: its own sampler entry, segments back to back
             self._bind_stream()
-            self.ctx.call("uavac_minsnap_sample_ragged_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets),
-                          _ptr(plan.row_offsets), plan.B, plan.max_m, int(plan.seg_offsets_host[-1]), float(plan.dt),
-                          _ptr(plan.traj), total, None, None, _ptr(plan.first_yaw))
+            self.ctx.call("uavac_minsnap_sample_ragged_dev", _ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(s.so), _ptr(plan.row_offsets),
+                          s.B, s.m, s.S, float(plan.dt), _ptr(plan.traj), total, None, None, _ptr(plan.first_yaw))
         else:
             self.sample(plan)
         return plan
 
-    def _coeff_plan(self, plan):
+    def _coeff_plan(self, plan, refuse: str = None):
         """What the calls that read coefficients and row counts take, as the Plan or RaggedBatch that holds them: a RaggedPlan goes
         through the batch it was sampled from; one without a batch -- `plan_collision_free(device_loop=False)` -- is re-planned
-        rows-free from its final waypoints, which gives the same coefficients bit for bit."""
-        if isinstance(plan, RaggedPlan):
-            batch = plan.batch
-            if batch is None:
-                batch = self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False, rows=False)
-            plan = batch
-        return plan
+        rows-free from its final waypoints, which gives the same coefficients bit for bit, or, for the calls that cannot work on a
+        re-planned copy, refused with a ValueError of the caller's words `refuse`."""
+        if not isinstance(plan, RaggedPlan):
+            return plan
+        if plan.batch is None and refuse is not None:
+            raise ValueError(refuse)
+        return plan.batch if plan.batch is not None else self.plan_ragged(plan.final_waypoints, plan.velocity, plan.dt, strict=False,
+                                                                          rows=False)
+
+    def _first_yaw_of(self, plan, clone: bool = False):
+        """The first headings a derived batch carries over: the plan's own (`clone`: a copy of them), or computed when it has none."""
+        fy = getattr(plan, "first_yaw", None)
+        if fy is None:
+            return self.first_yaw(plan)
+        return fy.clone() if clone else fy
+
+    def _derived(self, src, *, B, max_m, seg_offsets, seg_offsets_host, seg_rows, row_offsets, coeffs, times, total_rows, first_yaw,
+                 status=None, velocities=None):
+        """The rows-free RaggedBatch every plan transform returns, assembled like `ragged_from_parts`: no waypoints (it cannot be planned
+        again from waypoints; `start_positions` falls back to c0), no rows, `free_times`; velocity and dt are `src`'s; `status` None = ok."""
+        if status is None:
+            status = self._torch.zeros((B,), dtype=self._torch.int32, device=self.device)
+        return RaggedBatch(B, max_m, float(src.velocity), float(src.dt), seg_offsets=seg_offsets, seg_offsets_host=seg_offsets_host,
+                           waypoints=None, times=times, seg_rows=seg_rows, row_offsets=row_offsets, coeffs=coeffs, status=status,
+                           traj=None, total_rows=total_rows, first_yaw=first_yaw, hit=None, velocities=velocities, free_times=True)
 
     @staticmethod
     def _plan_args(plan):
         """The leading arguments of those calls: coeffs, seg_rows, seg_offsets (NULL for a uniform Plan), B, m (the largest), dt."""
-        ragged = hasattr(plan, "seg_offsets")
-        return (_ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(plan.seg_offsets) if ragged else None, int(plan.B),
-                plan.max_m if ragged else plan.m, float(plan.dt))
+        s = segments(plan)
+        return (_ptr(plan.coeffs), _ptr(plan.seg_rows), _ptr(s.so), s.B, s.m, float(plan.dt))
 
     def _groups(self, groups, B: int, max_group: int = None):
         """`groups` as the fleet calls take it (None, a group size, or the offsets as array or tensor) -> (the offsets (G + 1,) i64 on the
@@ -741,13 +456,31 @@ class Engine:
         missions (the last one shorter); or the offsets (G + 1,) themselves, ascending from 0 to B (array or tensor).  `start_rows`
         (B,) i32: the clock row at which each mission starts (None: all 0); before it a mission waits on its first row, after its end
         it holds its last.  Never reads `plan.traj`; stream-ordered like the other _dev calls, no sync."""
-        torch = self._torch
         B, held, pair_args = self._pair_args(plan, radius, groups, start_rows)      # (`held` keeps the pointers' tensors alive)
+        return self._separation_audit("uavac_minsnap_separation_dev", pair_args, B)
+
+    def _separation_audit(self, call: str, args, B: int) -> SeparationAudit:
+        """The planned or the flown separation audit: `call` on its leading arguments `args`, into a fresh result."""
+        torch = self._torch
         sep = torch.empty((B,), dtype=torch.float64, device=self.device)
         block = torch.empty((nat.SEP_ROWS, B), dtype=torch.int32, device=self.device)
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_separation_dev", *pair_args, _ptr(sep), _ptr(block))
+        self.ctx.call(call, *args, _ptr(sep), _ptr(block))
         return SeparationAudit(sep, *block.unbind(0), block)
+
+    def _conflict_list(self, offsets_call: str, fill_call: str, args, B: int) -> ConflictList:
+        """The planned or the flown conflict list, both calls on their leading arguments `args`: the offsets, ONE small host read (the
+        number of entries, to size the result), and the fill, which is skipped without entries."""
+        torch = self._torch
+        offsets = torch.empty((B + 1,), dtype=torch.int64, device=self.device)
+        self._bind_stream()
+        self.ctx.call(offsets_call, *args, _ptr(offsets))
+        E = int(offsets[B].item())                                       # the one sync
+        dist = torch.empty((E,), dtype=torch.float64, device=self.device)
+        block = torch.empty((nat.CONF_ROWS, E), dtype=torch.int32, device=self.device)
+        if E:
+            self.ctx.call(fill_call, *args, _ptr(offsets), E, _ptr(dist), _ptr(block))
+        return ConflictList(offsets, *block.unbind(0), dist, E, block)
 
     def _pair_args(self, plan, radius, groups, start_rows):
         """What `separation` and `conflicts` take, checked once -> (B, the tensors behind the pointers, the arguments of the C call up
@@ -768,17 +501,8 @@ class Engine:
         its `first_conflict`, and its (min_distance, row, partner) the least (min_distance, min_row, partner) of the mission's
         entries.  The two directions of a pair carry the same record (`uav_ac.scoring.conflict_pairs`).  Never reads `plan.traj`.
         ONE small host read: the number of entries, to size the result; without entries the second launch is skipped."""
-        torch = self._torch
         B, held, pair_args = self._pair_args(plan, radius, groups, start_rows)      # (`held` keeps the pointers' tensors alive)
-        offsets = torch.empty((B + 1,), dtype=torch.int64, device=self.device)
-        self._bind_stream()
-        self.ctx.call("uavac_minsnap_conflict_offsets_dev", *pair_args, _ptr(offsets))
-        E = int(offsets[B].item())                                       # the one sync
-        dist = torch.empty((E,), dtype=torch.float64, device=self.device)
-        block = torch.empty((nat.CONF_ROWS, E), dtype=torch.int32, device=self.device)
-        if E:
-            self.ctx.call("uavac_minsnap_conflicts_dev", *pair_args, _ptr(offsets), E, _ptr(dist), _ptr(block))
-        return ConflictList(offsets, *block.unbind(0), dist, E, block)
+        return self._conflict_list("uavac_minsnap_conflict_offsets_dev", "uavac_minsnap_conflicts_dev", pair_args, B)
 
     def stagger(self, plan, radius: float, groups=None, start_rows=None, step: int = 1, max_steps: int = 255,
                 priority=None) -> StaggerResult:
@@ -840,21 +564,19 @@ class Engine:
         carries on the host.  A plan whose missions already have UAVAC_MAX_SEGMENTS segments is a ValueError."""
         torch = self._torch
         plan = self._coeff_plan(plan)
-        ragged = hasattr(plan, "seg_offsets")
-        B, m = int(plan.B), int(plan.max_m if ragged else plan.m)
+        s = segments(plan)
+        B, m, S_in, so_in = s.B, s.m, s.S, _ptr(s.so)
         if m >= nat.MAX_SEGMENTS:
             raise ValueError(f"a mission of {m} segments cannot take a hold segment: at most {nat.MAX_SEGMENTS} per mission")
         start = self._start_rows(start_rows, B)
         kw = dict(device=self.device)
-        S_in = int(plan.seg_offsets_host[-1]) if ragged else B * m
-        so_in = _ptr(plan.seg_offsets) if ragged else None
         # (buffers for the largest result, S_in + B segments, narrowed once the offsets are known: the one read comes last)
         tail = torch.empty((B + 2,), dtype=torch.int64, **kw)            # the segment offsets (B + 1,) and, behind them, the row total
         co = torch.empty((S_in + B, 8, 3), dtype=torch.float64, **kw)
         sr = torch.empty((S_in + B,), dtype=torch.int32, **kw)
         tm = None if plan.times is None else torch.empty((S_in + B,), dtype=torch.float64, **kw)
         row_offsets = torch.empty((B + 1,), dtype=torch.int64, **kw)
-        first_yaw = plan.first_yaw.clone() if getattr(plan, "first_yaw", None) is not None else self.first_yaw(plan)
+        first_yaw = self._first_yaw_of(plan, clone=True)
         self._bind_stream()
         self.ctx.call("uavac_minsnap_delay_offsets_dev", so_in, B, m, _ptr(start), _ptr(tail))
         self.ctx.call("uavac_minsnap_delay_dev", _ptr(plan.coeffs), _ptr(plan.times), _ptr(plan.seg_rows), so_in, B, m, float(plan.dt),
@@ -862,11 +584,10 @@ class Engine:
         self.ctx.call("uavac_minsnap_row_offsets_ragged_dev", _ptr(sr), _ptr(tail), B, m + 1, _ptr(row_offsets))
         tail[B + 1:].copy_(row_offsets[B:])
         host = tail.cpu().numpy()                                        # the one sync
-        so_host, total = host[:B + 1].copy(), int(host[B + 1])
-        S = int(so_host[-1])
-        out = RaggedBatch(B, m + 1, float(plan.velocity), float(plan.dt), tail[:B + 1], so_host, None, None if tm is None else tm[:S],
-                          sr[:S], row_offsets, co[:S], torch.zeros((B,), dtype=torch.int32, **kw), None, total, first_yaw, None, None,
-                          True)
+        S = int(host[B])
+        out = self._derived(plan, B=B, max_m=m + 1, seg_offsets=tail[:B + 1], seg_offsets_host=host[:B + 1].copy(), seg_rows=sr[:S],
+                            row_offsets=row_offsets, coeffs=co[:S], times=None if tm is None else tm[:S], total_rows=int(host[B + 1]),
+                            first_yaw=first_yaw)
         return self.sample_rows(out) if rows else out
 
     def layer(self, plan, radius: float, groups=None, start_rows=None, delta=(0.0, 0.0, -0.5), max_steps: int = 63,
@@ -941,29 +662,22 @@ class Engine:
         can move a mission into a cuboid that the original plan avoided."""
         torch = self._torch
         plan = self._coeff_plan(plan)
-        ragged = hasattr(plan, "seg_offsets")
-        B, m = int(plan.B), int(plan.max_m if ragged else plan.m)
+        s = segments(plan)
+        B, m, S = s.B, s.m, s.S
         off = self._dev(offsets, torch.float64).reshape(-1)
         if off.numel() != 3 * B:
             raise ValueError(f"one offset (x, y, z) per mission: expected ({B}, 3), got {off.numel()} numbers")
         off = off.contiguous()
-        kw = dict(device=self.device)
-        if ragged:
-            so_host = np.asarray(plan.seg_offsets_host, dtype=np.int64).copy()
-            so = plan.seg_offsets.clone()
-        else:
-            so_host = np.arange(B + 1, dtype=np.int64) * m
-            so = torch.arange(B + 1, dtype=torch.int64, **kw) * m
-        S = int(so_host[-1])
+        so = s.so.clone() if s.ragged else uniform_offsets(B, m, self.device)
         src = plan.coeffs.reshape(S, 8, 3)
-        co = torch.empty((S, 8, 3), dtype=torch.float64, **kw)
-        first_yaw = plan.first_yaw.clone() if getattr(plan, "first_yaw", None) is not None else self.first_yaw(plan)
+        co = torch.empty((S, 8, 3), dtype=torch.float64, device=self.device)
+        first_yaw = self._first_yaw_of(plan, clone=True)
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_shift_dev", _ptr(src), _ptr(so) if ragged else None, B, m, S, _ptr(off), _ptr(co))
-        tm = None if plan.times is None else plan.times.reshape(-1).clone()
-        out = RaggedBatch(B, m, float(plan.velocity), float(plan.dt), so, so_host, None, tm, plan.seg_rows.reshape(-1).clone(),
-                          plan.row_offsets.clone(), co, torch.zeros((B,), dtype=torch.int32, **kw), None, int(plan.total_rows), first_yaw,
-                          None, None, True)
+        self.ctx.call("uavac_minsnap_shift_dev", _ptr(src), _ptr(s.so), B, m, S, _ptr(off), _ptr(co))
+        out = self._derived(plan, B=B, max_m=m, seg_offsets=so, seg_offsets_host=np.array(s.so_host, dtype=np.int64),
+                            seg_rows=plan.seg_rows.reshape(-1).clone(), row_offsets=plan.row_offsets.clone(), coeffs=co,
+                            times=None if plan.times is None else plan.times.reshape(-1).clone(), total_rows=int(plan.total_rows),
+                            first_yaw=first_yaw)
         return self.sample_rows(out) if rows else out
 
     def _take_index(self, index, B: int):
@@ -1004,19 +718,18 @@ class Engine:
         device adds the read of its count)."""
         torch = self._torch
         plan = self._coeff_plan(plan)
-        ragged = hasattr(plan, "seg_offsets")
-        B, m = int(plan.B), int(plan.max_m if ragged else plan.m)
+        s = segments(plan)
+        B, m, so_in = s.B, s.m, _ptr(s.so)
         idx = self._take_index(index, B)
         n = int(idx.numel())
         kw = dict(device=self.device)
-        so_in = _ptr(plan.seg_offsets) if ragged else None
         cap = n * m                                                      # (buffers for the largest result, narrowed once the offsets are known)
         tail = torch.empty((n + 2,), dtype=torch.int64, **kw)            # the segment offsets (n + 1,) and, behind them, the row total
         co = torch.empty((cap, 8, 3), dtype=torch.float64, **kw)
         sr = torch.empty((cap,), dtype=torch.int32, **kw)
         tm = None if plan.times is None else torch.empty((cap,), dtype=torch.float64, **kw)
         row_offsets = torch.empty((n + 1,), dtype=torch.int64, **kw)
-        fy_in = plan.first_yaw if getattr(plan, "first_yaw", None) is not None else self.first_yaw(plan)
+        fy_in = self._first_yaw_of(plan)
         first_yaw = torch.empty((n,), dtype=torch.float64, **kw)
         self._bind_stream()
         self.ctx.call("uavac_minsnap_take_offsets_dev", so_in, B, m, _ptr(idx), n, _ptr(tail))
@@ -1025,13 +738,13 @@ class Engine:
         self.ctx.call("uavac_minsnap_row_offsets_ragged_dev", _ptr(sr), _ptr(tail), n, m, _ptr(row_offsets))
         tail[n + 1:].copy_(row_offsets[n:])
         at = idx.clamp(0, B - 1).long()                                  # (as the kernel clamps it)
-        status = plan.status[at] if getattr(plan, "status", None) is not None else torch.zeros((n,), dtype=torch.int32, **kw)
+        status = plan.status[at] if getattr(plan, "status", None) is not None else None
         velocities = plan.velocities[at] if getattr(plan, "velocities", None) is not None else None
         host = tail.cpu().numpy()                                        # the one sync
-        so_host, total = host[:n + 1].copy(), int(host[n + 1])
-        S = int(so_host[-1])
-        out = RaggedBatch(n, m, float(plan.velocity), float(plan.dt), tail[:n + 1], so_host, None, None if tm is None else tm[:S], sr[:S],
-                          row_offsets, co[:S], status, None, total, first_yaw, None, velocities, True)
+        S = int(host[n])
+        out = self._derived(plan, B=n, max_m=m, seg_offsets=tail[:n + 1], seg_offsets_host=host[:n + 1].copy(), seg_rows=sr[:S],
+                            row_offsets=row_offsets, coeffs=co[:S], times=None if tm is None else tm[:S], total_rows=int(host[n + 1]),
+                            first_yaw=first_yaw, status=status, velocities=velocities)
         return self.sample_rows(out) if rows else out
 
     def concat(self, plans) -> RaggedBatch:
@@ -1050,34 +763,31 @@ class Engine:
         if len(dts) != 1:
             raise ValueError(f"the plans differ in dt ({sorted(dts)}): their rows would not share a clock")
         kw = dict(device=self.device)
-        B = sum(int(p.B) for p in parts)
+        views = [segments(p) for p in parts]
         so, so_host, counts, base = [], [], [], 0
-        for p in parts:
-            if hasattr(p, "seg_offsets"):
-                part, host = p.seg_offsets.to(dtype=torch.int64, **kw), np.asarray(p.seg_offsets_host, dtype=np.int64)
-            else:
-                part, host = torch.arange(p.B + 1, dtype=torch.int64, **kw) * p.m, np.arange(p.B + 1, dtype=np.int64) * p.m
-            so.append(part[:-1] + base), so_host.append(host[:-1] + base)
-            base += int(host[-1])
+        for p, s in zip(parts, views):
+            part = s.so.to(dtype=torch.int64, **kw) if s.ragged else uniform_offsets(s.B, s.m, self.device)
+            so.append(part[:-1] + base), so_host.append(np.asarray(s.so_host[:-1], dtype=np.int64) + base)
+            base += s.S
             counts.append(p.row_offsets[1:] - p.row_offsets[:-1])
         so = torch.cat(so + [torch.full((1,), base, dtype=torch.int64, **kw)])
         so_host = np.concatenate(so_host + [np.array([base], dtype=np.int64)])
         row_offsets = torch.cat([torch.zeros((1,), dtype=torch.int64, **kw), torch.cumsum(torch.cat(counts), 0)])
         times = torch.cat([p.times.reshape(-1) for p in parts]) if all(p.times is not None for p in parts) else None
-        first_yaw = torch.cat([p.first_yaw if getattr(p, "first_yaw", None) is not None else self.first_yaw(p) for p in parts])
+        first_yaw = torch.cat([self._first_yaw_of(p) for p in parts])
         status = torch.cat([p.status.to(torch.int32) if getattr(p, "status", None) is not None else torch.zeros((p.B,), dtype=torch.int32, **kw)
                             for p in parts])
+        out = self._derived(parts[0], B=sum(s.B for s in views), max_m=max(s.m for s in views), seg_offsets=so, seg_offsets_host=so_host,
+                            seg_rows=torch.cat([p.seg_rows.reshape(-1) for p in parts]), row_offsets=row_offsets,
+                            coeffs=torch.cat([p.coeffs.reshape(-1, 8, 3) for p in parts]), times=times,
+                            total_rows=sum(int(p.total_rows) for p in parts), first_yaw=first_yaw, status=status)
         speeds = {float(p.velocity) for p in parts}
-        velocity, velocities = float(parts[0].velocity), None
         per_mission = any(getattr(p, "velocities", None) is not None for p in parts)
-        if per_mission or (len(speeds) != 1 and not all(np.isnan(v) for v in speeds)):
-            velocity = float("nan")
-            velocities = torch.cat([p.velocities if getattr(p, "velocities", None) is not None
-                                    else torch.full((p.B,), float(p.velocity), dtype=torch.float64, **kw) for p in parts])
-        return RaggedBatch(B, max(int(p.max_m if hasattr(p, "seg_offsets") else p.m) for p in parts), velocity, float(parts[0].dt), so, so_host,
-                           None, times, torch.cat([p.seg_rows.reshape(-1) for p in parts]), row_offsets,
-                           torch.cat([p.coeffs.reshape(-1, 8, 3) for p in parts]), status, None, sum(int(p.total_rows) for p in parts),
-                           first_yaw, None, velocities, True)
+        if per_mission or (len(speeds) != 1 and not all(np.isnan(v) for v in speeds)):      # no common speed: one per mission
+            out.velocity = float("nan")
+            out.velocities = torch.cat([p.velocities if getattr(p, "velocities", None) is not None
+                                        else torch.full((p.B,), float(p.velocity), dtype=torch.float64, **kw) for p in parts])
+        return out
 
     def _put_index(self, index, B: int, n: int) -> np.ndarray:
         """Where `Engine.put` puts the n missions of `other` -> (n,) i64 on the host, checked: integers (or a boolean (B,) mask with n
@@ -1222,14 +932,9 @@ class Engine:
         (a tick too) against `radius`; `compared` = the partners with at least one pair-tick whose distance is a number, so a vehicle
         whose log holds NaN is visible.  A vehicle with nobody to compare with reports +inf / -1 / -1 / 0 / -1 / 0.
         `uav_ac.scoring.separation_ok` applies unchanged.  Stream-ordered like the other _dev calls, no sync."""
-        torch = self._torch
         K, B, pitch = self._log_view(state_log)
         go, G = self._groups(groups, B)
-        sep = torch.empty((B,), dtype=torch.float64, device=self.device)
-        block = torch.empty((nat.SEP_ROWS, B), dtype=torch.int32, device=self.device)
-        self._bind_stream()
-        self.ctx.call("uavac_flown_separation_dev", _ptr(state_log), K, B, pitch, _ptr(go), G, float(radius), _ptr(sep), _ptr(block))
-        return SeparationAudit(sep, *block.unbind(0), block)
+        return self._separation_audit("uavac_flown_separation_dev", (_ptr(state_log), K, B, pitch, _ptr(go), G, float(radius)), B)
 
     def flown_conflicts(self, state_log, radius: float, groups=None) -> ConflictList:
         """Every pair of vehicles that `Engine.flown_separation` counts as a conflict, with when and how near
@@ -1244,19 +949,10 @@ class Engine:
         the least (min_distance, min_row, partner) of the vehicle's entries; the two directions of a pair carry the same record
         (`uav_ac.scoring.conflict_pairs`; `scoring.conflict_diff` compares the list with `Engine.conflicts` of the plan).
         ONE small host read: the number of entries, to size the result; without entries the second launch is skipped."""
-        torch = self._torch
         K, B, pitch = self._log_view(state_log)
         go, G = self._groups(groups, B)
-        log_args = (_ptr(state_log), K, B, pitch, _ptr(go), G, float(radius))
-        offsets = torch.empty((B + 1,), dtype=torch.int64, device=self.device)
-        self._bind_stream()
-        self.ctx.call("uavac_flown_conflict_offsets_dev", *log_args, _ptr(offsets))
-        E = int(offsets[B].item())                                       # the one sync
-        dist = torch.empty((E,), dtype=torch.float64, device=self.device)
-        block = torch.empty((nat.CONF_ROWS, E), dtype=torch.int32, device=self.device)
-        if E:
-            self.ctx.call("uavac_flown_conflicts_dev", *log_args, _ptr(offsets), E, _ptr(dist), _ptr(block))
-        return ConflictList(offsets, *block.unbind(0), dist, E, block)
+        return self._conflict_list("uavac_flown_conflict_offsets_dev", "uavac_flown_conflicts_dev",
+                                   (_ptr(state_log), K, B, pitch, _ptr(go), G, float(radius)), B)
 
     def flown_audit(self, state_log, obstacles=None) -> FlightAudit:
         """The plan audit of a FLIGHT (`uavac_flown_audit_dev`): `Engine.audit` says what a plan's rows would show, this what the
@@ -1307,10 +1003,8 @@ class Engine:
         caller (`take_flags`)."""
         torch = self._torch
         wrapper = plan if isinstance(plan, RaggedPlan) else None
-        if wrapper is not None:
-            if plan.batch is None:
-                raise ValueError("this RaggedPlan has no batch (plan_collision_free(device_loop=False)): retime eng.plan_ragged(plan.final_waypoints, ...)")
-            plan = plan.batch
+        plan = self._coeff_plan(plan, refuse="this RaggedPlan has no batch (plan_collision_free(device_loop=False)): retime "
+                                             "eng.plan_ragged(plan.final_waypoints, ...)")
         if plan.waypoints is None:
             raise ValueError("retiming plans again from the waypoints: a plan assembled from gathered parts has none")
         if getattr(plan, "boundary", None) is not None:
@@ -1319,9 +1013,8 @@ class Engine:
         if getattr(plan, "free_times", False):
             raise ValueError("a plan from given durations cannot be retimed: retiming recomputes the durations from cruise speeds, "
                              "which would discard the given ones")
-        ragged = hasattr(plan, "seg_offsets")
-        B = int(plan.B)
-        m = int(plan.max_m if ragged else plan.m)
+        s = segments(plan)
+        B, m = s.B, s.m
         V = nat.Vehicle.default() if vehicle is None else vehicle
         limits = (C.c_double * 4)(float(V.max_speed_xy), float(V.max_ascent), float(V.max_descent), float(V.max_horiz_accel))
         kw = dict(device=self.device)
@@ -1336,21 +1029,20 @@ class Engine:
         converged = torch.empty((B,), dtype=torch.int32, **kw)
         passes = C.c_int(0)
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_retime_dev", _ptr(plan.waypoints), _ptr(plan.seg_offsets) if ragged else None, B, m, _ptr(speeds),
+        self.ctx.call("uavac_minsnap_retime_dev", _ptr(plan.waypoints), _ptr(s.so), B, m, _ptr(speeds),
                       float(plan.dt), limits, float(margin), int(max_passes), _ptr(times), _ptr(seg_rows), _ptr(row_offsets),
                       _ptr(coeffs), _ptr(status), _ptr(first_yaw), _ptr(block), _ptr(factors), _ptr(converged), C.byref(passes))
-        total = int(row_offsets[-1].item())
-        if ragged:
-            out = RaggedBatch(B, m, float("nan"), float(plan.dt), plan.seg_offsets, plan.seg_offsets_host, plan.waypoints, times,
-                              seg_rows, row_offsets, coeffs, status, None, total, first_yaw, None, speeds)
+        parts = dict(waypoints=plan.waypoints, times=times, seg_rows=seg_rows, row_offsets=row_offsets, coeffs=coeffs, status=status,
+                     traj=None, total_rows=int(row_offsets[-1].item()), first_yaw=first_yaw, velocities=speeds)
+        if s.ragged:
+            out = RaggedBatch(B, m, float("nan"), float(plan.dt), seg_offsets=s.so, seg_offsets_host=s.so_host, **parts)
         else:
-            out = Plan(B, m, float("nan"), float(plan.dt), plan.waypoints, times, seg_rows, row_offsets, coeffs, status, None, total,
-                       None, first_yaw, velocities=speeds)
+            out = Plan(B, m, float("nan"), float(plan.dt), **parts)
         if plan.traj is not None:
             self.sample_rows(out)                                # the rows, once
         if wrapper is not None:
-            out = RaggedPlan(B, float("nan"), float(plan.dt), wrapper.final_waypoints, out.row_offsets, out.traj, out.total_rows,
-                             wrapper.start_positions, wrapper.converged, out)
+            out = RaggedPlan(B, float("nan"), float(plan.dt), wrapper.final_waypoints, row_offsets=out.row_offsets, traj=out.traj,
+                             total_rows=out.total_rows, start_positions=wrapper.start_positions, converged=wrapper.converged, batch=out)
         empty = torch.empty((0, B), dtype=torch.int32, **kw)
         return RetimeResult(out, speeds, factors, int(passes.value), converged != 0, PlanAudit(*block.unbind(0), empty, empty, block))
 
@@ -1360,19 +1052,15 @@ class Engine:
         four-point Gauss-Legendre quadrature, exact for the integrand and free of c^T H c's cancellation).  NaN for a mission with a
         non-finite coefficient.  Stream-ordered, no sync."""
         torch = self._torch
-        if isinstance(plan, RaggedPlan):
-            if plan.batch is None:
-                raise ValueError("this RaggedPlan has no batch, hence no coefficients")
-            plan = plan.batch
+        plan = self._coeff_plan(plan, refuse="this RaggedPlan has no batch, hence no coefficients")
         if plan.coeffs is None or plan.times is None:
             raise ValueError("the cost needs the plan's coefficients and durations")
-        ragged = hasattr(plan, "seg_offsets")
-        out = torch.empty((int(plan.B),), dtype=torch.float64, device=self.device)
-        if plan.B == 0:
+        s = segments(plan)
+        out = torch.empty((s.B,), dtype=torch.float64, device=self.device)
+        if s.B == 0:
             return out
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_cost_dev", _ptr(plan.coeffs), _ptr(plan.times), _ptr(plan.seg_offsets) if ragged else None,
-                      int(plan.B), int(plan.max_m if ragged else plan.m), _ptr(out))
+        self.ctx.call("uavac_minsnap_cost_dev", _ptr(plan.coeffs), _ptr(plan.times), _ptr(s.so), s.B, s.m, _ptr(out))
         return out
 
     def optimize_times(self, plan, iterations: int = 8, rows: Optional[bool] = None) -> TimeOptResult:
@@ -1389,31 +1077,25 @@ class Engine:
         judge.  And the new curve passes the same waypoints but not the same points in between: a plan that came out of the obstacle
         loop must be audited against its cuboids again -- `Engine.audit(result.plan, obstacles)`."""
         torch = self._torch
-        if isinstance(plan, RaggedPlan):
-            if plan.batch is None:
-                raise ValueError("this RaggedPlan has no batch: optimise eng.plan_ragged(plan.final_waypoints, ...)")
-            plan = plan.batch
+        plan = self._coeff_plan(plan, refuse="this RaggedPlan has no batch: optimise eng.plan_ragged(plan.final_waypoints, ...)")
         if getattr(plan, "boundary", None) is not None:
             raise ValueError("the duration optimisation is rest to rest: not for a plan with boundary derivatives")
         if plan.waypoints is None:
             raise ValueError("the optimisation solves again from the waypoints: a plan assembled from gathered parts has none")
         if int(iterations) < 0:
             raise ValueError("iterations must be >= 0")
-        ragged = hasattr(plan, "seg_offsets")
-        B = int(plan.B)
-        m = int(plan.max_m if ragged else plan.m)
+        s = segments(plan)
+        B, m = s.B, s.m
         kw = dict(device=self.device)
         times = plan.times.clone()
         before = torch.empty((B,), dtype=torch.float64, **kw)
         after = torch.empty((B,), dtype=torch.float64, **kw)
         accepted = torch.empty((B,), dtype=torch.int32, **kw)
-        so = plan.seg_offsets if ragged else None
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_optimize_times_dev", _ptr(plan.waypoints), _ptr(so), B, m, _ptr(times), int(iterations),
+        self.ctx.call("uavac_minsnap_optimize_times_dev", _ptr(plan.waypoints), _ptr(s.so), B, m, _ptr(times), int(iterations),
                       _ptr(before), _ptr(after), _ptr(accepted))
         with_rows = (plan.traj is not None) if rows is None else bool(rows)
-        out = self._plan_from_times(plan.waypoints, times, plan.dt, with_rows, False, so=so,
-                                    so_host=plan.seg_offsets_host if ragged else None, max_m=m)
+        out = self._plan_from_times(plan.waypoints, times, plan.dt, with_rows, False, so=s.so, so_host=s.so_host, max_m=m)
         return TimeOptResult(out, before, after, accepted)
 
     def sample_range(self, plan: Plan, b0: int, b1: int):
@@ -1459,9 +1141,9 @@ class Engine:
             traj = torch.empty((total, nat.TRAJ_COLS), dtype=torch.float64, **kw)
         elif traj.shape[0] < total or traj.dtype != torch.float64 or not traj.is_contiguous():
             raise ValueError("traj must be a contiguous float64 tensor with at least total_rows rows")
-        first_yaw = torch.empty((B,), dtype=torch.float64, **kw)
-        status = torch.zeros((B,), dtype=torch.int32, **kw)
-        plan = Plan(B, int(m), float(velocity), float(dt), None, tm, sr, row_offsets, co, status, traj[:total], total, None, first_yaw)
+        plan = Plan(B, int(m), float(velocity), float(dt), waypoints=None, times=tm, seg_rows=sr, row_offsets=row_offsets, coeffs=co,
+                    status=torch.zeros((B,), dtype=torch.int32, **kw), traj=traj[:total], total_rows=total,
+                    first_yaw=torch.empty((B,), dtype=torch.float64, **kw))
         if sample:
             self.sample(plan)
         return plan
@@ -1493,8 +1175,9 @@ class Engine:
                       _ptr(traj), int(traj.shape[0]), None, None, _ptr(first_yaw))
         tm = None if times is None else self._dev(times, torch.float64).reshape(-1)
         # the first waypoint of every mission is c0 of its first spline; the others are not needed to fly or to ship the plan
-        return RaggedBatch(B, max_m, float(velocity), float(dt), so, so_host, None, tm, sr, row_offsets, co,
-                           torch.zeros((B,), dtype=torch.int32, **kw), traj[:total], total, first_yaw, None)
+        return RaggedBatch(B, max_m, float(velocity), float(dt), seg_offsets=so, seg_offsets_host=so_host, waypoints=None, times=tm,
+                           seg_rows=sr, row_offsets=row_offsets, coeffs=co, status=torch.zeros((B,), dtype=torch.int32, **kw),
+                           traj=traj[:total], total_rows=total, first_yaw=first_yaw)
 
     def take_flags(self):
         """Synchronise and return-and-clear the sticky device-side flags of the `_dev` planning entry points:
@@ -1632,8 +1315,8 @@ class Engine:
         wp_host = wp_final.cpu().numpy()
         final_wps = [wp_host[so_final[b] + b:so_final[b + 1] + b + 1].copy() for b in range(B)]
         converged = ~failed.cpu().numpy().astype(bool)
-        return RaggedPlan(B, float(velocity), float(dt), final_wps, batch.row_offsets, batch.traj, batch.total_rows,
-                          batch.start_positions.contiguous(), converged, batch)
+        return RaggedPlan(B, float(velocity), float(dt), final_wps, row_offsets=batch.row_offsets, traj=batch.traj,
+                          total_rows=batch.total_rows, start_positions=batch.start_positions.contiguous(), converged=converged, batch=batch)
 
     def _plan_collision_free_host(self, waypoints, obstacles, velocity, dt, max_iterations, strict, recheck_passes) -> RaggedPlan:
         """Round 2's loop: every round a ragged planning batch with rows, hit flags to the host, NumPy midpoint insertion."""
@@ -1722,7 +1405,8 @@ class Engine:
         starts = torch.as_tensor(np.stack([w[0] for w in wps]), dtype=torch.float64, device=self.device)
         converged = np.ones(B, dtype=bool)
         converged[sorted(failed)] = False
-        return RaggedPlan(B, float(velocity), float(dt), wps, offsets, traj, total, starts, converged)
+        return RaggedPlan(B, float(velocity), float(dt), wps, row_offsets=offsets, traj=traj, total_rows=total, start_positions=starts,
+                          converged=converged)
 
     def plan_ragged(self, waypoints, velocity=1.0, dt: float = 0.01, cuboid=None, strict: bool = True,
                     rows: bool = True, times=None) -> RaggedBatch:
@@ -1778,39 +1462,42 @@ class Engine:
             hit = torch.empty((S,), dtype=torch.int32, **kw)
             aabb = self._dev(np.asarray(cuboid, dtype=np.float64).reshape(6), torch.float64)
         self._bind_stream()
-        if speeds is None:
-            self.ctx.call("uavac_minsnap_row_counts_ragged_dev", _ptr(wp), _ptr(so), B, max_m, float(velocity), float(dt),
-                          _ptr(times), _ptr(seg_rows), _ptr(row_offsets))
-        else:
-            self.ctx.call("uavac_minsnap_row_counts_ragged_v_dev", _ptr(wp), _ptr(so), B, max_m, _ptr(speeds), float(dt),
-                          _ptr(times), _ptr(seg_rows), _ptr(row_offsets))
+        self._row_counts(wp, so, B, max_m, velocity, speeds, dt, times, seg_rows, row_offsets)
         self.ctx.call("uavac_minsnap_solve_ragged_dev", _ptr(wp), _ptr(times), _ptr(so), B, max_m, _ptr(coeffs), _ptr(status))
+        batch = RaggedBatch(B, max_m, float(velocity), float(dt), seg_offsets=so, seg_offsets_host=so_host, waypoints=wp, times=times,
+                            seg_rows=seg_rows, row_offsets=row_offsets, coeffs=coeffs, status=status, traj=None, total_rows=0,
+                            first_yaw=first_yaw, hit=hit, velocities=speeds)
         if not rows:
             if cuboid is not None:
                 raise ValueError("the collision scan walks the rows' positions: not with rows=False")
             self.ctx.call("uavac_minsnap_first_yaw_dev", _ptr(coeffs), _ptr(seg_rows), _ptr(so), B, max_m, float(dt), _ptr(first_yaw))
-            return RaggedBatch(B, max_m, float(velocity), float(dt), so, so_host, wp, times, seg_rows, row_offsets, coeffs, status,
-                               None, int(row_offsets[-1].item()), first_yaw, None, speeds)
-        total = int(row_offsets[-1].item())
-        traj = torch.empty((total, nat.TRAJ_COLS), dtype=torch.float64, **kw)
+            batch.total_rows = int(row_offsets[-1].item())
+            return batch
+        batch.total_rows = total = int(row_offsets[-1].item())
+        batch.traj = torch.empty((total, nat.TRAJ_COLS), dtype=torch.float64, **kw)
         self.ctx.call("uavac_minsnap_sample_ragged_dev", _ptr(coeffs), _ptr(seg_rows), _ptr(so), _ptr(row_offsets), B, max_m,
-                      S, float(dt), _ptr(traj), total, _ptr(aabb), _ptr(hit), _ptr(first_yaw))
-        return RaggedBatch(B, max_m, float(velocity), float(dt), so, so_host, wp, times, seg_rows, row_offsets, coeffs, status,
-                           traj, total, first_yaw, hit, speeds)
+                      S, float(dt), _ptr(batch.traj), total, _ptr(aabb), _ptr(hit), _ptr(first_yaw))
+        return batch
+
+    def _row_counts(self, wp, so, B: int, m: int, velocity, velocities, dt: float, times, seg_rows, row_offsets, free_times: bool = False):
+        """Durations, row counts and row offsets by the entry point that (`free_times`, `velocities`, ragged: `so` is not None) pick:
+        from the durations as given, or from |leg| / speed at one cruise speed or at one per mission.  (The caller binds the stream.)"""
+        out = (_ptr(seg_rows), _ptr(row_offsets))
+        if free_times:
+            self.ctx.call("uavac_minsnap_row_counts_t_dev", _ptr(times), _ptr(so), B, m, float(dt), *out)
+            return
+        name = {(False, False): "uavac_minsnap_row_counts_dev", (False, True): "uavac_minsnap_row_counts_v_dev",
+                (True, False): "uavac_minsnap_row_counts_ragged_dev", (True, True): "uavac_minsnap_row_counts_ragged_v_dev"}
+        head = (_ptr(wp),) if so is None else (_ptr(wp), _ptr(so))
+        self.ctx.call(name[so is not None, velocities is not None], *head, B, m, float(velocity) if velocities is None else _ptr(velocities),
+                      float(dt), _ptr(times), *out)
 
     def solve(self, plan: Plan):
         """Re-run times/row counts + coefficient solve into plan's buffers (no allocation, no sync); a `free_times` plan keeps its
         durations and re-runs the row counts and the solve from them."""
         self._bind_stream()
-        if getattr(plan, "free_times", False):
-            self.ctx.call("uavac_minsnap_row_counts_t_dev", _ptr(plan.times), None, plan.B, plan.m, plan.dt, _ptr(plan.seg_rows),
-                          _ptr(plan.row_offsets))
-        elif getattr(plan, "velocities", None) is None:
-            self.ctx.call("uavac_minsnap_row_counts_dev", _ptr(plan.waypoints), plan.B, plan.m, plan.velocity, plan.dt,
-                          _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets))
-        else:
-            self.ctx.call("uavac_minsnap_row_counts_v_dev", _ptr(plan.waypoints), plan.B, plan.m, _ptr(plan.velocities), plan.dt,
-                          _ptr(plan.times), _ptr(plan.seg_rows), _ptr(plan.row_offsets))
+        self._row_counts(plan.waypoints, None, plan.B, plan.m, plan.velocity, getattr(plan, "velocities", None), plan.dt, plan.times,
+                         plan.seg_rows, plan.row_offsets, free_times=getattr(plan, "free_times", False))
         if getattr(plan, "boundary", None) is not None:
             self.ctx.call("uavac_minsnap_solve_bc_dev", _ptr(plan.waypoints), _ptr(plan.times), None, plan.B, plan.m,
                           _ptr(plan.boundary), _ptr(plan.coeffs), _ptr(plan.status))
