@@ -25,6 +25,7 @@
 #pragma once
 
 #include "uavac_internal.h"
+#include "uavac_scratch.h"
 #include "mission_walk.h"
 #include "separation_reduce.h"
 
@@ -149,17 +150,11 @@ inline void shape_of(const uavac_ctx *ctx, int B, const int64_t *group_offsets, 
     s.rounds = (most + s.slots - 1) / s.slots;
 }
 
-// the arena bytes of count, words and owner, and the three taken (after the caller's uavac_arena_reserve of these and its own)
-inline size_t shape_bytes(const Shape &s, int B, long long capacity) {
-    const size_t Bs = (size_t)B, cap = (size_t)capacity;
-    return uavac_arena_size(Bs * 4) + uavac_arena_size(s.slots * Bs * 8) + uavac_arena_size(cap ? cap * 4 : 8);
-}
-inline bool shape_take(uavac_ctx *ctx, Shape &s, int B, long long capacity) {
-    const size_t Bs = (size_t)B, cap = (size_t)capacity;
-    s.count = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4));
-    s.words = static_cast<unsigned long long *>(uavac_arena_take(ctx, s.slots * Bs * 8));
-    s.owner = static_cast<int32_t *>(uavac_arena_take(ctx, cap * 4));
-    return s.count && s.words && s.owner;
+// count, words and owner on the caller's Scratch, beside the caller's own pieces
+inline void shape_want(Scratch &scratch, Shape &s, int B, long long capacity) {
+    scratch.want(&s.count, (size_t)B);
+    scratch.want(&s.words, s.slots * (size_t)B);
+    scratch.want(&s.owner, (size_t)capacity);
 }
 
 // the offsets call: per round the discovery and the counts, then the scan -> pair_offsets [B + 1]

@@ -6,6 +6,7 @@
 
 #include "control_law.h"
 #include "minsnap_yaw.h"
+#include "uavac_scratch.h"
 
 #include <cstring>
 #include <new>
@@ -141,20 +142,20 @@ __global__ void dynamics_step_kernel(const VehK V, double *__restrict__ state, i
     }
 }
 
-template <class T> T *take(uavac_ctx *ctx, size_t count) { return static_cast<T *>(uavac_arena_take(ctx, count * sizeof(T))); }
-
 template <class Kern>
 int run_probe(uavac_ctx *ctx, const uavac_vehicle *V, Kern kern, const double *in, int nin, int B, int mask,
               double *out, int nout) {
     UAVAC_ENTER(ctx);
     if (int rc = uavac_check_vehicle(ctx, V)) return rc;
     if (B < 1 || !in || !out) return uavac_fail(ctx, UAVAC_EINVAL, "bad B or null pointer");
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size((size_t)B * nin * 8) + uavac_arena_size((size_t)B * nout * 8))) return rc;
-    double *din = take<double>(ctx, (size_t)B * nin), *dout = take<double>(ctx, (size_t)B * nout);
-    if (int rc = uavac_h2d(ctx, din, in, (size_t)B * nin * 8)) return rc;
+    double *din = nullptr, *dout = nullptr;
+    Scratch s(ctx);
+    s.in(&din, in, (size_t)B * nin); s.out(&dout, out, (size_t)B * nout);
+    if (int rc = s.commit()) return rc;
+    if (int rc = s.upload()) return rc;
     hipLaunchKernelGGL(kern, dim3((B + 63) / 64), dim3(64), 0, ctx->stream, uavac_make_vehk(*V), din, B, mask, dout);
     UAVAC_HIP(ctx, hipGetLastError());
-    if (int rc = uavac_d2h(ctx, out, dout, (size_t)B * nout * 8)) return rc;
+    if (int rc = s.download()) return rc;
     UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return UAVAC_OK;
 }
@@ -291,19 +292,16 @@ int uavac_controller_tick(uavac_ctx *ctx, const uavac_vehicle *V, const double *
     if (B < 1 || !traj || !row_offsets || !state || !istate) return uavac_fail(ctx, UAVAC_EINVAL, "bad B or null pointer");
     if (row_offsets[0] != 0) return uavac_fail(ctx, UAVAC_EINVAL, "row_offsets must start at 0");
     const size_t ntr = (size_t)row_offsets[B] * UAVAC_TRAJ_COLS, ns = (size_t)B * UAVAC_STATE_ROWS, ni = (size_t)B * UAVAC_ISTATE_ROWS;
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size(ntr * 8) + uavac_arena_size(((size_t)B + 1) * 8) +
-                                              uavac_arena_size(ns * 8) + uavac_arena_size(ni * 4))) return rc;
-    double *dtr = take<double>(ctx, ntr);
-    int64_t *dro = take<int64_t>(ctx, (size_t)B + 1);
-    double *ds = take<double>(ctx, ns);
-    int32_t *di = take<int32_t>(ctx, ni);
-    if (int rc = uavac_h2d(ctx, dtr, traj, ntr * 8)) return rc;
-    if (int rc = uavac_h2d(ctx, dro, row_offsets, ((size_t)B + 1) * 8)) return rc;
-    if (int rc = uavac_h2d(ctx, ds, state, ns * 8)) return rc;
-    if (int rc = uavac_h2d(ctx, di, istate, ni * 4)) return rc;
+    double *dtr = nullptr, *ds = nullptr;
+    int64_t *dro = nullptr;
+    int32_t *di = nullptr;
+    Scratch s(ctx);
+    s.in(&dtr, traj, ntr); s.in(&dro, row_offsets, (size_t)B + 1);
+    s.inout(&ds, state, ns); s.inout(&di, istate, ni);
+    if (int rc = s.commit()) return rc;
+    if (int rc = s.upload()) return rc;
     if (int rc = uavac_controller_tick_dev(ctx, V, dtr, dro, ds, di, B)) return rc;
-    if (int rc = uavac_d2h(ctx, state, ds, ns * 8)) return rc;
-    if (int rc = uavac_d2h(ctx, istate, di, ni * 4)) return rc;
+    if (int rc = s.download()) return rc;
     UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return UAVAC_OK;
 }
@@ -315,17 +313,16 @@ int uavac_dynamics_step(uavac_ctx *ctx, const uavac_vehicle *V, double *state, i
     const bool obs = aabbs && n_obs > 0;
     const bool flag = istate && (obs || V->ground);          // istate carries the obstacle flag and the ground bits
     const size_t ns = (size_t)B * UAVAC_STATE_ROWS, ni = (size_t)B * UAVAC_ISTATE_ROWS;
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size(ns * 8) + uavac_arena_size(ni * 4) +
-                                              uavac_arena_size((size_t)n_obs * 48))) return rc;
-    double *ds = take<double>(ctx, ns);
-    int32_t *di = flag ? take<int32_t>(ctx, ni) : nullptr;
-    double *dab = obs ? take<double>(ctx, (size_t)n_obs * 6) : nullptr;
-    if (int rc = uavac_h2d(ctx, ds, state, ns * 8)) return rc;
-    if (flag) if (int rc = uavac_h2d(ctx, di, istate, ni * 4)) return rc;
-    if (obs) if (int rc = uavac_h2d(ctx, dab, aabbs, (size_t)n_obs * 48)) return rc;
+    double *ds = nullptr, *dab = nullptr;
+    int32_t *di = nullptr;
+    Scratch s(ctx);
+    s.inout(&ds, state, ns);
+    if (flag) s.inout(&di, istate, ni);
+    if (obs) s.in(&dab, aabbs, (size_t)n_obs * 6);
+    if (int rc = s.commit()) return rc;
+    if (int rc = s.upload()) return rc;
     if (int rc = uavac_dynamics_step_dev(ctx, V, ds, di, B, dab, obs ? n_obs : 0)) return rc;
-    if (int rc = uavac_d2h(ctx, state, ds, ns * 8)) return rc;
-    if (flag) if (int rc = uavac_d2h(ctx, istate, di, ni * 4)) return rc;
+    if (int rc = s.download()) return rc;
     UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return UAVAC_OK;
 }

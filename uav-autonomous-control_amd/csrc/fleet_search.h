@@ -28,6 +28,7 @@
 #pragma once
 
 #include "fleet_clock.h"
+#include "uavac_scratch.h"
 
 #include <limits>
 
@@ -271,10 +272,10 @@ template <bool OBS>
 int launch_layer_search(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
                         const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, Delta delta, int max_steps,
                         const double *cuboids, int n_cuboids, int32_t *ilayer, double *offsets) {
-    const size_t Bs = (size_t)B;
-    if (int rc = uavac_arena_reserve(ctx, 2 * uavac_arena_size(Bs * 4))) return rc;
-    int32_t *n_rows = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4)), *start = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4));
-    if (!n_rows || !start) return uavac_fail(ctx, UAVAC_ENOMEM, "layer: scratch arena too small");
+    int32_t *n_rows = nullptr, *start = nullptr;
+    Scratch s(ctx);
+    s.want(&n_rows, B); s.want(&start, B);
+    if (int rc = s.commit()) return rc;
     hipLaunchKernelGGL(layer_prepass_kernel<OBS>, dim3((B + kPreMissions - 1) / kPreMissions), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows,
                        seg_offsets, B, m, start_rows, delta, n_rows, start, ilayer, offsets, ctx->d_flags);
     hipLaunchKernelGGL(minsnap_layer_kernel<OBS>, dim3(group_offsets ? G : 1), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows, seg_offsets, B,

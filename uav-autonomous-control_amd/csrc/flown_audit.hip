@@ -28,6 +28,7 @@
 // comes last (max and sqrt are monotone), so a peak equals np.sqrt(vx * vx + vy * vy).max() over the valid ticks bit for bit.
 
 #include "uavac_internal.h"
+#include "uavac_scratch.h"
 
 #include <limits>
 
@@ -312,11 +313,12 @@ int uavac_launch_flown_audit(uavac_ctx *ctx, const double *state_log, int K, int
         P = P > most ? most : P;
     }
     P = P < 1 ? 1 : (P > UAVAC_FLOWN_AUDIT_MAX_SPLIT ? UAVAC_FLOWN_AUDIT_MAX_SPLIT : P);
-    const size_t Bs = (size_t)B, bytes_d = (size_t)P * rows_d(n_cuboids) * Bs * 8, bytes_i = (size_t)P * rows_i(n_cuboids) * Bs * 4;
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size(bytes_d) + uavac_arena_size(bytes_i))) return rc;
-    double *part_d = static_cast<double *>(uavac_arena_take(ctx, bytes_d));
-    int32_t *part_i = static_cast<int32_t *>(uavac_arena_take(ctx, bytes_i));
-    if (!part_d || !part_i) return uavac_fail(ctx, UAVAC_ENOMEM, "flown audit: scratch arena too small");
+    double *part_d = nullptr;
+    int32_t *part_i = nullptr;
+    Scratch s(ctx);
+    s.want(&part_d, (size_t)P * rows_d(n_cuboids) * B);
+    s.want(&part_i, (size_t)P * rows_i(n_cuboids) * B);
+    if (int rc = s.commit()) return rc;
     const size_t lds = lds_bytes(n_cuboids);                 // 16 cuboids: 80 KB, two workgroups per CU
     if (lds > 64 * 1024)
         UAVAC_HIP(ctx, hipFuncSetAttribute((const void *)flown_audit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -110,12 +110,12 @@ struct Shape : csr::Shape {
     int32_t *first, *tiles;
 };
 
-int shape_of(uavac_ctx *ctx, int B, const int64_t *group_offsets, int G, long long capacity, Shape &s) {
+int shape_of(uavac_ctx *ctx, Scratch &scratch, int B, const int64_t *group_offsets, int G, long long capacity, Shape &s) {
     csr::shape_of(ctx, B, group_offsets, G, s);
     const size_t Bs = (size_t)B;
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size(2 * Bs * 4) + csr::shape_bytes(s, B, capacity))) return rc;
-    s.first = static_cast<int32_t *>(uavac_arena_take(ctx, 2 * Bs * 4));
-    if (!s.first || !csr::shape_take(ctx, s, B, capacity)) return uavac_fail(ctx, UAVAC_ENOMEM, "flown conflict list: scratch arena too small");
+    scratch.want(&s.first, 2 * Bs);
+    csr::shape_want(scratch, s, B, capacity);
+    if (int rc = scratch.commit()) return rc;
     s.tiles = s.first + Bs;
     // a vehicle that no group holds (offsets that do not cover the batch) has no tiles
     UAVAC_HIP(ctx, hipMemsetAsync(s.first, 0, 2 * Bs * 4, ctx->stream));
@@ -135,15 +135,17 @@ auto discovery(uavac_ctx *ctx, const Shape &s, const double *state_log, int K, i
 
 int uavac_launch_flown_conflict_offsets(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets,
                                         int G, double radius, int64_t *pair_offsets) {
+    Scratch scratch(ctx);
     Shape s;
-    if (int rc = shape_of(ctx, B, group_offsets, G, 0, s)) return rc;
+    if (int rc = shape_of(ctx, scratch, B, group_offsets, G, 0, s)) return rc;
     return csr::csr_offsets(ctx, s, B, nullptr, s.tiles, discovery(ctx, s, state_log, K, B, pitch, group_offsets, G, radius), pair_offsets);
 }
 
 int uavac_launch_flown_conflicts(uavac_ctx *ctx, const double *state_log, int K, int B, int64_t pitch, const int64_t *group_offsets, int G,
                                  double radius, const int64_t *pair_offsets, int64_t capacity, double *pair_d, int32_t *pair_i) {
+    Scratch scratch(ctx);
     Shape s;
-    if (int rc = shape_of(ctx, B, group_offsets, G, capacity, s)) return rc;
+    if (int rc = shape_of(ctx, scratch, B, group_offsets, G, capacity, s)) return rc;
     if (int rc = csr::csr_list(ctx, s, B, nullptr, s.first, s.tiles, discovery(ctx, s, state_log, K, B, pitch, group_offsets, G, radius),
                                pair_offsets, (long long)capacity, pair_i))
         return rc;

@@ -15,6 +15,7 @@
 // pitch, nor on what else is in the batch; each output has one writer and there are no atomics.  Columns B .. pitch - 1 are never read.
 
 #include "pair_sweep.h"
+#include "uavac_scratch.h"
 
 #include <limits>
 
@@ -51,10 +52,11 @@ int uavac_launch_flown_separation(uavac_ctx *ctx, const double *state_log, int K
     int windows, P;
     sep_shares(ctx, B, group_offsets, G, windows, P);
     const size_t Bs = (size_t)B;
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size(P * Bs * 8) + uavac_arena_size(P * 5 * Bs * 4))) return rc;
-    double *part_d2 = static_cast<double *>(uavac_arena_take(ctx, P * Bs * 8));
-    int32_t *part_i = static_cast<int32_t *>(uavac_arena_take(ctx, P * 5 * Bs * 4));
-    if (!part_d2 || !part_i) return uavac_fail(ctx, UAVAC_ENOMEM, "flown separation: scratch arena too small");
+    double *part_d2 = nullptr;
+    int32_t *part_i = nullptr;
+    Scratch s(ctx);
+    s.want(&part_d2, P * Bs); s.want(&part_i, P * 5 * Bs);
+    if (int rc = s.commit()) return rc;
     hipLaunchKernelGGL(flown_separation_kernel, dim3(windows, P), dim3(kThreads), 0, ctx->stream, state_log, K, B, (long long)pitch,
                        group_offsets, group_offsets ? G : 1, radius * radius, part_d2, part_i);
     hipLaunchKernelGGL(flown_merge_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, ctx->stream, B, P, part_d2, part_i, sep,

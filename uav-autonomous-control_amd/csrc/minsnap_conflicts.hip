@@ -110,17 +110,12 @@ struct Shape : csr::Shape {
     int32_t *n_rows, *start, *info;
 };
 
-int shape_of(uavac_ctx *ctx, int B, const int64_t *group_offsets, int G, long long capacity, Shape &s) {
+int shape_of(uavac_ctx *ctx, Scratch &scratch, int B, const int64_t *group_offsets, int G, long long capacity, Shape &s) {
     csr::shape_of(ctx, B, group_offsets, G, s);
     const size_t Bs = (size_t)B;
-    if (int rc = uavac_arena_reserve(ctx, 2 * uavac_arena_size(Bs * 4) + uavac_arena_size(3 * Bs * 4) + csr::shape_bytes(s, B, capacity)))
-        return rc;
-    s.n_rows = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4));
-    s.start = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4));
-    s.info = static_cast<int32_t *>(uavac_arena_take(ctx, 3 * Bs * 4));
-    if (!s.n_rows || !s.start || !s.info || !csr::shape_take(ctx, s, B, capacity))
-        return uavac_fail(ctx, UAVAC_ENOMEM, "conflict list: scratch arena too small");
-    return UAVAC_OK;
+    scratch.want(&s.n_rows, Bs); scratch.want(&s.start, Bs); scratch.want(&s.info, 3 * Bs);
+    csr::shape_want(scratch, s, B, capacity);
+    return scratch.commit();
 }
 
 int launch_prepass(uavac_ctx *ctx, const Shape &s, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
@@ -146,8 +141,9 @@ auto discovery(uavac_ctx *ctx, const Shape &s, const double *coeffs, const int32
 int uavac_launch_conflict_offsets(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                                   double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius,
                                   int64_t *pair_offsets) {
+    Scratch scratch(ctx);
     Shape s;
-    if (int rc = shape_of(ctx, B, group_offsets, G, 0, s)) return rc;
+    if (int rc = shape_of(ctx, scratch, B, group_offsets, G, 0, s)) return rc;
     if (int rc = launch_prepass(ctx, s, coeffs, seg_rows, seg_offsets, B, m, start_rows)) return rc;
     const auto discover = discovery(ctx, s, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, radius);
     return csr::csr_offsets(ctx, s, B, s.n_rows, s.info + 2 * (size_t)B, discover, pair_offsets);
@@ -156,8 +152,9 @@ int uavac_launch_conflict_offsets(uavac_ctx *ctx, const double *coeffs, const in
 int uavac_launch_conflicts(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
                            const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, const int64_t *pair_offsets,
                            int64_t capacity, double *pair_d, int32_t *pair_i) {
+    Scratch scratch(ctx);
     Shape s;
-    if (int rc = shape_of(ctx, B, group_offsets, G, capacity, s)) return rc;
+    if (int rc = shape_of(ctx, scratch, B, group_offsets, G, capacity, s)) return rc;
     if (int rc = launch_prepass(ctx, s, coeffs, seg_rows, seg_offsets, B, m, start_rows)) return rc;
     const auto discover = discovery(ctx, s, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, radius);
     if (int rc = csr::csr_list(ctx, s, B, s.n_rows, s.info, s.info + 2 * (size_t)B, discover, pair_offsets, (long long)capacity, pair_i))

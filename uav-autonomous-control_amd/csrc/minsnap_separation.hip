@@ -26,6 +26,7 @@
 // xj, ..., d^2 = (dx dx + dy dy) + dz dz, each product and sum rounded on its own.
 
 #include "pair_sweep.h"
+#include "uavac_scratch.h"
 
 #include <cmath>
 #include <limits>
@@ -168,12 +169,12 @@ int uavac_launch_separation(uavac_ctx *ctx, const double *coeffs, const int32_t 
     int windows, P;
     sep_shares(ctx, B, group_offsets, G, windows, P);
     const size_t Bs = (size_t)B;
-    if (int rc = uavac_arena_reserve(ctx, 2 * uavac_arena_size(Bs * 4) + uavac_arena_size(P * Bs * 8) + uavac_arena_size(P * 5 * Bs * 4)))
-        return rc;
-    int32_t *n_rows = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4)), *start = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4));
-    double *part_d2 = static_cast<double *>(uavac_arena_take(ctx, P * Bs * 8));
-    int32_t *part_i = static_cast<int32_t *>(uavac_arena_take(ctx, P * 5 * Bs * 4));
-    if (!n_rows || !start || !part_d2 || !part_i) return uavac_fail(ctx, UAVAC_ENOMEM, "separation audit: scratch arena too small");
+    int32_t *n_rows = nullptr, *start = nullptr, *part_i = nullptr;
+    double *part_d2 = nullptr;
+    Scratch s(ctx);
+    s.want(&n_rows, Bs); s.want(&start, Bs);
+    s.want(&part_d2, P * Bs); s.want(&part_i, P * 5 * Bs);
+    if (int rc = s.commit()) return rc;
     hipLaunchKernelGGL(separation_prepass_kernel, dim3((B + kPreMissions - 1) / kPreMissions), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows,
                        seg_offsets, B, m, start_rows, n_rows, start, ctx->d_flags);
     hipLaunchKernelGGL(minsnap_separation_kernel, dim3(windows, P), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows, seg_offsets, B, m, dt,

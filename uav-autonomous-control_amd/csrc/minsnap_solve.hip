@@ -379,14 +379,8 @@ __global__ void __launch_bounds__(64) minsnap_solve_kernel(const double *__restr
 // totals [B] i32 followed by the tile sums [ceil(B/256)] i64 (8-byte aligned offset): scratch of the row-offset scan
 static int ensure_totals(uavac_ctx *ctx, int B, int64_t **tiles) {
     const int n_tiles = (B + 255) / 256;
-    if ((size_t)B > ctx->totals_cap) {
-        if (ctx->d_totals) UAVAC_HIP(ctx, hipFree(ctx->d_totals));
-        ctx->d_totals = nullptr;
-        ctx->totals_cap = 0;
-        const size_t bytes = (((size_t)B * 4 + 7) & ~(size_t)7) + (size_t)n_tiles * 8;
-        UAVAC_HIP(ctx, hipMalloc(&ctx->d_totals, bytes));
-        ctx->totals_cap = (size_t)B;
-    }
+    const size_t bytes = (((size_t)B * 4 + 7) & ~(size_t)7) + (size_t)n_tiles * 8;
+    if (int rc = uavac_grow(ctx, ctx->d_totals, ctx->totals_cap, (size_t)B, bytes)) return rc;
     *tiles = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(ctx->d_totals) +
                                          (((size_t)ctx->totals_cap * 4 + 7) & ~(size_t)7));
     return UAVAC_OK;

@@ -10,14 +10,7 @@ namespace {
 // The HBM workspace [m - 1][28][B] (rows = a knot's index in its mission) where blocks wait that have no place on chip.
 int ensure_solve_workspace(uavac_ctx *ctx, int B, int m) {
     const size_t need = (size_t)(m > 1 ? m - 1 : 1) * 28 * (size_t)B;
-    if (need > ctx->ws_cap) {
-        if (ctx->d_ws) UAVAC_HIP(ctx, hipFree(ctx->d_ws));
-        ctx->d_ws = nullptr;
-        ctx->ws_cap = 0;
-        UAVAC_HIP(ctx, hipMalloc(&ctx->d_ws, sizeof(double) * need));
-        ctx->ws_cap = need;
-    }
-    return UAVAC_OK;
+    return uavac_grow(ctx, ctx->d_ws, ctx->ws_cap, need, sizeof(double) * need);
 }
 
 // Launches `kern`, the instantiation `family`<ragged, park_lds, n, nreg> of a block-Thomas kernel (one wave per workgroup), with

@@ -44,10 +44,10 @@ __global__ void __launch_bounds__(kThreads, 3) minsnap_stagger_kernel(
 int uavac_launch_stagger(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
                          const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, int step, int max_steps,
                          int32_t *istag) {
-    const size_t Bs = (size_t)B;
-    if (int rc = uavac_arena_reserve(ctx, 2 * uavac_arena_size(Bs * 4))) return rc;
-    int32_t *n_rows = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4)), *start = static_cast<int32_t *>(uavac_arena_take(ctx, Bs * 4));
-    if (!n_rows || !start) return uavac_fail(ctx, UAVAC_ENOMEM, "stagger: scratch arena too small");
+    int32_t *n_rows = nullptr, *start = nullptr;
+    Scratch s(ctx);
+    s.want(&n_rows, B); s.want(&start, B);
+    if (int rc = s.commit()) return rc;
     hipLaunchKernelGGL(stagger_prepass_kernel, dim3((B + kPreMissions - 1) / kPreMissions), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows, seg_offsets, B,
                        m, start_rows, n_rows, start, istag, ctx->d_flags);
     hipLaunchKernelGGL(minsnap_stagger_kernel, dim3(group_offsets ? G : 1), dim3(kThreads), 0, ctx->stream, coeffs, seg_rows, seg_offsets, B, m,

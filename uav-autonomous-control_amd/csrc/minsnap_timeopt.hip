@@ -18,6 +18,7 @@
 // Contraction is off in every kernel of this file: each step is one rounded IEEE operation.
 
 #include "uavac_internal.h"
+#include "uavac_scratch.h"
 #include "mission_walk.h"
 
 #include <cmath>
@@ -352,8 +353,6 @@ __global__ void __launch_bounds__(kThreads) timeopt_select_kernel(Chunk C, const
 
 inline dim3 grid_for(size_t n) { return dim3((unsigned)((n + kThreads - 1) / kThreads)); }
 
-template <class T> T *take(uavac_ctx *ctx, size_t count) { return static_cast<T *>(uavac_arena_take(ctx, count * sizeof(T))); }
-
 }  // namespace
 
 int uavac_launch_row_counts_t(uavac_ctx *ctx, const double *times, const int64_t *seg_offsets, int B, int m, double dt,
@@ -411,24 +410,17 @@ int uavac_launch_optimize_times(uavac_ctx *ctx, const double *wp, const int64_t 
     if (chunk > B) chunk = B;
     const size_t Bc_max = (size_t)chunk, seg_max = Bc_max * m;
     const bool ragged = seg_offsets != nullptr;
-    auto so_size = [&](size_t n) { return ragged ? uavac_arena_size((Bc_max * n + 1) * 8) : 0; };
-    auto wp_size = [&](size_t n) { return uavac_arena_size((seg_max + Bc_max) * n * 24); };
-    const size_t need = wp_size(1) + wp_size(m) + wp_size(NC) + so_size(1) + so_size(m) + so_size(NC) +
-                        uavac_arena_size(seg_max * n_max * 8) + uavac_arena_size(seg_max * n_max * 192) +
-                        uavac_arena_size(Bc_max * n_max * 8) + uavac_arena_size(seg_max * 8) + 4 * uavac_arena_size(Bc_max * 8) +
-                        uavac_arena_size(Bc_max * NC * 4) + uavac_arena_size(Bc_max * 4);
-    if (int rc = uavac_arena_reserve(ctx, need)) return rc;
-    double *wp_1 = take<double>(ctx, (seg_max + Bc_max) * 3), *wp_p = take<double>(ctx, (seg_max + Bc_max) * m * 3),
-           *wp_c = take<double>(ctx, (seg_max + Bc_max) * NC * 3);
-    int64_t *so_1 = ragged ? take<int64_t>(ctx, Bc_max + 1) : nullptr, *so_p = ragged ? take<int64_t>(ctx, Bc_max * m + 1) : nullptr,
-            *so_c = ragged ? take<int64_t>(ctx, Bc_max * NC + 1) : nullptr;
-    double *times_x = take<double>(ctx, seg_max * n_max), *coeffs_x = take<double>(ctx, seg_max * n_max * 24),
-           *cost_x = take<double>(ctx, Bc_max * n_max), *D = take<double>(ctx, seg_max), *J = take<double>(ctx, Bc_max),
-           *alpha = take<double>(ctx, Bc_max), *total = take<double>(ctx, Bc_max), *min_t0 = take<double>(ctx, Bc_max);
-    int32_t *valid = take<int32_t>(ctx, Bc_max * NC), *go = take<int32_t>(ctx, Bc_max);
-    if (!wp_1 || !wp_p || !wp_c || !times_x || !coeffs_x || !cost_x || !D || !J || !alpha || !total || !min_t0 || !valid || !go ||
-        (ragged && (!so_1 || !so_p || !so_c)))
-        return uavac_fail(ctx, UAVAC_ENOMEM, "time optimisation: scratch arena too small");
+    double *wp_1 = nullptr, *wp_p = nullptr, *wp_c = nullptr, *times_x = nullptr, *coeffs_x = nullptr, *cost_x = nullptr, *D = nullptr,
+           *J = nullptr, *alpha = nullptr, *total = nullptr, *min_t0 = nullptr;
+    int64_t *so_1 = nullptr, *so_p = nullptr, *so_c = nullptr;
+    int32_t *valid = nullptr, *go = nullptr;
+    Scratch s(ctx);
+    s.want(&wp_1, (seg_max + Bc_max) * 3); s.want(&wp_p, (seg_max + Bc_max) * m * 3); s.want(&wp_c, (seg_max + Bc_max) * NC * 3);
+    if (ragged) { s.want(&so_1, Bc_max + 1); s.want(&so_p, Bc_max * m + 1); s.want(&so_c, Bc_max * NC + 1); }
+    s.want(&times_x, seg_max * n_max); s.want(&coeffs_x, seg_max * n_max * 24); s.want(&cost_x, Bc_max * n_max);
+    s.want(&D, seg_max); s.want(&J, Bc_max); s.want(&alpha, Bc_max); s.want(&total, Bc_max); s.want(&min_t0, Bc_max);
+    s.want(&valid, Bc_max * NC); s.want(&go, Bc_max);
+    if (int rc = s.commit()) return rc;
     // cost of the expanded batch of n copies at times_x -> out [Bc * n]
     auto solve_and_cost = [&](const double *wp_x, const int64_t *so_x, int Bc, int n, double *out) -> int {
         if (int rc = uavac_launch_coeff_solve(ctx, wp_x, times_x, Bc * n, m, coeffs_x, nullptr, so_x)) return rc;

@@ -643,13 +643,7 @@ int uavac_rrt_star_dev(uavac_ctx *ctx, const double *start, const double *goal, 
     const bool full_in_lds = lds_full <= kLdsLimit;
     if (!full_in_lds) {
         const size_t need = scratch_doubles_per_problem(cap) * (size_t)B;
-        if (need > ctx->ws_cap) {
-            if (ctx->d_ws) UAVAC_HIP(ctx, hipFree(ctx->d_ws));
-            ctx->d_ws = nullptr;
-            ctx->ws_cap = 0;
-            UAVAC_HIP(ctx, hipMalloc(&ctx->d_ws, need * sizeof(double)));
-            ctx->ws_cap = need;
-        }
+        if (int rc = uavac_grow(ctx, ctx->d_ws, ctx->ws_cap, need, need * sizeof(double))) return rc;
     }
     const size_t lds_max = full_in_lds ? lds_full : (lds_small <= kLdsLimit ? lds_small : 0);
     if (lds_max > 64 * 1024)

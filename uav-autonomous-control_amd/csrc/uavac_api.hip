@@ -2,11 +2,13 @@
 // their host-pointer twins (which stage through device scratch).  See include/uavac.h.
 
 #include "uavac_internal.h"
+#include "uavac_scratch.h"
 
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -19,14 +21,11 @@ constexpr size_t kStageChunk = (size_t)256 << 10;     // bytes per half of the p
 // tools/host_path_rate.py), a single-threaded copy through a staging buffer at 27.
 constexpr size_t kStageLimit = (size_t)1 << 20;
 static_assert(kStageLimit >= 2 * kStageChunk, "the ping-pong needs transfers of more than one piece to overlap anything");
+}  // namespace
 
 // Host <-> device copies of the host-pointer twins.  The caller's buffers are pageable; they travel through the ctx's
 // pinned staging buffer in kStageChunk pieces, two halves in flight: the DMA of one piece overlaps the CPU copy of the
 // next (h2d) or previous (d2h) one.  Ordered on the ctx stream like everything else.
-int h2d_staged(uavac_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes) { return uavac_h2d(ctx, dst_dev, src_host, bytes); }
-int d2h_staged(uavac_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes) { return uavac_d2h(ctx, dst_host, src_dev, bytes); }
-}  // namespace
-
 int uavac_h2d(uavac_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes) {
     if (!bytes) return UAVAC_OK;
     if (bytes > kStageLimit) {
@@ -81,8 +80,6 @@ int uavac_d2h(uavac_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes)
 
 namespace {
 
-template <class T> T *take(uavac_ctx *ctx, size_t count) { return static_cast<T *>(uavac_arena_take(ctx, count * sizeof(T))); }
-
 bool finite_all(const double *p, size_t n) {
     for (size_t i = 0; i < n; ++i)
         if (!std::isfinite(p[i])) return false;
@@ -93,6 +90,38 @@ int check_plan_args(uavac_ctx *ctx, const void *wp, int B, int m) {
     if (!ctx) return UAVAC_EINVAL;
     if (!wp) return uavac_fail(ctx, UAVAC_EINVAL, "null waypoint pointer");
     if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
+    if (m < 1 || m > UAVAC_MAX_SEGMENTS) return uavac_fail(ctx, UAVAC_EINVAL, "m must be in [1, UAVAC_MAX_SEGMENTS]");
+    return UAVAC_OK;
+}
+
+// The refusals that several entry points word alike, one spelling each.  dt: in one refusal ...
+int check_dt_positive(uavac_ctx *ctx, double dt) {
+    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
+    return UAVAC_OK;
+}
+// ... in two, where a non-finite value has its own code ...
+int check_dt(uavac_ctx *ctx, double dt) {
+    if (!std::isfinite(dt)) return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite dt");
+    if (!(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be > 0");
+    return UAVAC_OK;
+}
+// ... and together with the batch's one cruise speed
+int check_velocity_dt(uavac_ctx *ctx, double velocity, double dt) {
+    if (!std::isfinite(velocity) || !std::isfinite(dt)) return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite velocity or dt");
+    if (!(velocity > 0.0) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "velocity and dt must be > 0");
+    return UAVAC_OK;
+}
+int check_n_cuboids(uavac_ctx *ctx, int n_cuboids) {
+    if (n_cuboids < 0 || n_cuboids > UAVAC_AUDIT_MAX_CUBOIDS)
+        return uavac_fail(ctx, UAVAC_EINVAL, "n_cuboids must be in [0, UAVAC_AUDIT_MAX_CUBOIDS]");
+    return UAVAC_OK;
+}
+// the shapes of the take calls (n missions out of B) and of the delay calls (`delayed`, with n = 1: a delayed mission grows by a segment)
+int check_take_shape(uavac_ctx *ctx, int B, int n, int m, bool delayed = false) {
+    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
+    if (n < 1) return uavac_fail(ctx, UAVAC_EINVAL, "n must be >= 1");
+    if (delayed && (m < 1 || m > UAVAC_MAX_SEGMENTS - 1))
+        return uavac_fail(ctx, UAVAC_EINVAL, "m must be in [1, UAVAC_MAX_SEGMENTS - 1]: a delayed mission needs one more segment");
     if (m < 1 || m > UAVAC_MAX_SEGMENTS) return uavac_fail(ctx, UAVAC_EINVAL, "m must be in [1, UAVAC_MAX_SEGMENTS]");
     return UAVAC_OK;
 }
@@ -113,38 +142,12 @@ int read_flags(uavac_ctx *ctx, int32_t out[4]) {
 }  // namespace
 
 int uavac_arena_reserve(uavac_ctx *ctx, size_t bytes) {
-    if (bytes > ctx->arena_cap) {
-        UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));          // nothing enqueued may still use the old block
-        if (ctx->d_arena) UAVAC_HIP(ctx, hipFree(ctx->d_arena));
-        ctx->d_arena = nullptr;
-        ctx->arena_cap = 0;
-        size_t want = bytes + bytes / 4;
-        if (want < ((size_t)1 << 20)) want = (size_t)1 << 20;
-        void *p = nullptr;
-        if (hipMalloc(&p, want) != hipSuccess) {
-            (void)hipGetLastError();
-            want = bytes;
-            UAVAC_HIP(ctx, hipMalloc(&p, want));
-        }
-        ctx->d_arena = static_cast<char *>(p);
-        ctx->arena_cap = want;
-    }
-    ctx->arena_top = 0;
-    return UAVAC_OK;
-}
-
-void *uavac_arena_take(uavac_ctx *ctx, size_t bytes) {
-    const size_t n = uavac_arena_size(bytes ? bytes : 8);
-    if (ctx->arena_top + n > ctx->arena_cap) return nullptr;         // reserve() was given too small a total: a bug
-    void *p = ctx->d_arena + ctx->arena_top;
-    ctx->arena_top += n;
-    return p;
-}
-
-int uavac_scratch(uavac_ctx *ctx, size_t bytes, void **out) {
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size(bytes))) return rc;
-    *out = uavac_arena_take(ctx, bytes);
-    return UAVAC_OK;
+    if (bytes <= ctx->arena_cap) return UAVAC_OK;
+    size_t want = bytes + bytes / 4;                                 // headroom, so that a slowly growing need does not reallocate every call
+    if (want < ((size_t)1 << 20)) want = (size_t)1 << 20;
+    if (uavac_grow(ctx, ctx->d_arena, ctx->arena_cap, want, want) == UAVAC_OK) return UAVAC_OK;
+    (void)hipGetLastError();
+    return uavac_grow(ctx, ctx->d_arena, ctx->arena_cap, bytes, bytes);      // no room for the headroom: the exact size
 }
 
 int uavac_pin_reserve(uavac_ctx *ctx, size_t bytes) {
@@ -152,16 +155,7 @@ int uavac_pin_reserve(uavac_ctx *ctx, size_t bytes) {
         UAVAC_HIP(ctx, hipEventCreateWithFlags(&ctx->pin_ev[0], hipEventDisableTiming));
         UAVAC_HIP(ctx, hipEventCreateWithFlags(&ctx->pin_ev[1], hipEventDisableTiming));
     }
-    if (bytes <= ctx->pin_cap) return UAVAC_OK;
-    UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->h_pin) UAVAC_HIP(ctx, hipHostFree(ctx->h_pin));
-    ctx->h_pin = nullptr;
-    ctx->pin_cap = 0;
-    void *p = nullptr;
-    UAVAC_HIP(ctx, hipHostMalloc(&p, bytes, hipHostMallocDefault));
-    ctx->h_pin = static_cast<char *>(p);
-    ctx->pin_cap = bytes;
-    return UAVAC_OK;
+    return uavac_grow(ctx, ctx->h_pin, ctx->pin_cap, bytes, bytes, true);
 }
 
 VehK uavac_make_vehk(const uavac_vehicle &V) {
@@ -224,17 +218,20 @@ int launch_counts(uavac_ctx *ctx, const double *wp, int B, int m, const double *
     return uavac_launch_row_counts_v(ctx, wp, B, m, velocities, dt, times, seg_rows, row_offsets, seg_offsets);
 }
 
-// ctx->d_plan holds at least `need` bytes: where a chain with a row capacity keeps what it computes before it is committed
-int ensure_plan_scratch(uavac_ctx *ctx, size_t need) {
-    if (need <= ctx->plan_cap) return UAVAC_OK;
-    UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));          // nothing enqueued may still use the old block
-    if (ctx->d_plan) UAVAC_HIP(ctx, hipFree(ctx->d_plan));
-    ctx->d_plan = nullptr;
-    ctx->plan_cap = 0;
-    void *p = nullptr;
-    UAVAC_HIP(ctx, hipMalloc(&p, need));
-    ctx->d_plan = static_cast<char *>(p);
-    ctx->plan_cap = need;
+// ctx->d_plan: where a chain with a row capacity keeps what it computes before it is committed -- the durations [B m] (`with_times`;
+// otherwise they are the caller's input), the row counts [B m] and the row offsets [B + 1], each at a 256-byte boundary
+struct PlanScratch {
+    double *times;
+    int32_t *seg_rows;
+    int64_t *row_offsets;
+};
+int plan_scratch(uavac_ctx *ctx, int B, int m, bool with_times, PlanScratch &p) {
+    auto padded = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t nseg = (size_t)B * m, o_rows = with_times ? padded(nseg * 8) : 0, o_offs = o_rows + padded(nseg * 4);
+    const size_t need = o_offs + padded(((size_t)B + 1) * 8);
+    if (int rc = uavac_grow(ctx, ctx->d_plan, ctx->plan_cap, need, need)) return rc;
+    p = PlanScratch{reinterpret_cast<double *>(ctx->d_plan), reinterpret_cast<int32_t *>(ctx->d_plan + o_rows),
+                    reinterpret_cast<int64_t *>(ctx->d_plan + o_offs)};
     return UAVAC_OK;
 }
 
@@ -263,26 +260,86 @@ int plan_chain(uavac_ctx *ctx, const double *wp, int B, int m, Vel velocity, dou
     // the device (row_offsets_s[B]), so every later stage reads that one word: the commit kernel copies the three arrays
     // into the caller's only when it fits, the solver and the sampler do nothing when it does not (the sampler raises
     // flag 2).  A refused plan leaves times, seg_rows, row_offsets, coeffs, rows and first_yaw exactly as they were.
-    const size_t nseg = (size_t)B * m;
-    const size_t o_rows = uavac_arena_size(nseg * 8), o_offs = o_rows + uavac_arena_size(nseg * 4);
-    const size_t need = o_offs + uavac_arena_size(((size_t)B + 1) * 8);
-    if (int rc = ensure_plan_scratch(ctx, need)) return rc;
-    double *times_s = reinterpret_cast<double *>(ctx->d_plan);
-    int32_t *seg_rows_s = reinterpret_cast<int32_t *>(ctx->d_plan + o_rows);
-    int64_t *row_offsets_s = reinterpret_cast<int64_t *>(ctx->d_plan + o_offs);
-    if (int rc = launch_counts(ctx, wp, B, m, velocity, dt, times_s, seg_rows_s, row_offsets_s)) return rc;
-    if (int rc = uavac_launch_plan_commit(ctx, times_s, seg_rows_s, row_offsets_s, B, m, traj_capacity_rows, times, seg_rows,
+    PlanScratch s;
+    if (int rc = plan_scratch(ctx, B, m, true, s)) return rc;
+    if (int rc = launch_counts(ctx, wp, B, m, velocity, dt, s.times, s.seg_rows, s.row_offsets)) return rc;
+    if (int rc = uavac_launch_plan_commit(ctx, s.times, s.seg_rows, s.row_offsets, B, m, traj_capacity_rows, times, seg_rows,
                                           row_offsets)) return rc;
     // (Round 6 tried to hide this solve behind the sampler: the batch cut into 2 / 4 / 8 mission blocks, block i sampled on an
     // auxiliary stream while block i + 1 was being solved.  Bit-identical and SLOWER -- +1.3 % / +13 % / +23 % at 65 536 x 12 --
     // because a solve wave cannot get onto a SIMD the sampler's grid keeps full: commit 53921dc, profiles/r06_plan_blocks_ab*.jsonl.)
-    if (int rc = solve(times_s, row_offsets_s + B, traj_capacity_rows)) return rc;
+    if (int rc = solve(s.times, s.row_offsets + B, traj_capacity_rows)) return rc;
     SampleExtras x;
     x.yaw_dense = yaw;
     x.first_yaw = first_yaw;
     x.capacity_rows = traj_capacity_rows;         // the sampler refuses (flag 2) instead of overrunning the buffer
-    return uavac_launch_sample(ctx, coeffs, seg_rows_s, row_offsets_s, B, m, dt, traj, x);
+    return uavac_launch_sample(ctx, coeffs, s.seg_rows, s.row_offsets, B, m, dt, traj, x);
 }
+
+// The options of uavac_set_option: where each is kept, which values it takes and what a refusal says.
+//   kOneOf   one of the values a[] (zero ends the list: no set here holds it)      kClamp   every value is taken, clamped into a[0] .. a[1]
+//   kRange   a[0] <= value <= a[1]                                                kBool    every value is taken: 0 or not
+//   kPad8    kRange, rounded down to a multiple of 8
+enum class Rule { kOneOf, kRange, kClamp, kBool, kPad8 };
+struct Option {
+    const char *name;
+    int uavac_ctx::*field;
+    Rule rule;
+    int a[5];
+    const char *message;
+};
+constexpr int kIntMax = 0x7fffffff;
+const Option kOptions[] = {
+    {"yaw_group", &uavac_ctx::yaw_group, Rule::kOneOf, {1, 4, 8, 16}, "yaw_group is 1, 4, 8 or 16"},
+    {"audit_lanes", &uavac_ctx::audit_lanes, Rule::kOneOf, {16, 64}, "audit_lanes is 16 or 64"},
+    {"separation_split", &uavac_ctx::separation_split, Rule::kRange, {0, UAVAC_SEP_MAX_SPLIT},
+     "separation_split is 0 (automatic) or 1 .. UAVAC_SEP_MAX_SPLIT"},
+    {"conflict_slots", &uavac_ctx::conflict_slots, Rule::kRange, {0, 64}, "conflict_slots is 0 (automatic) or 1 .. 64"},
+    {"flown_audit_split", &uavac_ctx::flown_audit_split, Rule::kRange, {0, UAVAC_FLOWN_AUDIT_MAX_SPLIT},
+     "flown_audit_split is 0 (automatic) or 1 .. UAVAC_FLOWN_AUDIT_MAX_SPLIT"},
+    {"timeopt_chunk", &uavac_ctx::timeopt_chunk, Rule::kRange, {0, kIntMax}, "timeopt_chunk is 0 (automatic) or a number of missions"},
+    {"sampler_waves", &uavac_ctx::sampler_waves, Rule::kOneOf, {1, 2, 4, 8, 16}, "sampler_waves is 1, 2, 4, 8 or 16"},
+    {"sampler_group", &uavac_ctx::sampler_group, Rule::kRange, {1, 64}, "sampler_group is 1 .. 64"},
+    {"rollout_align", &uavac_ctx::rollout_align, Rule::kBool, {}, nullptr},
+    {"log_pitch", &uavac_ctx::log_pitch, Rule::kRange, {0, kIntMax}, "log_pitch is 0 (= B) or a number of doubles >= B"},
+    {"late_handover", &uavac_ctx::late_handover, Rule::kClamp, {-1, 1}, nullptr},
+    {"solve_order", &uavac_ctx::solve_order, Rule::kRange, {-1, 1}, "solve_order is 0 (one-ended), 1 (two-ended) or -1 (by the launch)"},
+    {"solve_park", &uavac_ctx::solve_park, Rule::kClamp, {-1, 1}, nullptr},
+    {"solve_keep", &uavac_ctx::solve_keep, Rule::kClamp, {-1, 1}, nullptr},
+    {"solve_lanes", &uavac_ctx::solve_lanes, Rule::kOneOf, {-1, 64, 32, 16}, "solve_lanes is -1, 64, 32 or 16"},
+    {"coeff_dma", &uavac_ctx::coeff_dma, Rule::kClamp, {-1, 2}, nullptr},
+    {"idle_waves", &uavac_ctx::idle_waves, Rule::kClamp, {-1, 1}, nullptr},
+    {"cu_balance", &uavac_ctx::cu_balance, Rule::kBool, {}, nullptr},
+    {"lds_pad", &uavac_ctx::lds_pad, Rule::kPad8, {0, 120 * 1024}, "lds_pad is 0 .. 122880 bytes"},
+};
+
+const Option *find_option(const char *name) {
+    for (const Option &o : kOptions)
+        if (!std::strcmp(o.name, name)) return &o;
+    return nullptr;
+}
+
+// -> false: the option does not take this value (nothing stored)
+bool apply_option(uavac_ctx *ctx, const Option &o, int value) {
+    bool listed = false;
+    for (int v : o.a) listed |= v != 0 && v == value;
+    const bool ranged = o.rule == Rule::kRange || o.rule == Rule::kPad8;
+    if ((o.rule == Rule::kOneOf && !listed) || (ranged && (value < o.a[0] || value > o.a[1]))) return false;
+    if (o.rule == Rule::kPad8) value &= ~7;
+    if (o.rule == Rule::kClamp) value = value < o.a[0] ? o.a[0] : (value > o.a[1] ? o.a[1] : value);
+    if (o.rule == Rule::kBool) value = value ? 1 : 0;
+    ctx->*o.field = value;
+    return true;
+}
+
+// an option's start value from the environment; a value the option does not take is ignored
+void option_from_env(uavac_ctx *ctx, const char *variable, const char *name) {
+    if (const char *e = getenv(variable)) (void)apply_option(ctx, *find_option(name), atoi(e));
+}
+
+struct ctx_deleter {
+    void operator()(uavac_ctx *ctx) const { uavac_destroy(ctx); }      // (copes with a ctx that was built in part)
+};
 
 }  // namespace
 
@@ -295,29 +352,28 @@ int uavac_create(uavac_ctx **out, int device_id) {
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return UAVAC_EHIP;   // no CPU fallback, ever
-    uavac_ctx *ctx = new (std::nothrow) uavac_ctx();
+    // whatever has been built when a step below fails is taken down by uavac_destroy
+    std::unique_ptr<uavac_ctx, ctx_deleter> owner(new (std::nothrow) uavac_ctx());
+    uavac_ctx *ctx = owner.get();
     if (!ctx) return UAVAC_ENOMEM;
     if (device_id >= 0) {
-        if (device_id >= ndev) { delete ctx; return UAVAC_EHIP; }
+        if (device_id >= ndev) return UAVAC_EHIP;
         ctx->device = device_id;
-    } else if (hipGetDevice(&ctx->device) != hipSuccess) { delete ctx; return UAVAC_EHIP; }
+    } else if (hipGetDevice(&ctx->device) != hipSuccess) return UAVAC_EHIP;
     uavac_device_guard guard(ctx);                // stream and buffers are created on the ctx's device
     {
         int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != ctx->device) { delete ctx; return UAVAC_EHIP; }
+        if (hipGetDevice(&cur) != hipSuccess || cur != ctx->device) return UAVAC_EHIP;
     }
-    if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return UAVAC_EHIP; }
+    if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) return UAVAC_EHIP;
     ctx->stream = ctx->own_stream;
     if (hipMalloc(&ctx->d_flags, 4 * sizeof(int32_t)) != hipSuccess ||
-        hipMemset(ctx->d_flags, 0, 4 * sizeof(int32_t)) != hipSuccess) {
-        (void)hipStreamDestroy(ctx->own_stream);
-        delete ctx;
+        hipMemset(ctx->d_flags, 0, 4 * sizeof(int32_t)) != hipSuccess)
         return UAVAC_EHIP;
-    }
-    if (const char *e = getenv("UAVAC_YAW_GROUP")) { const int v = atoi(e); if (v == 1 || v == 4 || v == 16) ctx->yaw_group = v; }
-    if (const char *e = getenv("UAVAC_ROLLOUT_ALIGN")) ctx->rollout_align = (e[0] == '0') ? 0 : 1;
-    if (const char *e = getenv("UAVAC_SAMPLER_WAVES")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) ctx->sampler_waves = v; }
-    if (const char *e = getenv("UAVAC_SAMPLER_GROUP")) { const int v = atoi(e); if (v >= 1 && v <= 64) ctx->sampler_group = v; }
+    option_from_env(ctx, "UAVAC_YAW_GROUP", "yaw_group");
+    if (const char *e = getenv("UAVAC_ROLLOUT_ALIGN")) ctx->rollout_align = (e[0] == '0') ? 0 : 1;      // (not the option's rule: "x" is on)
+    option_from_env(ctx, "UAVAC_SAMPLER_WAVES", "sampler_waves");
+    option_from_env(ctx, "UAVAC_SAMPLER_GROUP", "sampler_group");
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && cus > 0)
@@ -338,20 +394,17 @@ int uavac_create(uavac_ctx **out, int device_id) {
                                 "65680 operand pairs (built with: %s).  The device library's atan2 has changed: heading() in "
                                 "csrc/minsnap_yaw.h (polynomial, operation order) must be re-derived from it -- rebuilding alone "
                                 "reproduces this failure\n", bad, uavac_build_info());
-            (void)hipFree(ctx->d_flags);
-            (void)hipStreamDestroy(ctx->own_stream);
-            delete ctx;
             return rc != UAVAC_OK ? rc : UAVAC_ETOOLCHAIN;
         }
     }
-    *out = ctx;
+    *out = owner.release();
     return UAVAC_OK;
 }
 
 void uavac_destroy(uavac_ctx *ctx) {
     if (!ctx) return;
     uavac_device_guard guard(ctx);
-    (void)hipStreamSynchronize(ctx->own_stream);
+    if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
     if (ctx->d_flags) (void)hipFree(ctx->d_flags);
     if (ctx->d_totals) (void)hipFree(ctx->d_totals);
     if (ctx->d_ws) (void)hipFree(ctx->d_ws);
@@ -388,60 +441,9 @@ int uavac_device(const uavac_ctx *ctx) { return ctx ? ctx->device : UAVAC_EINVAL
 
 int uavac_set_option(uavac_ctx *ctx, const char *name, int value) {
     if (!ctx || !name) return UAVAC_EINVAL;
-    const std::string n(name);
-    if (n == "yaw_group") {
-        if (value != 1 && value != 4 && value != 8 && value != 16) return uavac_fail(ctx, UAVAC_EINVAL, "yaw_group is 1, 4, 8 or 16");
-        ctx->yaw_group = value;
-    } else if (n == "audit_lanes") {
-        if (value != 16 && value != 64) return uavac_fail(ctx, UAVAC_EINVAL, "audit_lanes is 16 or 64");
-        ctx->audit_lanes = value;
-    } else if (n == "separation_split") {
-        if (value < 0 || value > UAVAC_SEP_MAX_SPLIT) return uavac_fail(ctx, UAVAC_EINVAL, "separation_split is 0 (automatic) or 1 .. UAVAC_SEP_MAX_SPLIT");
-        ctx->separation_split = value;
-    } else if (n == "conflict_slots") {
-        if (value < 0 || value > 64) return uavac_fail(ctx, UAVAC_EINVAL, "conflict_slots is 0 (automatic) or 1 .. 64");
-        ctx->conflict_slots = value;
-    } else if (n == "flown_audit_split") {
-        if (value < 0 || value > UAVAC_FLOWN_AUDIT_MAX_SPLIT) return uavac_fail(ctx, UAVAC_EINVAL, "flown_audit_split is 0 (automatic) or 1 .. UAVAC_FLOWN_AUDIT_MAX_SPLIT");
-        ctx->flown_audit_split = value;
-    } else if (n == "timeopt_chunk") {
-        if (value < 0) return uavac_fail(ctx, UAVAC_EINVAL, "timeopt_chunk is 0 (automatic) or a number of missions");
-        ctx->timeopt_chunk = value;
-    } else if (n == "sampler_waves") {
-        if (value != 1 && value != 2 && value != 4 && value != 8 && value != 16) return uavac_fail(ctx, UAVAC_EINVAL, "sampler_waves is 1, 2, 4, 8 or 16");
-        ctx->sampler_waves = value;
-    } else if (n == "sampler_group") {
-        if (value < 1 || value > 64) return uavac_fail(ctx, UAVAC_EINVAL, "sampler_group is 1 .. 64");
-        ctx->sampler_group = value;
-    } else if (n == "rollout_align") {
-        ctx->rollout_align = value ? 1 : 0;
-    } else if (n == "log_pitch") {
-        if (value < 0) return uavac_fail(ctx, UAVAC_EINVAL, "log_pitch is 0 (= B) or a number of doubles >= B");
-        ctx->log_pitch = value;
-    } else if (n == "late_handover") {
-        ctx->late_handover = value < 0 ? -1 : (value ? 1 : 0);
-    } else if (n == "solve_order") {
-        if (value != 0 && value != 1 && value != -1) return uavac_fail(ctx, UAVAC_EINVAL, "solve_order is 0 (one-ended), 1 (two-ended) or -1 (by the launch)");
-        ctx->solve_order = value;
-    } else if (n == "solve_park") {
-        ctx->solve_park = value < 0 ? -1 : (value ? 1 : 0);
-    } else if (n == "solve_keep") {
-        ctx->solve_keep = value < 0 ? -1 : (value ? 1 : 0);
-    } else if (n == "solve_lanes") {
-        if (value != -1 && value != 64 && value != 32 && value != 16) return uavac_fail(ctx, UAVAC_EINVAL, "solve_lanes is -1, 64, 32 or 16");
-        ctx->solve_lanes = value;
-    } else if (n == "coeff_dma") {
-        ctx->coeff_dma = value < 0 ? -1 : (value > 2 ? 2 : value);
-    } else if (n == "idle_waves") {
-        ctx->idle_waves = value < 0 ? -1 : (value ? 1 : 0);
-    } else if (n == "cu_balance") {
-        ctx->cu_balance = value ? 1 : 0;
-    } else if (n == "lds_pad") {
-        if (value < 0 || value > 120 * 1024) return uavac_fail(ctx, UAVAC_EINVAL, "lds_pad is 0 .. 122880 bytes");
-        ctx->lds_pad = value & ~7;
-    } else {
-        return uavac_fail(ctx, UAVAC_EINVAL, "unknown option");
-    }
+    const Option *o = find_option(name);
+    if (!o) return uavac_fail(ctx, UAVAC_EINVAL, "unknown option");
+    if (!apply_option(ctx, *o, value)) return uavac_fail(ctx, UAVAC_EINVAL, o->message);
     return UAVAC_OK;
 }
 
@@ -514,8 +516,7 @@ int uavac_minsnap_row_counts_dev(uavac_ctx *ctx, const double *wp, int B, int m,
     UAVAC_ENTER(ctx);
     if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
     if (!times || !seg_rows || !row_offsets) return uavac_fail(ctx, UAVAC_EINVAL, "null output pointer");
-    if (!std::isfinite(velocity) || !std::isfinite(dt)) return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite velocity or dt");
-    if (!(velocity > 0.0) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "velocity and dt must be > 0");
+    if (int rc = check_velocity_dt(ctx, velocity, dt)) return rc;
     return uavac_launch_row_counts(ctx, wp, B, m, velocity, dt, times, seg_rows, row_offsets);
 }
 
@@ -539,7 +540,7 @@ static int check_sample_args(uavac_ctx *ctx, const double *coeffs, const int32_t
                              int B, int m, double dt, const double *traj) {
     if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
     if (!seg_rows || !row_offsets || !traj) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
+    if (int rc = check_dt_positive(ctx, dt)) return rc;
     return UAVAC_OK;
 }
 
@@ -607,8 +608,7 @@ int uavac_minsnap_row_counts_ragged_dev(uavac_ctx *ctx, const double *wp, const 
     UAVAC_ENTER(ctx);
     if (int rc = check_plan_args(ctx, wp, B, max_m)) return rc;
     if (!seg_offsets || !times || !seg_rows || !row_offsets) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (!std::isfinite(velocity) || !std::isfinite(dt)) return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite velocity or dt");
-    if (!(velocity > 0.0) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "velocity and dt must be > 0");
+    if (int rc = check_velocity_dt(ctx, velocity, dt)) return rc;
     return uavac_launch_row_counts(ctx, wp, B, max_m, velocity, dt, times, seg_rows, row_offsets, seg_offsets);
 }
 
@@ -646,18 +646,11 @@ int uavac_minsnap_plan_dev(uavac_ctx *ctx, const double *wp, int B, int m, doubl
     UAVAC_ENTER(ctx);
     if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
     if (!times || !seg_rows || !row_offsets || !coeffs) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (!std::isfinite(velocity) || !std::isfinite(dt)) return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite velocity or dt");
-    if (!(velocity > 0.0) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "velocity and dt must be > 0");
+    if (int rc = check_velocity_dt(ctx, velocity, dt)) return rc;
     return plan_chain(ctx, wp, B, m, velocity, dt, times, seg_rows, row_offsets, coeffs, status, traj, traj_capacity_rows, yaw, first_yaw);
 }
 
 // ---------------------------------------------------------------- planning, device, one cruise speed per mission
-static int check_dt(uavac_ctx *ctx, double dt) {
-    if (!std::isfinite(dt)) return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite dt");
-    if (!(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be > 0");
-    return UAVAC_OK;
-}
-
 int uavac_minsnap_row_counts_v_dev(uavac_ctx *ctx, const double *wp, int B, int m, const double *velocities, double dt,
                                    double *times, int32_t *seg_rows, int64_t *row_offsets) {
     UAVAC_ENTER(ctx);
@@ -741,9 +734,11 @@ int uavac_minsnap_retime_dev(uavac_ctx *ctx, const double *wp, const int64_t *se
     if (int rc = check_dt(ctx, dt)) return rc;
     if (max_passes < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative max_passes");
     *passes = 0;
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size((size_t)B * 8) + uavac_arena_size(2 * sizeof(int32_t)))) return rc;
-    double *d_factors = take<double>(ctx, (size_t)B);
-    int32_t *d_counters = take<int32_t>(ctx, 2);
+    double *d_factors = nullptr;
+    int32_t *d_counters = nullptr;
+    Scratch s(ctx);
+    s.want(&d_factors, (size_t)B); s.want(&d_counters, 2);
+    if (int rc = s.commit()) return rc;
     if (int rc = uavac_launch_fill_f64(ctx, factors_total, (size_t)B, 1.0)) return rc;
     for (int retimed = 0;; ++retimed) {
         // the rows-free chain at the current speeds, its audit, and what the audit asks for -- no row is sampled anywhere
@@ -756,7 +751,7 @@ int uavac_minsnap_retime_dev(uavac_ctx *ctx, const double *wp, const int64_t *se
         if (int rc = uavac_launch_retime_factors(ctx, audit, B, L, margin, apply, velocities, d_factors, d_counters, factors_total,
                                                  converged)) return rc;
         int32_t cnt[2];
-        if (int rc = d2h_staged(ctx, cnt, d_counters, sizeof cnt)) return rc;           // the pass's one read-back (synchronises)
+        if (int rc = uavac_d2h(ctx, cnt, d_counters, sizeof cnt)) return rc;           // the pass's one read-back (synchronises)
         if (cnt[0] == 0 || !apply) break;
         *passes = retimed + 1;
     }
@@ -790,22 +785,19 @@ int uavac_minsnap_plan_t_dev(uavac_ctx *ctx, const double *wp, const int64_t *se
     if (traj_capacity_rows < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative capacity");
     // With a row capacity, as in plan_chain: counts and offsets to ctx scratch, every later stage reads row_offsets_s[B] on the device
     // and does nothing when the plan does not fit (the sampler raises flag 2).  A ragged batch has at most B * m segments.
-    const size_t nseg = (size_t)B * m;
-    const size_t o_offs = uavac_arena_size(nseg * 4);
-    if (int rc = ensure_plan_scratch(ctx, o_offs + uavac_arena_size(((size_t)B + 1) * 8))) return rc;
-    int32_t *seg_rows_s = reinterpret_cast<int32_t *>(ctx->d_plan);
-    int64_t *row_offsets_s = reinterpret_cast<int64_t *>(ctx->d_plan + o_offs);
-    if (int rc = uavac_launch_row_counts_t(ctx, times, seg_offsets, B, m, dt, seg_rows_s, row_offsets_s)) return rc;
-    if (int rc = uavac_launch_plan_t_commit(ctx, seg_rows_s, row_offsets_s, seg_offsets, B, m, traj_capacity_rows, seg_rows, row_offsets))
+    PlanScratch s;
+    if (int rc = plan_scratch(ctx, B, m, false, s)) return rc;
+    if (int rc = uavac_launch_row_counts_t(ctx, times, seg_offsets, B, m, dt, s.seg_rows, s.row_offsets)) return rc;
+    if (int rc = uavac_launch_plan_t_commit(ctx, s.seg_rows, s.row_offsets, seg_offsets, B, m, traj_capacity_rows, seg_rows, row_offsets))
         return rc;
-    if (int rc = uavac_launch_coeff_solve(ctx, wp, times, B, m, coeffs, status, seg_offsets, row_offsets_s + B, traj_capacity_rows)) return rc;
+    if (int rc = uavac_launch_coeff_solve(ctx, wp, times, B, m, coeffs, status, seg_offsets, s.row_offsets + B, traj_capacity_rows)) return rc;
     SampleExtras x;
     x.yaw_dense = yaw;
     x.first_yaw = first_yaw;
     x.capacity_rows = traj_capacity_rows;
     x.seg_offsets = seg_offsets;
-    if (seg_offsets) x.total_segments = (int64_t)nseg;        // (sizes the hit flags only, and there are none)
-    return uavac_launch_sample(ctx, coeffs, seg_rows_s, row_offsets_s, B, m, dt, traj, x);
+    if (seg_offsets) x.total_segments = (int64_t)B * m;       // (sizes the hit flags only, and there are none)
+    return uavac_launch_sample(ctx, coeffs, s.seg_rows, s.row_offsets, B, m, dt, traj, x);
 }
 
 int uavac_minsnap_cost_dev(uavac_ctx *ctx, const double *coeffs, const double *times, const int64_t *seg_offsets, int B, int m,
@@ -830,7 +822,7 @@ int uavac_minsnap_first_yaw_dev(uavac_ctx *ctx, const double *coeffs, const int3
     UAVAC_ENTER(ctx);
     if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
     if (!seg_rows || !first_yaw) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
+    if (int rc = check_dt_positive(ctx, dt)) return rc;
     return uavac_launch_first_yaw(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, first_yaw);
 }
 
@@ -839,9 +831,8 @@ int uavac_minsnap_audit_dev(uavac_ctx *ctx, const double *coeffs, const int32_t 
     UAVAC_ENTER(ctx);
     if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
     if (!seg_rows || !audit) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
-    if (n_cuboids < 0 || n_cuboids > UAVAC_AUDIT_MAX_CUBOIDS)
-        return uavac_fail(ctx, UAVAC_EINVAL, "n_cuboids must be in [0, UAVAC_AUDIT_MAX_CUBOIDS]");
+    if (int rc = check_dt_positive(ctx, dt)) return rc;
+    if (int rc = check_n_cuboids(ctx, n_cuboids)) return rc;
     if (n_cuboids == 0 ? (cuboids || hit_rows || first_hit) : (!cuboids || !hit_rows || !first_hit))
         return uavac_fail(ctx, UAVAC_EINVAL, "cuboids, hit_rows and first_hit go with n_cuboids > 0: all three or none");
     return uavac_launch_audit(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, cuboids, n_cuboids, audit, hit_rows, first_hit);
@@ -852,7 +843,7 @@ static int check_pair_args(uavac_ctx *ctx, const double *coeffs, const int32_t *
                            int G, double radius, bool outputs) {
     if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
     if (!seg_rows || !outputs) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
+    if (int rc = check_dt_positive(ctx, dt)) return rc;
     if (!std::isfinite(radius) || radius < 0.0) return uavac_fail(ctx, UAVAC_EINVAL, "radius must be finite and >= 0");
     if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
     return UAVAC_OK;
@@ -902,9 +893,7 @@ int uavac_minsnap_delay_offsets_dev(uavac_ctx *ctx, const int64_t *seg_offsets, 
                                     int64_t *out_seg_offsets) {
     UAVAC_ENTER(ctx);
     if (!start_rows || !out_seg_offsets) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
-    if (m < 1 || m > UAVAC_MAX_SEGMENTS - 1)
-        return uavac_fail(ctx, UAVAC_EINVAL, "m must be in [1, UAVAC_MAX_SEGMENTS - 1]: a delayed mission needs one more segment");
+    if (int rc = check_take_shape(ctx, B, 1, m, true)) return rc;
     return uavac_launch_delay_offsets(ctx, seg_offsets, B, m, start_rows, out_seg_offsets);
 }
 
@@ -914,10 +903,8 @@ int uavac_minsnap_delay_dev(uavac_ctx *ctx, const double *coeffs, const double *
     UAVAC_ENTER(ctx);
     if (!coeffs || !seg_rows || !start_rows || !out_seg_offsets || !out_coeffs || !out_seg_rows)
         return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
-    if (m < 1 || m > UAVAC_MAX_SEGMENTS - 1)
-        return uavac_fail(ctx, UAVAC_EINVAL, "m must be in [1, UAVAC_MAX_SEGMENTS - 1]: a delayed mission needs one more segment");
-    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
+    if (int rc = check_take_shape(ctx, B, 1, m, true)) return rc;
+    if (int rc = check_dt_positive(ctx, dt)) return rc;
     if (!times != !out_times) return uavac_fail(ctx, UAVAC_EINVAL, "times and out_times go together: both or none");
     return uavac_launch_delay(ctx, coeffs, times, seg_rows, seg_offsets, B, m, dt, start_rows, out_seg_offsets, out_coeffs, out_times,
                               out_seg_rows);
@@ -952,8 +939,7 @@ int uavac_minsnap_layer_obs_dev(uavac_ctx *ctx, const double *coeffs, const int3
     UAVAC_ENTER(ctx);
     if (int rc = check_layer_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, delta_x, delta_y, delta_z, max_steps, ilayer, offsets))
         return rc;
-    if (n_cuboids < 0 || n_cuboids > UAVAC_AUDIT_MAX_CUBOIDS)
-        return uavac_fail(ctx, UAVAC_EINVAL, "n_cuboids must be in [0, UAVAC_AUDIT_MAX_CUBOIDS]");
+    if (int rc = check_n_cuboids(ctx, n_cuboids)) return rc;
     if (n_cuboids > 0 && !cuboids) return uavac_fail(ctx, UAVAC_EINVAL, "cuboids must be given when n_cuboids > 0");
     return uavac_launch_layer_obs(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, delta_x, delta_y, delta_z,
                                   max_steps, cuboids, n_cuboids, ilayer, offsets);
@@ -973,9 +959,7 @@ int uavac_minsnap_take_offsets_dev(uavac_ctx *ctx, const int64_t *seg_offsets, i
                                    int64_t *out_seg_offsets) {
     UAVAC_ENTER(ctx);
     if (!index || !out_seg_offsets) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
-    if (n < 1) return uavac_fail(ctx, UAVAC_EINVAL, "n must be >= 1");
-    if (m < 1 || m > UAVAC_MAX_SEGMENTS) return uavac_fail(ctx, UAVAC_EINVAL, "m must be in [1, UAVAC_MAX_SEGMENTS]");
+    if (int rc = check_take_shape(ctx, B, n, m)) return rc;
     return uavac_launch_take_offsets(ctx, seg_offsets, B, m, index, n, out_seg_offsets);
 }
 
@@ -985,9 +969,7 @@ int uavac_minsnap_take_dev(uavac_ctx *ctx, const double *coeffs, const double *t
     UAVAC_ENTER(ctx);
     if (!coeffs || !seg_rows || !index || !out_seg_offsets || !out_coeffs || !out_seg_rows)
         return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
-    if (n < 1) return uavac_fail(ctx, UAVAC_EINVAL, "n must be >= 1");
-    if (m < 1 || m > UAVAC_MAX_SEGMENTS) return uavac_fail(ctx, UAVAC_EINVAL, "m must be in [1, UAVAC_MAX_SEGMENTS]");
+    if (int rc = check_take_shape(ctx, B, n, m)) return rc;
     if (!times != !out_times) return uavac_fail(ctx, UAVAC_EINVAL, "times and out_times go together: both or none");
     if (!first_yaw != !out_first_yaw) return uavac_fail(ctx, UAVAC_EINVAL, "first_yaw and out_first_yaw go together: both or none");
     return uavac_launch_take(ctx, coeffs, times, seg_rows, seg_offsets, B, m, first_yaw, index, n, out_seg_offsets, out_coeffs, out_times,
@@ -1046,8 +1028,7 @@ int uavac_flown_audit_dev(uavac_ctx *ctx, const double *state_log, int K, int B,
     if (K < 1) return uavac_fail(ctx, UAVAC_EINVAL, "K must be >= 1");
     if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
     if (pitch < B) return uavac_fail(ctx, UAVAC_EINVAL, "pitch must be >= B");
-    if (n_cuboids < 0 || n_cuboids > UAVAC_AUDIT_MAX_CUBOIDS)
-        return uavac_fail(ctx, UAVAC_EINVAL, "n_cuboids must be in [0, UAVAC_AUDIT_MAX_CUBOIDS]");
+    if (int rc = check_n_cuboids(ctx, n_cuboids)) return rc;
     if (n_cuboids == 0 ? (cuboids || hit_ticks || first_hit || clearance || clearance_tick)
                        : (!cuboids || !hit_ticks || !first_hit || !clearance || !clearance_tick))
         return uavac_fail(ctx, UAVAC_EINVAL, "cuboids, hit_ticks, first_hit, clearance and clearance_tick go with n_cuboids > 0: all five or none");
@@ -1079,8 +1060,7 @@ int uavac_minsnap_obstacle_round_dev(uavac_ctx *ctx, const double *wp, const int
     if (!seg_offsets || !aabb || !active || !overflow || !touched || !wp_out || !seg_offsets_out || !counters || !times ||
         !seg_rows || !row_offsets || !coeffs || !hit)
         return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (!std::isfinite(velocity) || !std::isfinite(dt)) return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite velocity or dt");
-    if (!(velocity > 0.0) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "velocity and dt must be > 0");
+    if (int rc = check_velocity_dt(ctx, velocity, dt)) return rc;
     UAVAC_HIP(ctx, hipMemsetAsync(counters, 0, 4 * sizeof(int32_t), ctx->stream));
     if (int rc = uavac_launch_row_counts(ctx, wp, B, max_m, velocity, dt, times, seg_rows, row_offsets, seg_offsets)) return rc;
     if (int rc = uavac_launch_coeff_solve(ctx, wp, times, B, max_m, coeffs, nullptr, seg_offsets, nullptr, 0, active)) return rc;
@@ -1103,17 +1083,16 @@ int uavac_minsnap_row_counts(uavac_ctx *ctx, const double *wp, int B, int m, dou
     const size_t nwp = (size_t)B * (m + 1) * 3, nseg = (size_t)B * m;
     if (!finite_all(wp, nwp) || !std::isfinite(velocity) || !std::isfinite(dt))
         return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite waypoint, velocity or dt");
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size(nwp * 8) + uavac_arena_size(nseg * 8) +
-                                              uavac_arena_size(nseg * 4) + uavac_arena_size(((size_t)B + 1) * 8))) return rc;
-    double *dwp = take<double>(ctx, nwp), *dt_ = take<double>(ctx, nseg);
-    int32_t *dsr = take<int32_t>(ctx, nseg);
-    int64_t *dro = take<int64_t>(ctx, (size_t)B + 1);
+    double *dwp = nullptr, *dt_ = nullptr;
+    int32_t *dsr = nullptr;
+    int64_t *dro = nullptr;
+    Scratch s(ctx);
+    s.in(&dwp, wp, nwp); s.out(&dt_, times, nseg); s.out(&dsr, seg_rows, nseg); s.out(&dro, row_offsets, (size_t)B + 1);
+    if (int rc = s.commit()) return rc;
     if (int rc = clear_flags(ctx)) return rc;
-    if (int rc = h2d_staged(ctx, dwp, wp, nwp * 8)) return rc;
+    if (int rc = s.upload()) return rc;
     if (int rc = uavac_minsnap_row_counts_dev(ctx, dwp, B, m, velocity, dt, dt_, dsr, dro)) return rc;
-    if (times) if (int rc = d2h_staged(ctx, times, dt_, nseg * 8)) return rc;
-    if (seg_rows) if (int rc = d2h_staged(ctx, seg_rows, dsr, nseg * 4)) return rc;
-    if (int rc = d2h_staged(ctx, row_offsets, dro, ((size_t)B + 1) * 8)) return rc;
+    if (int rc = s.download()) return rc;
     int32_t fl[4];
     if (int rc = read_flags(ctx, fl)) return rc;
     if (fl[0]) return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite segment duration");
@@ -1130,20 +1109,18 @@ int uavac_minsnap_solve(uavac_ctx *ctx, const double *wp, int B, int m, double v
     if (!finite_all(wp, nwp) || !std::isfinite(velocity))
         return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite waypoint or velocity");
     if (!(velocity > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "velocity must be > 0");
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size(nwp * 8) + uavac_arena_size(nseg * 8) +
-                                              uavac_arena_size(nseg * 4) + uavac_arena_size(((size_t)B + 1) * 8) +
-                                              uavac_arena_size(nco * 8))) return rc;
-    double *dwp = take<double>(ctx, nwp), *dt_ = take<double>(ctx, nseg);
-    int32_t *dsr = take<int32_t>(ctx, nseg);
-    int64_t *dro = take<int64_t>(ctx, (size_t)B + 1);
-    double *dco = take<double>(ctx, nco);
+    double *dwp = nullptr, *dt_ = nullptr, *dco = nullptr;
+    int32_t *dsr = nullptr;
+    int64_t *dro = nullptr;
+    Scratch s(ctx);
+    s.in(&dwp, wp, nwp); s.out(&dt_, times, nseg); s.want(&dsr, nseg); s.want(&dro, (size_t)B + 1); s.out(&dco, coeffs, nco);
+    if (int rc = s.commit()) return rc;
     if (int rc = clear_flags(ctx)) return rc;
-    if (int rc = h2d_staged(ctx, dwp, wp, nwp * 8)) return rc;
+    if (int rc = s.upload()) return rc;
     // dt only shapes the row counts, which this entry point does not return
     if (int rc = uavac_launch_row_counts(ctx, dwp, B, m, velocity, 1.0, dt_, dsr, dro)) return rc;
     if (int rc = uavac_launch_coeff_solve(ctx, dwp, dt_, B, m, dco, nullptr)) return rc;
-    if (int rc = d2h_staged(ctx, coeffs, dco, nco * 8)) return rc;
-    if (times) if (int rc = d2h_staged(ctx, times, dt_, nseg * 8)) return rc;
+    if (int rc = s.download()) return rc;
     int32_t fl[4];
     if (int rc = read_flags(ctx, fl)) return rc;
     if (fl[0]) return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite segment duration");
@@ -1156,7 +1133,7 @@ int uavac_minsnap_sample(uavac_ctx *ctx, const double *coeffs, const double *tim
     UAVAC_ENTER(ctx);
     if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
     if (!times || !row_offsets || !traj) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
+    if (int rc = check_dt_positive(ctx, dt)) return rc;
     const size_t nseg = (size_t)B * m, nco = (size_t)B * 24 * m;
     // rows per segment, as uavac_minsnap_row_counts computes them; must agree with the caller's offsets
     std::vector<int32_t> sr(nseg);
@@ -1174,17 +1151,15 @@ int uavac_minsnap_sample(uavac_ctx *ctx, const double *coeffs, const double *tim
     const int64_t total = row_offsets[B] - row_offsets[0];
     if (row_offsets[0] != 0 || total < 0) return uavac_fail(ctx, UAVAC_EINVAL, "row_offsets must start at 0");
     const size_t ntr = (size_t)total * UAVAC_TRAJ_COLS;
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size(nco * 8) + uavac_arena_size(nseg * 4) +
-                                              uavac_arena_size(((size_t)B + 1) * 8) + uavac_arena_size(ntr * 8))) return rc;
-    double *dco = take<double>(ctx, nco);
-    int32_t *dsr = take<int32_t>(ctx, nseg);
-    int64_t *dro = take<int64_t>(ctx, (size_t)B + 1);
-    double *dtr = take<double>(ctx, ntr);
-    if (int rc = h2d_staged(ctx, dco, coeffs, nco * 8)) return rc;
-    if (int rc = h2d_staged(ctx, dsr, sr.data(), nseg * 4)) return rc;
-    if (int rc = h2d_staged(ctx, dro, row_offsets, ((size_t)B + 1) * 8)) return rc;
+    double *dco = nullptr, *dtr = nullptr;
+    int32_t *dsr = nullptr;
+    int64_t *dro = nullptr;
+    Scratch s(ctx);
+    s.in(&dco, coeffs, nco); s.in(&dsr, sr.data(), nseg); s.in(&dro, row_offsets, (size_t)B + 1); s.out(&dtr, traj, ntr);
+    if (int rc = s.commit()) return rc;
+    if (int rc = s.upload()) return rc;
     if (int rc = uavac_launch_sample(ctx, dco, dsr, dro, B, m, dt, dtr, SampleExtras{})) return rc;
-    if (int rc = d2h_staged(ctx, traj, dtr, ntr * 8)) return rc;
+    if (int rc = s.download()) return rc;
     UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return UAVAC_OK;
 }
@@ -1207,24 +1182,20 @@ int uavac_minsnap_plan_ragged(uavac_ctx *ctx, const double *wp, const int64_t *s
     if (!finite_all(wp, nwp) || !std::isfinite(velocity) || !std::isfinite(dt))
         return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite waypoint, velocity or dt");
     if (!(velocity > 0.0) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "velocity and dt must be > 0");
-    const size_t fixed = uavac_arena_size(nwp * 8) + 2 * uavac_arena_size(((size_t)B + 1) * 8) + uavac_arena_size(S * 8) +
-                         uavac_arena_size(S * 4) + uavac_arena_size(nco * 8);
-    auto stage_inputs = [&](size_t row_bytes, double *&dwp, int64_t *&dso, double *&dtm, int32_t *&dsr, int64_t *&dro,
-                            double *&dco, double *&dtr) -> int {
-        if (int rc = uavac_arena_reserve(ctx, fixed + uavac_arena_size(row_bytes))) return rc;
-        dwp = take<double>(ctx, nwp); dso = take<int64_t>(ctx, (size_t)B + 1); dtm = take<double>(ctx, S);
-        dsr = take<int32_t>(ctx, S); dro = take<int64_t>(ctx, (size_t)B + 1); dco = take<double>(ctx, nco);
-        dtr = row_bytes ? take<double>(ctx, row_bytes / 8) : nullptr;
-        if (int rc = h2d_staged(ctx, dwp, wp, nwp * 8)) return rc;
-        return h2d_staged(ctx, dso, seg_offsets, ((size_t)B + 1) * 8);
+    double *dwp = nullptr, *dtm = nullptr, *dco = nullptr, *dtr = nullptr;
+    int64_t *dso = nullptr, *dro = nullptr;
+    int32_t *dsr = nullptr;
+    Scratch s(ctx);
+    s.want(&dwp, nwp); s.want(&dso, (size_t)B + 1); s.want(&dtm, S); s.want(&dsr, S); s.want(&dro, (size_t)B + 1); s.want(&dco, nco);
+    auto stage_inputs = [&]() -> int {          // (again once the rows are registered: a commit lays every piece out anew)
+        if (int rc = s.commit()) return rc;
+        if (int rc = uavac_h2d(ctx, dwp, wp, nwp * 8)) return rc;
+        return uavac_h2d(ctx, dso, seg_offsets, ((size_t)B + 1) * 8);
     };
-    double *dwp, *dtm, *dco, *dtr;
-    int64_t *dso, *dro;
-    int32_t *dsr;
     if (int rc = clear_flags(ctx)) return rc;
-    if (int rc = stage_inputs(0, dwp, dso, dtm, dsr, dro, dco, dtr)) return rc;
+    if (int rc = stage_inputs()) return rc;
     if (int rc = uavac_launch_row_counts(ctx, dwp, B, max_m, velocity, dt, dtm, dsr, dro, dso)) return rc;
-    if (int rc = d2h_staged(ctx, row_offsets, dro, ((size_t)B + 1) * 8)) return rc;
+    if (int rc = uavac_d2h(ctx, row_offsets, dro, ((size_t)B + 1) * 8)) return rc;
     UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     int32_t fl[4];
     if (int rc = read_flags(ctx, fl)) return rc;
@@ -1233,7 +1204,8 @@ int uavac_minsnap_plan_ragged(uavac_ctx *ctx, const double *wp, const int64_t *s
     const int64_t total = row_offsets[B];
     const bool rows = traj && traj_capacity_rows >= total && total > 0;
     if (rows) {             // the arena grows for the rows: stage again (cheap next to the rows) and redo the counts
-        if (int rc = stage_inputs((size_t)total * UAVAC_TRAJ_COLS * 8, dwp, dso, dtm, dsr, dro, dco, dtr)) return rc;
+        s.want(&dtr, (size_t)total * UAVAC_TRAJ_COLS);
+        if (int rc = stage_inputs()) return rc;
         if (int rc = uavac_launch_row_counts(ctx, dwp, B, max_m, velocity, dt, dtm, dsr, dro, dso)) return rc;
     }
     if (int rc = uavac_launch_coeff_solve(ctx, dwp, dtm, B, max_m, dco, nullptr, dso)) return rc;
@@ -1243,10 +1215,10 @@ int uavac_minsnap_plan_ragged(uavac_ctx *ctx, const double *wp, const int64_t *s
         x.total_segments = (int64_t)S;
         x.capacity_rows = total;
         if (int rc = uavac_launch_sample(ctx, dco, dsr, dro, B, max_m, dt, dtr, x)) return rc;
-        if (int rc = d2h_staged(ctx, traj, dtr, (size_t)total * UAVAC_TRAJ_COLS * 8)) return rc;
+        if (int rc = uavac_d2h(ctx, traj, dtr, (size_t)total * UAVAC_TRAJ_COLS * 8)) return rc;
     }
-    if (times) if (int rc = d2h_staged(ctx, times, dtm, S * 8)) return rc;
-    if (coeffs) if (int rc = d2h_staged(ctx, coeffs, dco, nco * 8)) return rc;
+    if (times) if (int rc = uavac_d2h(ctx, times, dtm, S * 8)) return rc;
+    if (coeffs) if (int rc = uavac_d2h(ctx, coeffs, dco, nco * 8)) return rc;
     UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (int rc = read_flags(ctx, fl)) return rc;
     if (fl[1]) return uavac_fail(ctx, UAVAC_ESINGULAR, "singular knot system (repeated waypoint?)");
@@ -1280,26 +1252,19 @@ int uavac_minsnap_obstacle_waypoints(uavac_ctx *ctx, const double *wp, const int
         return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite waypoint, cuboid, velocity or dt");
     if (!(velocity > 0.0) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "velocity and dt must be > 0");
     const size_t S_cap = nB * UAVAC_MAX_SEGMENTS, W_cap = (S_cap + nB) * 3;         // no mission ever has more segments
-    if (int rc = uavac_arena_reserve(ctx, 2 * uavac_arena_size(W_cap * 8) + 2 * uavac_arena_size((nB + 1) * 8) +
-                                              4 * uavac_arena_size(nB * 4) + uavac_arena_size(16) + uavac_arena_size(S_cap * 8) +
-                                              2 * uavac_arena_size(S_cap * 4) + uavac_arena_size((nB + 1) * 8) +
-                                              uavac_arena_size(S_cap * 192) + uavac_arena_size((size_t)(n_cuboids ? n_cuboids : 1) * 48)))
-        return rc;
-    double *wp_a = take<double>(ctx, W_cap), *wp_b = take<double>(ctx, W_cap);
-    int64_t *so_a = take<int64_t>(ctx, nB + 1), *so_b = take<int64_t>(ctx, nB + 1);
-    int32_t *d_active = take<int32_t>(ctx, nB), *d_overflow = take<int32_t>(ctx, nB), *d_touched = take<int32_t>(ctx, nB);
-    int32_t *d_spare = take<int32_t>(ctx, nB);
-    (void)d_spare;
-    int32_t *d_counters = take<int32_t>(ctx, 4);
-    double *d_times = take<double>(ctx, S_cap);
-    int32_t *d_seg_rows = take<int32_t>(ctx, S_cap), *d_hit = take<int32_t>(ctx, S_cap);
-    int64_t *d_row_offsets = take<int64_t>(ctx, nB + 1);
-    double *d_coeffs = take<double>(ctx, S_cap * 24);
-    double *d_cub = take<double>(ctx, (size_t)(n_cuboids ? n_cuboids : 1) * 6);
+    double *wp_a = nullptr, *wp_b = nullptr, *d_times = nullptr, *d_coeffs = nullptr, *d_cub = nullptr;
+    int64_t *so_a = nullptr, *so_b = nullptr, *d_row_offsets = nullptr;
+    int32_t *d_active = nullptr, *d_overflow = nullptr, *d_touched = nullptr, *d_counters = nullptr, *d_seg_rows = nullptr, *d_hit = nullptr;
+    Scratch s(ctx);
+    s.want(&wp_a, W_cap); s.want(&wp_b, W_cap); s.want(&so_a, nB + 1); s.want(&so_b, nB + 1);
+    s.want(&d_active, nB); s.want(&d_overflow, nB); s.want(&d_touched, nB); s.want(&d_counters, 4);
+    s.want(&d_times, S_cap); s.want(&d_seg_rows, S_cap); s.want(&d_hit, S_cap); s.want(&d_row_offsets, nB + 1);
+    s.want(&d_coeffs, S_cap * 24); s.want(&d_cub, (size_t)n_cuboids * 6);
+    if (int rc = s.commit()) return rc;
     if (int rc = clear_flags(ctx)) return rc;
-    if (int rc = h2d_staged(ctx, wp_a, wp, (S0 + nB) * 24)) return rc;
-    if (int rc = h2d_staged(ctx, so_a, seg_offsets, (nB + 1) * 8)) return rc;
-    if (n_cuboids) if (int rc = h2d_staged(ctx, d_cub, cuboids, (size_t)n_cuboids * 48)) return rc;
+    if (int rc = uavac_h2d(ctx, wp_a, wp, (S0 + nB) * 24)) return rc;
+    if (int rc = uavac_h2d(ctx, so_a, seg_offsets, (nB + 1) * 8)) return rc;
+    if (n_cuboids) if (int rc = uavac_h2d(ctx, d_cub, cuboids, (size_t)n_cuboids * 48)) return rc;
     UAVAC_HIP(ctx, hipMemsetAsync(d_overflow, 0, nB * 4, ctx->stream));
     std::vector<int32_t> todo(nB, 1), failed(nB, 0), active(nB), touched(nB), overflow(nB);
     for (int sweep = 0; sweep <= recheck_passes && n_cuboids > 0; ++sweep) {
@@ -1307,7 +1272,7 @@ int uavac_minsnap_obstacle_waypoints(uavac_ctx *ctx, const double *wp, const int
         for (int c = 0; c < n_cuboids; ++c) {
             int n_active = 0;
             for (size_t b = 0; b < nB; ++b) { active[b] = todo[b] && !failed[b]; n_active += active[b]; }
-            if (int rc = h2d_staged(ctx, d_active, active.data(), nB * 4)) return rc;
+            if (int rc = uavac_h2d(ctx, d_active, active.data(), nB * 4)) return rc;
             int it = 0;
             for (; it <= max_iterations && n_active > 0; ++it) {
                 if (int rc = uavac_minsnap_obstacle_round_dev(ctx, wp_a, so_a, B, max_m, velocity, dt, d_cub + 6 * c, d_active,
@@ -1316,32 +1281,32 @@ int uavac_minsnap_obstacle_waypoints(uavac_ctx *ctx, const double *wp, const int
                 std::swap(wp_a, wp_b);
                 std::swap(so_a, so_b);
                 int32_t cnt[4];
-                if (int rc = d2h_staged(ctx, cnt, d_counters, 16)) return rc;           // the round's one read-back (synchronises)
+                if (int rc = uavac_d2h(ctx, cnt, d_counters, 16)) return rc;           // the round's one read-back (synchronises)
                 n_active = cnt[0];
                 if (cnt[2] > max_m) max_m = cnt[2];
                 if (cnt[1]) {                                                           // outgrew UAVAC_MAX_SEGMENTS: stays as it is
-                    if (int rc = d2h_staged(ctx, overflow.data(), d_overflow, nB * 4)) return rc;
+                    if (int rc = uavac_d2h(ctx, overflow.data(), d_overflow, nB * 4)) return rc;
                     for (size_t b = 0; b < nB; ++b) failed[b] |= overflow[b];
                 }
             }
             if (n_active > 0) {                                                         // the bounded loop ran out
-                if (int rc = d2h_staged(ctx, active.data(), d_active, nB * 4)) return rc;
+                if (int rc = uavac_d2h(ctx, active.data(), d_active, nB * 4)) return rc;
                 for (size_t b = 0; b < nB; ++b) failed[b] |= (active[b] != 0);
             }
         }
-        if (int rc = d2h_staged(ctx, touched.data(), d_touched, nB * 4)) return rc;
+        if (int rc = uavac_d2h(ctx, touched.data(), d_touched, nB * 4)) return rc;
         int again = 0;
         for (size_t b = 0; b < nB; ++b) { todo[b] = touched[b] && !failed[b]; again += todo[b]; }
         if (!again) break;                                                              // only missions that changed can have new conflicts
     }
-    if (int rc = d2h_staged(ctx, seg_offsets_out, so_a, (nB + 1) * 8)) return rc;
+    if (int rc = uavac_d2h(ctx, seg_offsets_out, so_a, (nB + 1) * 8)) return rc;
     UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const int64_t n_wp = seg_offsets_out[B] + B;
     int32_t fl[4];
     if (int rc = read_flags(ctx, fl)) return rc;
     if (fl[0]) return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite segment duration");
     if (n_wp > wp_capacity) return uavac_fail(ctx, UAVAC_EINVAL, "wp_capacity too small: seg_offsets_out[B] + B waypoints are needed");
-    if (int rc = d2h_staged(ctx, wp_out, wp_a, (size_t)n_wp * 24)) return rc;
+    if (int rc = uavac_d2h(ctx, wp_out, wp_a, (size_t)n_wp * 24)) return rc;
     UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (converged) for (size_t b = 0; b < nB; ++b) converged[b] = failed[b] ? 0 : 1;
     // a singular knot system (a repeated waypoint) gives NaN coefficients, and NaN positions are inside no cuboid: such a
@@ -1354,15 +1319,15 @@ int uavac_yaw_scan(uavac_ctx *ctx, const double *velocities, int64_t n, double *
     UAVAC_ENTER(ctx);
     if (n < 0 || (n > 0 && (!velocities || !yaws))) return uavac_fail(ctx, UAVAC_EINVAL, "bad n or null pointer");
     if (n == 0) return UAVAC_OK;
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size((size_t)n * 24) + uavac_arena_size((size_t)n * 8) +
-                                              uavac_arena_size(16))) return rc;
-    double *dv = take<double>(ctx, (size_t)n * 3), *dy = take<double>(ctx, (size_t)n);
-    int64_t *doff = take<int64_t>(ctx, 2);
+    double *dv = nullptr, *dy = nullptr;
+    int64_t *doff = nullptr;
     const int64_t off[2] = {0, n};
-    if (int rc = h2d_staged(ctx, dv, velocities, (size_t)n * 24)) return rc;
-    if (int rc = h2d_staged(ctx, doff, off, 16)) return rc;
+    Scratch s(ctx);
+    s.in(&dv, velocities, (size_t)n * 3); s.out(&dy, yaws, (size_t)n); s.in(&doff, off, 2);
+    if (int rc = s.commit()) return rc;
+    if (int rc = s.upload()) return rc;
     if (int rc = uavac_launch_yaw_scan(ctx, dv, doff, 1, dy)) return rc;
-    if (int rc = d2h_staged(ctx, yaws, dy, (size_t)n * 8)) return rc;
+    if (int rc = s.download()) return rc;
     UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return UAVAC_OK;
 }
@@ -1390,41 +1355,24 @@ static int rollout_rows(uavac_ctx *ctx, const uavac_vehicle *V, const double *tr
                                 aabbs, n_obs, nullptr, score);
 }
 
-static int rollout_plan(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs, const int32_t *seg_rows,
-                        const int64_t *row_offsets, const double *yaw, const double *first_yaw, int m, double dt, double *state,
-                        int32_t *istate, int B, int K, double *state_log, double *cmd_log, const double *aabbs, int n_obs,
-                        double *score) {
+// The plan-fed rollout, uniform (`ragged` false: seg_offsets is NULL; the dense yaw column or the first headings) or ragged (seg_offsets
+// and first_yaw are required, there is no dense yaw column: yaw is NULL)
+static int rollout_plan(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs, const int32_t *seg_rows, bool ragged,
+                        const int64_t *seg_offsets, const int64_t *row_offsets, const double *yaw, const double *first_yaw, int m,
+                        double dt, double *state, int32_t *istate, int B, int K, double *state_log, double *cmd_log,
+                        const double *aabbs, int n_obs, double *score) {
     UAVAC_ENTER(ctx);
     if (int rc = uavac_check_vehicle(ctx, V)) return rc;
     if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
-    if (K < 0 || !seg_rows || !row_offsets || !state || !istate || n_obs < 0)
+    if (K < 0 || !seg_rows || !row_offsets || !state || !istate || n_obs < 0 || (ragged && (!seg_offsets || !first_yaw)))
         return uavac_fail(ctx, UAVAC_EINVAL, "bad size or null pointer");
     if (!yaw && !first_yaw) return uavac_fail(ctx, UAVAC_EINVAL, "need the dense yaw column or the missions' first headings");
-    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
+    if (int rc = check_dt_positive(ctx, dt)) return rc;
     if (K == 0) return UAVAC_OK;
     if ((state_log || cmd_log) && ctx->log_pitch > 0 && ctx->log_pitch < B)
         return uavac_fail(ctx, UAVAC_EINVAL, "option log_pitch is smaller than B");
     PlanRef plan;
     plan.coeffs = coeffs; plan.seg_rows = seg_rows; plan.yaw = yaw; plan.first_yaw = first_yaw; plan.dt = dt; plan.m = m;
-    return uavac_launch_rollout(ctx, uavac_make_vehk(*V), nullptr, row_offsets, state, istate, B, K, state_log, cmd_log,
-                                aabbs, n_obs, &plan, score);
-}
-
-static int rollout_plan_ragged(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs, const int32_t *seg_rows,
-                               const int64_t *seg_offsets, const int64_t *row_offsets, const double *first_yaw, int max_m,
-                               double dt, double *state, int32_t *istate, int B, int K, double *state_log, double *cmd_log,
-                               const double *aabbs, int n_obs, double *score) {
-    UAVAC_ENTER(ctx);
-    if (int rc = uavac_check_vehicle(ctx, V)) return rc;
-    if (int rc = check_plan_args(ctx, coeffs, B, max_m)) return rc;
-    if (K < 0 || !seg_rows || !seg_offsets || !row_offsets || !first_yaw || !state || !istate || n_obs < 0)
-        return uavac_fail(ctx, UAVAC_EINVAL, "bad size or null pointer");
-    if (!std::isfinite(dt) || !(dt > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "dt must be finite and > 0");
-    if (K == 0) return UAVAC_OK;
-    if ((state_log || cmd_log) && ctx->log_pitch > 0 && ctx->log_pitch < B)
-        return uavac_fail(ctx, UAVAC_EINVAL, "option log_pitch is smaller than B");
-    PlanRef plan;
-    plan.coeffs = coeffs; plan.seg_rows = seg_rows; plan.first_yaw = first_yaw; plan.dt = dt; plan.m = max_m;
     plan.seg_offsets = seg_offsets;
     return uavac_launch_rollout(ctx, uavac_make_vehk(*V), nullptr, row_offsets, state, istate, B, K, state_log, cmd_log,
                                 aabbs, n_obs, &plan, score);
@@ -1447,16 +1395,16 @@ int uavac_control_rollout_plan_dev(uavac_ctx *ctx, const uavac_vehicle *V, const
                                    const int64_t *row_offsets, const double *yaw, const double *first_yaw, int m, double dt,
                                    double *state, int32_t *istate, int B, int K, double *state_log, double *cmd_log,
                                    const double *aabbs, int n_obs) {
-    return rollout_plan(ctx, V, coeffs, seg_rows, row_offsets, yaw, first_yaw, m, dt, state, istate, B, K, state_log, cmd_log,
-                        aabbs, n_obs, nullptr);
+    return rollout_plan(ctx, V, coeffs, seg_rows, false, nullptr, row_offsets, yaw, first_yaw, m, dt, state, istate, B, K, state_log,
+                        cmd_log, aabbs, n_obs, nullptr);
 }
 
 int uavac_control_rollout_plan_ragged_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs, const int32_t *seg_rows,
                                           const int64_t *seg_offsets, const int64_t *row_offsets, const double *first_yaw,
                                           int max_m, double dt, double *state, int32_t *istate, int B, int K,
                                           double *state_log, double *cmd_log, const double *aabbs, int n_obs) {
-    return rollout_plan_ragged(ctx, V, coeffs, seg_rows, seg_offsets, row_offsets, first_yaw, max_m, dt, state, istate, B, K,
-                               state_log, cmd_log, aabbs, n_obs, nullptr);
+    return rollout_plan(ctx, V, coeffs, seg_rows, true, seg_offsets, row_offsets, nullptr, first_yaw, max_m, dt, state, istate, B, K,
+                        state_log, cmd_log, aabbs, n_obs, nullptr);
 }
 
 int uavac_control_rollout_scored_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *traj, const int64_t *row_offsets,
@@ -1473,8 +1421,8 @@ int uavac_control_rollout_plan_scored_dev(uavac_ctx *ctx, const uavac_vehicle *V
                                           const double *aabbs, int n_obs, double *score) {
     UAVAC_ENTER(ctx);
     if (int rc = check_score_args(ctx, cmd_log, score)) return rc;
-    return rollout_plan(ctx, V, coeffs, seg_rows, row_offsets, yaw, first_yaw, m, dt, state, istate, B, K, state_log, cmd_log,
-                        aabbs, n_obs, score);
+    return rollout_plan(ctx, V, coeffs, seg_rows, false, nullptr, row_offsets, yaw, first_yaw, m, dt, state, istate, B, K, state_log,
+                        cmd_log, aabbs, n_obs, score);
 }
 
 int uavac_control_rollout_plan_ragged_scored_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *coeffs,
@@ -1484,8 +1432,8 @@ int uavac_control_rollout_plan_ragged_scored_dev(uavac_ctx *ctx, const uavac_veh
                                                  double *score) {
     UAVAC_ENTER(ctx);
     if (int rc = check_score_args(ctx, cmd_log, score)) return rc;
-    return rollout_plan_ragged(ctx, V, coeffs, seg_rows, seg_offsets, row_offsets, first_yaw, max_m, dt, state, istate, B, K,
-                               state_log, cmd_log, aabbs, n_obs, score);
+    return rollout_plan(ctx, V, coeffs, seg_rows, true, seg_offsets, row_offsets, nullptr, first_yaw, max_m, dt, state, istate, B, K,
+                        state_log, cmd_log, aabbs, n_obs, score);
 }
 
 int uavac_control_step_dev(uavac_ctx *ctx, const uavac_vehicle *V, const double *traj, const int64_t *row_offsets,
@@ -1500,15 +1448,15 @@ int uavac_state_init(uavac_ctx *ctx, const uavac_vehicle *V, const double *posit
     if (B < 1 || !state || !istate) return uavac_fail(ctx, UAVAC_EINVAL, "bad B or null state");
     if (positions && !finite_all(positions, (size_t)B * 3)) return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite position");
     const size_t ns = (size_t)B * UAVAC_STATE_ROWS, ni = (size_t)B * UAVAC_ISTATE_ROWS;
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size(ns * 8) + uavac_arena_size(ni * 4) +
-                                              uavac_arena_size((size_t)B * 24))) return rc;
-    double *ds = take<double>(ctx, ns);
-    int32_t *di = take<int32_t>(ctx, ni);
-    double *dp = positions ? take<double>(ctx, (size_t)B * 3) : nullptr;
-    if (positions) if (int rc = h2d_staged(ctx, dp, positions, (size_t)B * 24)) return rc;
+    double *ds = nullptr, *dp = nullptr;
+    int32_t *di = nullptr;
+    Scratch s(ctx);
+    s.out(&ds, state, ns); s.out(&di, istate, ni);
+    if (positions) s.in(&dp, positions, (size_t)B * 3);
+    if (int rc = s.commit()) return rc;
+    if (int rc = s.upload()) return rc;
     if (int rc = uavac_state_init_dev(ctx, V, dp, B, hover, ds, di)) return rc;
-    if (int rc = d2h_staged(ctx, state, ds, ns * 8)) return rc;
-    if (int rc = d2h_staged(ctx, istate, di, ni * 4)) return rc;
+    if (int rc = s.download()) return rc;
     UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return UAVAC_OK;
 }
@@ -1527,33 +1475,24 @@ int uavac_control_rollout(uavac_ctx *ctx, const uavac_vehicle *V, const double *
     const size_t ntr = total * UAVAC_TRAJ_COLS, ns = (size_t)B * UAVAC_STATE_ROWS, ni = (size_t)B * UAVAC_ISTATE_ROWS;
     const size_t nsl = state_log ? (size_t)K * 13 * B : 0, ncl = cmd_log ? (size_t)K * UAVAC_CMD_COLS * B : 0;
     const bool obs = aabbs && n_obs > 0;
-    if (int rc = uavac_arena_reserve(ctx, uavac_arena_size(ntr * 8) + uavac_arena_size(((size_t)B + 1) * 8) +
-                                              uavac_arena_size(ns * 8) + uavac_arena_size(ni * 4) +
-                                              uavac_arena_size(nsl * 8) + uavac_arena_size(ncl * 8) +
-                                              uavac_arena_size((size_t)n_obs * 48))) return rc;
-    double *dtr = take<double>(ctx, ntr);
-    int64_t *dro = take<int64_t>(ctx, (size_t)B + 1);
-    double *ds = take<double>(ctx, ns);
-    int32_t *di = take<int32_t>(ctx, ni);
-    double *dsl = state_log ? take<double>(ctx, nsl) : nullptr;
-    double *dcl = cmd_log ? take<double>(ctx, ncl) : nullptr;
-    double *dab = obs ? take<double>(ctx, (size_t)n_obs * 6) : nullptr;
-    if (int rc = h2d_staged(ctx, dtr, traj, ntr * 8)) return rc;
-    if (int rc = h2d_staged(ctx, dro, row_offsets, ((size_t)B + 1) * 8)) return rc;
-    if (int rc = h2d_staged(ctx, ds, state, ns * 8)) return rc;
-    if (int rc = h2d_staged(ctx, di, istate, ni * 4)) return rc;
-    if (obs) if (int rc = h2d_staged(ctx, dab, aabbs, (size_t)n_obs * 48)) return rc;
+    double *dtr = nullptr, *ds = nullptr, *dsl = nullptr, *dcl = nullptr, *dab = nullptr;
+    int64_t *dro = nullptr;
+    int32_t *di = nullptr;
+    Scratch s(ctx);
+    s.in(&dtr, traj, ntr); s.in(&dro, row_offsets, (size_t)B + 1); s.inout(&ds, state, ns); s.inout(&di, istate, ni);
+    if (state_log) s.out(&dsl, state_log, nsl);
+    if (cmd_log) s.out(&dcl, cmd_log, ncl);
+    if (obs) s.in(&dab, aabbs, (size_t)n_obs * 6);
+    if (int rc = s.commit()) return rc;
+    if (int rc = s.upload()) return rc;
     {
-        const int64_t pitch = ctx->log_pitch;          // the host logs are dense [K][13 | 12][B]
+        const int pitch = ctx->log_pitch;              // the host logs are dense [K][13 | 12][B]
         ctx->log_pitch = 0;
         const int rc = uavac_control_rollout_dev(ctx, V, dtr, dro, ds, di, B, K, dsl, dcl, dab, obs ? n_obs : 0);
         ctx->log_pitch = pitch;
         if (rc) return rc;
     }
-    if (int rc = d2h_staged(ctx, state, ds, ns * 8)) return rc;
-    if (int rc = d2h_staged(ctx, istate, di, ni * 4)) return rc;
-    if (state_log) if (int rc = d2h_staged(ctx, state_log, dsl, nsl * 8)) return rc;
-    if (cmd_log) if (int rc = d2h_staged(ctx, cmd_log, dcl, ncl * 8)) return rc;
+    if (int rc = s.download()) return rc;
     UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return UAVAC_OK;
 }

@@ -9,6 +9,7 @@
 // (The reference has no counterpart: it plans and flies one mission per process, uav_ac/main.py:87-120.)
 
 #include "uavac_internal.h"
+#include "uavac_scratch.h"
 
 #include <rccl/rccl.h>
 
@@ -117,7 +118,9 @@ int uavac_gather_counts(uavac_ctx *ctx, void *nccl_comm, int64_t n_rows, int64_t
     int world = 0, rank = 0;
     if (int rc = comm_shape(ctx, comm, &world, &rank)) return rc;
     int64_t *d = nullptr;                                          // [1 + world] i64 of device scratch
-    if (int rc = uavac_scratch(ctx, (size_t)(1 + world) * 8, reinterpret_cast<void **>(&d))) return rc;
+    Scratch s(ctx);
+    s.want(&d, (size_t)(1 + world));
+    if (int rc = s.commit()) return rc;
     UAVAC_HIP(ctx, hipMemcpyAsync(d, &n_rows, 8, hipMemcpyHostToDevice, ctx->stream));
     UAVAC_NCCL(ctx, ncclAllGather(d, d + 1, 1, ncclInt64, comm, ctx->stream));
     UAVAC_HIP(ctx, hipMemcpyAsync(counts, d + 1, (size_t)world * 8, hipMemcpyDeviceToHost, ctx->stream));

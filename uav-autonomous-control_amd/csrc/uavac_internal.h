@@ -21,10 +21,10 @@ struct uavac_ctx {
     char *d_plan = nullptr;          // uavac_minsnap_plan_dev: times / seg_rows / row_offsets before they are committed
     size_t plan_cap = 0;             // in bytes
     // Device scratch of the host-pointer twins and small internal temporaries: one arena, grown on demand and kept,
-    // handed out by bump allocation inside one entry point (uavac_arena_reserve, then uavac_arena_take).  Reuse across
-    // calls is ordered by the ctx stream.
+    // laid out anew by every Scratch (uavac_scratch.h) that commits.  Reuse across calls is ordered by the ctx stream.
     char *d_arena = nullptr;
-    size_t arena_cap = 0, arena_top = 0;
+    size_t arena_cap = 0;
+    bool scratch_live = false;       // a committed Scratch holds pieces of the arena: a second one must not lay it out again
     // Pinned host staging (hipHostMalloc) of the host-pointer twins: two halves used as a ping-pong pipeline.
     char *h_pin = nullptr;
     size_t pin_cap = 0;
@@ -48,7 +48,7 @@ struct uavac_ctx {
     int idle_waves = -1;             // tuning: placeholder wave between compute and store wave (0 / 1); -1 = the launcher picks
     int cu_balance = 1;              // tuning: a logged rollout below a full chip asks for as much LDS per workgroup as keeps a CU from taking more workgroups than its even share (0: off)
     int lds_pad = 0;                 // tuning: extra dynamic LDS per rollout workgroup (bytes): caps the workgroups a CU takes
-    int64_t log_pitch = 0;           // doubles per row of the rollout's logs; 0 = B (option "log_pitch")
+    int log_pitch = 0;               // doubles per row of the rollout's logs; 0 = B (option "log_pitch")
     int n_simds = 1024;              // SIMDs of the device (4 per CU): the logged rollout launches one workgroup per SIMD at most
     std::string last_rollout;        // name and template arguments of the rollout kernel launched last (diagnostics)
     int last_rollout_vgprs = 0;      // ... and its vector registers per lane (hipFuncGetAttributes); 0 = unknown
@@ -123,13 +123,25 @@ __device__ __forceinline__ int xcd_contiguous(int block, int n) {
 // yaw scan uses, on 2^16 + 144 operand pairs; *mismatches = pairs whose bits differ.
 int uavac_heading_selfcheck(uavac_ctx *ctx, int *mismatches);
 
-// Device scratch arena (uavac_api.hip).  reserve() makes room for `bytes` in total (synchronises the stream and
-// reallocates when it has to grow) and rewinds the arena; take() hands out 256-byte aligned pieces of it.
+// "Grow this ctx buffer if it is too small", for every buffer the ctx owns: `cap` and `need` are in the buffer's own unit, `bytes`
+// is what `need` takes.  The old block is freed after the ctx stream has drained (nothing enqueued may still use it); what it
+// held is lost.  `pinned`: page-locked host memory instead of device memory.
+template <class T>
+int uavac_grow(uavac_ctx *ctx, T *&buf, size_t &cap, size_t need, size_t bytes, bool pinned = false) {
+    if (need <= cap) return UAVAC_OK;
+    UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (buf) UAVAC_HIP(ctx, pinned ? hipHostFree(buf) : hipFree(buf));
+    buf = nullptr;
+    cap = 0;
+    void *p = nullptr;
+    UAVAC_HIP(ctx, pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes));
+    buf = static_cast<T *>(p);
+    cap = need;
+    return UAVAC_OK;
+}
+// Device scratch arena (uavac_api.hip): room for `bytes` in total, with headroom when it has to grow.  Scratch::commit
+// (uavac_scratch.h) is its one caller.
 int uavac_arena_reserve(uavac_ctx *ctx, size_t bytes);
-void *uavac_arena_take(uavac_ctx *ctx, size_t bytes);
-static inline size_t uavac_arena_size(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-// One small temporary: reserve + take.
-int uavac_scratch(uavac_ctx *ctx, size_t bytes, void **out);
 // Pinned staging: at least `bytes` of page-locked host memory in ctx->h_pin.
 int uavac_pin_reserve(uavac_ctx *ctx, size_t bytes);
 // Pageable host buffer <-> device through the pinned ping-pong buffer, ordered on the ctx stream (uavac_api.hip).
