@@ -4,7 +4,12 @@
 device entry points.  Every comparison is of bytes.  B = 3 missions of m = 2 segments (the ragged batch: 1, 2 and 2), K = 2 ticks; every
 twin runs with its optional pieces present and absent.  `uavac_yaw_scan` runs at n = 3, 20 000, 50 000 and 3 again on one ctx: 480 000
 bytes in and 160 000 out are two pinned pieces and one, 1.2 MB in goes down the runtime's pageable path and 400 000 out are two pieces,
-the arena grows twice and then serves a small request from the grown block."""
+the arena grows twice and then serves a small request from the grown block.
+
+The six RRT* twins (`uavac_rrt_star`, `uavac_rrt_segment_hits`, `uavac_rrt_edge_lengths`, `uavac_rrt_simplify`, `uavac_rrt_path_cost`,
+`uavac_rrt_steer`) the same way: B = 3 problems of 40 iterations with and without a cuboid, E = 5 edges, and `uavac_rrt_edge_lengths` at the
+yaw scan's four sizes on one ctx: the arena grows and then serves a small request from the grown block (this twin, one of the four called
+per tree operation, copies on the caller's pointers itself, so the sizes are no thresholds of its copies)."""
 import ctypes as C
 
 import numpy as np
@@ -280,3 +285,97 @@ def test_dynamics_step(gpu, obstacle):
     ctx.call("uavac_dynamics_step", C.byref(V), P(state), P(istate if obstacle else None), B, P(box), 1 if obstacle else 0)
     assert same(state, state_d) and same(istate, istate_d)
     assert (istate[2, 0] != 0) == obstacle
+
+
+# ------------------------------------------------------------------------------------------------------- the RRT* twins
+RRT_ITER, RRT_STEP, RRT_SEEDS = 40, 2.0, (0, 1, 2)
+RRT_LW, RRT_UP = np.array([0.0, 0.0, 0.0]), np.array([6.0, 6.0, 3.0])
+RRT_STARTS = np.array([[0.5, 0.5, 0.5], [0.5, 5.5, 1.0], [1.0, 3.0, 2.0]])
+RRT_GOALS = np.array([[5.5, 5.5, 2.5], [5.5, 0.5, 2.0], [5.0, 3.0, 1.0]])
+# problem 2 runs from (1, 3, 2) to (5, 3, 1): straight through this cuboid
+RRT_CUBOID = np.array([[2.5, 3.5, 2.0, 4.0, 0.0, 3.0]])
+EDGES_A = np.array([[0.0, 0.0, 0.0], [1.0, 3.0, 2.0], [5.0, 5.0, 1.0], [0.5, 0.5, 2.5], [3.0, 3.0, 1.5]])
+EDGES_B = np.array([[1.0, 1.0, 1.0], [5.0, 3.0, 1.0], [5.0, 1.0, 1.0], [0.5, 0.5, 2.6], [3.0, 3.0, 1.5]])
+TWO_CUBOIDS = np.array([[2.5, 3.5, 2.0, 4.0, 0.0, 3.0], [4.5, 5.5, 2.5, 3.5, 0.0, 3.0]])
+
+
+def both(ctx, torch, twin, args, outs):
+    """`twin` on NumPy arrays and `twin`_dev on the same inputs in torch tensors.  `args`: the arguments in order, arrays and numbers, with
+    "out" where the outputs go; `outs`: (shape, dtype) of each output.  Outputs start out as sevens.  -> (host outputs, device outputs)"""
+    d = Dev(torch)
+    host = [np.full(shape, 7, dtype) for shape, dtype in outs]
+    dev = [d.up(h) for h in host]
+    held = [d.up(a) if isinstance(a, np.ndarray) else a for a in args]           # (kept alive over the call)
+    for name, ins, res in ((twin, args, host), (twin + "_dev", held, dev)):
+        at = iter(res)
+        ctx.call(name, *[P(next(at)) if isinstance(a, str) else a if isinstance(a, (int, float)) else P(a) for a in ins])
+    torch.cuda.synchronize()
+    return host, dev
+
+
+def all_same(host, dev):
+    return all(same(h, t) for h, t in zip(host, dev))
+
+
+@pytest.mark.parametrize("cuboids", [RRT_CUBOID, None], ids=["one cuboid", "no cuboid"])
+def test_rrt_star_and_simplify(gpu, cuboids):
+    ctx, N, torch = gpu
+    from uav_ac.planning.rrt import draw_random_nodes_batch
+    nb, cap, n_obs = len(RRT_STARTS), RRT_ITER + 1, 0 if cuboids is None else len(cuboids)
+    samples = draw_random_nodes_batch(RRT_SEEDS, RRT_LW, RRT_UP, RRT_GOALS, RRT_ITER)
+    outs = [((nb, cap, 3), np.float64), ((nb, cap), np.int32), ((nb, cap), np.int32), ((nb, cap), np.int32), ((nb, cap, 3), np.float64),
+            ((nb, 6), np.int32), ((nb,), np.float64)]
+    host, dev = both(ctx, torch, "uavac_rrt_star", [RRT_STARTS, RRT_GOALS, nb, RRT_STEP, RRT_ITER, samples, cuboids, n_obs] + ["out"] * 7, outs)
+    assert all_same(host, dev)
+    best_path, counts = host[4], host[5]
+    assert (counts[:, 2] == 0).any() and (counts[:, 0] > 1).all()                 # (UAVAC_RRT_OK somewhere, and trees everywhere)
+    lens = np.ascontiguousarray(counts[:, 4])
+    assert lens.max() > 2
+    host, dev = both(ctx, torch, "uavac_rrt_simplify", [best_path, lens, nb, cap, cuboids, n_obs, "out", "out"],
+                     [((nb, cap, 3), np.float64), ((nb,), np.int32)])
+    assert all_same(host, dev)
+    assert (host[1] <= lens).all() and (host[1][lens > 0] >= 2).all()
+
+
+@pytest.mark.parametrize("cuboids", [TWO_CUBOIDS, None], ids=["two cuboids", "no cuboid"])
+def test_rrt_segment_hits(gpu, cuboids):
+    ctx, N, torch = gpu
+    n_obs = 0 if cuboids is None else len(cuboids)
+    host, dev = both(ctx, torch, "uavac_rrt_segment_hits", [EDGES_A, EDGES_B, 5, cuboids, n_obs, "out"], [((5,), np.int32)])
+    assert all_same(host, dev)
+    assert list(host[0]) == ([0, 1, 1, 0, 1] if n_obs else [0] * 5)      # edge 1 crosses the first cuboid, 2 the second, 4 lies in the first
+
+
+@pytest.mark.parametrize("single", [0, 1])
+def test_rrt_edge_lengths(gpu, single):
+    ctx, N, torch = gpu
+    host, dev = both(ctx, torch, "uavac_rrt_edge_lengths", [EDGES_A, EDGES_B[1] if single else EDGES_B, single, 5, "out"], [((5,), np.float64)])
+    assert all_same(host, dev)
+    assert host[0][0] == np.sqrt(35.0 if single else 3.0)
+
+
+def test_rrt_path_cost(gpu):
+    ctx, N, torch = gpu
+    for n in (0, 4):
+        host, dev = both(ctx, torch, "uavac_rrt_path_cost", [EDGES_A[:n] if n else None, n, "out"], [((1,), np.float64)])
+        assert all_same(host, dev)
+        assert (host[0][0] > 0.0) == (n > 0)
+
+
+@pytest.mark.parametrize("E", [1, 3])
+def test_rrt_steer(gpu, E):
+    ctx, N, torch = gpu
+    # (edges 0 and 2 are longer than the step and get cut; edges 3 and 4 of the E = 3 call are not)
+    a, b = (EDGES_A[:1], EDGES_B[:1]) if E == 1 else (EDGES_A[2:], EDGES_B[2:])
+    host, dev = both(ctx, torch, "uavac_rrt_steer", [np.ascontiguousarray(b), np.ascontiguousarray(a), E, 1.0, "out"], [((E, 3), np.float64)])
+    assert all_same(host, dev)
+    assert host[0].tobytes() != b.tobytes()
+
+
+def test_rrt_edge_lengths_as_the_arena_grows(gpu):
+    ctx, N, torch = gpu
+    rng = np.random.default_rng(6)
+    for E in (3, 20_000, 50_000, 3):
+        a, b = rng.uniform(-5.0, 5.0, (E, 3)), rng.uniform(-5.0, 5.0, (E, 3))
+        host, dev = both(ctx, torch, "uavac_rrt_edge_lengths", [a, b, 0, E, "out"], [((E,), np.float64)])
+        assert all_same(host, dev), E

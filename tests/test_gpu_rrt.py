@@ -390,37 +390,68 @@ def test_reference_unit_tests_tree_bookkeeping(rrt_object):
 
 
 def test_rrt_entry_points_reject_bad_arguments():
-    """Negative UAVAC_E* codes with a message, never a crash: sizes < 1, null pointers, a non-positive step,
-    non-finite host inputs."""
+    """Negative UAVAC_E* codes with their texts, never a crash: sizes < 1, null pointers, a non-positive step, non-finite host inputs.
+    Each host-pointer twin on NumPy arrays and its `_dev` entry point on tensors get the same rows: (arguments replaced by position,
+    return code, `uavac_last_error`), "twin" / "dev" where a row is for one of the two.  A twin reads host memory, so it alone refuses a
+    NaN sample or a path length past `cap`; with two defects it reports the obstacle list and the NaN before the step, which its
+    `_dev` call checks, while `uavac_rrt_star_dev` checks the step before the obstacle list."""
     import ctypes as C
+    import torch
     from uav_ac import _native as nat
     ctx = nat.Context(0)
     lib = nat.lib()
-    P = nat.np_ptr
+    OK, EINVAL, ENONFINITE = nat.OK, nat.EINVAL, nat.ENONFINITE
+    NULL, COUNT, SIZES, STEP = "null pointer", "negative count", "B and max_iter must be >= 1", "max_distance must be finite and > 0"
+    OBSTACLES, NONFINITE = "bad obstacle list", "non-finite start, goal, sample or cuboid"
+    SHAPE, LENGTH = "B and cap must be >= 1", "path length outside [0, cap]"
+
+    def refusals(twin, valid, rows):
+        held = [torch.as_tensor(a).cuda() if isinstance(a, np.ndarray) else a for a in valid]
+        torch.cuda.synchronize()
+        wrong = []
+        for which, entry, args, ptr in (("twin", twin, valid, nat.np_ptr), ("dev", twin + "_dev", held, lambda t: C.c_void_p(t.data_ptr()))):
+            for changes, want_rc, want_text, *only in [({}, OK, None)] + rows:
+                if only and only[0] != which:
+                    continue
+                a = list(args)
+                for i, v in changes.items():
+                    a[i] = v
+                rc = getattr(lib, entry)(ctx._h, *[v if v is None or isinstance(v, (int, float)) else ptr(v) for v in a])
+                text = lib.uavac_last_error(ctx._h).decode()
+                if rc != want_rc or (want_text is not None and text != want_text):
+                    wrong.append((entry, changes, rc, text))
+        torch.cuda.synchronize()
+        assert not wrong, wrong
+
     s = np.zeros((1, 3)); g = np.ones((1, 3)); smp = np.zeros((1, 4, 3)); cap = 5
-    nodes = np.empty((1, cap, 3)); path = np.empty((1, cap, 3))
+    nodes = np.empty((1, cap, 3)); path = np.zeros((1, cap, 3))
     canon = np.empty((1, cap), np.int32); par = np.empty((1, cap), np.int32); bpar = np.empty((1, cap), np.int32)
     counts = np.empty((1, 6), np.int32); cost = np.empty(1)
-    outs = (P(nodes), P(canon), P(par), P(bpar), P(path), P(counts), P(cost))
-
-    def call(*a):
-        return lib.uavac_rrt_star(ctx._h, *a)
-    assert call(P(s), P(g), 1, 1.0, 4, P(smp), None, 0, *outs) == nat.OK
-    assert call(P(s), P(g), 0, 1.0, 4, P(smp), None, 0, *outs) == nat.EINVAL
-    assert call(P(s), P(g), 1, 1.0, 0, P(smp), None, 0, *outs) == nat.EINVAL
-    assert call(P(s), P(g), 1, 0.0, 4, P(smp), None, 0, *outs) == nat.EINVAL
-    assert call(P(s), P(g), 1, 1.0, 4, P(smp), None, 2, *outs) == nat.EINVAL          # obstacles announced, none given
-    assert call(None, P(g), 1, 1.0, 4, P(smp), None, 0, *outs) == nat.EINVAL
-    assert b"" != lib.uavac_last_error(ctx._h)
     bad = smp.copy(); bad[0, 2, 1] = np.nan
-    assert call(P(s), P(g), 1, 1.0, 4, P(bad), None, 0, *outs) == nat.ENONFINITE
-    hit = np.empty(2, np.int32)
-    assert lib.uavac_rrt_segment_hits(ctx._h, P(np.zeros((2, 3))), P(np.ones((2, 3))), -1, None, 0, P(hit)) == nat.EINVAL
-    assert lib.uavac_rrt_segment_hits(ctx._h, P(np.zeros((2, 3))), P(np.ones((2, 3))), 2, None, 1, P(hit)) == nat.EINVAL
-    assert lib.uavac_rrt_segment_hits(ctx._h, P(np.zeros((2, 3))), P(np.ones((2, 3))), 0, None, 0, P(hit)) == nat.OK
-    out = np.empty(1)
-    assert lib.uavac_rrt_path_cost(ctx._h, None, 3, P(out)) == nat.EINVAL
-    assert lib.uavac_rrt_path_cost(ctx._h, None, 0, P(out)) == nat.OK and out[0] == 0.0
-    lens = np.array([9], np.int32); outp = np.empty((1, cap, 3)); outl = np.empty(1, np.int32)
-    assert lib.uavac_rrt_simplify(ctx._h, P(path), P(lens), 1, cap, None, 0, P(outp), P(outl)) == nat.EINVAL   # longer than cap
+    #                                 0  1  2  3    4  5    6     7  8 ..
+    refusals("uavac_rrt_star", [s, g, 1, 1.0, 4, smp, None, 0, nodes, canon, par, bpar, path, counts, cost], [
+        ({2: 0}, EINVAL, SIZES), ({4: 0}, EINVAL, SIZES), ({3: 0.0}, EINVAL, STEP), ({3: float("nan")}, EINVAL, STEP),
+        ({7: 2}, EINVAL, OBSTACLES),                                    # obstacles announced, none given
+        ({7: -1}, EINVAL, OBSTACLES), ({0: None}, EINVAL, NULL), ({14: None}, EINVAL, NULL),
+        ({5: bad}, ENONFINITE, NONFINITE, "twin"),
+        ({3: 0.0, 5: bad}, ENONFINITE, NONFINITE, "twin"),              # two defects
+        ({3: 0.0, 7: 2}, EINVAL, OBSTACLES, "twin"), ({3: 0.0, 7: 2}, EINVAL, STEP, "dev")])
+    a, b, cub = np.zeros((2, 3)), np.ones((2, 3)), np.array([[0.4, 0.6, 0.4, 0.6, 0.4, 0.6]])
+    refusals("uavac_rrt_segment_hits", [a, b, 2, cub, 1, np.empty(2, np.int32)], [
+        ({2: -1}, EINVAL, COUNT), ({4: -1}, EINVAL, COUNT), ({3: None}, EINVAL, NULL), ({0: None}, EINVAL, NULL), ({5: None}, EINVAL, NULL),
+        ({2: 0}, OK, None), ({2: 0, 0: None, 5: None}, OK, None)])
+    refusals("uavac_rrt_edge_lengths", [a, b, 0, 2, np.empty(2)], [
+        ({3: -1}, EINVAL, COUNT), ({0: None}, EINVAL, NULL), ({1: None}, EINVAL, NULL), ({4: None}, EINVAL, NULL), ({3: 0, 0: None}, OK, None)])
+    refusals("uavac_rrt_steer", [a, b, 2, 1.0, np.empty((2, 3))], [
+        ({2: -1}, EINVAL, COUNT), ({0: None}, EINVAL, NULL), ({1: None}, EINVAL, NULL), ({4: None}, EINVAL, NULL), ({2: 0, 4: None}, OK, None)])
+    out = np.ones(1)
+    refusals("uavac_rrt_path_cost", [np.arange(9.0).reshape(3, 3), 3, out], [
+        ({1: -1}, EINVAL, COUNT), ({0: None}, EINVAL, NULL), ({2: None}, EINVAL, NULL), ({0: None, 1: 0}, OK, None)])
+    out[0] = 7.0
+    assert lib.uavac_rrt_path_cost(ctx._h, None, 0, nat.np_ptr(out)) == OK and out[0] == 0.0          # the empty polyline costs nothing
+    lens = np.array([2], np.int32); outp = np.empty((1, cap, 3)); outl = np.empty(1, np.int32)
+    refusals("uavac_rrt_simplify", [path, lens, 1, cap, None, 0, outp, outl], [
+        ({2: 0}, EINVAL, SHAPE), ({3: 0}, EINVAL, SHAPE), ({5: -1}, EINVAL, SHAPE), ({0: None}, EINVAL, NULL), ({7: None}, EINVAL, NULL),
+        ({5: 1}, EINVAL, NULL),                                         # obstacles announced, none given
+        ({1: np.array([9], np.int32)}, EINVAL, LENGTH, "twin")])        # longer than cap
     ctx.close()

@@ -9,6 +9,7 @@ OTHER.so to see what ratio this method gives to no difference at all."""
 import ctypes as C
 import json
 import os
+import time
 
 import numpy as np
 import torch
@@ -74,6 +75,30 @@ class Builds:
                                           "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4),
                                           "spread (max - min) / median": round((max(ts) - min(ts)) / med, 5), "rounds": rounds,
                                           "median / the other build's median": round(med / float(np.median(ms[OTHER])), 5),
+                                          "outputs of the two builds agree": True, "box": self.box}))
+            print(self.lines[-1], flush=True)
+
+    def wall(self, arm, call, rounds, **meta):
+        """`alternate` for calls that return to the host (the twins, N back-to-back calls): `call(lib, ctx)` -> the arrays one call wrote
+        (NumPy or tensors); wall-clock seconds per call and round, the device drained before and after."""
+        got = {}
+        for name in self.lib:
+            got[name] = [np.array(a.cpu().numpy() if hasattr(a, "cpu") else a) for a in call(self.lib[name], self.ctx[name])]
+            torch.cuda.synchronize()
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(got[THIS], got[OTHER])), f"{arm}: the two builds' outputs differ"
+        sec = {name: [] for name in self.lib}
+        for rnd in range(rounds):
+            for name in (list(self.lib) if rnd % 2 == 0 else list(self.lib)[::-1]):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                call(self.lib[name], self.ctx[name])
+                torch.cuda.synchronize()
+                sec[name].append(time.perf_counter() - t0)
+        for name, ts in sec.items():
+            med = float(np.median(ts))
+            self.lines.append(json.dumps({"arm": f"{arm}, {name}, alternating with the other", "library": os.path.relpath(self.paths[name], ROOT),
+                                          **meta, "ms_per_round": [round(t * 1e3, 4) for t in ts], "median_ms": round(med * 1e3, 4),
+                                          "rounds": rounds, "median / the other build's median": round(med / float(np.median(sec[OTHER])), 5),
                                           "outputs of the two builds agree": True, "box": self.box}))
             print(self.lines[-1], flush=True)
 

@@ -8,17 +8,15 @@ Run it with a byte-identical copy of one library as OTHER.so: the spread of that
     python tools/host_layer_ab.py --against OTHER.so [--rounds 7] [--call-rounds 7] [--out profiles/host_layer_ab.jsonl]
 (--rounds: of the twins, milliseconds each; --call-rounds: of the back-to-back arms, N calls each)"""
 import ctypes as C
-import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "uav-autonomous-control_amd"), os.path.join(ROOT, "tools")]
-from against import OTHER, THIS, Builds, ptr, split_argv         # noqa: E402
+from against import THIS, Builds, ptr, split_argv                # noqa: E402
 from bench import missions                                       # noqa: E402
 from uav_ac import _native as nat                                # noqa: E402
 
@@ -33,30 +31,6 @@ NAMES = ("uavac_minsnap_row_counts", "uavac_minsnap_solve", "uavac_minsnap_sampl
 builds = Builds(other, {name: nat._SIGNATURES[name][1] for name in NAMES})
 dev = torch.device("cuda:0")
 np_ptr = nat.np_ptr
-
-
-def alternate(arm, call, rounds, **meta):
-    """`call(lib, ctx)` -> the arrays one call wrote (NumPy or tensors); wall-clock seconds per call and round."""
-    got = {}
-    for name in builds.lib:
-        got[name] = [np.array(a.cpu().numpy() if hasattr(a, "cpu") else a) for a in call(builds.lib[name], builds.ctx[name])]
-        torch.cuda.synchronize()
-    assert all(a.tobytes() == b.tobytes() for a, b in zip(got[THIS], got[OTHER])), f"{arm}: the two builds' outputs differ"
-    sec = {name: [] for name in builds.lib}
-    for rnd in range(rounds):
-        for name in (list(builds.lib) if rnd % 2 == 0 else list(builds.lib)[::-1]):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            call(builds.lib[name], builds.ctx[name])
-            torch.cuda.synchronize()
-            sec[name].append(time.perf_counter() - t0)
-    for name, ts in sec.items():
-        med = float(np.median(ts))
-        builds.lines.append(json.dumps({"arm": f"{arm}, {name}, alternating with the other", "library": os.path.relpath(builds.paths[name], ROOT),
-                                        **meta, "ms_per_round": [round(t * 1e3, 4) for t in ts], "median_ms": round(med * 1e3, 4),
-                                        "rounds": rounds, "median / the other build's median": round(med / float(np.median(sec[OTHER])), 5),
-                                        "outputs of the two builds agree": True, "box": builds.box}))
-        print(builds.lines[-1], flush=True)
 
 
 # ---- the host-pointer twins at tools/host_path_rate.py's shape
@@ -75,7 +49,7 @@ def plan(lib, ctx):
     return times, seg, offs, coeffs, traj[0]
 
 
-alternate("host-pointer plan", plan, twin_rounds, B=B, m=m)
+builds.wall("host-pointer plan", plan, twin_rounds, B=B, m=m)
 V = nat.Vehicle.default()
 state0, istate0 = np.zeros((nat.STATE_ROWS, B)), np.zeros((nat.ISTATE_ROWS, B), np.int32)
 assert builds.lib[THIS].uavac_state_init(builds.ctx[THIS], C.byref(V), np_ptr(np.ascontiguousarray(wps[:, 0, :])), B, 1, np_ptr(state0),
@@ -90,7 +64,7 @@ def roll(lib, ctx):
     return state, istate, log
 
 
-alternate("host-pointer rollout", roll, twin_rounds, B=B, K=K)
+builds.wall("host-pointer rollout", roll, twin_rounds, B=B, K=K)
 
 # ---- back-to-back calls of two device entry points
 B, m = 64, 4
@@ -117,6 +91,6 @@ def cost(lib, ctx):
     return (cost_d,)
 
 
-alternate(f"uavac_minsnap_separation_dev x {N}", separation, call_rounds, B=B, m=m, calls=N)
-alternate(f"uavac_minsnap_cost_dev x {N}", cost, call_rounds, B=B, m=m, calls=N)
+builds.wall(f"uavac_minsnap_separation_dev x {N}", separation, call_rounds, B=B, m=m, calls=N)
+builds.wall(f"uavac_minsnap_cost_dev x {N}", cost, call_rounds, B=B, m=m, calls=N)
 builds.write(out_path)

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "uavac_internal.h"
+#include "uavac_scratch.h"
 
 #pragma clang fp contract(off)
 
@@ -607,17 +608,57 @@ constexpr size_t kLdsLimit = 160 * 1024;
 
 size_t scratch_doubles_per_problem(int cap) { return 3 * (size_t)cap; }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
-    template <class T> T *as() { return static_cast<T *>(p); }
-};
-
 bool finite_all(const double *p, size_t n) {
     for (size_t i = 0; i < n; ++i)
         if (!std::isfinite(p[i])) return false;
     return true;
+}
+
+// The refusals that a host-pointer twin and its _dev entry point share, one spelling each; the twin asks first, before it reads host
+// memory.  uavac_rrt_star's come in two functions because the two callers order them differently around checks of their own:
+// uavac_rrt_star_dev refuses a bad step between them, uavac_rrt_star a non-finite input after both and a bad step last (in its _dev call).
+int check_star_shape(uavac_ctx *ctx, const void *start, const void *goal, int B, int max_iter, const void *samples, const void *nodes,
+                     const void *canon, const void *parent, const void *best_parent, const void *best_path, const void *counts,
+                     const void *best_cost) {
+    if (!start || !goal || !samples || !nodes || !canon || !parent || !best_parent || !best_path || !counts || !best_cost)
+        return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (B < 1 || max_iter < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B and max_iter must be >= 1");
+    return UAVAC_OK;
+}
+int check_obstacle_list(uavac_ctx *ctx, const void *cuboids, int n_obs) {
+    if (n_obs < 0 || (n_obs > 0 && !cuboids)) return uavac_fail(ctx, UAVAC_EINVAL, "bad obstacle list");
+    return UAVAC_OK;
+}
+// the per-edge calls (segment hits, edge lengths, steer): E = 0 is a valid empty call whose pointers nobody looks at
+int check_edges(uavac_ctx *ctx, const void *a, const void *b, int E, const void *out, const void *cuboids = nullptr, int n_obs = 0) {
+    if (E < 0 || n_obs < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative count");
+    if (E > 0 && (!a || !b || !out || (n_obs > 0 && !cuboids))) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    return UAVAC_OK;
+}
+int check_simplify(uavac_ctx *ctx, const void *paths, const void *lens, int B, int cap, const void *cuboids, int n_obs,
+                   const void *out_paths, const void *out_lens) {
+    if (B < 1 || cap < 1 || n_obs < 0) return uavac_fail(ctx, UAVAC_EINVAL, "B and cap must be >= 1");
+    if (!paths || !lens || !out_paths || !out_lens || (n_obs > 0 && !cuboids)) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    return UAVAC_OK;
+}
+int check_path_cost(uavac_ctx *ctx, const void *path, int n, const void *cost) {
+    if (n < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative count");
+    if (!cost || (n > 0 && !path)) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    return UAVAC_OK;
+}
+
+// The copies of the four per-call twins (segment hits, edge lengths, path cost, steer), which the facade calls once per tree operation
+// on a few bytes: hipMemcpyAsync on the caller's pageable pointers and one wait at the end, as these twins always copied.  Through
+// Scratch's upload() / download() every piece ends with a wait of its own on the pinned staging buffer, three or four a call, and these
+// calls took 1.25 times as long.  `count` may be zero.
+template <class T> int copy_in(uavac_ctx *ctx, T *dst_dev, const T *src_host, size_t count) {
+    if (count) UAVAC_HIP(ctx, hipMemcpyAsync(dst_dev, src_host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    return UAVAC_OK;                      // pageable source: the runtime has read it when the call returns
+}
+template <class T> int copy_out(uavac_ctx *ctx, T *dst_host, const T *src_dev, size_t count) {
+    UAVAC_HIP(ctx, hipMemcpyAsync(dst_host, src_dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return UAVAC_OK;
 }
 
 }  // namespace
@@ -629,11 +670,10 @@ int uavac_rrt_star_dev(uavac_ctx *ctx, const double *start, const double *goal, 
                        int32_t *parent, int32_t *best_parent, double *best_path, int32_t *counts,
                        double *best_cost) {
     UAVAC_ENTER(ctx);
-    if (!start || !goal || !samples || !nodes || !canon || !parent || !best_parent || !best_path || !counts || !best_cost)
-        return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (B < 1 || max_iter < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B and max_iter must be >= 1");
+    if (int rc = check_star_shape(ctx, start, goal, B, max_iter, samples, nodes, canon, parent, best_parent, best_path, counts, best_cost))
+        return rc;
     if (!std::isfinite(step) || !(step > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "max_distance must be finite and > 0");
-    if (n_obs < 0 || (n_obs > 0 && !cuboids)) return uavac_fail(ctx, UAVAC_EINVAL, "bad obstacle list");
+    if (int rc = check_obstacle_list(ctx, cuboids, n_obs)) return rc;
     const int cap = max_iter + 1;
     // first-pass capacity: 384 nodes = 20 KB of LDS = 8 problems per CU (lab obstacle set, 1 000 iterations allowed:
     // mean tree 210 nodes; measured at B = 16 384: one pass 49.6 ms, 256 / 384 / 512 nodes first 39.6 / 35.9 / 38.1 ms)
@@ -671,9 +711,8 @@ int uavac_rrt_star_dev(uavac_ctx *ctx, const double *start, const double *goal, 
 int uavac_rrt_segment_hits_dev(uavac_ctx *ctx, const double *p0, const double *p1, int E, const double *cuboids,
                                int n_obs, int32_t *hit) {
     UAVAC_ENTER(ctx);
-    if (E < 0 || n_obs < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative count");
+    if (int rc = check_edges(ctx, p0, p1, E, hit, cuboids, n_obs)) return rc;
     if (E == 0) return UAVAC_OK;
-    if (!p0 || !p1 || !hit || (n_obs > 0 && !cuboids)) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
     hipLaunchKernelGGL(rrt_segment_hits_kernel, dim3((E + 255) / 256), dim3(256), 0, ctx->stream, p0, p1, E, cuboids,
                        n_obs, hit);
     UAVAC_HIP(ctx, hipGetLastError());
@@ -683,9 +722,8 @@ int uavac_rrt_segment_hits_dev(uavac_ctx *ctx, const double *p0, const double *p
 int uavac_rrt_edge_lengths_dev(uavac_ctx *ctx, const double *p0, const double *p1, int p1_is_single, int E,
                                double *out) {
     UAVAC_ENTER(ctx);
-    if (E < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative count");
+    if (int rc = check_edges(ctx, p0, p1, E, out)) return rc;
     if (E == 0) return UAVAC_OK;
-    if (!p0 || !p1 || !out) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
     hipLaunchKernelGGL(rrt_edge_lengths_kernel, dim3((E + 255) / 256), dim3(256), 0, ctx->stream, p0, p1,
                        p1_is_single ? 0 : 3, E, out);
     UAVAC_HIP(ctx, hipGetLastError());
@@ -711,8 +749,7 @@ int uavac_rrt_draw_nodes_dev(uavac_ctx *ctx, const uint32_t *seeds, const double
 int uavac_rrt_simplify_dev(uavac_ctx *ctx, const double *paths, const int32_t *lens, int B, int cap, const double *cuboids,
                            int n_obs, double *out_paths, int32_t *out_lens) {
     UAVAC_ENTER(ctx);
-    if (B < 1 || cap < 1 || n_obs < 0) return uavac_fail(ctx, UAVAC_EINVAL, "B and cap must be >= 1");
-    if (!paths || !lens || !out_paths || !out_lens || (n_obs > 0 && !cuboids)) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_simplify(ctx, paths, lens, B, cap, cuboids, n_obs, out_paths, out_lens)) return rc;
     hipLaunchKernelGGL(rrt_simplify_kernel, dim3(B), dim3(W), 0, ctx->stream, paths, lens, cap, cuboids, n_obs, out_paths,
                        out_lens);
     UAVAC_HIP(ctx, hipGetLastError());
@@ -721,8 +758,7 @@ int uavac_rrt_simplify_dev(uavac_ctx *ctx, const double *paths, const int32_t *l
 
 int uavac_rrt_path_cost_dev(uavac_ctx *ctx, const double *path, int n, double *cost) {
     UAVAC_ENTER(ctx);
-    if (n < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative count");
-    if (!cost || (n > 0 && !path)) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_path_cost(ctx, path, n, cost)) return rc;
     hipLaunchKernelGGL(rrt_path_cost_kernel, dim3(1), dim3(64), 0, ctx->stream, path, n, cost);
     UAVAC_HIP(ctx, hipGetLastError());
     return UAVAC_OK;
@@ -730,54 +766,39 @@ int uavac_rrt_path_cost_dev(uavac_ctx *ctx, const double *path, int n, double *c
 
 int uavac_rrt_steer_dev(uavac_ctx *ctx, const double *sample, const double *nearest, int E, double step, double *out) {
     UAVAC_ENTER(ctx);
-    if (E < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative count");
+    if (int rc = check_edges(ctx, sample, nearest, E, out)) return rc;
     if (E == 0) return UAVAC_OK;
-    if (!sample || !nearest || !out) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
     hipLaunchKernelGGL(rrt_steer_kernel, dim3((E + 255) / 256), dim3(256), 0, ctx->stream, sample, nearest, E, step, out);
     UAVAC_HIP(ctx, hipGetLastError());
     return UAVAC_OK;
 }
 
 // ------------------------------------------------------------------------------------------ host twins
+// Device scratch from the ctx arena, like every other twin (uavac_scratch.h).  The two batch twins, uavac_rrt_star and uavac_rrt_simplify,
+// stage through it as well: register the pieces, commit, upload, the _dev call, download.  The four per-call twins take their pieces
+// with want() and copy with copy_in / copy_out above.  uavac_rrt_star_dev grows d_ws, never the arena, so nothing nests.
 int uavac_rrt_star(uavac_ctx *ctx, const double *start, const double *goal, int B, double step, int max_iter,
                    const double *samples, const double *cuboids, int n_obs, double *nodes, int32_t *canon,
                    int32_t *parent, int32_t *best_parent, double *best_path, int32_t *counts, double *best_cost) {
     UAVAC_ENTER(ctx);
-    if (!start || !goal || !samples || !nodes || !canon || !parent || !best_parent || !best_path || !counts || !best_cost)
-        return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (B < 1 || max_iter < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B and max_iter must be >= 1");
-    if (n_obs < 0 || (n_obs > 0 && !cuboids)) return uavac_fail(ctx, UAVAC_EINVAL, "bad obstacle list");
+    if (int rc = check_star_shape(ctx, start, goal, B, max_iter, samples, nodes, canon, parent, best_parent, best_path, counts, best_cost))
+        return rc;
+    if (int rc = check_obstacle_list(ctx, cuboids, n_obs)) return rc;
     const size_t cap = (size_t)max_iter + 1, zB = (size_t)B;
     if (!finite_all(start, 3 * zB) || !finite_all(goal, 3 * zB) || !finite_all(samples, 3 * zB * max_iter) ||
         (n_obs > 0 && !finite_all(cuboids, 6 * (size_t)n_obs)))
         return uavac_fail(ctx, UAVAC_ENONFINITE, "non-finite start, goal, sample or cuboid");
-    DevBuf ds, dg, dsm, dc, dn, dca, dp, dbp, dpath, dcnt, dcost;
-    UAVAC_HIP(ctx, ds.alloc(24 * zB));
-    UAVAC_HIP(ctx, dg.alloc(24 * zB));
-    UAVAC_HIP(ctx, dsm.alloc(24 * zB * max_iter));
-    UAVAC_HIP(ctx, dc.alloc(48 * (size_t)n_obs));
-    UAVAC_HIP(ctx, dn.alloc(24 * zB * cap));
-    UAVAC_HIP(ctx, dca.alloc(4 * zB * cap));
-    UAVAC_HIP(ctx, dp.alloc(4 * zB * cap));
-    UAVAC_HIP(ctx, dbp.alloc(4 * zB * cap));
-    UAVAC_HIP(ctx, dpath.alloc(24 * zB * cap));
-    UAVAC_HIP(ctx, dcnt.alloc(24 * zB));
-    UAVAC_HIP(ctx, dcost.alloc(8 * zB));
-    UAVAC_HIP(ctx, hipMemcpyAsync(ds.p, start, 24 * zB, hipMemcpyHostToDevice, ctx->stream));
-    UAVAC_HIP(ctx, hipMemcpyAsync(dg.p, goal, 24 * zB, hipMemcpyHostToDevice, ctx->stream));
-    UAVAC_HIP(ctx, hipMemcpyAsync(dsm.p, samples, 24 * zB * max_iter, hipMemcpyHostToDevice, ctx->stream));
-    if (n_obs > 0) UAVAC_HIP(ctx, hipMemcpyAsync(dc.p, cuboids, 48 * (size_t)n_obs, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = uavac_rrt_star_dev(ctx, ds.as<double>(), dg.as<double>(), B, step, max_iter, dsm.as<double>(),
-                                    n_obs > 0 ? dc.as<double>() : nullptr, n_obs, dn.as<double>(), dca.as<int32_t>(),
-                                    dp.as<int32_t>(), dbp.as<int32_t>(), dpath.as<double>(), dcnt.as<int32_t>(),
-                                    dcost.as<double>())) return rc;
-    UAVAC_HIP(ctx, hipMemcpyAsync(nodes, dn.p, 24 * zB * cap, hipMemcpyDeviceToHost, ctx->stream));
-    UAVAC_HIP(ctx, hipMemcpyAsync(canon, dca.p, 4 * zB * cap, hipMemcpyDeviceToHost, ctx->stream));
-    UAVAC_HIP(ctx, hipMemcpyAsync(parent, dp.p, 4 * zB * cap, hipMemcpyDeviceToHost, ctx->stream));
-    UAVAC_HIP(ctx, hipMemcpyAsync(best_parent, dbp.p, 4 * zB * cap, hipMemcpyDeviceToHost, ctx->stream));
-    UAVAC_HIP(ctx, hipMemcpyAsync(best_path, dpath.p, 24 * zB * cap, hipMemcpyDeviceToHost, ctx->stream));
-    UAVAC_HIP(ctx, hipMemcpyAsync(counts, dcnt.p, 24 * zB, hipMemcpyDeviceToHost, ctx->stream));
-    UAVAC_HIP(ctx, hipMemcpyAsync(best_cost, dcost.p, 8 * zB, hipMemcpyDeviceToHost, ctx->stream));
+    double *ds = nullptr, *dg = nullptr, *dsm = nullptr, *dc = nullptr, *dn = nullptr, *dpath = nullptr, *dcost = nullptr;
+    int32_t *dca = nullptr, *dp = nullptr, *dbp = nullptr, *dcnt = nullptr;
+    Scratch s(ctx);
+    s.in(&ds, start, 3 * zB); s.in(&dg, goal, 3 * zB); s.in(&dsm, samples, 3 * zB * max_iter); s.in(&dc, cuboids, 6 * (size_t)n_obs);
+    s.out(&dn, nodes, 3 * zB * cap); s.out(&dca, canon, zB * cap); s.out(&dp, parent, zB * cap); s.out(&dbp, best_parent, zB * cap);
+    s.out(&dpath, best_path, 3 * zB * cap); s.out(&dcnt, counts, 6 * zB); s.out(&dcost, best_cost, zB);
+    if (int rc = s.commit()) return rc;
+    if (int rc = s.upload()) return rc;
+    if (int rc = uavac_rrt_star_dev(ctx, ds, dg, B, step, max_iter, dsm, n_obs > 0 ? dc : nullptr, n_obs, dn, dca, dp, dbp, dpath, dcnt,
+                                    dcost)) return rc;
+    if (int rc = s.download()) return rc;
     UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return UAVAC_OK;
 }
@@ -785,99 +806,81 @@ int uavac_rrt_star(uavac_ctx *ctx, const double *start, const double *goal, int 
 int uavac_rrt_segment_hits(uavac_ctx *ctx, const double *p0, const double *p1, int E, const double *cuboids, int n_obs,
                            int32_t *hit) {
     UAVAC_ENTER(ctx);
-    if (E < 0 || n_obs < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative count");
+    if (int rc = check_edges(ctx, p0, p1, E, hit, cuboids, n_obs)) return rc;
     if (E == 0) return UAVAC_OK;
-    if (!p0 || !p1 || !hit || (n_obs > 0 && !cuboids)) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    const size_t zE = (size_t)E;
-    DevBuf d0, d1, dc, dh;
-    UAVAC_HIP(ctx, d0.alloc(24 * zE));
-    UAVAC_HIP(ctx, d1.alloc(24 * zE));
-    UAVAC_HIP(ctx, dc.alloc(48 * (size_t)n_obs));
-    UAVAC_HIP(ctx, dh.alloc(4 * zE));
-    UAVAC_HIP(ctx, hipMemcpyAsync(d0.p, p0, 24 * zE, hipMemcpyHostToDevice, ctx->stream));
-    UAVAC_HIP(ctx, hipMemcpyAsync(d1.p, p1, 24 * zE, hipMemcpyHostToDevice, ctx->stream));
-    if (n_obs > 0) UAVAC_HIP(ctx, hipMemcpyAsync(dc.p, cuboids, 48 * (size_t)n_obs, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = uavac_rrt_segment_hits_dev(ctx, d0.as<double>(), d1.as<double>(), E, dc.as<double>(), n_obs,
-                                            dh.as<int32_t>())) return rc;
-    UAVAC_HIP(ctx, hipMemcpyAsync(hit, dh.p, 4 * zE, hipMemcpyDeviceToHost, ctx->stream));
-    UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return UAVAC_OK;
+    double *d0 = nullptr, *d1 = nullptr, *dc = nullptr;
+    int32_t *dh = nullptr;
+    Scratch s(ctx);
+    const size_t n = 3 * (size_t)E, nc = 6 * (size_t)n_obs;
+    s.want(&d0, n); s.want(&d1, n); s.want(&dc, nc); s.want(&dh, (size_t)E);
+    if (int rc = s.commit()) return rc;
+    if (int rc = copy_in(ctx, d0, p0, n)) return rc;
+    if (int rc = copy_in(ctx, d1, p1, n)) return rc;
+    if (int rc = copy_in(ctx, dc, cuboids, nc)) return rc;
+    if (int rc = uavac_rrt_segment_hits_dev(ctx, d0, d1, E, dc, n_obs, dh)) return rc;
+    return copy_out(ctx, hit, dh, (size_t)E);
 }
 
 int uavac_rrt_edge_lengths(uavac_ctx *ctx, const double *p0, const double *p1, int p1_is_single, int E, double *out) {
     UAVAC_ENTER(ctx);
-    if (E < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative count");
+    if (int rc = check_edges(ctx, p0, p1, E, out)) return rc;
     if (E == 0) return UAVAC_OK;
-    if (!p0 || !p1 || !out) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    const size_t zE = (size_t)E, n1 = p1_is_single ? 1 : zE;
-    DevBuf d0, d1, dout;
-    UAVAC_HIP(ctx, d0.alloc(24 * zE));
-    UAVAC_HIP(ctx, d1.alloc(24 * n1));
-    UAVAC_HIP(ctx, dout.alloc(8 * zE));
-    UAVAC_HIP(ctx, hipMemcpyAsync(d0.p, p0, 24 * zE, hipMemcpyHostToDevice, ctx->stream));
-    UAVAC_HIP(ctx, hipMemcpyAsync(d1.p, p1, 24 * n1, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = uavac_rrt_edge_lengths_dev(ctx, d0.as<double>(), d1.as<double>(), p1_is_single, E, dout.as<double>()))
-        return rc;
-    UAVAC_HIP(ctx, hipMemcpyAsync(out, dout.p, 8 * zE, hipMemcpyDeviceToHost, ctx->stream));
-    UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return UAVAC_OK;
+    double *d0 = nullptr, *d1 = nullptr, *dout = nullptr;
+    Scratch s(ctx);
+    const size_t n = 3 * (size_t)E, n1 = p1_is_single ? 3 : n;
+    s.want(&d0, n); s.want(&d1, n1); s.want(&dout, (size_t)E);
+    if (int rc = s.commit()) return rc;
+    if (int rc = copy_in(ctx, d0, p0, n)) return rc;
+    if (int rc = copy_in(ctx, d1, p1, n1)) return rc;
+    if (int rc = uavac_rrt_edge_lengths_dev(ctx, d0, d1, p1_is_single, E, dout)) return rc;
+    return copy_out(ctx, out, dout, (size_t)E);
 }
 
 int uavac_rrt_simplify(uavac_ctx *ctx, const double *paths, const int32_t *lens, int B, int cap, const double *cuboids,
                        int n_obs, double *out_paths, int32_t *out_lens) {
     UAVAC_ENTER(ctx);
-    if (B < 1 || cap < 1 || n_obs < 0) return uavac_fail(ctx, UAVAC_EINVAL, "B and cap must be >= 1");
-    if (!paths || !lens || !out_paths || !out_lens || (n_obs > 0 && !cuboids)) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_simplify(ctx, paths, lens, B, cap, cuboids, n_obs, out_paths, out_lens)) return rc;
     for (int b = 0; b < B; ++b)
         if (lens[b] < 0 || lens[b] > cap) return uavac_fail(ctx, UAVAC_EINVAL, "path length outside [0, cap]");
     const size_t np = (size_t)B * cap * 3;
-    DevBuf dp, dl, dc, dout, dol;
-    UAVAC_HIP(ctx, dp.alloc(8 * np));
-    UAVAC_HIP(ctx, dl.alloc(4 * (size_t)B));
-    UAVAC_HIP(ctx, dc.alloc(48 * (size_t)n_obs));
-    UAVAC_HIP(ctx, dout.alloc(8 * np));
-    UAVAC_HIP(ctx, dol.alloc(4 * (size_t)B));
-    UAVAC_HIP(ctx, hipMemcpyAsync(dp.p, paths, 8 * np, hipMemcpyHostToDevice, ctx->stream));
-    UAVAC_HIP(ctx, hipMemcpyAsync(dl.p, lens, 4 * (size_t)B, hipMemcpyHostToDevice, ctx->stream));
-    if (n_obs > 0) UAVAC_HIP(ctx, hipMemcpyAsync(dc.p, cuboids, 48 * (size_t)n_obs, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = uavac_rrt_simplify_dev(ctx, dp.as<double>(), dl.as<int32_t>(), B, cap, n_obs > 0 ? dc.as<double>() : nullptr,
-                                        n_obs, dout.as<double>(), dol.as<int32_t>())) return rc;
-    UAVAC_HIP(ctx, hipMemcpyAsync(out_paths, dout.p, 8 * np, hipMemcpyDeviceToHost, ctx->stream));
-    UAVAC_HIP(ctx, hipMemcpyAsync(out_lens, dol.p, 4 * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+    double *dp = nullptr, *dc = nullptr, *dout = nullptr;
+    int32_t *dl = nullptr, *dol = nullptr;
+    Scratch s(ctx);
+    s.in(&dp, paths, np); s.in(&dl, lens, (size_t)B); s.in(&dc, cuboids, 6 * (size_t)n_obs);
+    s.out(&dout, out_paths, np); s.out(&dol, out_lens, (size_t)B);
+    if (int rc = s.commit()) return rc;
+    if (int rc = s.upload()) return rc;
+    if (int rc = uavac_rrt_simplify_dev(ctx, dp, dl, B, cap, n_obs > 0 ? dc : nullptr, n_obs, dout, dol)) return rc;
+    if (int rc = s.download()) return rc;
     UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return UAVAC_OK;
 }
 
 int uavac_rrt_path_cost(uavac_ctx *ctx, const double *path, int n, double *cost) {
     UAVAC_ENTER(ctx);
-    if (n < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative count");
-    if (!cost || (n > 0 && !path)) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    DevBuf dp, dc;
-    UAVAC_HIP(ctx, dp.alloc(24 * (size_t)n));
-    UAVAC_HIP(ctx, dc.alloc(8));
-    if (n > 0) UAVAC_HIP(ctx, hipMemcpyAsync(dp.p, path, 24 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = uavac_rrt_path_cost_dev(ctx, dp.as<double>(), n, dc.as<double>())) return rc;
-    UAVAC_HIP(ctx, hipMemcpyAsync(cost, dc.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return UAVAC_OK;
+    if (int rc = check_path_cost(ctx, path, n, cost)) return rc;
+    double *dp = nullptr, *dc = nullptr;
+    Scratch s(ctx);
+    s.want(&dp, 3 * (size_t)n); s.want(&dc, 1);
+    if (int rc = s.commit()) return rc;
+    if (int rc = copy_in(ctx, dp, path, 3 * (size_t)n)) return rc;
+    if (int rc = uavac_rrt_path_cost_dev(ctx, dp, n, dc)) return rc;
+    return copy_out(ctx, cost, dc, 1);
 }
 
 int uavac_rrt_steer(uavac_ctx *ctx, const double *sample, const double *nearest, int E, double step, double *out) {
     UAVAC_ENTER(ctx);
-    if (E < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative count");
+    if (int rc = check_edges(ctx, sample, nearest, E, out)) return rc;
     if (E == 0) return UAVAC_OK;
-    if (!sample || !nearest || !out) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    const size_t zE = (size_t)E;
-    DevBuf d0, d1, dout;
-    UAVAC_HIP(ctx, d0.alloc(24 * zE));
-    UAVAC_HIP(ctx, d1.alloc(24 * zE));
-    UAVAC_HIP(ctx, dout.alloc(24 * zE));
-    UAVAC_HIP(ctx, hipMemcpyAsync(d0.p, sample, 24 * zE, hipMemcpyHostToDevice, ctx->stream));
-    UAVAC_HIP(ctx, hipMemcpyAsync(d1.p, nearest, 24 * zE, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = uavac_rrt_steer_dev(ctx, d0.as<double>(), d1.as<double>(), E, step, dout.as<double>())) return rc;
-    UAVAC_HIP(ctx, hipMemcpyAsync(out, dout.p, 24 * zE, hipMemcpyDeviceToHost, ctx->stream));
-    UAVAC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return UAVAC_OK;
+    double *d0 = nullptr, *d1 = nullptr, *dout = nullptr;
+    Scratch s(ctx);
+    const size_t n = 3 * (size_t)E;
+    s.want(&d0, n); s.want(&d1, n); s.want(&dout, n);
+    if (int rc = s.commit()) return rc;
+    if (int rc = copy_in(ctx, d0, sample, n)) return rc;
+    if (int rc = copy_in(ctx, d1, nearest, n)) return rc;
+    if (int rc = uavac_rrt_steer_dev(ctx, d0, d1, E, step, dout)) return rc;
+    return copy_out(ctx, out, dout, n);
 }
 
 }  // extern "C"
