@@ -212,7 +212,8 @@ def _row_fed_kernel():
     kernels = _buildcheck._disassemble_cfg(os.path.join(PKG, "build", "control_rollout.o"))
     if kernels is None:
         pytest.skip("no object file / LLVM tools here")
-    name, ins = next((n, i) for n, i in kernels.items() if "control_rollout_kernel" in n and "ELb0ELb0ELb0ELi0E" in n)
+    name, ins = next((n, i) for n, i in kernels.items()            # (neither POLY nor GROUND nor YAWSCAN, PMODE 0)
+                     if "control_rollout_kernel" in n and _buildcheck.template_args(n)[5:] == (False, False, False, 0))
     at = max(j for j, x in enumerate(ins) if _buildcheck._ROW_LOAD.match(x) and "offset:64" in x)
     return kernels, name, ins, at, _buildcheck._ROW_LOAD.match(ins[at]).group(1)
 

@@ -82,7 +82,7 @@ def test_the_build_keeps_the_layer_kernels_in_registers():
     assert len(counts) == 3 and max(counts.values()) <= 168
     for k in ("minsnap_layer_kernel", "layer_prepass_kernel", "minsnap_shift_kernel"):
         assert any(k in n for n in counts), k
-    lds = dict(_buildcheck.kernel_lds_bytes(os.path.join(_buildcheck.PKG, "build", "minsnap_layer.o"), "minsnap_layer_kernel"))
+    lds = {k.name: k.group_segment_fixed_size for k in _buildcheck.check_budgets("layer_kernels") if "minsnap_layer_kernel" in k.name}
     assert len(lds) == 1 and 3 * max(lds.values()) <= _buildcheck.LDS_BYTES_PER_CU          # three workgroups per CU
 
 

@@ -83,10 +83,9 @@ def test_the_build_keeps_the_new_kernels_in_their_budget_and_the_old_ones_where_
     counts = _buildcheck.check_layer_obs_kernels()
     if counts is not None:                                   # (None: no object files here, a library that was built elsewhere)
         assert len(counts) == 2 and max(counts.values()) <= 168
-        obj = os.path.join(_buildcheck.PKG, "build", "minsnap_layer_obs.o")
-        lds = dict(_buildcheck.kernel_lds_bytes(obj, "minsnap_layer_kernel"))
+        lds, old = ({k.name: k.group_segment_fixed_size for k in _buildcheck.check_budgets(key) if "minsnap_layer_kernel" in k.name}
+                    for key in ("layer_obs_kernels", "layer_kernels"))
         assert len(lds) == 1 and 3 * max(lds.values()) <= _buildcheck.LDS_BYTES_PER_CU      # three workgroups per CU
-        old = dict(_buildcheck.kernel_lds_bytes(os.path.join(_buildcheck.PKG, "build", "minsnap_layer.o"), "minsnap_layer_kernel"))
         assert max(lds.values()) - max(old.values()) == 16 * 6 * 8 + 16                    # the cuboids and two words
         assert len(_buildcheck.check_layer_kernels()) == 3
 

@@ -107,5 +107,5 @@ def test_scored_row_fed_kernels_pass_the_row_prefetch_check():
         pytest.skip("no object files here (library built elsewhere)")
     assert _buildcheck.check_row_prefetch(scored=True) == 8
     assert _buildcheck.check_row_prefetch() == 16
-    names = [n for n, _, _ in _buildcheck.rollout_register_counts()]
+    names = [n for n, _, _ in _buildcheck.check_rollout_registers()]
     assert sum("scored_control_rollout_kernel" in n for n in names) == 50

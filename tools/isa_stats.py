@@ -1,36 +1,20 @@
-import re, collections, sys, subprocess, os, tempfile, shutil
+"""Static instruction mix of one kernel's tick loop: `python3 tools/isa_stats.py <object file> <kernel name fragment (a regex)>`.
+Code object, disassembly and the kernel's record come from the build checks' reader (uav_ac/_buildcheck.py)."""
+import re, collections, sys, os
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "uav-autonomous-control_amd"))
+from uav_ac import _buildcheck
 obj=sys.argv[1]; frag=sys.argv[2]
-tmp=tempfile.mkdtemp(); shutil.copy(obj, tmp+'/o.o')
-subprocess.run(['/opt/rocm/lib/llvm/bin/llvm-objdump','--offloading','o.o'],cwd=tmp,capture_output=True)
-co=[f for f in os.listdir(tmp) if 'gfx950' in f][0]
-txt=subprocess.run(['/opt/rocm/lib/llvm/bin/llvm-objdump','-d','--no-show-raw-insn',tmp+'/'+co],capture_output=True,text=True).stdout
-notes=subprocess.run(['/opt/rocm/lib/llvm/bin/llvm-readelf','--notes',tmp+'/'+co],capture_output=True,text=True).stdout
-m=re.search(r"^[0-9a-f]+ <(_Z[^>]*"+frag+r"[^>]*)>:\n(.*?)(?=^[0-9a-f]+ <|\Z)", txt, re.S|re.M)
-name=m.group(1)
-lines=m.group(2).splitlines()
-ins=[]
-for l in lines:
-    mm=re.match(r"\s*(\S+)\s*(.*?)\s*//\s*([0-9A-Fa-f]+):(.*)$", l)
-    if mm: ins.append((int(mm.group(3),16), mm.group(1), mm.group(2), mm.group(4)))
-base=ins[0][0]; addr={a:i for i,(a,_,_,_) in enumerate(ins)}
-br=[]
-for i,(a,op,args,c) in enumerate(ins):
-    if op.startswith('s_cbranch') or op=='s_branch':
-        mm=re.search(r"\+0x([0-9a-fA-F]+)>", c)
-        if mm and base+int(mm.group(1),16) in addr: br.append((i,addr[base+int(mm.group(1),16)],op))
-bars=[i for i,x in enumerate(ins) if x[1]=='s_barrier']
+name,ins=next((n,i) for n,i in _buildcheck._disassemble_cfg(obj).items() if n.startswith('_Z') and re.search(frag,n))
+rec=next(k for k in _buildcheck.read_object(obj)["kernels"] if k.name==name)
+ops=[x.split()[0] for x in ins]; addr={x.addr:i for i,x in enumerate(ins)}
+br=[(i,addr[x.target],op) for i,(x,op) in enumerate(zip(ins,ops)) if (op.startswith('s_cbranch') or op=='s_branch') and x.target in addr]
+bars=[i for i,op in enumerate(ops) if op=='s_barrier']
 loops=[(i-t,t,i) for i,t,op in br if t<=i and (not bars or any(t<=b<=i for b in bars))]
 big=[l for l in loops if l[0]>=400]; _,lo,hi=min(big) if big else max(loops)      # the tick loop: the smallest loop around a barrier that is long enough to be it (the persistent-tile loop around it is larger)
 fwd=[(t-i,i,t) for i,t,op in br if lo<=i<t<=hi and op=='s_cbranch_execz']
 _,olo,ohi=max(fwd)
-inner=[ins[i] for i in range(lo,hi+1) if not (olo<i<ohi)]
-c=collections.Counter(x[1] for x in inner)
-blk=re.search(r"\.name:\s+"+re.escape(name)+r".*?\n(.*?)\.symbol", notes, re.S)
-vg=re.findall(r"\.vgpr_count:\s+(\d+)", notes); 
-idx=[m.start() for m in re.finditer(re.escape(name), notes)]
-seg=notes[max(0,idx[0]-1500):idx[0]+200]
+c=collections.Counter(ops[i] for i in range(lo,hi+1) if not (olo<i<ohi))
 print(name[:70])
-print(' loop', hi-lo+1, 'outer', ohi-olo, 'inner', len(inner), '| inner: s_mov', c['s_mov_b32'], 'lane ops', sum(v for k,v in c.items() if 'lane' in k), 'valu', sum(v for k,v in c.items() if k.startswith('v_')), 'branches', sum(v for k,v in c.items() if 'branch' in k),
+print(' loop', hi-lo+1, 'outer', ohi-olo, 'inner', sum(c.values()), '| inner: s_mov', c['s_mov_b32'], 'lane ops', sum(v for k,v in c.items() if 'lane' in k), 'valu', sum(v for k,v in c.items() if k.startswith('v_')), 'branches', sum(v for k,v in c.items() if 'branch' in k),
       '| scalar loads', sum(v for k,v in c.items() if k.startswith('s_load')), 'waits', c['s_waitcnt'])
-print(' regs:', re.findall(r"\.(?:sgpr_count|sgpr_spill_count|vgpr_count|vgpr_spill_count|private_segment_fixed_size):\s+\d+", seg)[-5:])
-shutil.rmtree(tmp)
+print(' regs:', [f"{'.'+f+':':<16} {getattr(rec,f)}" for f in ('private_segment_fixed_size','sgpr_count','sgpr_spill_count','vgpr_count','vgpr_spill_count')])

@@ -1,9 +1,19 @@
-"""Build-time check of the rollout kernels' register budget (used by __graft_entry__.build() and by the CPU tests).
+"""The build checks: what `make`, `__graft_entry__.build()` and the autobuild of `uav_ac._native.lib()` run on the object files
+under build/ before a library counts as built (`run_all`), and what the CPU tests call piece by piece.
 
-Every variant of `control_rollout_kernel` must fit TWO wavefronts on a SIMD: at most 256 of its 512 vector registers, no
-vector-register spills.  A logged launch puts a compute and a store wave of the same kernel on every SIMD; at 258 registers
-(a 6-register 'optimisation' tried in round 3) the bench launch took 1.96 ms instead of 1.27 ms -- a cliff that no functional
-test sees and that a toolchain bump can cross silently.  Read from the code object inside build/control_rollout.o."""
+* One reader (`read_object`) takes an object file's gfx950 code object apart once per process: a record per kernel from the
+  metadata notes (`parse_kernels`), the disassembly on demand (`_disassemble_cfg`).
+* One table (`BUDGETS`) says per object file which kernels must be there, how many, and how many vector registers each may
+  take; one function (`check_budget`) applies a row.  A kernel past its budget still computes the right thing, only slower -- a
+  logged rollout launch at 258 vector registers (a 6-register 'optimisation' tried in round 3) took 1.96 ms instead of 1.27 ms:
+  one wave per SIMD instead of two -- so no functional test sees it and a toolchain bump can cross it silently.
+* `UNBUDGETED` lists the object files that have no budget; an object file in neither list fails the build (`check_inventory`).
+* The two hand-placed prefetches are followed in the disassembly (`check_row_prefetch`, `check_heading_prefetch`); the shipped
+  library exports no diagnostic symbol (`check_no_diagnostics`).
+
+A check that cannot run (no object files, no LLVM tools: a library that was built elsewhere) answers None; `run_all` treats
+that as a failure."""
+import collections
 import os
 import re
 import shutil
@@ -12,285 +22,34 @@ import tempfile
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM_BIN = "/opt/rocm/lib/llvm/bin"
-VGPR_LIMIT = 256
+
+Kernel = collections.namedtuple("Kernel", "name vgpr_count vgpr_spill_count sgpr_count sgpr_spill_count agpr_count "
+                                          "private_segment_fixed_size group_segment_fixed_size")
 
 
-def _kernel_notes(obj: str):
-    """The metadata notes of the gfx950 code object inside an object file, or None when the object file or the LLVM tools are not
-    there (a library that was built elsewhere)."""
-    objdump, readelf = os.path.join(LLVM_BIN, "llvm-objdump"), os.path.join(LLVM_BIN, "llvm-readelf")
-    if not (os.path.exists(obj) and os.path.exists(objdump) and os.path.exists(readelf)):
-        return None
-    tmp = tempfile.mkdtemp()
-    try:
-        shutil.copy(obj, os.path.join(tmp, "o.o"))
-        subprocess.run([objdump, "--offloading", "o.o"], cwd=tmp, check=True, capture_output=True)
-        co = [f for f in os.listdir(tmp) if "gfx950" in f][0]
-        notes = subprocess.run([readelf, "--notes", os.path.join(tmp, co)], check=True, capture_output=True, text=True).stdout
-    finally:
-        shutil.rmtree(tmp)
-    return notes
+def parse_kernels(notes: str):
+    """[Kernel] from the text of a code object's metadata notes (`llvm-readelf --notes`): the items of the `amdhsa.kernels:` list,
+    each read from the keys that stand at the item's own indentation -- by name, in whatever order; the `.name` of a kernel
+    argument stands deeper and is not one of them.  Notes without that list (no device code): no kernels."""
+    body = re.search(r"^amdhsa\.kernels:[^\n]*\n((?:[ \t]+[^\n]*\n?)*)", notes, flags=re.M)
+    dash = re.match(r"( *)- ", body.group(1)) if body else None
+    if not dash:
+        return []
+    indent, kernels = dash.group(1), []
+    for item in re.split(rf"^{indent}- ", body.group(1), flags=re.M)[1:]:
+        keys = dict(re.findall(rf"^(?:{indent}  )?\.(\w+):[ \t]*(\S*)", item, flags=re.M))     # (the item's first line lost its indentation to the split)
+        try:
+            kernels.append(Kernel(keys["name"], *(int(keys[f]) for f in Kernel._fields[1:])))
+        except KeyError as exc:
+            raise RuntimeError(f"kernel {keys.get('name')}: no {exc} in the code object's metadata")
+    return kernels
 
 
-def kernel_register_counts(obj: str, kernel: str):
-    """[(kernel name, vgpr_count, vgpr_spill_count)] of every kernel of the object file whose name contains `kernel`, or None
-    when the object file or the LLVM tools are not there (a library that was built elsewhere)."""
-    notes = _kernel_notes(obj)
-    if notes is None:
-        return None
-    found = re.findall(r"\.name:\s+(\S*" + re.escape(kernel) + r"\S*).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", notes, flags=re.S)
-    return [(n, int(v), int(s)) for n, v, s in found]
-
-
-def kernel_private_bytes(obj: str, kernel: str):
-    """[(kernel name, private_segment_fixed_size)] -- the scratch memory per lane, which is 0 for a kernel that lives in registers --
-    of every kernel of the object file whose name contains `kernel`; None like `kernel_register_counts`."""
-    notes = _kernel_notes(obj)
-    if notes is None:
-        return None
-    # (the metadata lists a kernel's keys in alphabetical order: .name comes before .private_segment_fixed_size)
-    found = re.findall(r"\.name:\s+(\S*" + re.escape(kernel) + r"\S*)\s.*?\.private_segment_fixed_size:\s+(\d+)", notes, flags=re.S)
-    return [(n, int(v)) for n, v in found]
-
-
-def rollout_register_counts(obj: str = None):
-    """The same for every control_rollout_kernel variant."""
-    return kernel_register_counts(obj or os.path.join(PKG, "build", "control_rollout.o"), "control_rollout_kernel")
-
-
-def check_planning_registers():
-    """The planning kernels' budgets: the chunk-streaming sampler without jerk / snap runs six waves per SIMD (<= 80 vector
-    registers; with jerk / snap four: <= 128), the solve one or two (the variant that keeps five knots in registers: <= 512, the
-    others <= 256), the solve with boundary derivatives two (<= 256, and no scratch memory at all: zero private-segment bytes), the
-    plan audit three (<= 168); none may spill (a spill in the sampler showed as 3 % more HBM writes and no other symptom, NOTES R4-2).
-    Returns the counts, None when they cannot be read."""
-    s = kernel_register_counts(os.path.join(PKG, "build", "minsnap_sample_stream.o"), "minsnap_sample_stream_kernel")
-    k = kernel_register_counts(os.path.join(PKG, "build", "minsnap_solve_bt.o"), "minsnap_solve_bt_kernel")
-    k2 = kernel_register_counts(os.path.join(PKG, "build", "minsnap_solve_tw.o"), "minsnap_solve_tw_kernel")
-    a = kernel_register_counts(os.path.join(PKG, "build", "minsnap_audit.o"), "minsnap_audit_kernel")
-    bc_obj = os.path.join(PKG, "build", "minsnap_solve_bc.o")
-    kb, pb = kernel_register_counts(bc_obj, "minsnap_solve_bc_kernel"), kernel_private_bytes(bc_obj, "minsnap_solve_bc_kernel")
-    if s is None or k is None or k2 is None or a is None or kb is None or pb is None:
-        return None
-    k = k + k2                                        # (the two-ended solve: same budgets, same naming of the last template argument)
-    bad = []
-    for n, v, sp in s:
-        args = re.search(r"minsnap_sample_stream_kernelILi(\d+)ELb([01])ELb([01])ELb([01])E", n)
-        waves, derivs = int(args.group(1)), args.group(3) == "1"
-        limit = 128 if (derivs or waves == 16) else 80
-        if v > limit or sp:
-            bad.append((n[:70], v, sp, limit))
-    for n, v, sp in k:
-        limit = 512 if n.rstrip("E").endswith("Li5") or "Li5EE" in n else 256
-        if v > limit or sp:
-            bad.append((n[:70], v, sp, limit))
-    for n, v, sp in a:                                # the plan audit: three waves per SIMD (built: 100 .. 146 registers)
-        if v > 168 or sp:
-            bad.append((n[:70], v, sp, 168))
-    for n, v, sp in kb:                               # the solve with boundary derivatives: two waves per SIMD (built: 211 / 217 registers)
-        if v > 256 or sp:
-            bad.append((n[:70], v, sp, 256))
-    for n, priv in pb:
-        if priv:
-            bad.append((n[:70], f"{priv} private-segment bytes", 0, 0))
-    if len(s) < 20 or len(k) < 20 or len(a) < 4 or len(kb) != 2 or len(pb) != 2 or bad:
-        raise RuntimeError(f"planning kernels outside their register budgets (name, VGPRs, spills, limit): {bad}; {len(s)} sampler, "
-                           f"{len(k)} solve, {len(kb)} boundary-solve and {len(a)} audit variants found (compiler: {compiler_version()})")
-    return s + k + a + kb
-
-
-LDS_BYTES_PER_CU = 160 * 1024
-VGPRS_AT_WAVES_PER_SIMD = {8: 64, 7: 72, 6: 80, 5: 96, 4: 128, 3: 168, 2: 256, 1: 512}     # the largest allocation that still runs that many
-
-
-def kernel_lds_bytes(obj: str, kernel: str):
-    """[(kernel name, group_segment_fixed_size)] -- the static LDS of a workgroup -- of every kernel of the object file whose name
-    contains `kernel`; None like `kernel_register_counts`."""
-    notes = _kernel_notes(obj)
-    if notes is None:
-        return None
-    # (the metadata lists a kernel's keys in alphabetical order: .group_segment_fixed_size comes before .name)
-    found = re.findall(r"\.group_segment_fixed_size:\s+(\d+)(?:(?!\.group_segment_fixed_size:).)*?\.name:\s+(\S*" + re.escape(kernel) + r"\S*)",
-                       notes, flags=re.S)
-    return [(n, int(v)) for v, n in found]
-
-
-def _check_object(obj_name: str, kernels, what: str, vgpr_limit=None, extra_kernels: int = 0):
-    """The budget of the kernels of one object file under build/: every kernel of `kernels` must be there and the object must hold
-    exactly len(kernels) + `extra_kernels` of them (further instantiations of a listed kernel), none may spill or use scratch memory at
-    all (zero private-segment bytes), and none may need more than `vgpr_limit` vector registers.  `vgpr_limit` None: the limit of each
-    kernel follows from the LDS it ends up with -- workgroups of four waves, so min(8, 160 KiB // LDS) workgroups per CU are as many
-    waves per SIMD, and the kernel must fit the allocation that still runs that many --, and a decision kernel of the layer search must
-    keep three workgroups per CU.  Returns {kernel: VGPRs}, None when the counts cannot be read."""
-    obj = os.path.join(PKG, "build", obj_name)
-    regs, priv = kernel_register_counts(obj, "_kernel"), kernel_private_bytes(obj, "_kernel")
-    lds = kernel_lds_bytes(obj, "_kernel") if vgpr_limit is None else []
-    if regs is None or priv is None or lds is None:
-        return None
-    lds = dict(lds)
-    bad = [(n[:70], f"{p} private-segment bytes", 0, 0) for n, p in priv if p]
-    for n, v, sp in regs:
-        limit = vgpr_limit
-        if limit is None:
-            if n not in lds:
-                bad.append((n[:70], "no LDS size found", 0, 0))
-                continue
-            waves = min(8, LDS_BYTES_PER_CU // lds[n]) if lds[n] else 8
-            limit = VGPRS_AT_WAVES_PER_SIMD.get(waves, 0)      # (a workgroup that does not fit a CU at all: limit 0)
-            if "minsnap_layer_kernel" in n and waves < 3:
-                bad.append((n[:70], f"{lds[n]} bytes of LDS: fewer than three workgroups per CU", 0, 0))
-        if v > limit or sp:
-            bad.append((n[:70], v, sp, limit))
-    missing = [k for k in kernels if not any(k in n for n, _, _ in regs)]
-    if bad or missing or len(regs) != len(kernels) + extra_kernels or len(priv) != len(regs):
-        raise RuntimeError(f"{what} kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; "
-                           f"{len(regs)} kernels found (compiler: {compiler_version()})")
-    return {n: v for n, v, _ in regs}
-
-
-TIMEOPT_KERNELS = ("row_counts_t_kernel", "plan_t_commit_kernel", "minsnap_cost_kernel", "timeopt_expand_kernel", "timeopt_init_kernel",
-                   "timeopt_probe_kernel", "timeopt_direction_kernel", "timeopt_candidate_kernel", "timeopt_select_kernel")
-
-
-def check_timeopt_kernels():
-    """The kernels of csrc/minsnap_timeopt.hip (plans from given durations, the snap cost, the bookkeeping of the duration
-    optimisation): `_check_object` -- their loops over a mission's segments keep no per-segment arrays -- with all of them at least
-    four waves per SIMD (<= 128 vector registers; built: the cost kernel 64, the others 10 .. 40).  Returns {kernel: VGPRs} (the two
-    row-count variants under their mangled names), None when the counts cannot be read."""
-    return _check_object("minsnap_timeopt.o", TIMEOPT_KERNELS, "time-optimisation", vgpr_limit=128, extra_kernels=1)
-
-
-SEPARATION_KERNELS = ("separation_prepass_kernel", "minsnap_separation_kernel", "separation_merge_kernel")
-
-
-def check_separation_kernels():
-    """The kernels of csrc/minsnap_separation.hip (the fleet's separation audit): `_check_object` -- the two coefficient sets of the pair
-    kernel are indexed by constants only --, and the pair kernel, whose 48 KB LDS tile admits three workgroups per CU, must run three
-    waves per SIMD (<= 168 vector registers; built: 164, the pre-pass 14, the merge 20).  Returns {kernel: VGPRs}, None when the
-    counts cannot be read."""
-    return _check_object("minsnap_separation.o", SEPARATION_KERNELS, "separation", vgpr_limit=168)
-
-
-CONFLICT_KERNELS = ("conflict_prepass_kernel", "conflict_discover_kernel", "conflict_count_kernel", "conflict_list_kernel",
-                    "conflict_measure_kernel")
-
-
-def check_conflict_kernels():
-    """The kernels of csrc/minsnap_conflicts.hip (the separation audit's conflict list): `_check_object` -- the coefficient sets of the
-    discovery and of the measure are indexed by constants only -- with the register limit of each from the LDS it ends up with: the
-    discovery and the measure keep the audit's 48 KB tile, hence three workgroups per CU and <= 168; the pre-pass, the counts (32 B for
-    its scan) and the list run eight waves per SIMD and <= 64.  Returns {kernel: VGPRs}, None when the counts cannot be read."""
-    return _check_object("minsnap_conflicts.o", CONFLICT_KERNELS, "conflict-list")
-
-
-STAGGER_KERNELS = ("stagger_prepass_kernel", "minsnap_stagger_kernel")
-
-
-def check_stagger_kernels():
-    """The kernels of csrc/minsnap_stagger.hip (start delays that clear the separation audit): `_check_object` -- the two coefficient
-    sets of the decision kernel are indexed by constants only --, and the decision kernel, whose 48 KB LDS tile plus 1 KB of granted
-    starts admits three workgroups per CU, must run three waves per SIMD (<= 168 vector registers; built: 145, the pre-pass 14).
-    Returns {kernel: VGPRs}, None when the counts cannot be read."""
-    return _check_object("minsnap_stagger.o", STAGGER_KERNELS, "stagger", vgpr_limit=168)
-
-
-FLOWN_SEPARATION_KERNELS = ("flown_separation_kernel", "flown_merge_kernel")
-
-
-def check_flown_separation_kernels():
-    """The kernels of csrc/flown_separation.hip (the separation the fleet flew, from a state log): `_check_object`, and the pair kernel,
-    whose 48 KB LDS tile admits three workgroups per CU like the plan audit's, must run three waves per SIMD (<= 168 vector registers;
-    built: 143, the merge 18).  Returns {kernel: VGPRs}, None when the counts cannot be read."""
-    return _check_object("flown_separation.o", FLOWN_SEPARATION_KERNELS, "flown-separation", vgpr_limit=168)
-
-
-FLOWN_CONFLICT_KERNELS = ("flown_discover_kernel", "conflict_count_kernel", "conflict_list_kernel", "flown_measure_kernel")
-FLOWN_CONFLICT_LIMITS = {"flown_discover_kernel": 168, "conflict_count_kernel": 64, "conflict_list_kernel": 64, "flown_measure_kernel": 128}
-
-
-def check_flown_conflict_kernels():
-    """The kernels of csrc/flown_conflicts.hip (the conflict list of a flight, from a state log): `_check_object`, and each kernel
-    inside its own limit: the discovery, whose 48 KB LDS tile admits three workgroups per CU like `flown_separation_kernel`'s, must
-    run three waves per SIMD (<= 168 vector registers; built: 114); the measure keeps 48 log values per lane in flight and is
-    launched for four waves per SIMD (`__launch_bounds__(256, 4)`: <= 128; built: 112); the counts and the list of conflict_csr.h run
-    eight (<= 64; built: 24 each, as in minsnap_conflicts.o).  Returns {kernel: VGPRs}, None when the counts cannot be read."""
-    regs = _check_object("flown_conflicts.o", FLOWN_CONFLICT_KERNELS, "flown-conflict-list", vgpr_limit=168)
-    if regs is None:
-        return None
-    over = [(n[:70], v, limit) for k, limit in FLOWN_CONFLICT_LIMITS.items() for n, v in regs.items() if k in n and v > limit]
-    if over:
-        raise RuntimeError(f"flown-conflict-list kernels outside their budgets (name, VGPRs, limit): {over} (compiler: {compiler_version()})")
-    return regs
-
-
-FLOWN_AUDIT_KERNELS = ("flown_audit_kernel", "flown_audit_merge_kernel")
-
-
-def check_flown_audit_kernels():
-    """The kernels of csrc/flown_audit.hip (the plan audit of a flight, from a state log): `_check_object`, and the streaming kernel,
-    which is launched for four waves per SIMD (`__launch_bounds__(256, 4)`: one workgroup per SIMD keeps 26 row loads per wavefront
-    in flight), must fit that (<= 128 vector registers; built: 82, the merge 44).  Returns {kernel: VGPRs}, None when the counts
-    cannot be read."""
-    return _check_object("flown_audit.o", FLOWN_AUDIT_KERNELS, "flown-audit", vgpr_limit=128)
-
-
-DELAY_KERNELS = ("delay_counts_kernel", "minsnap_delay_kernel")
-
-
-def check_delay_kernels():
-    """The kernels of csrc/minsnap_delay.hip (start delays as a leading hold segment of the plan): `_check_object`; both are plain
-    copies that run at least eight waves per SIMD (<= 64 vector registers; built: 24 each).  Returns {kernel: VGPRs}, None when the
-    counts cannot be read."""
-    return _check_object("minsnap_delay.o", DELAY_KERNELS, "delay", vgpr_limit=64)
-
-
-TAKE_KERNELS = ("take_counts_kernel", "minsnap_take_kernel", "fleet_order_kernel")
-
-
-def check_take_kernels():
-    """The kernels of csrc/minsnap_take.hip (missions of a plan selected and reordered, priorities into a within-group order):
-    `_check_object`; the first two are plain copies like the delay kernels, the third counts over 2 KB LDS tiles of keys, and all run at
-    least eight waves per SIMD (<= 64 vector registers; built: 24, 28 and 18).  Returns {kernel: VGPRs}, None when the counts cannot
-    be read."""
-    return _check_object("minsnap_take.o", TAKE_KERNELS, "take", vgpr_limit=64)
-
-
-LAYER_KERNELS = ("layer_prepass_kernel", "minsnap_layer_kernel", "minsnap_shift_kernel")
-
-
-def check_layer_kernels():
-    """The kernels of csrc/minsnap_layer.hip (offset layers that clear the separation audit, and the offset transform): `_check_object`
-    -- the coefficient sets of the decision kernel are indexed by constants only -- with the register limit of each from the LDS it
-    ends up with (built: the decision kernel 50192 B of LDS -- the 48 KB tile, 1 KB of granted layers, two words -- hence three
-    workgroups per CU and <= 168, at 137; the pre-pass and the transform no LDS, hence eight and <= 64, at 14 and 21).  Returns
-    {kernel: VGPRs}, None when the counts cannot be read."""
-    return _check_object("minsnap_layer.o", LAYER_KERNELS, "layer")
-
-
-LAYER_OBS_KERNELS = ("layer_prepass_kernel", "minsnap_layer_kernel")
-
-
-def check_layer_obs_kernels():
-    """The kernels of csrc/minsnap_layer_obs.hip (the same search, refusing layers that put a mission into a cuboid): the same check as
-    `check_layer_kernels` on the two instantiations with cuboids (built: the decision kernel 50976 B of LDS -- the search's 50192 B,
-    768 B of cuboids, two more words -- hence still three workgroups per CU and <= 168, at 142; the pre-pass no LDS, <= 64, at 14).
-    Returns {kernel: VGPRs}, None when the counts cannot be read."""
-    return _check_object("minsnap_layer_obs.o", LAYER_OBS_KERNELS, "obstacle-aware layer")
-
-
-def check_rollout_registers(obj: str = None):
-    """Raise RuntimeError when a rollout variant needs more than 256 vector registers or spills any; returns the counts."""
-    counts = rollout_register_counts(obj)
-    if counts is None:
-        return None
-    if len(counts) < 40:
-        raise RuntimeError(f"only {len(counts)} control_rollout_kernel variants found in the code object")
-    over = [(n[:80], v) for n, v, _ in counts if v > VGPR_LIMIT]
-    spills = [(n[:80], s) for n, _, s in counts if s > 0]
-    if over or spills:
-        raise RuntimeError(f"rollout kernels outside the two-waves-per-SIMD budget: > {VGPR_LIMIT} VGPRs {over}; spills {spills} "
-                           f"(compiler: {compiler_version()})")
-    return counts
+def template_args(name: str):
+    """The literal template arguments at the head of a mangled kernel name's argument list, ints and bools in order:
+    `..control_rollout_kernelILi4ELi2ELb0E..EEv..` -> (4, 2, False, ..); () for a kernel that is no template."""
+    head = re.search(r"I((?:L[a-z]n?\d+E)+)", name)
+    return tuple(v == "1" if t == "b" else int(v.replace("n", "-")) for t, v in re.findall(r"L([a-z])(n?\d+)E", head.group(1))) if head else ()
 
 
 class Ins(str):
@@ -308,21 +67,9 @@ _BRANCH = ("s_cbranch", "s_branch")
 _INDIRECT = ("s_setpc", "s_swappc", "s_call", "s_rfe", "s_cbranch_g_fork", "s_cbranch_i_fork", "s_cbranch_join")
 
 
-def _disassemble_cfg(obj: str):
-    """{kernel name: [Ins]} of the gfx950 code object inside `obj` -- instruction text with its address and branch target, which is
-    what a check needs to follow the control flow -- or None when the object file or the LLVM tools are missing."""
-    objdump = os.path.join(LLVM_BIN, "llvm-objdump")
-    if not (os.path.exists(obj) and os.path.exists(objdump)):
-        return None
-    tmp = tempfile.mkdtemp()
-    try:
-        shutil.copy(obj, os.path.join(tmp, "o.o"))
-        subprocess.run([objdump, "--offloading", "o.o"], cwd=tmp, check=True, capture_output=True)
-        co = [f for f in os.listdir(tmp) if "gfx950" in f][0]
-        text = subprocess.run([objdump, "-d", "--no-show-raw-insn", os.path.join(tmp, co)], check=True, capture_output=True,
-                              text=True).stdout
-    finally:
-        shutil.rmtree(tmp)
+def parse_listing(text: str):
+    """{kernel name: [Ins]} from the text of `llvm-objdump -d --no-show-raw-insn`: instruction text with its address and branch
+    target, which is what a check needs to follow the control flow."""
     kernels, cur, base = {}, None, 0
     for line in text.splitlines():
         head = re.match(r"([0-9a-f]+) <([^>]+)>:", line)
@@ -344,11 +91,224 @@ def _disassemble_cfg(obj: str):
     return kernels
 
 
-def _disassemble(obj: str):
-    """{kernel name: [instruction text]}: `_disassemble_cfg` for the checks that read straight-line code."""
-    return _disassemble_cfg(obj)
+_objects = {}            # what `read_object` has read in this process, by path
 
 
+def read_object(obj: str):
+    """The gfx950 code object inside an object file, taken out once: {"kernels": [Kernel], "image": the code object's bytes,
+    "listing": None until `_disassemble_cfg` fills it}.  An object file without device code reads as no kernels; None when the
+    object file or the LLVM tools are not there.  Kept per process and read again when the file's size or modification time, or
+    LLVM_BIN, is no longer what it was."""
+    objdump, readelf = os.path.join(LLVM_BIN, "llvm-objdump"), os.path.join(LLVM_BIN, "llvm-readelf")
+    if not (os.path.exists(obj) and os.path.exists(objdump) and os.path.exists(readelf)):
+        return None
+    stat = os.stat(obj)
+    seen = (stat.st_size, stat.st_mtime_ns, LLVM_BIN)
+    if obj not in _objects or _objects[obj]["seen"] != seen:
+        notes, image = "", b""
+        with tempfile.TemporaryDirectory() as tmp:
+            shutil.copy(obj, os.path.join(tmp, "o.o"))
+            subprocess.run([objdump, "--offloading", "o.o"], cwd=tmp, check=True, capture_output=True)
+            for co in (f for f in os.listdir(tmp) if "gfx950" in f):
+                notes = subprocess.run([readelf, "--notes", os.path.join(tmp, co)], check=True, capture_output=True, text=True).stdout
+                with open(os.path.join(tmp, co), "rb") as fh:
+                    image = fh.read()
+        _objects[obj] = {"seen": seen, "kernels": parse_kernels(notes), "image": image, "listing": None}
+    return _objects[obj]
+
+
+def _disassemble_cfg(obj: str):
+    """{kernel name: [Ins]} of the code object inside `obj` (`parse_listing`), disassembled once; None like `read_object`."""
+    co = read_object(obj)
+    if co is None:
+        return None
+    if co["listing"] is None:
+        with tempfile.NamedTemporaryFile(suffix=".co") as fh:
+            fh.write(co["image"])
+            fh.flush()
+            co["listing"] = parse_listing(subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "-d", "--no-show-raw-insn", fh.name],
+                                                         check=True, capture_output=True, text=True).stdout if co["image"] else "")
+    return co["listing"]
+
+
+# ------------------------------------------------------------------------------------------------ the budgets
+LDS_BYTES_PER_CU = 160 * 1024
+VGPRS_AT_WAVES_PER_SIMD = {8: 64, 7: 72, 6: 80, 5: 96, 4: 128, 3: 168, 2: 256, 1: 512}     # the largest allocation that still runs that many
+FROM_LDS = "from the LDS the kernel ends up with"
+
+# One row per budget.  `key`: where `run_all` reports the row (rows may share one); `obj`: the object file(s) under build/;
+# `noun`: what messages call the kernels; `kernels`: names that must be there.  The object holds exactly len(kernels) + `extra`
+# kernels (further instantiations of a listed one) -- or, with `at_least`, at least that many kernels of the listed names, and
+# the row speaks of those alone.  `limit`, the most vector registers a kernel may take: a number; {kernel: number}; a function
+# of the kernel's template arguments; or FROM_LDS -- workgroups of four waves, so min(8, 160 KiB // LDS) workgroups per CU are
+# as many waves per SIMD, and the kernel must fit the allocation that still runs that many; a decision kernel of the layer
+# search must keep three workgroups per CU.  No kernel may spill a vector register; with `scratch_free` none may use scratch
+# memory at all (zero private-segment bytes).
+Budget = collections.namedtuple("Budget", "key obj noun kernels limit extra at_least scratch_free", defaults=(0, None, True))
+BUDGETS = (
+    # every rollout variant fits TWO waves on a SIMD: a logged launch puts a compute and a store wave of one kernel on each
+    Budget("rollout_registers", "control_rollout.o", "rollout", ("control_rollout_kernel",), 256, at_least=40, scratch_free=False),
+    # the chunk-streaming sampler: six waves per SIMD, four with jerk / snap or sixteen waves (a spill here showed as 3 % more HBM
+    # writes and no other symptom, NOTES R4-2)
+    Budget("planning_registers", "minsnap_sample_stream.o", "streaming-sampler", ("minsnap_sample_stream_kernel",),
+           lambda w, hits, derivs, ragged: 128 if derivs or w == 16 else 80, at_least=20, scratch_free=False),
+    # the one-ended and the two-ended solve: two waves per SIMD, one for the variant that keeps five knots in registers
+    Budget("planning_registers", "minsnap_solve_bt.o minsnap_solve_tw.o", "solve", ("minsnap_solve_bt_kernel", "minsnap_solve_tw_kernel"),
+           lambda ragged, park_lds, n, nreg: 512 if nreg == 5 else 256, at_least=20, scratch_free=False),
+    # the plan audit: three waves per SIMD (built: 100 .. 146)
+    Budget("planning_registers", "minsnap_audit.o", "plan-audit", ("minsnap_audit_kernel",), 168, at_least=4, scratch_free=False),
+    # the solve with boundary derivatives, uniform and ragged: two waves per SIMD (built: 211 / 217)
+    Budget("planning_registers", "minsnap_solve_bc.o", "boundary-solve", ("minsnap_solve_bc_kernel",), 256, extra=1),
+    # plans from given durations, the snap cost, the duration optimisation's bookkeeping: loops over a mission's segments that keep
+    # no per-segment arrays; at least four waves per SIMD (built: the cost kernel 64, the others 10 .. 40; two row-count variants)
+    Budget("timeopt_kernels", "minsnap_timeopt.o", "time-optimisation",
+           ("row_counts_t_kernel", "plan_t_commit_kernel", "minsnap_cost_kernel", "timeopt_expand_kernel", "timeopt_init_kernel",
+            "timeopt_probe_kernel", "timeopt_direction_kernel", "timeopt_candidate_kernel", "timeopt_select_kernel"), 128, extra=1),
+    # the fleet's separation audit: the pair kernel's 48 KB LDS tile admits three workgroups per CU, so three waves per SIMD; its
+    # two coefficient sets are indexed by constants only (built: 164, the pre-pass 14, the merge 20)
+    Budget("separation_kernels", "minsnap_separation.o", "separation",
+           ("separation_prepass_kernel", "minsnap_separation_kernel", "separation_merge_kernel"), 168),
+    # the audit's conflict list: the discovery and the measure keep the 48 KB tile (three workgroups per CU, <= 168); the
+    # pre-pass, the counts (32 B for their scan) and the list run eight waves per SIMD (<= 64)
+    Budget("conflict_kernels", "minsnap_conflicts.o", "conflict-list",
+           ("conflict_prepass_kernel", "conflict_discover_kernel", "conflict_count_kernel", "conflict_list_kernel", "conflict_measure_kernel"),
+           FROM_LDS),
+    # start delays that clear the audit: the decision kernel's 48 KB tile plus 1 KB of granted starts, three workgroups per CU
+    # (built: 145, the pre-pass 14)
+    Budget("stagger_kernels", "minsnap_stagger.o", "stagger", ("stagger_prepass_kernel", "minsnap_stagger_kernel"), 168),
+    # start delays as a leading hold segment: plain copies, eight waves per SIMD (built: 24 each)
+    Budget("delay_kernels", "minsnap_delay.o", "delay", ("delay_counts_kernel", "minsnap_delay_kernel"), 64),
+    # missions selected and reordered, priorities into a within-group order: two plain copies and a count over 2 KB LDS tiles
+    # of keys, eight waves per SIMD (built: 24, 28 and 18)
+    Budget("take_kernels", "minsnap_take.o", "take", ("take_counts_kernel", "minsnap_take_kernel", "fleet_order_kernel"), 64),
+    # the separation the fleet flew, from a state log: the 48 KB tile like the plan audit's (built: 143, the merge 18)
+    Budget("flown_separation_kernels", "flown_separation.o", "flown-separation", ("flown_separation_kernel", "flown_merge_kernel"), 168),
+    # the conflict list of a flight: the discovery keeps the 48 KB tile (built: 114); the measure keeps 48 log values per lane
+    # in flight and is launched for four waves per SIMD (`__launch_bounds__(256, 4)`; built: 112); the counts and the list of
+    # conflict_csr.h run eight (built: 24 each, as in minsnap_conflicts.o)
+    Budget("flown_conflict_kernels", "flown_conflicts.o", "flown-conflict-list",
+           ("flown_discover_kernel", "conflict_count_kernel", "conflict_list_kernel", "flown_measure_kernel"),
+           {"flown_discover_kernel": 168, "conflict_count_kernel": 64, "conflict_list_kernel": 64, "flown_measure_kernel": 128}),
+    # the plan audit of a flight: the streaming kernel is launched for four waves per SIMD (`__launch_bounds__(256, 4)`: one
+    # workgroup per SIMD keeps 26 row loads per wavefront in flight; built: 82, the merge 44)
+    Budget("flown_audit_kernels", "flown_audit.o", "flown-audit", ("flown_audit_kernel", "flown_audit_merge_kernel"), 128),
+    # offset layers that clear the audit, and the offset transform (built: the decision kernel 50192 B of LDS -- the 48 KB tile,
+    # 1 KB of granted layers, two words -- hence three workgroups per CU and <= 168, at 137; the pre-pass and the transform no
+    # LDS, hence eight and <= 64, at 14 and 21)
+    Budget("layer_kernels", "minsnap_layer.o", "layer", ("layer_prepass_kernel", "minsnap_layer_kernel", "minsnap_shift_kernel"), FROM_LDS),
+    # the same search refusing layers that put a mission into a cuboid, the two instantiations with cuboids (built: 50976 B of
+    # LDS -- 768 B of cuboids, two more words -- hence still three workgroups per CU, at 142; the pre-pass 14)
+    Budget("layer_obs_kernels", "minsnap_layer_obs.o", "obstacle-aware layer", ("layer_prepass_kernel", "minsnap_layer_kernel"), FROM_LDS),
+)
+COUNTED = ("rollout_registers", "planning_registers")      # `run_all` reports these as a number of kernels, the others as {kernel: VGPRs}
+
+# The object files that have no budget, and why not.
+UNBUDGETED = {
+    "control_probe.o": "the single-tick kernels of the host-owned loops, the heading self-check and measurement probes: off the flagship path, never given a limit",
+    "minsnap_first_yaw.o": "one kernel, a mission's first heading without rows: one short pass per plan, never given a limit",
+    "minsnap_obstacles.o": "the obstacle loop's scan, count and scatter: never given a limit",
+    "minsnap_retime.o": "the retiming factors and a fill: never given a limit",
+    "minsnap_sample.o": "the sampler before the streaming one and the yaw scan: kept for small batches, never given a limit",
+    "minsnap_solve.o": "row offsets, row counts, the plan commit and the first solve kernel: bookkeeping, never given a limit",
+    "rrt_star.o": "one wavefront per problem with the tree in LDS: its occupancy is set by LDS, never given a register limit",
+    "uavac_api.o": "host code only: the context and the C ABI's entry points",
+    "uavac_comm.o": "host code only: the multi-GPU gather over RCCL",
+}
+
+
+def vgpr_limit(rule, k: Kernel):
+    """The most vector registers the kernel `k` may take under the limit rule of a BUDGETS row, or a str that says why it has none."""
+    if callable(rule):
+        return rule(*template_args(k.name))
+    if isinstance(rule, dict):
+        mine = [limit for name, limit in rule.items() if name in k.name]
+        return min(mine) if mine else "no limit listed for it"
+    if rule is FROM_LDS:
+        lds = k.group_segment_fixed_size
+        waves = min(8, LDS_BYTES_PER_CU // lds) if lds else 8
+        if "minsnap_layer_kernel" in k.name and waves < 3:
+            return f"{lds} bytes of LDS: fewer than three workgroups per CU"
+        return VGPRS_AT_WAVES_PER_SIMD.get(waves, 0)           # (a workgroup that does not fit a CU at all: limit 0)
+    return rule
+
+
+def check_budget(row: Budget, kernels):
+    """Apply one row of BUDGETS to the kernel records of its object file(s).  Raises RuntimeError naming every kernel outside
+    the row; returns the records the row speaks of."""
+    mine = [k for k in kernels if any(name in k.name for name in row.kernels)] if row.at_least else list(kernels)
+    bad = []
+    for k in mine:
+        limit = vgpr_limit(row.limit, k)
+        if isinstance(limit, str):
+            bad.append((k.name[:90], limit))
+        elif k.vgpr_count > limit or k.vgpr_spill_count:
+            bad.append((k.name[:90], k.vgpr_count, k.vgpr_spill_count, limit))
+        if row.scratch_free and k.private_segment_fixed_size:
+            bad.append((k.name[:90], f"{k.private_segment_fixed_size} private-segment bytes"))
+    missing = [] if row.at_least else [name for name in row.kernels if not any(name in k.name for k in mine)]
+    short = len(mine) < row.at_least if row.at_least else len(mine) != len(row.kernels) + row.extra
+    if bad or missing or short:
+        raise RuntimeError(f"{row.noun} kernels outside their budgets (name, VGPRs, spills, limit): {bad}; missing: {missing}; {len(mine)} kernels "
+                           f"found in {row.obj} where {'at least ' + str(row.at_least) if row.at_least else len(row.kernels) + row.extra} of "
+                           f"{', '.join(row.kernels)} belong (compiler: {compiler_version()})")
+    return mine
+
+
+def check_budgets(key: str):
+    """Every row of BUDGETS that reports under `key`, on the object files under build/.  Raises RuntimeError like `check_budget`;
+    returns the [Kernel] the rows speak of, None when an object file cannot be read."""
+    found = []
+    for row in (r for r in BUDGETS if r.key == key):
+        read = [read_object(os.path.join(PKG, "build", o)) for o in row.obj.split()]
+        if None in read:
+            return None
+        found += check_budget(row, [k for co in read for k in co["kernels"]])
+    return found
+
+
+def vgprs(kernels):
+    """{kernel name: vector registers} of [Kernel], the form in which `run_all` reports a budget; None stays None."""
+    return None if kernels is None else {k.name: k.vgpr_count for k in kernels}
+
+
+def _triples(kernels):
+    """[(kernel name, vector registers, spills)] of [Kernel]; None stays None."""
+    return None if kernels is None else [k[:3] for k in kernels]
+
+
+# The names by which the host tests (tests/test_*_host.py) and DESIGN.md section 3 know the rows: one-line lookups, nothing else.
+def check_rollout_registers(): return _triples(check_budgets("rollout_registers"))                      # noqa: E704
+def check_planning_registers(): return _triples(check_budgets("planning_registers"))                    # noqa: E704
+def check_timeopt_kernels(): return vgprs(check_budgets("timeopt_kernels"))                             # noqa: E704
+def check_separation_kernels(): return vgprs(check_budgets("separation_kernels"))                       # noqa: E704
+def check_conflict_kernels(): return vgprs(check_budgets("conflict_kernels"))                           # noqa: E704
+def check_stagger_kernels(): return vgprs(check_budgets("stagger_kernels"))                             # noqa: E704
+def check_delay_kernels(): return vgprs(check_budgets("delay_kernels"))                                 # noqa: E704
+def check_take_kernels(): return vgprs(check_budgets("take_kernels"))                                   # noqa: E704
+def check_flown_separation_kernels(): return vgprs(check_budgets("flown_separation_kernels"))           # noqa: E704
+def check_flown_conflict_kernels(): return vgprs(check_budgets("flown_conflict_kernels"))               # noqa: E704
+def check_flown_audit_kernels(): return vgprs(check_budgets("flown_audit_kernels"))                     # noqa: E704
+def check_layer_kernels(): return vgprs(check_budgets("layer_kernels"))                                 # noqa: E704
+def check_layer_obs_kernels(): return vgprs(check_budgets("layer_obs_kernels"))                         # noqa: E704
+TIMEOPT_KERNELS = next(row.kernels for row in BUDGETS if row.key == "timeopt_kernels")
+FLOWN_CONFLICT_KERNELS = next(row.kernels for row in BUDGETS if row.key == "flown_conflict_kernels")
+
+
+def check_inventory():
+    """Every object file under build/ stands in BUDGETS or in UNBUDGETED, and every one listed there was built.  Raises
+    RuntimeError otherwise; returns their number, None without a build directory."""
+    build = os.path.join(PKG, "build")
+    if not os.path.isdir(build):
+        return None
+    have = {f for f in os.listdir(build) if f.endswith(".o")}
+    listed = {o for row in BUDGETS for o in row.obj.split()} | set(UNBUDGETED)
+    if have != listed:
+        raise RuntimeError(f"object files under build/ that neither BUDGETS nor UNBUDGETED of uav_ac/_buildcheck.py lists: {sorted(have - listed)}; "
+                           f"listed there but not built: {sorted(listed - have)}")
+    return len(have)
+
+
+# ------------------------------------------------------------------------------------------------ the prefetches
 def _successors(ins):
     """Successor indices of every instruction of a kernel (fall-through and branch targets); raises on a branch the disassembly
     gives no target for."""
@@ -404,8 +364,7 @@ def check_row_prefetch(obj: str = None, scored: bool = False):
                 i += 5
             else:
                 i += 1
-        poly = re.search(r"control_rollout_kernelILi\d+ELi\d+ELb[01]ELb[01]ELb[01]ELb([01])E", name).group(1) == "1"
-        if poly:                                   # (its coefficient loads look alike; the compiler issues and waits for those itself)
+        if template_args(name)[5]:                 # POLY (its coefficient loads look alike; the compiler issues and waits for those itself)
             continue
         checked += 1
         if len(groups) != 2 or len({g for _, g in groups}) != 1 or len(groups[0][1]) != 20:
@@ -451,7 +410,7 @@ def check_heading_prefetch(obj: str = None):
     prefetch, same answer: in every sampler variant, between each group of ten such loads and the next `s_waitcnt ... lgkmcnt(0)` no
     instruction touches a destination register and no branch intervenes.  Raises RuntimeError otherwise; returns the number of groups
     checked, None when the object file cannot be read."""
-    kernels = _disassemble(obj or os.path.join(PKG, "build", "minsnap_sample_stream.o"))
+    kernels = _disassemble_cfg(obj or os.path.join(PKG, "build", "minsnap_sample_stream.o"))
     if kernels is None:
         return None
     groups, bad = 0, []
@@ -502,52 +461,39 @@ STAMP = os.path.join(PKG, "lib", "libuavac.buildcheck.json")
 
 def run_all(verbose: bool = False, write_stamp: bool = True) -> dict:
     """EVERY build check, for every place that builds the library (`__graft_entry__.build()`, the autobuild of
-    `uav_ac._native.lib()`, `make check`): the rollout kernels' register budget, the row prefetch and the sampler's heading
-    prefetch in the disassembly, no diagnostic symbol, the planning kernels' budgets.  A check that cannot run (no object files,
-    no LLVM tools) is a FAILURE here: the output-only asm operands of row_issue / HeadingFromLds are only as safe as these
-    checks, so a build they did not see must not pass for one they did.  Raises RuntimeError; on success writes
+    `uav_ac._native.lib()`, `make`): every object file under build/ listed, every row of BUDGETS, then the row prefetch and the
+    sampler's heading prefetch in the disassembly and no diagnostic symbol.  A check that cannot run (no object files, no LLVM
+    tools) is a FAILURE here: the output-only asm operands of row_issue / HeadingFromLds are only as safe as these checks, so a
+    build they did not see must not pass for one they did.  Raises RuntimeError; on success writes
     lib/libuavac.buildcheck.json -- the library's sha256, its uavac_build_info() and the compiler the checks saw -- which
     travels with the library (tests/test_gpu_round6.py compares it with the library the GPU process loaded)."""
     import ctypes
     import json
-    result = {}
-    steps = (("rollout_registers", check_rollout_registers, lambda r: f"{len(r)} rollout kernels, at most {max(v for _, v, _ in r)} VGPRs, no spills"),
-             ("row_prefetch", check_row_prefetch, lambda r: f"row prefetch of {r} row-fed rollout kernels verified on the control-flow graph of the disassembly"),
-             ("scored_row_prefetch", lambda: check_row_prefetch(scored=True),
-              lambda r: f"row prefetch of {r} row-fed scored rollout kernels verified the same way"),
-             ("heading_prefetch", check_heading_prefetch, lambda r: f"{r} coefficient prefetches of the streaming sampler verified in the disassembly"),
-             ("no_diagnostics", check_no_diagnostics, lambda r: "no diagnostic symbol exported"),
-             ("planning_registers", check_planning_registers, lambda r: f"{len(r)} sampler / solve kernels inside their register budgets, no spills"),
-             ("timeopt_kernels", check_timeopt_kernels,
-              lambda r: f"{len(r)} time-optimisation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
-             ("separation_kernels", check_separation_kernels,
-              lambda r: f"{len(r)} separation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
-             ("conflict_kernels", check_conflict_kernels,
-              lambda r: f"{len(r)} conflict-list kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
-             ("stagger_kernels", check_stagger_kernels,
-              lambda r: f"{len(r)} stagger kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
-             ("delay_kernels", check_delay_kernels,
-              lambda r: f"{len(r)} delay kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
-             ("take_kernels", check_take_kernels,
-              lambda r: f"{len(r)} take kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
-             ("flown_separation_kernels", check_flown_separation_kernels,
-              lambda r: f"{len(r)} flown-separation kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
-             ("flown_conflict_kernels", check_flown_conflict_kernels,
-              lambda r: f"{len(r)} flown-conflict-list kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
-             ("flown_audit_kernels", check_flown_audit_kernels,
-              lambda r: f"{len(r)} flown-audit kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
-             ("layer_kernels", check_layer_kernels,
-              lambda r: f"{len(r)} layer kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"),
-             ("layer_obs_kernels", check_layer_obs_kernels,
-              lambda r: f"{len(r)} obstacle-aware layer kernels, at most {max(r.values())} VGPRs, no spills, no scratch memory"))
-    for key, fn, say in steps:
-        r = fn()
+
+    def ran(key, r, said):
         if r is None:
             raise RuntimeError(f"build check '{key}' could not run (object files under {PKG}/build or the LLVM tools under {LLVM_BIN} are "
                                "missing): the library would ship unchecked")
-        result[key] = len(r) if isinstance(r, list) else r      # (the time-optimisation, separation, stagger, delay and flown-separation checks: their {kernel: VGPRs} records)
         if verbose:
-            print(f"build: {say(r)}")
+            print(f"build: {said(r)}")
+        return r
+
+    ran("inventory", check_inventory(), lambda r: f"{r} object files, each with a budget or a reason to have none")
+    budgets = {}
+    for key in dict.fromkeys(row.key for row in BUDGETS):
+        rows = [row for row in BUDGETS if row.key == key]
+        found = ran(key, check_budgets(key), lambda r: f"{len(r)} {' / '.join(row.noun for row in rows)} kernels, at most {max(k.vgpr_count for k in r)} "
+                    f"VGPRs, no spills{', no scratch memory' if all(row.scratch_free for row in rows) else ''}")
+        budgets[key] = len(found) if key in COUNTED else vgprs(found)
+    result = {"rollout_registers": budgets.pop("rollout_registers"),
+              "row_prefetch": ran("row_prefetch", check_row_prefetch(),
+                                  lambda r: f"row prefetch of {r} row-fed rollout kernels verified on the control-flow graph of the disassembly"),
+              "scored_row_prefetch": ran("scored_row_prefetch", check_row_prefetch(scored=True),
+                                         lambda r: f"row prefetch of {r} row-fed scored rollout kernels verified the same way"),
+              "heading_prefetch": ran("heading_prefetch", check_heading_prefetch(),
+                                      lambda r: f"{r} coefficient prefetches of the streaming sampler verified in the disassembly"),
+              "no_diagnostics": ran("no_diagnostics", check_no_diagnostics(), lambda r: "no diagnostic symbol exported"),
+              **budgets}
     lib_path = os.path.join(PKG, "lib", "libuavac.so")
     fn = ctypes.CDLL(lib_path).uavac_build_info
     fn.restype = ctypes.c_char_p
