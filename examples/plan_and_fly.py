@@ -9,7 +9,8 @@
 Both planners see the obstacles inflated by `clearance`; the flight is tested against the true ones.
 `--retime` (opt-in) puts a step between 3 and 4: the missions whose plan asks for more than the control law gives (the vehicle's
 speed, climb, descent and horizontal-acceleration limits) are slowed down by exactly the factor they need (Engine.retime); the
-curves stay where the obstacle loop put them.
+curves stay where the obstacle loop put them.  Either way the plan that is flown is asked what it demands of the vehicle (Engine.demand):
+how many missions need a bank beyond `max_tilt`, which the control law clips and retiming does not bound.
 
     python examples/plan_and_fly.py [B] [--retime]
 """
@@ -23,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "uav-autonomous-control_amd")]
 
 from uav_ac.fleet import Engine                                   # noqa: E402
+from uav_ac.scoring import demand_feasibility                     # noqa: E402
 from uav_ac.simulation.mujoco_sim import MujocoSimulation         # noqa: E402
 
 
@@ -65,11 +67,12 @@ def main(B: int = 256, velocity: float = 2.0, seed: int = 0, clearance: float = 
     miss = (fleet.X[0:3] - goal_of).norm(dim=0).cpu().numpy()
     collided = fleet.collided.cpu().numpy().astype(bool)
     arrived = (miss < 0.5) & ~collided & plan.converged
+    over_tilt = int((~demand_feasibility(eng.demand(plan))["tilt_ok"]).sum())   # (of the plan that was flown: after --retime too)
     print(f"{B} vehicles: RRT* found {len(ok)} paths in {1e3 * (t1 - t0):.0f} ms (mean {res.best_len[ok].mean():.1f} nodes, "
           f"{np.mean([len(w) for w in waypoints]):.1f} after thinning, {1e3 * (t2 - t1):.0f} ms); "
           f"min-snap around obstacles {1e3 * (t3 - t2):.0f} ms ({plan.total_rows} rows, {int((~plan.converged).sum())} not converged){retimed}; "
-          f"flight {1e3 * (t4 - t3):.0f} ms: {int(arrived.sum())} arrived within 0.5 m, {int(collided.sum())} touched an obstacle")
-    return {"found": len(ok), "arrived": int(arrived.sum()), "collided": int(collided.sum()), "flown": len(ok)}
+          f"{over_tilt} missions demand a bank beyond max_tilt; flight {1e3 * (t4 - t3):.0f} ms: {int(arrived.sum())} arrived within 0.5 m, {int(collided.sum())} touched an obstacle")
+    return {"found": len(ok), "arrived": int(arrived.sum()), "collided": int(collided.sum()), "flown": len(ok), "over_tilt": over_tilt}
 
 
 if __name__ == "__main__":

@@ -308,6 +308,46 @@ int uavac_minsnap_first_yaw_dev(uavac_ctx *ctx, const double *coeffs, const int3
 int uavac_minsnap_audit_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                             double dt, const double *cuboids, int n_cuboids, double *audit, int32_t *hit_rows, int32_t *first_hit);
 
+/* PLAN DEMAND: what a solved plan ASKS OF THE VEHICLE, per mission, WITHOUT sampling its rows -- the plan-side counterpart of
+ * uavac_flown_audit_dev's bank_x / bank_y / body_rate / clearance.  The control law clips the bank command (csrc/control_law.h: bxc =
+ * clamp(acx / acc_z, +-max_tilt)), which on a perfectly tracked plan is |ax| / |a - g e3|: it depends on the vertical acceleration of
+ * the same row, binds long before max_horiz_accel does, and the law divides by g - az, which a fast plan drives through zero.
+ * uavac_minsnap_audit_dev reports none of this.  One kernel walks the rows as the plan audit does (csrc/minsnap_demand.hip) and stores
+ * none of them.  coeffs / seg_rows / seg_offsets / B / m / dt as in uavac_minsnap_audit_dev (seg_offsets NULL = uniform, otherwise
+ * ragged and clamped); g: the gravitational acceleration (uavac_vehicle.g), m/s^2.
+ * PER ROW, from the sampler's position p and acceleration a (the values uavac_minsnap_sample_dev writes) and the jerk j that
+ * uavac_minsnap_sample_derivs_dev writes, bit for bit; every product, sum, quotient and fmax is ONE rounded operation (no fused
+ * multiply-add), in exactly this order:
+ *     fz  = g - az                                        (NED: hover has fz = g)
+ *     n2  = (ax * ax + ay * ay) + fz * fz                 specific thrust, squared
+ *     bx2 = n2 > 0 ? (ax * ax) / n2 : 0                   by2 likewise with ay
+ *     jj  = (jx * jx + jy * jy) + jz * jz
+ *     jf  = (jx * ax + jy * ay) - jz * fz
+ *     w2  = n2 > 0 ? fmax(jj - (jf * jf) / n2, 0) / n2 : 0      the roll / pitch rate the curve demands, squared (no yaw rate)
+ *     inverted = fz <= 0                                  the row asks for thrust downward
+ *     per cuboid: ex = px < xmin ? xmin - px : (px > xmax ? px - xmax : 0), ey, ez likewise; d2 = (ex * ex + ey * ey) + ez * ez
+ * The maxima and minima are taken of these SQUARES and one correctly rounded sqrt comes last.
+ *   demand  [UAVAC_DEMAND_ROWS][B] f64:   0 the mission's row total      3 sqrt(max bx2)  the bank about x the plan demands
+ *                                          1 sqrt(max n2)  m/s^2          4 sqrt(max by2)
+ *                                          2 sqrt(min n2)                 5 sqrt(max w2)   rad/s
+ *   idemand [UAVAC_IDEMAND_ROWS][B] i32:  0 the number of inverted rows, 1 the mission-local index of the first one (-1: none)
+ *   cuboids [n_cuboids][6] xmin xmax ymin ymax zmin zmax, 0 <= n_cuboids <= UAVAC_AUDIT_MAX_CUBOIDS
+ *   clearance     [n_cuboids][B] f64 = sqrt(min d2): 0 when a sample lies inside the cuboid or on a face
+ *   clearance_row [n_cuboids][B] i32: the mission-local index of the FIRST row that attains it
+ * n_cuboids == 0: cuboids, clearance and clearance_row must all be NULL.
+ * The reductions are max, min, integer add and the lexicographic minimum of (d2, row): exact and order-free, so the outputs depend
+ * neither on the launch shape nor on the batch split (option "audit_lanes": 16 or 64 lanes per mission, same results).  They equal
+ * what NumPy computes from the sampled rows and jerk, bit for bit (uav_ac/scoring.py demand_from_rows).
+ * A mission with ANY non-finite sample (position, velocity, acceleration or jerk), and a mission without rows, reports NaN in rows
+ * 1-5, clearance NaN, every index -1 and 0 inverted rows: a singular plan never looks feasible.
+ * UAVAC_EINVAL before anything is enqueued: n_cuboids outside 0 .. UAVAC_AUDIT_MAX_CUBOIDS, a NULL where a pointer is required (or
+ * a pointer where n_cuboids == 0 requires NULL), B < 1, m outside 1 .. UAVAC_MAX_SEGMENTS, dt or g not positive and finite. */
+#define UAVAC_DEMAND_ROWS 6
+#define UAVAC_IDEMAND_ROWS 2
+int uavac_minsnap_demand_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                             double dt, double g, const double *cuboids, int n_cuboids, double *demand, int32_t *idemand,
+                             double *clearance, int32_t *clearance_row);
+
 /* SEPARATION AUDIT: the fleet's audit against itself.  For every mission of a GROUP of missions that share an airspace: the closest
  * approach to any other mission of the group, to which one and when; how many others come inside a protection radius and when the
  * first one does -- from coefficients and row counts alone (csrc/minsnap_separation.hip, csrc/fleet_clock.h): no row is written, nothing is read back,

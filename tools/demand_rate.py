@@ -1,0 +1,183 @@
+"""The plan demand (`uavac_minsnap_demand_dev`, `Engine.demand`) against its yardstick, `Engine.audit` on the same plan -- the same walk
+over the same rows with the cheaper arithmetic --, and against the only other route to the same answers: sample the rows and the jerk,
+then torch reductions.  B = 65 536 missions of 8 segments (the bench's generator), velocity 3, dt 0.01, with 0, 4 and 16 cuboids (the four
+of the laboratory course; for 16, twelve more boxes of 0.6 m around waypoints the missions pass).
+
+    demand_rate.py [OUT.jsonl] [rounds]
+
+The two routes must give the SAME answers (every output, bit for bit) before anything is timed.  hipEvents around each arm, warm-up first,
+the arms interleaved over rounds in one process; per cuboid count one JSON line, APPENDED to OUT.jsonl: median (min .. max) ms of the call
+at 16 and at 64 lanes per mission, of the audit at both, and of the rows route; and the ratios call / audit (same lanes) and rows route /
+call, each formed per round, with median, minimum and maximum.
+
+The rows route, per call: `uavac_minsnap_sample_derivs_dev` through `Engine.sample_derivatives` (rows, jerk and snap of every mission),
+then every product, sum and quotient of include/uavac.h as an eager torch operation of its own (so the bits are the kernel's), scatter
+amax / amin over a row -> mission index built once outside the timing, and per cuboid the three selects, d^2, its minimum per mission and
+the lowest row that attains it."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "uav-autonomous-control_amd")]
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from bench import missions  # noqa: E402
+from uav_ac import _native as nat  # noqa: E402
+from uav_ac.fleet import Engine  # noqa: E402
+
+LAB_AABBS = np.array([[3.7, 4.3, 4.0, 10.0, -3.4, -2.8], [10.7, 11.3, 4.0, 10.0, -2.2, 0.0], [13.3, 14.7, 6.3, 7.7, -6.0, 0.0],
+                      [20.2, 20.8, 4.0, 10.0, -3.3, -2.7]])
+B, M, VEL, DT = 65536, 8, 3.0, 0.01
+CUBOIDS = (0, 4, 16)
+NO_ROW = 1 << 40
+
+
+def timed(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def rows_route(eng, plan, g, cub, mission, local):
+    """-> (demand (6, B), idemand (2, B), clearance (n, B), clearance_row (n, B)) from freshly sampled rows and jerk; `cub`: n lists of six
+    numbers on the host (or None); `mission` (N,) the mission of every row, `local` (N,) its index within that mission."""
+    jerk, _ = eng.sample_derivatives(plan)
+    t, dev = plan.traj, plan.traj.device
+    n_missions = plan.B
+    inf, nan = float("inf"), float("nan")
+    px, py, pz, ax, ay, az = t[:, 0], t[:, 1], t[:, 2], t[:, 6], t[:, 7], t[:, 8]
+    jx, jy, jz = jerk.unbind(1)
+    zero = torch.zeros_like(ax)
+    fz = g - az
+    xx, yy = ax * ax, ay * ay
+    n2 = (xx + yy) + fz * fz
+    some = n2 > 0.0
+    over = torch.where(some, n2, torch.ones_like(n2))
+    bx2, by2 = torch.where(some, xx / over, zero), torch.where(some, yy / over, zero)
+    jj = (jx * jx + jy * jy) + jz * jz
+    jf = (jx * ax + jy * ay) - jz * fz
+    w2 = torch.where(some, torch.fmax(jj - (jf * jf) / over, zero) / over, zero)
+    inverted = fz <= 0.0
+    finite = torch.isfinite(t[:, 0:9]).all(dim=1) & torch.isfinite(jerk).all(dim=1)
+
+    def per_mission(values, how, start):
+        out = torch.full((n_missions,), start, dtype=values.dtype, device=dev)
+        return out.scatter_reduce_(0, mission, values, how, include_self=True)
+    lengths = plan.row_offsets[1:] - plan.row_offsets[:-1]
+    good = (per_mission((~finite).to(torch.int64), "amax", 0) == 0) & (lengths > 0)
+    bad_f = torch.full((n_missions,), nan, dtype=torch.float64, device=dev)
+    demand = torch.empty((nat.DEMAND_ROWS, n_missions), dtype=torch.float64, device=dev)
+    demand[0] = lengths
+    for row, (values, how, start) in enumerate(((n2, "amax", -inf), (n2, "amin", inf), (bx2, "amax", -inf), (by2, "amax", -inf),
+                                                (w2, "amax", -inf)), start=1):
+        demand[row] = torch.where(good, torch.sqrt(per_mission(values, how, start)), bad_f)
+    count = per_mission(inverted.to(torch.int64), "sum", 0)
+    first = per_mission(torch.where(inverted, local, torch.full_like(local, NO_ROW)), "amin", NO_ROW)
+    minus = torch.full((n_missions,), -1, dtype=torch.int64, device=dev)
+    idemand = torch.stack([torch.where(good, count, torch.zeros_like(count)), torch.where(good & (first != NO_ROW), first, minus)]).to(torch.int32)
+    n = 0 if cub is None else len(cub)
+    clearance = torch.empty((n, n_missions), dtype=torch.float64, device=dev)
+    clearance_row = torch.empty((n, n_missions), dtype=torch.int32, device=dev)
+    for c in range(n):
+        x0, x1, y0, y1, z0, z1 = cub[c]
+        ex = torch.where(px < x0, x0 - px, torch.where(px > x1, px - x1, zero))
+        ey = torch.where(py < y0, y0 - py, torch.where(py > y1, py - y1, zero))
+        ez = torch.where(pz < z0, z0 - pz, torch.where(pz > z1, pz - z1, zero))
+        d2 = (ex * ex + ey * ey) + ez * ez
+        least = per_mission(d2, "amin", inf)
+        at = per_mission(torch.where(d2 == least[mission], local, torch.full_like(local, NO_ROW)), "amin", NO_ROW)
+        clearance[c] = torch.where(good, torch.sqrt(least), bad_f)
+        clearance_row[c] = torch.where(good, at, minus)
+    return demand, idemand, clearance, clearance_row
+
+
+def same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and bool((a.view(torch.int64) == b.view(torch.int64)).all() if a.dtype == torch.float64
+                                                               else (a == b).all())
+
+
+def spread(values, digits=4):
+    return {"median": round(float(np.median(values)), digits), "min": round(float(min(values)), digits), "max": round(float(max(values)), digits)}
+
+
+def main():
+    out_path = sys.argv[1] if len(sys.argv) > 1 else None
+    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    eng = Engine("cuda:0")
+    dev = eng.device
+    box = eng.ctx.device_identity()
+    g = float(nat.Vehicle.default().g)
+    wps = missions(B, M, 0, B)
+    plan = eng.plan(wps, VEL, DT)                     # with a row buffer: the rows route samples into it
+    free = eng.plan(wps, VEL, DT, rows=False)
+    N = plan.total_rows
+    lengths = plan.row_offsets[1:] - plan.row_offsets[:-1]
+    mission = torch.repeat_interleave(torch.arange(B, device=dev), lengths)
+    local = torch.arange(N, device=dev) - plan.row_offsets[:-1][mission]
+    at = np.asarray(wps, dtype=np.float64)[:: B // 12, M // 2][:12]      # a middle waypoint of twelve missions
+    more = np.stack([at[:, 0] - 0.3, at[:, 0] + 0.3, at[:, 1] - 0.3, at[:, 1] + 0.3, at[:, 2] - 0.3, at[:, 2] + 0.3], axis=1)
+    sixteen = np.concatenate([LAB_AABBS, more])
+    lines = []
+    for n in CUBOIDS:
+        cub_host = None if n == 0 else sixteen[:n].tolist()
+        cub = None if n == 0 else torch.as_tensor(sixteen[:n]).to(dev)
+
+        def demand(lanes):
+            eng.ctx.set_option("audit_lanes", lanes)
+            return eng.demand(free, cub)
+
+        def audit(lanes):
+            eng.ctx.set_option("audit_lanes", lanes)
+            return eng.audit(free, cub)
+
+        # the two routes agree before anything is timed: every output, bit for bit, at both lane counts
+        want = rows_route(eng, plan, g, cub_host, mission, local)
+        names = ("demand", "idemand", "clearance", "clearance_row")
+        differ = []
+        for lanes in (16, 64):
+            d = demand(lanes)
+            got = (d.block, torch.stack([d.inverted_rows, d.first_inverted]), d.clearance, d.clearance_row)
+            torch.cuda.synchronize()
+            differ += [f"{name} at {lanes} lanes" for name, x, w in zip(names, got, want) if not same_bits(x, w)]
+        print(json.dumps({"cuboids": n, "outputs that differ between the two routes": differ, "rows": int(N),
+                          "missions that demand more than max_tilt": int(((d.bank_x > 0.7) | (d.bank_y > 0.7)).sum()),
+                          "missions inside a cuboid": int((d.clearance == 0).any(dim=0).sum()) if n else 0,
+                          "inverted rows": int(d.inverted_rows.sum()), "peak bank": float(torch.maximum(d.bank_x, d.bank_y).max()),
+                          "least thrust m/s^2": float(d.thrust_min.min()), "peak rate rad/s": float(d.body_rate.max())}), flush=True)
+        assert not differ, differ
+        del want, got, d
+
+        arms = {"demand16": (lambda: demand(16), 10), "audit16": (lambda: audit(16), 10), "demand64": (lambda: demand(64), 10),
+                "audit64": (lambda: audit(64), 10), "rows": (lambda: rows_route(eng, plan, g, cub_host, mission, local), 1)}
+        for fn, _ in arms.values():                      # warm-up of every arm
+            fn()
+        torch.cuda.synchronize()
+        times = {name: [] for name in arms}
+        for _ in range(rounds):
+            for name, (fn, reps) in arms.items():
+                times[name].append(timed(fn, reps))
+        eng.ctx.set_option("audit_lanes", 16)
+        ratio = lambda a, b: [x / y for x, y in zip(times[a], times[b])]      # noqa: E731  (formed per round)
+        line = {"B": B, "m": M, "rows": int(N), "cuboids": n, "rounds": rounds, "outputs_equal_bit_for_bit": True,
+                "demand_ms": {"lanes16": spread(times["demand16"]), "lanes64": spread(times["demand64"])},
+                "audit_ms": {"lanes16": spread(times["audit16"]), "lanes64": spread(times["audit64"])},
+                "rows_route_ms": spread(times["rows"], 2),
+                "demand_over_audit": {"lanes16": spread(ratio("demand16", "audit16"), 3), "lanes64": spread(ratio("demand64", "audit64"), 3)},
+                "rows_route_over_demand": spread(ratio("rows", "demand16"), 1),
+                "rows_per_s": round(N / (float(np.median(times["demand16"])) * 1e-3), 0), "box": box}
+        lines.append(json.dumps(line))
+        print(lines[-1], flush=True)
+        torch.cuda.empty_cache()
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "a") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -838,6 +838,21 @@ int uavac_minsnap_audit_dev(uavac_ctx *ctx, const double *coeffs, const int32_t 
     return uavac_launch_audit(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, cuboids, n_cuboids, audit, hit_rows, first_hit);
 }
 
+int uavac_minsnap_demand_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                             double dt, double g, const double *cuboids, int n_cuboids, double *demand, int32_t *idemand,
+                             double *clearance, int32_t *clearance_row) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
+    if (!seg_rows || !demand || !idemand) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_dt_positive(ctx, dt)) return rc;
+    if (!std::isfinite(g) || !(g > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "g must be finite and > 0");
+    if (int rc = check_n_cuboids(ctx, n_cuboids)) return rc;
+    if (n_cuboids == 0 ? (cuboids || clearance || clearance_row) : (!cuboids || !clearance || !clearance_row))
+        return uavac_fail(ctx, UAVAC_EINVAL, "cuboids, clearance and clearance_row go with n_cuboids > 0: all three or none");
+    return uavac_launch_demand(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, g, cuboids, n_cuboids, demand, idemand, clearance,
+                               clearance_row);
+}
+
 // what the fleet's pair calls (separation, stagger, layer) refuse alike, in this order; `outputs`: every output pointer of the call is there
 static int check_pair_args(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, int B, int m, double dt, const int64_t *group_offsets,
                            int G, double radius, bool outputs) {

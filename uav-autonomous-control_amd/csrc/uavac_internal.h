@@ -241,6 +241,11 @@ int uavac_launch_first_yaw(uavac_ctx *ctx, const double *coeffs, const int32_t *
 // hit_rows / first_hit [n_cuboids][B]
 int uavac_launch_audit(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                        double dt, const double *cuboids, int n_cuboids, double *audit, int32_t *hit_rows, int32_t *first_hit);
+// what a plan asks of the vehicle, per mission, without the rows (minsnap_demand.hip): demand [UAVAC_DEMAND_ROWS][B], idemand
+// [UAVAC_IDEMAND_ROWS][B], and per cuboid clearance / clearance_row [n_cuboids][B]
+int uavac_launch_demand(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
+                        double g, const double *cuboids, int n_cuboids, double *demand, int32_t *idemand, double *clearance,
+                        int32_t *clearance_row);
 // the fleet's audit against itself (minsnap_separation.hip): sep [B], isep [UAVAC_SEP_ROWS][B]; scratch from the ctx arena
 int uavac_launch_separation(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
                             const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double *sep, int32_t *isep);

@@ -157,6 +157,9 @@ BUDGETS = (
            lambda ragged, park_lds, n, nreg: 512 if nreg == 5 else 256, at_least=20, scratch_free=False),
     # the plan audit: three waves per SIMD (built: 100 .. 146)
     Budget("planning_registers", "minsnap_audit.o", "plan-audit", ("minsnap_audit_kernel",), 168, at_least=4, scratch_free=False),
+    # the plan demand: the audit's budget -- with sixteen cuboids 49 920 B of LDS, three workgroups per CU, hence three waves
+    # per SIMD (built: 122 .. 136, no scratch memory)
+    Budget("planning_registers", "minsnap_demand.o", "plan-demand", ("minsnap_demand_kernel",), 168, at_least=4),
     # the solve with boundary derivatives, uniform and ragged: two waves per SIMD (built: 211 / 217)
     Budget("planning_registers", "minsnap_solve_bc.o", "boundary-solve", ("minsnap_solve_bc_kernel",), 256, extra=1),
     # plans from given durations, the snap cost, the duration optimisation's bookkeeping: loops over a mission's segments that keep

@@ -12,7 +12,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as nat
-from .plans import (ConflictList, DeconflictResult, FlightAudit, LayerResult, Plan, PlanAudit, RaggedBatch, RaggedPlan,  # noqa: F401
+from .plans import (ConflictList, DeconflictResult, FlightAudit, LayerResult, Plan, PlanAudit, PlanDemand, RaggedBatch, RaggedPlan,  # noqa: F401
                     RetimeResult, RRTDeviceBatch, Segments, SeparationAudit, StaggerResult, TimeOptResult, _ptr, segments,
                     uniform_offsets)  # (the plans and result records live in uav_ac/plans.py; every name is re-exported here)
 
@@ -446,6 +446,31 @@ class Engine:
         self.ctx.call("uavac_minsnap_audit_dev", *self._plan_args(plan), _ptr(cub) if n else None, n, _ptr(block),
                       _ptr(hit_rows) if n else None, _ptr(first_hit) if n else None)
         return PlanAudit(*block.unbind(0), hit_rows, first_hit, block)
+
+    def demand(self, plan, obstacles=None, vehicle: Optional[nat.Vehicle] = None) -> PlanDemand:
+        """What the plan asks of the vehicle, per mission, without sampling its rows (`uavac_minsnap_demand_dev`): the largest and the
+        least specific thrust a perfectly tracked plan needs, the bank it needs about each axis -- the bank command the control law
+        clips to `max_tilt`, which `Engine.audit` does not report and `Engine.retime` does not bound --, the roll / pitch rate the curve
+        demands, the rows that ask for thrust downward, and for each cuboid of `obstacles` (as `Engine.audit` takes them, n <= 16) how
+        near the samples pass it and at which row first: the plan-side counterpart of `Engine.flown_audit`'s bank_x, bank_y, body_rate
+        and clearance.  `plan`: what `Engine.audit` takes.  `vehicle`: its `g` is used; None = `uavac_vehicle_default`.
+        -> PlanDemand, bit for bit what NumPy gives on the sampled rows and jerk (`uav_ac.scoring.demand_from_rows`).  Reads
+        coefficients and row counts only, never `plan.traj`; stream-ordered like the other _dev calls, no sync.
+        `uav_ac.scoring.demand_feasibility` turns the result into verdicts, `uav_ac.scoring.audit_gap` sets it beside a flight audit."""
+        torch = self._torch
+        plan = self._coeff_plan(plan)
+        B = int(plan.B)
+        kw = dict(device=self.device)
+        cub, n = (None, 0) if obstacles is None else self._cuboids(obstacles, "demand")
+        g = float((nat.Vehicle.default() if vehicle is None else vehicle).g)
+        block = torch.empty((nat.DEMAND_ROWS, B), dtype=torch.float64, **kw)
+        iblock = torch.empty((nat.IDEMAND_ROWS, B), dtype=torch.int32, **kw)
+        clearance = torch.empty((n, B), dtype=torch.float64, **kw)
+        clearance_row = torch.empty((n, B), dtype=torch.int32, **kw)
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_demand_dev", *self._plan_args(plan), g, _ptr(cub) if n else None, n, _ptr(block), _ptr(iblock),
+                      _ptr(clearance) if n else None, _ptr(clearance_row) if n else None)
+        return PlanDemand(*block.unbind(0), *iblock.unbind(0), clearance, clearance_row, block)
 
     def separation(self, plan, radius: float, groups=None, start_rows=None) -> SeparationAudit:
         """The plan's missions audited against each other (`uavac_minsnap_separation_dev`): per mission the closest approach to any

@@ -204,6 +204,25 @@ class PlanAudit:
 
 
 @dataclass
+class PlanDemand:
+    """What a plan asks of the vehicle, per mission (`Engine.demand`, include/uavac.h uavac_minsnap_demand_dev): device tensors, maxima
+    and minima over exactly the rows the sampler writes -- NaN, and -1 in every index, for a mission with a non-finite sample or
+    without rows.  The thrust columns are SPECIFIC thrust in m/s^2; newtons are `vehicle.mass` times that.
+    `uav_ac.scoring.demand_feasibility` judges it against the vehicle, `uav_ac.scoring.audit_gap` sets it beside a FlightAudit."""
+    rows: "object"           # (B,) f64: the mission's row total
+    thrust_max: "object"     # peak |a - g e3|: the specific thrust a perfectly tracked plan needs
+    thrust_min: "object"     # ... and the least of it (0: a row in free fall)
+    bank_x: "object"         # peak |ax| / |a - g e3|: the bank command that max_tilt clips (control_law.h), as the plan demands it
+    bank_y: "object"         # peak |ay| / |a - g e3|
+    body_rate: "object"      # peak roll / pitch rate the curve demands, rad/s (no yaw rate)
+    inverted_rows: "object"  # (B,) i32: rows that ask for thrust downward (g - az <= 0)
+    first_inverted: "object"  # (B,) i32: the mission-local index of the first of them (-1: none)
+    clearance: "object"      # (n, B) f64: closest approach of a sample to cuboid c (0 inside or on a face)
+    clearance_row: "object"  # (n, B) i32: the mission-local index of the first row that attains it
+    block: "object" = None   # the [DEMAND_ROWS][B] block the six f64 rows above are views of
+
+
+@dataclass
 class SeparationAudit:
     """The fleet's audit against itself (`Engine.separation`, include/uavac.h uavac_minsnap_separation_dev): device tensors, per
     mission over the shared row clock of its group.  An excluded mission (no rows, or a coefficient that is not finite) reports NaN /

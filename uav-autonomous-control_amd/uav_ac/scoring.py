@@ -28,6 +28,9 @@ search when it also refuses layers inside cuboids (uavac_minsnap_layer_obs_dev),
 `shift_coeffs` states the transform that makes granted offsets part of the plan (`Engine.shift`, uavac_minsnap_shift_dev).
 `audit_from_log` is the plan audit of a FLIGHT: the rule of `Engine.flown_audit` (uavac_flown_audit_dev) on a rollout's state log --
 valid ticks, flown peaks, and per cuboid hits and closest approach --, and `flight_feasibility` judges it as `plan_feasibility` judges a plan.
+`demand_from_rows` states what a plan ASKS of the vehicle -- specific thrust, bank, roll / pitch rate, rows that ask for thrust downward,
+and per cuboid the planned clearance: the rule of `Engine.demand` (uavac_minsnap_demand_dev) on sampled rows and jerk --,
+`demand_feasibility` judges it against what the vehicle can give, and `audit_gap` sets it beside the flight audit of the same missions.
 """
 from __future__ import annotations
 
@@ -598,6 +601,162 @@ def flight_feasibility(audit, K, vehicle=None, slack: float = 0.0) -> dict:
             clear = clear & (hits.reshape(-1, len(ticks)) == 0).all(axis=0)
     return {"complete": complete, "speed_ok": speed_ok, "ascent_ok": ascent_ok, "descent_ok": descent_ok, "tilt_ok": tilt_ok,
             "clear": clear, "flown_ok": complete & speed_ok & ascent_ok & descent_ok & clear}
+
+
+DEMAND_ROWS_TOTAL, DEMAND_THRUST_MAX, DEMAND_THRUST_MIN, DEMAND_BANK_X, DEMAND_BANK_Y, DEMAND_BODY_RATE = range(nat.DEMAND_ROWS)
+DEMAND_INVERTED, DEMAND_FIRST_INVERTED = range(nat.IDEMAND_ROWS)                                # idemand rows (include/uavac.h)
+
+
+def demand_from_rows(rows, jerk, row_offsets, g, cuboids=None):
+    """What a plan asks of the vehicle, recomputed from SAMPLED rows and jerk -- the SPECIFICATION of `uavac_minsnap_demand_dev`
+    (csrc/minsnap_demand.hip), which is tested against it bit for bit.  NumPy on the host.
+    `rows` (N, 11): x y z | vx vy vz | ax ay az | yaw | spline, missions back to back, as the sampler writes them; `jerk` (N, 3) as
+    `Engine.sample_derivatives` gives it; `row_offsets` (B + 1,); `g` the gravitational acceleration (`vehicle.g`), finite and > 0;
+    `cuboids` (n, 6) xmin xmax ymin ymax zmin zmax, or None = none.
+
+    Per row, every product, sum, quotient and fmax one rounded operation, in this order (NED: hover has fz = g):
+        fz = g - az;  n2 = (ax ax + ay ay) + fz fz;  bx2 = n2 > 0 ? (ax ax) / n2 : 0, by2 likewise with ay
+        jj = (jx jx + jy jy) + jz jz;  jf = (jx ax + jy ay) - jz fz;  w2 = n2 > 0 ? fmax(jj - (jf jf) / n2, 0) / n2 : 0
+        inverted = fz <= 0;  per cuboid ex, ey, ez and d2 = (ex ex + ey ey) + ez ez exactly as `audit_from_log` defines them
+    n2 is the specific thrust a perfectly tracked row needs, squared; bx2 and by2 the squares of the bank command the control law would
+    form (csrc/control_law.h: acx / acc_z before its clamp to max_tilt); w2 the square of the roll / pitch rate the curve demands (the
+    jerk across the thrust direction over the thrust; no yaw rate).  A maximum or minimum is taken of the SQUARES (fmax / fmin: a NaN
+    that overflow makes of finite samples is dropped) and one sqrt comes last; on a tie the lowest row wins.
+    -> dict of host arrays: `demand` (DEMAND_ROWS, B) f64 -- 0 the row total, 1 sqrt(max n2), 2 sqrt(min n2), 3 sqrt(max bx2), 4
+    sqrt(max by2), 5 sqrt(max w2) --, `idemand` (IDEMAND_ROWS, B) i32 -- 0 the inverted rows, 1 the mission-local index of the first one
+    (-1: none) --, and per cuboid (n, B): `clearance` f64 = sqrt(min d2) (0 inside or on a face) and `clearance_row` i32 the FIRST row
+    that attains it.  A mission with a non-finite position, velocity, acceleration or jerk, and one without rows: NaN in rows 1-5,
+    clearance NaN, every index -1, 0 inverted rows -- the plan audit's rule: a singular plan never looks feasible."""
+    rows, jerk = _host(rows), _host(jerk)
+    ro = _host_i64(row_offsets)
+    B = len(ro) - 1
+    if rows.ndim != 2 or rows.shape[1] != nat.TRAJ_COLS or jerk.shape != (rows.shape[0], 3):
+        raise ValueError(f"rows must be (N, {nat.TRAJ_COLS}) and jerk (N, 3)")
+    if B < 1 or ro[0] != 0 or ro[-1] != len(rows) or (np.diff(ro) < 0).any():
+        raise ValueError("row_offsets must ascend from 0 to the number of rows")
+    g = float(g)
+    if not (np.isfinite(g) and g > 0.0):
+        raise ValueError("g must be finite and > 0")
+    cub = np.zeros((0, 6)) if cuboids is None else _host(cuboids)
+    if cub.size % 6 or (cub.ndim == 2 and cub.shape[1] != 6):
+        raise ValueError("cuboids must be (n, 6): xmin xmax ymin ymax zmin zmax")
+    cub = cub.reshape(-1, 6)
+    n = len(cub)
+    if n > nat.AUDIT_MAX_CUBOIDS:
+        raise ValueError(f"{n} cuboids; at most {nat.AUDIT_MAX_CUBOIDS} per call")
+    px, py, pz = rows[:, 0], rows[:, 1], rows[:, 2]
+    ax, ay, az = rows[:, 6], rows[:, 7], rows[:, 8]
+    jx, jy, jz = jerk[:, 0], jerk[:, 1], jerk[:, 2]
+    with np.errstate(all="ignore"):
+        fz = g - az
+        xx, yy = ax * ax, ay * ay
+        n2 = (xx + yy) + fz * fz
+        some = n2 > 0.0
+        over = np.where(some, n2, 1.0)
+        bx2, by2 = np.where(some, xx / over, 0.0), np.where(some, yy / over, 0.0)
+        jj = (jx * jx + jy * jy) + jz * jz
+        jf = (jx * ax + jy * ay) - jz * fz
+        w2 = np.where(some, np.fmax(jj - (jf * jf) / over, 0.0) / over, 0.0)
+        inverted = fz <= 0.0
+        d2 = np.empty((n, len(rows)))
+        for c, (x0, x1, y0, y1, z0, z1) in enumerate(cub):
+            ex = np.where(px < x0, x0 - px, np.where(px > x1, px - x1, 0.0))
+            ey = np.where(py < y0, y0 - py, np.where(py > y1, py - y1, 0.0))
+            ez = np.where(pz < z0, z0 - pz, np.where(pz > z1, pz - z1, 0.0))
+            d2[c] = (ex * ex + ey * ey) + ez * ez
+    finite = np.isfinite(rows[:, 0:9]).all(axis=1) & np.isfinite(jerk).all(axis=1)
+    demand = np.full((nat.DEMAND_ROWS, B), np.nan)
+    idemand = np.zeros((nat.IDEMAND_ROWS, B), dtype=np.int32)
+    idemand[DEMAND_FIRST_INVERTED] = -1
+    clearance = np.full((n, B), np.nan)
+    clearance_row = np.full((n, B), -1, dtype=np.int32)
+    demand[DEMAND_ROWS_TOTAL] = np.diff(ro)
+    for b in range(B):
+        s = slice(int(ro[b]), int(ro[b + 1]))
+        if s.start == s.stop or not finite[s].all():
+            continue
+        with np.errstate(invalid="ignore"):
+            demand[1:, b] = np.sqrt([np.fmax.reduce(n2[s]), np.fmin.reduce(n2[s]), np.fmax.reduce(bx2[s]), np.fmax.reduce(by2[s]),
+                                     np.fmax.reduce(w2[s])])
+        upside = np.flatnonzero(inverted[s])
+        idemand[:, b] = (len(upside), upside[0] if len(upside) else -1)
+        for c in range(n):
+            at = int(np.argmin(d2[c, s]))                                                  # the first minimum: the lowest row
+            clearance[c, b], clearance_row[c, b] = np.sqrt(d2[c, s][at]), at
+    return {"demand": demand, "idemand": idemand, "clearance": clearance, "clearance_row": clearance_row}
+
+
+_DEMAND_FIELDS = ("rows", "thrust_max", "thrust_min", "bank_x", "bank_y", "body_rate")
+
+
+def _demand_columns(demand) -> dict:
+    """A PlanDemand (or anything with its fields; tensors on any device or arrays), or the dict `demand_from_rows` gives -> its columns
+    as host arrays under PlanDemand's names."""
+    if isinstance(demand, dict):
+        block, iblock = _host(demand["demand"]), _host(demand["idemand"], np.int64)
+        if block.ndim != 2 or block.shape[0] != nat.DEMAND_ROWS or iblock.shape != (nat.IDEMAND_ROWS, block.shape[1]):
+            raise ValueError(f"a demand block is [{nat.DEMAND_ROWS}][B] and its integer block [{nat.IDEMAND_ROWS}][B]")
+        out = dict(zip(_DEMAND_FIELDS, block))
+        out.update(inverted_rows=iblock[DEMAND_INVERTED], first_inverted=iblock[DEMAND_FIRST_INVERTED],
+                   clearance=_host(demand["clearance"]), clearance_row=_host(demand["clearance_row"], np.int64))
+    else:
+        out = {f: _host(getattr(demand, f)).reshape(-1) for f in _DEMAND_FIELDS}
+        out.update(inverted_rows=_host(demand.inverted_rows, np.int64).reshape(-1),
+                   first_inverted=_host(demand.first_inverted, np.int64).reshape(-1), clearance=_host(demand.clearance),
+                   clearance_row=_host(demand.clearance_row, np.int64))
+    B = len(out["rows"])
+    out["clearance"] = out["clearance"].reshape(-1, B)
+    out["clearance_row"] = out["clearance_row"].reshape(-1, B)
+    return out
+
+
+def demand_feasibility(demand, vehicle=None, slack: float = 0.0, min_clearance: float = 0.0) -> dict:
+    """A plan demand (`Engine.demand` -> PlanDemand, anything with its fields, or the dict `demand_from_rows` gives; tensors on any
+    device or arrays) against what the vehicle can give -> dict of (B,) bool host arrays:
+    thrust_ok (mass thrust_max <= 4 max_thrust + slack and mass thrust_min >= 4 min_thrust - slack: four rotors, newtons), tilt_ok
+    (bank_x and bank_y <= max_tilt + slack: the bank command the control law clips, csrc/control_law.h), upright (no row asks for
+    thrust downward), clear (every clearance > min_clearance, strictly: at 0 a sample is inside a cuboid or on a face; all true when no
+    cuboid was given), demand_ok (all four).  A NaN -- a mission with a non-finite sample or without rows -- fails every test, `upright`
+    and `clear` included.  `vehicle`: a `Vehicle` (or anything with mass, min_thrust, max_thrust and max_tilt); None =
+    `uavac_vehicle_default`.  `plan_feasibility` judges the other four limits."""
+    V = nat.Vehicle.default() if vehicle is None else vehicle
+    slack, min_clearance = float(slack), float(min_clearance)
+    d = _demand_columns(demand)
+    mass = float(V.mass)
+    with np.errstate(invalid="ignore"):
+        thrust_ok = (mass * d["thrust_max"] <= 4.0 * float(V.max_thrust) + slack) & \
+                    (mass * d["thrust_min"] >= 4.0 * float(V.min_thrust) - slack)
+        tilt_ok = (d["bank_x"] <= float(V.max_tilt) + slack) & (d["bank_y"] <= float(V.max_tilt) + slack)
+        finite = ~(np.isnan(d["thrust_max"]) | np.isnan(d["thrust_min"]) | np.isnan(d["bank_x"]) | np.isnan(d["bank_y"]))
+        upright = finite & (d["inverted_rows"] == 0)
+        clear = finite & (d["clearance"] > min_clearance).all(axis=0)
+    return {"thrust_ok": thrust_ok, "tilt_ok": tilt_ok, "upright": upright, "clear": clear,
+            "demand_ok": thrust_ok & tilt_ok & upright & clear}
+
+
+def audit_gap(demand, flight) -> dict:
+    """Did tracking error eat the clearance, or was it planned that tight?  A plan demand (`Engine.demand`, or the dict of
+    `demand_from_rows`) beside the flight audit of the same missions and cuboids (`Engine.flown_audit` -> FlightAudit, anything with
+    bank_x, bank_y and clearance, or the dict of `audit_from_log`), on the host -> dict of
+      `bank_excess`         (2, B) f64: flown bank - demanded bank, about x and about y (the flight banked more than a perfect track needs),
+      `clearance_lost`      (n, B) f64: planned - flown clearance per cuboid (positive: the flight passed nearer than the plan),
+      `hit_in_flight_only`  (n, B) bool: flown clearance 0 while the planned one is > 0.
+    A NaN on either side gives NaN, and False in `hit_in_flight_only`.  Different batch sizes or cuboid counts are a ValueError."""
+    d = _demand_columns(demand)
+    B = len(d["rows"])
+    if isinstance(flight, dict):
+        block = _host(flight["audit"])
+        f_bank, f_clear = np.stack([block[5], block[6]]), _host(flight["clearance"])
+    else:
+        f_bank, f_clear = np.stack([_host(flight.bank_x).reshape(-1), _host(flight.bank_y).reshape(-1)]), _host(flight.clearance)
+    if f_bank.shape != (2, B):
+        raise ValueError(f"the demand holds {B} missions, the flight audit {f_bank.shape[-1]} vehicles")
+    f_clear = f_clear.reshape(-1, B)
+    if f_clear.shape != d["clearance"].shape:
+        raise ValueError(f"the demand holds {len(d['clearance'])} cuboids, the flight audit {len(f_clear)}")
+    with np.errstate(invalid="ignore"):
+        return {"bank_excess": f_bank - np.stack([d["bank_x"], d["bank_y"]]), "clearance_lost": d["clearance"] - f_clear,
+                "hit_in_flight_only": (f_clear == 0.0) & (d["clearance"] > 0.0)}
 
 
 def delay_rows(rows, row_offsets, start_rows, first_yaw):
