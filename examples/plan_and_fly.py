@@ -10,9 +10,11 @@ Both planners see the obstacles inflated by `clearance`; the flight is tested ag
 `--retime` (opt-in) puts a step between 3 and 4: the missions whose plan asks for more than the control law gives (the vehicle's
 speed, climb, descent and horizontal-acceleration limits) are slowed down by exactly the factor they need (Engine.retime); the
 curves stay where the obstacle loop put them.  Either way the plan that is flown is asked what it demands of the vehicle (Engine.demand):
-how many missions need a bank beyond `max_tilt`, which the control law clips and retiming does not bound.
+how many missions need a bank beyond `max_tilt`, which the control law clips and `--retime` does not bound.
+`--retime-demand` is `--retime` with the tilt bound and the rotor thrust limits as well (Engine.retime(..., demand=True)): afterwards
+no mission demands a bank beyond `max_tilt`.
 
-    python examples/plan_and_fly.py [B] [--retime]
+    python examples/plan_and_fly.py [B] [--retime | --retime-demand]
 """
 import os
 import sys
@@ -28,7 +30,8 @@ from uav_ac.scoring import demand_feasibility                     # noqa: E402
 from uav_ac.simulation.mujoco_sim import MujocoSimulation         # noqa: E402
 
 
-def main(B: int = 256, velocity: float = 2.0, seed: int = 0, clearance: float = 0.3, retime: bool = False):
+def main(B: int = 256, velocity: float = 2.0, seed: int = 0, clearance: float = 0.3, retime: bool = False,
+         retime_demand: bool = False):
     import torch
     sim = MujocoSimulation()                                       # packaged lab course: obstacles, bounds, start, goal
     keep_out = sim.obstacles + np.array([-1, 1, -1, 1, -1, 1]) * clearance     # planners see inflated cuboids
@@ -50,8 +53,8 @@ def main(B: int = 256, velocity: float = 2.0, seed: int = 0, clearance: float = 
     t2 = time.perf_counter()
     plan = eng.plan_collision_free(waypoints, keep_out, velocity, 0.01, strict=False, recheck_passes=4)
     retimed = ""
-    if retime:
-        result = eng.retime(plan)
+    if retime or retime_demand:
+        result = eng.retime(plan, demand=retime_demand)
         plan = result.plan
         slowed = result.factors > 1.0
         retimed = (f"; retimed {int(slowed.sum())} missions in {result.passes} passes (largest factor "
@@ -76,5 +79,5 @@ def main(B: int = 256, velocity: float = 2.0, seed: int = 0, clearance: float = 
 
 
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if a != "--retime"]
-    main(int(args[0]) if args else 256, retime="--retime" in sys.argv[1:])
+    args = [a for a in sys.argv[1:] if a not in ("--retime", "--retime-demand")]
+    main(int(args[0]) if args else 256, retime="--retime" in sys.argv[1:], retime_demand="--retime-demand" in sys.argv[1:])

@@ -828,6 +828,66 @@ int uavac_minsnap_retime_dev(uavac_ctx *ctx, const double *wp, const int64_t *se
                              int32_t *seg_rows, int64_t *row_offsets, double *coeffs, int32_t *status, double *first_yaw,
                              double *audit, double *factors_total, int32_t *converged, int *passes);
 
+/* RETIMING TO THE TILT AND THRUST LIMITS AS WELL.  The four limits above are the ones the control law clips its TARGETS to; it also clips
+ * the bank command to max_tilt (csrc/control_law.h), and the rotors give between min_thrust and max_thrust.  uavac_minsnap_demand_dev
+ * reports what a plan asks of these; the three calls below act on it.  Slowing a mission by k > 1 leaves its curve in place and divides
+ * its accelerations by u = k^2.
+ *   demand_limits [4] HOST: g (uavac_vehicle.g), max_tilt, Fmax = 4 max_thrust / mass, Fmin = 4 min_thrust / mass (specific thrust, m/s^2)
+ * The host forms t2 = max_tilt * max_tilt, D = Fmax * Fmax - g * g and E = g * g - Fmin * Fmin once, each product and difference ONE
+ * rounded operation.
+ *
+ * uavac_minsnap_need_dev (csrc/minsnap_need.hip): need [UAVAC_NEED_ROWS][B] f64, per mission the slowdown FACTOR each limit asks for on
+ * its own -- 0 tilt, 1 upright, 2 thrust_max, 3 thrust_min -- from coefficients and row counts alone; coeffs / seg_rows / seg_offsets /
+ * B / m / dt as in uavac_minsnap_audit_dev.  Stream-ordered, no sync.  PER ROW, from the sampler's acceleration a (the values
+ * uavac_minsnap_sample_dev writes, bit for bit); every product, sum, difference, fmax and sqrt is ONE rounded operation (no fused
+ * multiply-add), in exactly this order (tau = max_tilt):
+ *     xx = ax * ax; yy = ay * ay; h = xx + yy; A = h + az * az; gz = g * az
+ *     q  = fmax(fmax(xx - t2 * h, yy - t2 * h), 0)
+ *     T  = q > 0 ? tau * az + sqrt(q) : -inf              tilt:       u >= T / (tau g)
+ *     U  = az                                             upright:    u >= U / g   (non-strict, see below)
+ *     H  = sqrt(gz * gz + A * D) - gz                     thrust max: u >= H / D
+ *     d  = gz * gz - A * E
+ *     Lo = (az > 0 && d >= 0) ? gz + sqrt(d) : -inf       thrust min: u >= Lo / E  (the admissible interval that reaches to infinity;
+ *                                                         a second one at faster timing lies beyond a thrust reversal and is not used)
+ * Division by a positive constant is monotone under rounding, so the maxima are taken of these NUMERATORS (fmax from -inf) and each is
+ * divided once per mission:
+ *     need[0] = sqrt(fmax(max T / (tau * g), 0))    need[1] = sqrt(fmax(max U / g, 0))
+ *     need[2] = sqrt(fmax(max H / D, 0))            need[3] = sqrt(fmax(max Lo / E, 0))
+ * The reductions are maxima: exact and order-free, so the outputs depend neither on the launch shape nor on the batch split (option
+ * "audit_lanes": 16 or 64 lanes per mission, same results).  They equal what NumPy computes from the sampled rows, bit for bit
+ * (uav_ac/scoring.py need_from_rows).  Hover gives 0, 0, 0, 0.  A mission with ANY non-finite sample (position, velocity or
+ * acceleration), and a mission without rows, reports NaN in all four: a singular plan never looks feasible.
+ * KNOWN EDGE: a row in exact free fall (az == g) with min_thrust = 0 gives need[1] = 1 and is not slowed, although
+ * uavac_minsnap_demand_dev counts it as inverted; with Fmin > 0 the thrust_min term covers it (u = g / (g - Fmin) > 1).
+ * The body rate (no closed form) and the cuboid clearance (slowing down moves no curve) are not retimed to.
+ *
+ * uavac_minsnap_retime_demand_factors_dev: uavac_minsnap_retime_factors_dev with the need block beside the audit block.  With r_audit
+ * the four-term maximum formed exactly as there,
+ *     r = fmax(r_audit, fmax(fmax(need[0], need[1]), fmax(need[2], need[3])))
+ * a NaN among the four peaks OR the four needs: factors[b] = NaN, velocity untouched, counters[1] += 1; r <= 1: factors[b] = 1.0,
+ * velocity untouched bit for bit; else k = r / (1 - margin), factors[b] = k, velocities[b] = velocities[b] / k, counters[0] += 1.
+ *   binding [B] i32: the index of the FIRST term that attains r, in the order 0 speed_xy, 1 ascent, 2 descent, 3 accel_xy, 4 tilt,
+ *   5 upright, 6 thrust_max, 7 thrust_min; -1 for a NaN mission.  Written for every mission, also where r <= 1 (the nearest limit).
+ *
+ * uavac_minsnap_retime_demand_dev: THE LOOP of uavac_minsnap_retime_dev with demand_limits as a further input, need
+ * [UAVAC_NEED_ROWS][B] and binding [B] as further outputs (both describe the plan at the returned velocities, like audit), and one more
+ * launch per pass: the need kernel after the audit.  One counter read per pass, as there.
+ *
+ * UAVAC_EINVAL before anything is enqueued: g or max_tilt not positive and finite; Fmax not finite or <= g (the vehicle cannot hover);
+ * Fmin < 0 or >= g; and every refusal of the call each of the three mirrors (uavac_minsnap_audit_dev, uavac_minsnap_retime_factors_dev,
+ * uavac_minsnap_retime_dev). */
+#define UAVAC_NEED_ROWS 4
+int uavac_minsnap_need_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                           double dt, const double demand_limits[4], double *need);
+int uavac_minsnap_retime_demand_factors_dev(uavac_ctx *ctx, const double *audit, const double *need, int B, const double limits[4],
+                                            const double demand_limits[4], double margin, double *velocities, double *factors,
+                                            int32_t *binding, int32_t *counters);
+int uavac_minsnap_retime_demand_dev(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B, int m, double *velocities,
+                                    double dt, const double limits[4], const double demand_limits[4], double margin, int max_passes,
+                                    double *times, int32_t *seg_rows, int64_t *row_offsets, double *coeffs, int32_t *status,
+                                    double *first_yaw, double *audit, double *need, double *factors_total, int32_t *binding,
+                                    int32_t *converged, int *passes);
+
 /* PLANS FROM GIVEN DURATIONS, THE SNAP COST, AND OPTIMISED SEGMENT TIMES (csrc/minsnap_timeopt.hip).  Every chain above takes its
  * durations from upstream's rule T_s = |leg_s| / velocity [* 1.5 on the first and last leg] (minimum_snap.py:311-321); these four take
  * them as they are given, measure a plan, and divide a mission's total time between its legs so that the snap cost falls -- the second

@@ -4,6 +4,14 @@ and how much of a pass is the rows-free chain and how much the audit -- and what
 both flown to the end with score=True and their tracking scores reported side by side.
 
     retime_rate.py [OUT.jsonl] [rounds] [B] [m]
+    retime_rate.py --demand [--against OTHER.so] [OUT.jsonl] [rounds] [B] [m]
+
+`--demand`: retiming to the tilt and thrust limits as well (`Engine.need`, `Engine.retime(..., demand=True)`), B = 65 536 missions of 8
+segments, with the FAST vehicle -- the default one with the four flight limits at 10 / 10 / 10 / 12, so that they are not the bottleneck.
+`Engine.need` beside `Engine.audit` and `Engine.demand` without cuboids in the same rounds, the ratio formed per round; the demand loop
+beside the four-limit loop on the same plans; both results flown with score=True.  `--against OTHER.so` (tools/against.py): the
+four-limit loop through this build and through another build of the same ABI (the parent commit's), the outputs compared byte for byte
+first, alternating -- to show that the loop that was there did not move.
 
 Timing: the loop synchronises once per pass, so it is timed with the host clock around calls that end in a device synchronise;
 its parts (the rows-free chain at per-mission speeds, the audit, the factors kernel) with hipEvents around batches of launches.
@@ -16,7 +24,7 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "uav-autonomous-control_amd")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "uav-autonomous-control_amd"), os.path.join(ROOT, "tools")]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from bench import missions  # noqa: E402
@@ -46,9 +54,9 @@ def wall(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
-def fly(eng, plan, chunk=4000):
+def fly(eng, plan, chunk=4000, vehicle=None):
     """The whole plan flown plan-fed with score=True -> the tracking summary (host floats)."""
-    fleet = eng.fleet(plan, from_plan=True)
+    fleet = eng.fleet(plan, vehicle, from_plan=True)
     rows = int((plan.row_offsets[1:] - plan.row_offsets[:-1]).max().item())
     ticks = (rows + 2) * int(fleet.vehicle.inner_per_outer)
     for _ in range((ticks + chunk - 1) // chunk):
@@ -62,7 +70,115 @@ def fly(eng, plan, chunk=4000):
             "final_error_mean": f(s["final_error"]), "passed": int(acc["passed"].sum().item())}
 
 
+def fast_vehicle():
+    V = nat.Vehicle.default()
+    V.max_speed_xy, V.max_ascent, V.max_descent, V.max_horiz_accel = 10.0, 10.0, 10.0, 12.0
+    return V
+
+
+def stats(ts):
+    return {"median_ms": round(float(np.median(ts)), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4)}
+
+
+def main_demand(argv):
+    from against import Builds, P, ptr, split_argv
+    from uav_ac.scoring import BINDING_NAMES, demand_feasibility
+    argv, other = split_argv(argv)
+    out_path = argv[0] if len(argv) > 0 else None
+    rounds = int(argv[1]) if len(argv) > 1 else 7
+    B = int(argv[2]) if len(argv) > 2 else 65536
+    M = int(argv[3]) if len(argv) > 3 else 8
+    eng = Engine("cuda:0")
+    V = fast_vehicle()
+    wps = missions(B, M, 0, B)
+    free = eng.plan(wps, VEL, DT, rows=False)
+    four = eng.retime(free, V, margin=MARGIN, max_passes=MAX_PASSES)
+    res = eng.retime(free, V, margin=MARGIN, max_passes=MAX_PASSES, demand=True)
+    torch.cuda.synchronize()
+
+    def verdicts(plan):
+        f = demand_feasibility(eng.demand(plan, vehicle=V), V)
+        ok = f["thrust_ok"] & f["tilt_ok"] & f["upright"]
+        return {"tilt_ok": int(f["tilt_ok"].sum()), "thrust_ok": int(f["thrust_ok"].sum()), "upright": int(f["upright"].sum()),
+                "all_three": int(ok.sum()), "flight_limits_ok": int(plan_feasibility(eng.audit(plan), V)["feasible"].sum().item())}
+    binding = np.bincount(res.binding.cpu().numpy()[(res.factors > 1.0).cpu().numpy()], minlength=len(BINDING_NAMES))
+    worst = res.need.block.amax(dim=0)
+    slowed = res.factors > 1.0
+    by_need = slowed & (res.binding >= 4)                                          # bound by a term of the need block, not by the audit's
+    outcome = {"B": B, "m": M, "vehicle": "default with flight limits 10 / 10 / 10 / 12", "as_planned": verdicts(free),
+               "four_limit_loop": {"passes": four.passes, "slowed": int((four.factors > 1.0).sum().item()), **verdicts(four.plan)},
+               "demand_loop": {"passes": res.passes, "converged": int(res.converged.sum().item()), "slowed": int(slowed.sum().item()),
+                               "binding_of_the_slowed": {n: int(c) for n, c in zip(BINDING_NAMES, binding) if c},
+                               "factor_median": float(res.factors.median().item()), "factor_max": float(res.factors.max().item()),
+                               "need_after_of_those_a_need_binds_min": float(worst[by_need].min().item()) if bool(by_need.any()) else None,
+                               "need_after_of_those_a_need_binds_max": float(worst[by_need].max().item()) if bool(by_need.any()) else None,
+                               "rows_before": int(free.total_rows), "rows_after": int(res.plan.total_rows), **verdicts(res.plan)},
+               "flags": eng.take_flags()}
+    lines = [json.dumps({"outcome": outcome})]
+    print(lines[-1], flush=True)
+
+    kernels = {"Engine.audit, no cuboids": lambda: eng.audit(free), "Engine.demand, no cuboids": lambda: eng.demand(free, vehicle=V),
+               "Engine.need": lambda: eng.need(free, V)}
+    loops = {"Engine.retime, four limits (host clock, allocations and syncs included)":
+             lambda: eng.retime(free, V, margin=MARGIN, max_passes=MAX_PASSES),
+             "Engine.retime, demand=True (host clock, allocations and syncs included)":
+             lambda: eng.retime(free, V, margin=MARGIN, max_passes=MAX_PASSES, demand=True)}
+    for fn in list(kernels.values()) * 3 + list(loops.values()) * 2:               # warm-up
+        fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in list(kernels) + list(loops)}
+    for _ in range(rounds):
+        for k, fn in kernels.items():
+            times[k].append(timed(fn, 20))
+        for k, fn in loops.items():
+            times[k].append(wall(fn)[0])
+    box = eng.ctx.device_identity()
+    for k, ts in times.items():
+        lines.append(json.dumps({"arm": k, "B": B, "m": M, **stats(ts), "ms_per_round": [round(t, 4) for t in ts], "rounds": rounds, "box": box}))
+        print(lines[-1], flush=True)
+    per_round = lambda a, b: [x / y for x, y in zip(times[a], times[b])]          # noqa: E731
+    ratios = {"need / audit": per_round("Engine.need", "Engine.audit, no cuboids"),
+              "need / demand": per_round("Engine.need", "Engine.demand, no cuboids"),
+              "demand loop / four-limit loop": per_round(list(loops)[1], list(loops)[0])}
+    lines.append(json.dumps({"ratios per round": {k: {"median": round(float(np.median(r)), 4), "min": round(min(r), 4), "max": round(max(r), 4)}
+                                                  for k, r in ratios.items()}, "rounds": rounds}))
+    print(lines[-1], flush=True)
+
+    if other:
+        # the four-limit loop, this build against the other: the C entry point on buffers of the tool's own
+        types = [P, P, P, C.c_int, C.c_int, P, C.c_double, P, C.c_double, C.c_int] + [P] * 10
+        builds = Builds(other, {"uavac_minsnap_retime_dev": types})
+        dev = dict(device=eng.device)
+        out = {n: torch.empty_like(getattr(free, n)) for n in ("times", "seg_rows", "coeffs")}
+        ro, fy = torch.empty((B + 1,), dtype=torch.int64, **dev), torch.empty((B,), dtype=torch.float64, **dev)
+        status, conv = torch.zeros((B,), dtype=torch.int32, **dev), torch.empty((B,), dtype=torch.int32, **dev)
+        block, tot = torch.empty((nat.AUDIT_ROWS, B), dtype=torch.float64, **dev), torch.empty((B,), dtype=torch.float64, **dev)
+        vel = torch.empty((B,), dtype=torch.float64, **dev)
+        limits = (C.c_double * 4)(10.0, 10.0, 10.0, 12.0)
+        passes = C.c_int(0)
+
+        def loop(lib, ctx):
+            vel.fill_(VEL)
+            assert lib.uavac_minsnap_retime_dev(ctx, ptr(free.waypoints), None, B, M, ptr(vel), DT, limits, MARGIN, MAX_PASSES, ptr(out["times"]),
+                                                ptr(out["seg_rows"]), ptr(ro), ptr(out["coeffs"]), ptr(status), ptr(fy), ptr(block), ptr(tot),
+                                                ptr(conv), C.byref(passes)) == 0
+            return vel, tot, conv, block, out["coeffs"], out["seg_rows"]
+        builds.wall("uavac_minsnap_retime_dev, four limits", loop, max(rounds, 8), B=B, m=M)
+        lines += builds.lines
+
+    # what it buys: the fast-vehicle fleet flown after each loop, scored
+    flights = {"after retime(demand=False)": fly(eng, four.plan, vehicle=V), "after retime(demand=True)": fly(eng, res.plan, vehicle=V)}
+    lines.append(json.dumps({"tracking": flights}))
+    print(lines[-1], flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
 def main():
+    if "--demand" in sys.argv:
+        return main_demand([a for a in sys.argv[1:] if a != "--demand"])
     out_path = sys.argv[1] if len(sys.argv) > 1 else None
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 7
     B = int(sys.argv[3]) if len(sys.argv) > 3 else 65536

@@ -721,18 +721,12 @@ int uavac_minsnap_retime_factors_dev(uavac_ctx *ctx, const double *audit, int B,
     return uavac_launch_retime_factors(ctx, audit, B, L, margin, 1, velocities, factors, counters, nullptr, nullptr);
 }
 
-int uavac_minsnap_retime_dev(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B, int m, double *velocities,
-                             double dt, const double limits[4], double margin, int max_passes, double *times, int32_t *seg_rows,
-                             int64_t *row_offsets, double *coeffs, int32_t *status, double *first_yaw, double *audit,
-                             double *factors_total, int32_t *converged, int *passes) {
-    UAVAC_ENTER(ctx);
-    if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
-    RetimeLimits L;
-    if (int rc = check_retime_args(ctx, B, limits, margin, &L)) return rc;
-    if (!velocities || !times || !seg_rows || !row_offsets || !coeffs || !audit || !factors_total || !converged || !passes)
-        return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
-    if (int rc = check_dt(ctx, dt)) return rc;
-    if (max_passes < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative max_passes");
+// The loop of uavac_minsnap_retime_dev and uavac_minsnap_retime_demand_dev, arguments checked by the caller.  N == NULL: the four flight
+// limits alone; otherwise one more launch per pass, the need kernel after the audit, and the factors kernel that reads both blocks.
+static int retime_loop(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B, int m, double *velocities, double dt,
+                       const RetimeLimits &L, const NeedLimits *N, double margin, int max_passes, double *times, int32_t *seg_rows,
+                       int64_t *row_offsets, double *coeffs, int32_t *status, double *first_yaw, double *audit, double *need,
+                       double *factors_total, int32_t *binding, int32_t *converged, int *passes) {
     *passes = 0;
     double *d_factors = nullptr;
     int32_t *d_counters = nullptr;
@@ -746,16 +740,99 @@ int uavac_minsnap_retime_dev(uavac_ctx *ctx, const double *wp, const int64_t *se
         if (int rc = uavac_launch_coeff_solve(ctx, wp, times, B, m, coeffs, status, seg_offsets)) return rc;
         if (first_yaw) if (int rc = uavac_launch_first_yaw(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, first_yaw)) return rc;
         if (int rc = uavac_launch_audit(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, nullptr, 0, audit, nullptr, nullptr)) return rc;
+        if (N) if (int rc = uavac_launch_need(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, *N, need)) return rc;
         UAVAC_HIP(ctx, hipMemsetAsync(d_counters, 0, 2 * sizeof(int32_t), ctx->stream));
         const int apply = retimed < max_passes;            // out of passes: the verdict only, the speeds stay what the plan was made at
-        if (int rc = uavac_launch_retime_factors(ctx, audit, B, L, margin, apply, velocities, d_factors, d_counters, factors_total,
-                                                 converged)) return rc;
+        if (int rc = N ? uavac_launch_retime_demand_factors(ctx, audit, need, B, L, margin, apply, velocities, d_factors, binding, d_counters,
+                                                            factors_total, converged)
+                       : uavac_launch_retime_factors(ctx, audit, B, L, margin, apply, velocities, d_factors, d_counters, factors_total,
+                                                     converged)) return rc;
         int32_t cnt[2];
         if (int rc = uavac_d2h(ctx, cnt, d_counters, sizeof cnt)) return rc;           // the pass's one read-back (synchronises)
         if (cnt[0] == 0 || !apply) break;
         *passes = retimed + 1;
     }
     return UAVAC_OK;
+}
+
+int uavac_minsnap_retime_dev(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B, int m, double *velocities,
+                             double dt, const double limits[4], double margin, int max_passes, double *times, int32_t *seg_rows,
+                             int64_t *row_offsets, double *coeffs, int32_t *status, double *first_yaw, double *audit,
+                             double *factors_total, int32_t *converged, int *passes) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
+    RetimeLimits L;
+    if (int rc = check_retime_args(ctx, B, limits, margin, &L)) return rc;
+    if (!velocities || !times || !seg_rows || !row_offsets || !coeffs || !audit || !factors_total || !converged || !passes)
+        return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_dt(ctx, dt)) return rc;
+    if (max_passes < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative max_passes");
+    return retime_loop(ctx, wp, seg_offsets, B, m, velocities, dt, L, nullptr, margin, max_passes, times, seg_rows, row_offsets, coeffs, status,
+                       first_yaw, audit, nullptr, factors_total, nullptr, converged, passes);
+}
+
+// ---------------------------------------------------------------- retiming to the tilt and thrust limits as well
+// demand_limits [4] HOST: g, max_tilt, Fmax, Fmin -> the constants the need kernel reads, each ONE rounded operation (nothing contracted:
+// the NumPy specification forms them the same way).  Refuses a vehicle that cannot hover, or whose least thrust holds it up.
+static int need_limits(uavac_ctx *ctx, const double *demand_limits, NeedLimits *N) {
+#pragma clang fp contract(off)
+    if (!demand_limits) return uavac_fail(ctx, UAVAC_EINVAL, "null demand_limits");
+    const double g = demand_limits[0], tau = demand_limits[1], fmax_ = demand_limits[2], fmin_ = demand_limits[3];
+    if (!std::isfinite(g) || !(g > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "g must be finite and > 0");
+    if (!std::isfinite(tau) || !(tau > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "max_tilt must be finite and > 0");
+    if (!std::isfinite(fmax_) || !(fmax_ > g)) return uavac_fail(ctx, UAVAC_EINVAL, "the largest specific thrust must be finite and > g");
+    if (!(fmin_ >= 0.0) || !(fmin_ < g)) return uavac_fail(ctx, UAVAC_EINVAL, "the least specific thrust must be in [0, g)");
+    const double gg = g * g, hh = fmax_ * fmax_, ll = fmin_ * fmin_;
+    N->g = g; N->tau = tau;
+    N->t2 = tau * tau;
+    N->tg = tau * g;
+    N->D = hh - gg;
+    N->E = gg - ll;
+    if (!std::isfinite(N->D) || !(N->D > 0.0) || !(N->E > 0.0)) return uavac_fail(ctx, UAVAC_EINVAL, "thrust limits too close to g");
+    return UAVAC_OK;
+}
+
+int uavac_minsnap_need_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                           double dt, const double demand_limits[4], double *need) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
+    if (!seg_rows || !need) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_dt_positive(ctx, dt)) return rc;
+    NeedLimits N;
+    if (int rc = need_limits(ctx, demand_limits, &N)) return rc;
+    return uavac_launch_need(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, N, need);
+}
+
+int uavac_minsnap_retime_demand_factors_dev(uavac_ctx *ctx, const double *audit, const double *need, int B, const double limits[4],
+                                            const double demand_limits[4], double margin, double *velocities, double *factors,
+                                            int32_t *binding, int32_t *counters) {
+    UAVAC_ENTER(ctx);
+    RetimeLimits L;
+    if (int rc = check_retime_args(ctx, B, limits, margin, &L)) return rc;
+    NeedLimits N;                                          // (the need block was made with them: the same refusals, nothing else is read)
+    if (int rc = need_limits(ctx, demand_limits, &N)) return rc;
+    if (!audit || !need || !velocities || !factors || !binding || !counters) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    return uavac_launch_retime_demand_factors(ctx, audit, need, B, L, margin, 1, velocities, factors, binding, counters, nullptr, nullptr);
+}
+
+int uavac_minsnap_retime_demand_dev(uavac_ctx *ctx, const double *wp, const int64_t *seg_offsets, int B, int m, double *velocities,
+                                    double dt, const double limits[4], const double demand_limits[4], double margin, int max_passes,
+                                    double *times, int32_t *seg_rows, int64_t *row_offsets, double *coeffs, int32_t *status,
+                                    double *first_yaw, double *audit, double *need, double *factors_total, int32_t *binding,
+                                    int32_t *converged, int *passes) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, wp, B, m)) return rc;
+    RetimeLimits L;
+    if (int rc = check_retime_args(ctx, B, limits, margin, &L)) return rc;
+    NeedLimits N;
+    if (int rc = need_limits(ctx, demand_limits, &N)) return rc;
+    if (!velocities || !times || !seg_rows || !row_offsets || !coeffs || !audit || !need || !factors_total || !binding || !converged ||
+        !passes)
+        return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_dt(ctx, dt)) return rc;
+    if (max_passes < 0) return uavac_fail(ctx, UAVAC_EINVAL, "negative max_passes");
+    return retime_loop(ctx, wp, seg_offsets, B, m, velocities, dt, L, &N, margin, max_passes, times, seg_rows, row_offsets, coeffs, status,
+                       first_yaw, audit, need, factors_total, binding, converged, passes);
 }
 
 // ---------------------------------------------------------------- given durations, the snap cost, optimised durations

@@ -301,6 +301,22 @@ struct RetimeLimits {
 };
 int uavac_launch_retime_factors(uavac_ctx *ctx, const double *audit, int B, const RetimeLimits &limits, double margin, int apply,
                                 double *velocities, double *factors, int32_t *counters, double *factors_total, int32_t *converged);
+// The slowdown factors the vehicle's tilt and thrust limits ask for, per mission, without the rows (minsnap_need.hip): need
+// [UAVAC_NEED_ROWS][B].  The constants are formed once on the host (uavac_api.hip need_limits), each ONE rounded operation.
+struct NeedLimits {
+    double g, tau;       // gravitational acceleration, max_tilt
+    double t2;           // tau * tau
+    double tg;           // tau * g
+    double D;            // Fmax * Fmax - g * g   (> 0: the vehicle can hover)
+    double E;            // g * g - Fmin * Fmin   (> 0)
+};
+int uavac_launch_need(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
+                      const NeedLimits &limits, double *need);
+// The retiming factors with the need block's four terms beside the audit's four (minsnap_retime.hip); binding [B] = the first term
+// that attains the maximum (0 .. 7, -1 for a NaN mission).  Everything else as uavac_launch_retime_factors.
+int uavac_launch_retime_demand_factors(uavac_ctx *ctx, const double *audit, const double *need, int B, const RetimeLimits &limits,
+                                       double margin, int apply, double *velocities, double *factors, int32_t *binding, int32_t *counters,
+                                       double *factors_total, int32_t *converged);
 // Plans from given durations, the snap cost and the optimisation of the durations (minsnap_timeopt.hip); seg_offsets as above.
 // seg_rows = ceil(times / dt) and row_offsets [B+1]; a duration that is not positive and finite raises flag 0 and leaves its mission
 // without rows

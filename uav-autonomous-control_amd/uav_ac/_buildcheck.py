@@ -160,6 +160,9 @@ BUDGETS = (
     # the plan demand: the audit's budget -- with sixteen cuboids 49 920 B of LDS, three workgroups per CU, hence three waves
     # per SIMD (built: 122 .. 136, no scratch memory)
     Budget("planning_registers", "minsnap_demand.o", "plan-demand", ("minsnap_demand_kernel",), 168, at_least=4),
+    # the slowdown factors of the tilt and thrust limits: the audit's shape and budget, no LDS (built: 112 and 120 at 64 and 16 lanes
+    # per mission, no scratch memory)
+    Budget("planning_registers", "minsnap_need.o", "plan-need", ("minsnap_need_kernel",), 168, at_least=2),
     # the solve with boundary derivatives, uniform and ragged: two waves per SIMD (built: 211 / 217)
     Budget("planning_registers", "minsnap_solve_bc.o", "boundary-solve", ("minsnap_solve_bc_kernel",), 256, extra=1),
     # plans from given durations, the snap cost, the duration optimisation's bookkeeping: loops over a mission's segments that keep

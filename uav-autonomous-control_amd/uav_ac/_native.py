@@ -23,6 +23,7 @@ TRAJ_COLS, STATE_ROWS, ISTATE_ROWS, CMD_COLS = 11, 30, 4, 12
 SCORE_ROWS = 11                  # tracking scores of the scored rollouts (include/uavac.h UAVAC_SCORE_ROWS)
 AUDIT_ROWS, AUDIT_MAX_CUBOIDS = 8, 16       # plan audit (include/uavac.h uavac_minsnap_audit_dev)
 DEMAND_ROWS, IDEMAND_ROWS = 6, 2            # plan demand (include/uavac.h uavac_minsnap_demand_dev)
+NEED_ROWS = 4                               # slowdown factors of the tilt and thrust limits (include/uavac.h uavac_minsnap_need_dev)
 SEP_ROWS, SEP_MAX_SPLIT = 5, 64             # separation audits (include/uavac.h uavac_minsnap_separation_dev, uavac_flown_separation_dev)
 CONF_ROWS = 5                               # rows of the conflict list's pair_i (include/uavac.h uavac_minsnap_conflicts_dev)
 STATE_LOG_ROWS = 13                         # rows of the rollout's state log per tick (positions: 0-2)
@@ -124,6 +125,9 @@ _SIGNATURES = {
     "uavac_minsnap_plan_bc_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
     "uavac_minsnap_retime_factors_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_double, _P, _P, _P]),
     "uavac_minsnap_retime_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_double, _P, C.c_double, C.c_int] + [_P] * 10),
+    "uavac_minsnap_need_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P]),
+    "uavac_minsnap_retime_demand_factors_dev": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, C.c_double, _P, _P, _P, _P]),
+    "uavac_minsnap_retime_demand_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, C.c_double, C.c_int] + [_P] * 12),
     "uavac_minsnap_row_counts_t_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P]),
     "uavac_minsnap_plan_t_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_double, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
     "uavac_minsnap_cost_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P]),

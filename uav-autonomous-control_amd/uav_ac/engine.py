@@ -12,8 +12,8 @@ from typing import Optional
 import numpy as np
 
 from . import _native as nat
-from .plans import (ConflictList, DeconflictResult, FlightAudit, LayerResult, Plan, PlanAudit, PlanDemand, RaggedBatch, RaggedPlan,  # noqa: F401
-                    RetimeResult, RRTDeviceBatch, Segments, SeparationAudit, StaggerResult, TimeOptResult, _ptr, segments,
+from .plans import (ConflictList, DeconflictResult, FlightAudit, LayerResult, Plan, PlanAudit, PlanDemand, PlanNeed, RaggedBatch,  # noqa: F401
+                    RaggedPlan, RetimeResult, RRTDeviceBatch, Segments, SeparationAudit, StaggerResult, TimeOptResult, _ptr, segments,
                     uniform_offsets)  # (the plans and result records live in uav_ac/plans.py; every name is re-exported here)
 
 
@@ -450,7 +450,7 @@ class Engine:
     def demand(self, plan, obstacles=None, vehicle: Optional[nat.Vehicle] = None) -> PlanDemand:
         """What the plan asks of the vehicle, per mission, without sampling its rows (`uavac_minsnap_demand_dev`): the largest and the
         least specific thrust a perfectly tracked plan needs, the bank it needs about each axis -- the bank command the control law
-        clips to `max_tilt`, which `Engine.audit` does not report and `Engine.retime` does not bound --, the roll / pitch rate the curve
+        clips to `max_tilt`, which `Engine.audit` does not report and `Engine.retime` bounds only with `demand=True` --, the roll / pitch rate the curve
         demands, the rows that ask for thrust downward, and for each cuboid of `obstacles` (as `Engine.audit` takes them, n <= 16) how
         near the samples pass it and at which row first: the plan-side counterpart of `Engine.flown_audit`'s bank_x, bank_y, body_rate
         and clearance.  `plan`: what `Engine.audit` takes.  `vehicle`: its `g` is used; None = `uavac_vehicle_default`.
@@ -471,6 +471,27 @@ class Engine:
         self.ctx.call("uavac_minsnap_demand_dev", *self._plan_args(plan), g, _ptr(cub) if n else None, n, _ptr(block), _ptr(iblock),
                       _ptr(clearance) if n else None, _ptr(clearance_row) if n else None)
         return PlanDemand(*block.unbind(0), *iblock.unbind(0), clearance, clearance_row, block)
+
+    @staticmethod
+    def _demand_limits(vehicle):
+        """The HOST array `demand_limits` of the need calls: g, max_tilt and the specific thrust of four rotors at max_thrust / min_thrust."""
+        from .scoring import demand_limits
+        return (C.c_double * 4)(*demand_limits(vehicle))
+
+    def need(self, plan, vehicle: Optional[nat.Vehicle] = None) -> PlanNeed:
+        """By how much each mission of `plan` must be slowed down for `vehicle` (None = `uavac_vehicle_default`) to be able to give what
+        it asks, per limit, without sampling its rows (`uavac_minsnap_need_dev`): the slowdown factor that the tilt bound, the upright
+        condition, the largest and the least rotor thrust each ask for on their own -- above 1 where `scoring.demand_feasibility` fails
+        the plan on tilt_ok, upright or thrust_ok.  `plan`: what `Engine.audit` takes.  -> PlanNeed, bit for bit what NumPy gives on the
+        sampled rows (`uav_ac.scoring.need_from_rows`).  Reads coefficients and row counts only, never `plan.traj`; stream-ordered like
+        the other _dev calls, no sync.  `Engine.retime(..., demand=True)` acts on it."""
+        torch = self._torch
+        plan = self._coeff_plan(plan)
+        limits = self._demand_limits(vehicle)
+        block = torch.empty((nat.NEED_ROWS, int(plan.B)), dtype=torch.float64, device=self.device)
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_need_dev", *self._plan_args(plan), limits, _ptr(block))
+        return PlanNeed(*block.unbind(0), block)
 
     def separation(self, plan, radius: float, groups=None, start_rows=None) -> SeparationAudit:
         """The plan's missions audited against each other (`uavac_minsnap_separation_dev`): per mission the closest approach to any
@@ -1008,7 +1029,8 @@ class Engine:
 
     DEFAULT_RETIME_MARGIN = 1e-3
 
-    def retime(self, plan, vehicle: Optional[nat.Vehicle] = None, margin: float = DEFAULT_RETIME_MARGIN, max_passes: int = 4) -> RetimeResult:
+    def retime(self, plan, vehicle: Optional[nat.Vehicle] = None, margin: float = DEFAULT_RETIME_MARGIN, max_passes: int = 4,
+               demand: bool = False) -> RetimeResult:
         """Slow down exactly the missions of `plan` that ask for more than the control law gives (`vehicle`'s max_speed_xy,
         max_ascent, max_descent, max_horiz_accel; None = `uavac_vehicle_default`), by exactly the factor they need
         (`uavac_minsnap_retime_dev`): per pass the rows-free chain at the current per-mission speeds, the audit, and per mission
@@ -1025,7 +1047,13 @@ class Engine:
         derivatives (`plan(..., boundary=...)`) is refused (ValueError): its curve moves when its durations change; so is a `free_times`
         plan, whose durations did not come from a speed.  Missions whose plan
         is singular (or has no rows) keep their speed, report a NaN factor and converged = False; the device flags are left to the
-        caller (`take_flags`)."""
+        caller (`take_flags`).
+        `demand`: False = the four limits above and nothing else.  True = also the limits `Engine.demand` reports on and
+        `scoring.demand_feasibility` judges -- the bank command within max_tilt, no thrust downward, the rotor thrust between
+        min_thrust and max_thrust (`uavac_minsnap_retime_demand_dev`: per pass one more kernel, `Engine.need`'s, and r is the larger of
+        the maximum above and the four slowdown factors of the PlanNeed).  The result then carries `need`, the PlanNeed of the returned
+        plan, and `binding`, per mission the index into `scoring.BINDING_NAMES` of the limit that is nearest in the last audit.  The
+        body rate and the cuboid clearance are not retimed to: the one has no closed form, the other does not move with the timing."""
         torch = self._torch
         wrapper = plan if isinstance(plan, RaggedPlan) else None
         plan = self._coeff_plan(plan, refuse="this RaggedPlan has no batch (plan_collision_free(device_loop=False)): retime "
@@ -1053,10 +1081,22 @@ class Engine:
         factors = torch.empty((B,), dtype=torch.float64, **kw)
         converged = torch.empty((B,), dtype=torch.int32, **kw)
         passes = C.c_int(0)
+        need = binding = None
+        if demand:
+            dlimits = self._demand_limits(V)
+            nblock = torch.empty((nat.NEED_ROWS, B), dtype=torch.float64, **kw)
+            binding = torch.empty((B,), dtype=torch.int32, **kw)
+            need = PlanNeed(*nblock.unbind(0), nblock)
         self._bind_stream()
-        self.ctx.call("uavac_minsnap_retime_dev", _ptr(plan.waypoints), _ptr(s.so), B, m, _ptr(speeds),
-                      float(plan.dt), limits, float(margin), int(max_passes), _ptr(times), _ptr(seg_rows), _ptr(row_offsets),
-                      _ptr(coeffs), _ptr(status), _ptr(first_yaw), _ptr(block), _ptr(factors), _ptr(converged), C.byref(passes))
+        if demand:
+            self.ctx.call("uavac_minsnap_retime_demand_dev", _ptr(plan.waypoints), _ptr(s.so), B, m, _ptr(speeds),
+                          float(plan.dt), limits, dlimits, float(margin), int(max_passes), _ptr(times), _ptr(seg_rows), _ptr(row_offsets),
+                          _ptr(coeffs), _ptr(status), _ptr(first_yaw), _ptr(block), _ptr(nblock), _ptr(factors), _ptr(binding),
+                          _ptr(converged), C.byref(passes))
+        else:
+            self.ctx.call("uavac_minsnap_retime_dev", _ptr(plan.waypoints), _ptr(s.so), B, m, _ptr(speeds),
+                          float(plan.dt), limits, float(margin), int(max_passes), _ptr(times), _ptr(seg_rows), _ptr(row_offsets),
+                          _ptr(coeffs), _ptr(status), _ptr(first_yaw), _ptr(block), _ptr(factors), _ptr(converged), C.byref(passes))
         parts = dict(waypoints=plan.waypoints, times=times, seg_rows=seg_rows, row_offsets=row_offsets, coeffs=coeffs, status=status,
                      traj=None, total_rows=int(row_offsets[-1].item()), first_yaw=first_yaw, velocities=speeds)
         if s.ragged:
@@ -1069,7 +1109,8 @@ class Engine:
             out = RaggedPlan(B, float("nan"), float(plan.dt), wrapper.final_waypoints, row_offsets=out.row_offsets, traj=out.traj,
                              total_rows=out.total_rows, start_positions=wrapper.start_positions, converged=wrapper.converged, batch=out)
         empty = torch.empty((0, B), dtype=torch.int32, **kw)
-        return RetimeResult(out, speeds, factors, int(passes.value), converged != 0, PlanAudit(*block.unbind(0), empty, empty, block))
+        return RetimeResult(out, speeds, factors, int(passes.value), converged != 0, PlanAudit(*block.unbind(0), empty, empty, block),
+                            need, binding)
 
     def cost(self, plan):
         """The snap cost of every mission of a Plan / RaggedBatch (or a RaggedPlan that has its batch) -> (B,) f64 on the device: the

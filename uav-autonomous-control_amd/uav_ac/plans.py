@@ -223,6 +223,19 @@ class PlanDemand:
 
 
 @dataclass
+class PlanNeed:
+    """By how much each mission must be slowed down for the vehicle to be able to give what the plan asks (`Engine.need`, include/uavac.h
+    uavac_minsnap_need_dev): device tensors (B,) f64, per limit the slowdown FACTOR it asks for on its own -- above 1: the plan breaks
+    that limit; 0: no row comes near it -- from maxima over exactly the rows the sampler writes; NaN for a mission with a non-finite
+    sample or without rows.  `uav_ac.scoring.retime_factors(..., need=...)` and `Engine.retime(..., demand=True)` act on it."""
+    tilt: "object"           # the bank command within max_tilt about both axes
+    upright: "object"        # no row asks for thrust downward
+    thrust_max: "object"     # four rotors at max_thrust suffice
+    thrust_min: "object"     # four rotors at min_thrust do not push too hard
+    block: "object" = None   # the [NEED_ROWS][B] block the four rows above are views of
+
+
+@dataclass
 class SeparationAudit:
     """The fleet's audit against itself (`Engine.separation`, include/uavac.h uavac_minsnap_separation_dev): device tensors, per
     mission over the shared row clock of its group.  An excluded mission (no rows, or a coefficient that is not finite) reports NaN /
@@ -325,6 +338,9 @@ class RetimeResult:
     passes: int              # retimings done (0: every mission was inside the limits, or max_passes = 0)
     converged: "object"      # (B,) bool: the mission's last audit asked for no retiming
     audit: PlanAudit         # the audit of `plan` (no cuboids)
+    need: "object" = None    # `retime(demand=True)`: the PlanNeed of `plan`; None otherwise
+    binding: "object" = None  # `retime(demand=True)`: (B,) i32, the index into scoring.BINDING_NAMES of the limit nearest to each mission in
+                              # its last audit (the first of equals; -1: a NaN mission); None otherwise
 
 
 @dataclass

@@ -121,7 +121,87 @@ def _host_i64(x) -> np.ndarray:
     return _host(x, np.int64).reshape(-1)
 
 
-def retime_factors(audit, vehicle=None, margin: float = DEFAULT_RETIME_MARGIN, velocities=None) -> dict:
+NEED_TILT, NEED_UPRIGHT, NEED_THRUST_MAX, NEED_THRUST_MIN = range(nat.NEED_ROWS)                # need rows (include/uavac.h)
+# the terms of the extended retiming rule, in the order `binding` counts them: the audit's four, then the need block's four
+BINDING_NAMES = ("speed_xy", "ascent", "descent", "accel_xy", "tilt", "upright", "thrust_max", "thrust_min")
+
+
+def demand_limits(vehicle=None):
+    """g, max_tilt, Fmax = 4 max_thrust / mass, Fmin = 4 min_thrust / mass (specific thrust, m/s^2) of a `Vehicle` (anything with g,
+    max_tilt, mass, max_thrust, min_thrust; None = `uavac_vehicle_default`) -> four floats: the HOST array `demand_limits` of
+    `uavac_minsnap_need_dev`, checked as the library checks it (ValueError)."""
+    V = nat.Vehicle.default() if vehicle is None else vehicle
+    g, tau, mass = float(V.g), float(V.max_tilt), float(V.mass)
+    if not (np.isfinite(mass) and mass > 0.0):
+        raise ValueError("mass must be finite and > 0")
+    hi, lo = (4.0 * float(V.max_thrust)) / mass, (4.0 * float(V.min_thrust)) / mass
+    if not (np.isfinite(g) and g > 0.0 and np.isfinite(tau) and tau > 0.0):
+        raise ValueError("g and max_tilt must be finite and > 0")
+    if not (np.isfinite(hi) and hi > g):
+        raise ValueError("the vehicle cannot hover: 4 max_thrust / mass must be finite and > g")
+    if not (0.0 <= lo < g):
+        raise ValueError("4 min_thrust / mass must be in [0, g)")
+    D, E = hi * hi - g * g, g * g - lo * lo
+    if not (np.isfinite(D) and D > 0.0 and E > 0.0):
+        raise ValueError("thrust limits too close to g")
+    return g, tau, hi, lo
+
+
+def need_from_rows(rows, row_offsets, vehicle=None):
+    """The slowdown factor each of the vehicle's tilt and thrust limits asks for, per mission, recomputed from SAMPLED rows -- the
+    SPECIFICATION of `uavac_minsnap_need_dev` (csrc/minsnap_need.hip), which is tested against it bit for bit.  NumPy on the host.
+    `rows` (N, 11) as the sampler writes them, missions back to back; `row_offsets` (B + 1,); `vehicle` as `demand_limits` takes it.
+
+    Slowing a mission by k > 1 leaves its curve in place and divides its accelerations by u = k^2.  With tau = max_tilt, t2 = tau tau,
+    D = Fmax Fmax - g g, E = g g - Fmin Fmin (each one rounded operation), per row, every product, sum, difference, fmax and sqrt one
+    rounded operation, in this order:
+        xx = ax ax; yy = ay ay; h = xx + yy; A = h + az az; gz = g az
+        q  = fmax(fmax(xx - t2 h, yy - t2 h), 0)
+        T  = q > 0 ? tau az + sqrt(q) : -inf                tilt:       ax^2 / n2 <= tau^2 and ay^2 / n2 <= tau^2  <=>  u >= T / (tau g)
+        U  = az                                             upright:    g u - az >= 0                              <=>  u >= U / g
+        H  = sqrt(gz gz + A D) - gz                         thrust max: n2(u) <= Fmax^2                            <=>  u >= H / D
+        d  = gz gz - A E
+        Lo = (az > 0 and d >= 0) ? gz + sqrt(d) : -inf      thrust min: n2(u) >= Fmin^2 on the interval that reaches to infinity
+    and per mission (fmax over its rows from -inf; division by a positive constant is monotone, so it comes once, after the maximum):
+        need = sqrt(fmax([max T / (tau g), max U / g, max H / D, max Lo / E], 0))
+    -> (NEED_ROWS, B) f64: 0 tilt, 1 upright, 2 thrust_max, 3 thrust_min; hover gives 0, 0, 0, 0.  A mission with a non-finite position,
+    velocity or acceleration, and one without rows: NaN in all four -- the audit's rule: a singular plan never looks feasible.
+    Known edge: a row in exact free fall with min_thrust = 0 gives upright = 1 and asks for no slowdown, although `demand_feasibility`
+    calls it inverted; with min_thrust > 0 the thrust_min row covers it."""
+    rows = _host(rows)
+    ro = _host_i64(row_offsets)
+    B = len(ro) - 1
+    if rows.ndim != 2 or rows.shape[1] != nat.TRAJ_COLS:
+        raise ValueError(f"rows must be (N, {nat.TRAJ_COLS})")
+    if B < 1 or ro[0] != 0 or ro[-1] != len(rows) or (np.diff(ro) < 0).any():
+        raise ValueError("row_offsets must ascend from 0 to the number of rows")
+    g, tau, hi, lo = demand_limits(vehicle)
+    t2, tg, D, E = tau * tau, tau * g, hi * hi - g * g, g * g - lo * lo
+    ax, ay, az = rows[:, 6], rows[:, 7], rows[:, 8]
+    with np.errstate(all="ignore"):
+        xx, yy = ax * ax, ay * ay
+        h = xx + yy
+        A = h + az * az
+        gz = g * az
+        q = np.fmax(np.fmax(xx - t2 * h, yy - t2 * h), 0.0)
+        T = np.where(q > 0.0, tau * az + np.sqrt(q), -np.inf)
+        H = np.sqrt(gz * gz + A * D) - gz
+        d = gz * gz - A * E
+        Lo = np.where((az > 0.0) & (d >= 0.0), gz + np.sqrt(d), -np.inf)
+    finite = np.isfinite(rows[:, 0:9]).all(axis=1)
+    need = np.full((nat.NEED_ROWS, B), np.nan)
+    over = np.array([tg, g, D, E])
+    for b in range(B):
+        s = slice(int(ro[b]), int(ro[b + 1]))
+        if s.start == s.stop or not finite[s].all():
+            continue
+        peaks = np.array([np.fmax.reduce(x[s], initial=-np.inf) for x in (T, az, H, Lo)])
+        with np.errstate(invalid="ignore"):
+            need[:, b] = np.sqrt(np.fmax(peaks / over, 0.0))
+    return need
+
+
+def retime_factors(audit, vehicle=None, margin: float = DEFAULT_RETIME_MARGIN, velocities=None, need=None) -> dict:
     """By how much each mission of an audited plan must be slowed down to stay inside the limits the control law clips its targets
     to -- the SPECIFICATION of `uavac_minsnap_retime_factors_dev` (csrc/minsnap_retime.hip), which is tested against it bit for bit.
     `audit`: a PlanAudit (or anything with speed_xy, ascent, descent, accel_xy), or the (AUDIT_ROWS, B) block itself; tensors (any
@@ -139,7 +219,13 @@ def retime_factors(audit, vehicle=None, margin: float = DEFAULT_RETIME_MARGIN, v
     distribution (3 m legs at 3 m/s) at dt = 0.01, growing with dt.  With a margin above the gap one pass suffices; the default 1e-3
     costs 0.1 % of cruise speed.
     -> dict of host arrays / ints: factors (B,) f64, retimed (B,) bool, nan (B,) bool, n_retimed, n_nan -- the kernel's two counters
-    -- and, when `velocities` (B,) was given, velocities (B,) f64: the new ones."""
+    -- and, when `velocities` (B,) was given, velocities (B,) f64: the new ones.
+
+    `need`: None (the four limits only, as ever), or the (NEED_ROWS, B) block of `Engine.need` / `need_from_rows`, or a PlanNeed, made
+    with the same `vehicle` -- then the SPECIFICATION of `uavac_minsnap_retime_demand_factors_dev`: with r_audit the maximum above,
+        r = fmax(r_audit, fmax(fmax(need[0], need[1]), fmax(need[2], need[3])))
+    a NaN in either block gives factor NaN, and the dict gains `binding` (B,) i32: the index into `BINDING_NAMES` of the FIRST term that
+    attains r, -1 for a NaN mission; given for every mission, also where r <= 1 (the nearest limit)."""
     V = nat.Vehicle.default() if vehicle is None else vehicle
     limits = [float(V.max_speed_xy), float(V.max_ascent), float(V.max_descent), float(V.max_horiz_accel)]
     margin = float(margin)
@@ -156,13 +242,24 @@ def retime_factors(audit, vehicle=None, margin: float = DEFAULT_RETIME_MARGIN, v
         peaks = [block[1], block[2], block[3], block[4]]
     speed_xy, ascent, descent, accel_xy = (p.reshape(-1) for p in peaks)
     nan = np.isnan(speed_xy) | np.isnan(ascent) | np.isnan(descent) | np.isnan(accel_xy)
+    binding = None
     with np.errstate(invalid="ignore"):
-        r = np.fmax(np.fmax(speed_xy / limits[0], ascent / limits[1]),
-                    np.fmax(descent / limits[2], np.sqrt(accel_xy / limits[3])))
+        terms = [speed_xy / limits[0], ascent / limits[1], descent / limits[2], np.sqrt(accel_xy / limits[3])]
+        r = np.fmax(np.fmax(terms[0], terms[1]), np.fmax(terms[2], terms[3]))
+        if need is not None:
+            block = _host(need.block if hasattr(need, "block") else need)
+            if block.shape != (nat.NEED_ROWS, len(speed_xy)):
+                raise ValueError(f"a need block is [{nat.NEED_ROWS}][B] with the audit's B = {len(speed_xy)}, got {block.shape}")
+            nan = nan | np.isnan(block).any(axis=0)
+            terms += list(block)
+            r = np.fmax(r, np.fmax(np.fmax(block[0], block[1]), np.fmax(block[2], block[3])))
+            binding = np.where(nan, -1, np.argmax(np.stack(terms) == r, axis=0)).astype(np.int32)      # argmax of bools: the first True
         retimed = ~nan & (r > 1.0)
         k = r / (1.0 - margin)
     factors = np.where(nan, np.nan, np.where(retimed, k, 1.0))
     out = {"factors": factors, "retimed": retimed, "nan": nan, "n_retimed": int(retimed.sum()), "n_nan": int(nan.sum())}
+    if binding is not None:
+        out["binding"] = binding
     if velocities is not None:
         v = _host(velocities).reshape(-1).copy()
         v[retimed] = v[retimed] / factors[retimed]
