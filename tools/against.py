@@ -1,4 +1,4 @@
-"""`--against OTHER.so` of the rate tools (separation_rate.py, conflicts_rate.py, flown_separation_rate.py, flown_conflicts_rate.py): the
+"""`--against OTHER.so` of the rate tools (separation_rate.py, conflicts_rate.py, flown_separation_rate.py, flown_conflicts_rate.py, plan_audit_rate.py, retime_rate.py): the
 gate of a change to a kernel that must not change a bit nor cost time.  The same calls through this build (lib/libuavac.so, or the one
 UAVAC_LIB names) and through another build of the same ABI (the parent commit's, say), both loaded privately into one process (RTLD_LOCAL,
 and RTLD_DEEPBIND: a library's calls into itself stay in it even where the tool has made its inputs through `uav_ac`, which loads this

@@ -19,9 +19,10 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "uav-autonomous-control_amd")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "uav-autonomous-control_amd"), os.path.join(ROOT, "tools")]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from against import timed  # noqa: E402
 from bench import missions  # noqa: E402
 from uav_ac import _native as nat  # noqa: E402
 from uav_ac.fleet import Engine  # noqa: E402
@@ -31,16 +32,6 @@ LAB_AABBS = np.array([[3.7, 4.3, 4.0, 10.0, -3.4, -2.8], [10.7, 11.3, 4.0, 10.0,
 B, M, VEL, DT = 65536, 8, 3.0, 0.01
 CUBOIDS = (0, 4, 16)
 NO_ROW = 1 << 40
-
-
-def timed(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def rows_route(eng, plan, g, cub, mission, local):

@@ -27,6 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "uav-autonomous-control_amd"), os.path.join(ROOT, "tools")]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+from against import timed  # noqa: E402
 from bench import missions  # noqa: E402
 from uav_ac import _native as nat  # noqa: E402
 from uav_ac.engine import _ptr  # noqa: E402
@@ -34,16 +35,6 @@ from uav_ac.fleet import Engine  # noqa: E402
 from uav_ac.scoring import acceptance, plan_feasibility  # noqa: E402
 
 VEL, DT, MARGIN, MAX_PASSES = 3.0, 0.01, 1e-3, 4
-
-
-def timed(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def wall(fn):

@@ -7,12 +7,9 @@
 // waypoints are clear of ALL of them is not reported by anything.  Getting the same answers from rows means writing 88 bytes per
 // sample, one hit-sampler pass per cuboid and reductions over all of it.
 //
-// Shape of minsnap_first_yaw.hip: a group of lanes per mission walks the mission's rows a group-width at a time with the sampler's
-// own arithmetic -- the segment of row r from the row counts (walked forward from where the lane stood: rows only grow), t = (r -
-// first row of the segment) * dt, minsnap_eval_row -- no prefix sums, no row buffer.  A lane keeps its segment's 24 coefficients in
-// registers and reloads them only when its row enters another segment.  Every lane carries seven running maxima and, per cuboid,
-// a count and a first index; after the walk the group reduces them with __shfl_xor: max, integer add and min, all exact and
-// independent of order, so the outputs depend neither on the lanes per mission nor on the launch shape or the batch split.
+// Shape: the row walk of row_walk.h -- a group of 16 or 64 lanes per mission (the option "audit_lanes") walks exactly the sampler's
+// rows with the sampler's own arithmetic (minsnap_eval_row).  Every lane carries seven running maxima and, per cuboid, a count and a
+// first index; after the walk the group reduces them with __shfl_xor: max, integer add and min, all exact and independent of order.
 //
 // ROUNDING (part of the contract, include/uavac.h): the squares are separately rounded products and sums (no fused multiply-add:
 // contraction is off in the function, as in minsnap_yaw.h has_heading), the running maximum is taken of the SQUARES and one
@@ -24,7 +21,7 @@
 
 #include "uavac_internal.h"
 #include "minsnap_eval.h"
-#include "mission_walk.h"
+#include "row_walk.h"
 
 #include <cmath>
 #include <limits>
@@ -52,16 +49,6 @@ __device__ __forceinline__ RowPeaks row_peaks(double vx, double vy, double vz, d
     return p;
 }
 
-// 0 when all nine are finite, NaN otherwise (0 * inf and 0 * NaN are NaN; the sum of finite zeros is 0)
-__device__ __forceinline__ double nonfinite_probe(double px, double py, double pz, double vx, double vy, double vz, double ax,
-                                                  double ay, double az) {
-    double z = 0.0 * px;
-    z = fma(0.0, py, z); z = fma(0.0, pz, z);
-    z = fma(0.0, vx, z); z = fma(0.0, vy, z); z = fma(0.0, vz, z);
-    z = fma(0.0, ax, z); z = fma(0.0, ay, z); z = fma(0.0, az, z);
-    return z;
-}
-
 // kLanes (16 or 64) lanes per mission, 64 / kLanes missions per wavefront.  HITS: cuboids were given.
 // Dynamic LDS (HITS only): the cuboids [n_cuboids][6] -- the same for every lane, so a read is one broadcast -- then every lane's
 // own count and first index per cuboid, [n_cuboids][threads] i32 each.  They live there and not in registers because the loop over
@@ -78,37 +65,20 @@ __global__ void __launch_bounds__(64 * kWaves) minsnap_audit_kernel(
     int *count = reinterpret_cast<int *>(lds + 6 * n_cuboids) + threadIdx.x;      // [n_cuboids][kThreads], this lane's column
     int *first = count + n_cuboids * kThreads;                                    // [n_cuboids][kThreads]
     if (HITS) {
-        for (int i = threadIdx.x; i < n_cuboids * 6; i += kThreads) lds[i] = cuboids[i];
+        stage_cuboids<kThreads>(lds, cuboids, n_cuboids);
         for (int q = 0; q < n_cuboids; ++q) { count[q * kThreads] = 0; first[q * kThreads] = kNoHit; }
         __syncthreads();
     }
-    const LaneGroup<kLanes, kWaves> G(B);                    // (dead groups shadow the last mission, walk nothing and write nothing)
-    const int b = G.b, l = G.l;
-    const bool live = G.live;
-    const Mission M = mission_of(seg_offsets, G.shadow, m);
-    const int mb = M.m;
-    const int32_t *rows_of = seg_rows + M.s0;
-    const double *cm = coeffs + (size_t)M.s0 * 24;
-
-    long long total = 0;                                     // the mission's rows: what the sampler's row offsets give it
-    for (int s = 0; s < mb; ++s) total += rows_of[s];
-    const long long n_rows = live ? total : 0;
+    const RowWalk<kLanes, kWaves> W(coeffs, seg_rows, seg_offsets, B, m);
+    const int b = W.b, l = W.l;
+    const bool live = W.live;
+    const long long total = W.total, n_rows = W.n_rows;
 
     const double ninf = -std::numeric_limits<double>::infinity();
     double m_vxy2 = ninf, m_climb = ninf, m_descent = ninf, m_axy2 = ninf, m_up = ninf, m_down = ninf, m_v2 = ninf;
     double bad = 0.0;                                        // becomes NaN with the first non-finite sample
 
-    double c[24];                                            // coefficients of the segment this lane stands in
-    int s = 0, loaded = -1, cnt = rows_of[0];                // this lane's segment, the one in `c`, its row count
-    long long base = 0;                                      // ... and its first row
-    for (long long r = l; r < n_rows; r += kLanes) {
-        seek(rows_of, mb, r, s, base, cnt);
-        if (s != loaded) {
-#pragma unroll
-            for (int k = 0; k < 24; ++k) c[k] = cm[s * 24 + k];
-            loaded = s;
-        }
-        const double t = (double)(int)(r - base) * dt;
+    W.each_row(dt, [&](const double (&c)[24], double t, long long r) {
         double px, py, pz, vx, vy, vz, ax, ay, az;
         minsnap_eval_row<1>(c, t, px, py, pz, vx, vy, vz, ax, ay, az);
         const RowPeaks p = row_peaks(vx, vy, vz, ax, ay, az);
@@ -128,7 +98,7 @@ __global__ void __launch_bounds__(64 * kWaves) minsnap_audit_kernel(
                 }
             }
         }
-    }
+    });
 
     // across the group: max, integer add, min -- exact whatever the order
     const auto peak = [](double a, double o) { return fmax(a, o); };
@@ -162,26 +132,17 @@ __global__ void __launch_bounds__(64 * kWaves) minsnap_audit_kernel(
     }
 }
 
-template <int kLanes>
-void launch(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
-            const double *cuboids, int n_cuboids, double *audit, int32_t *hit_rows, int32_t *first_hit) {
-    const int per_wg = kWaves * (64 / kLanes);
-    const dim3 grid((B + per_wg - 1) / per_wg), block(64 * kWaves);
-    const size_t lds = (size_t)n_cuboids * (6 * sizeof(double) + 2 * sizeof(int) * 64 * kWaves);      // 16 cuboids: 33.5 KB
-    if (n_cuboids > 0)
-        hipLaunchKernelGGL((minsnap_audit_kernel<kLanes, true>), grid, block, lds, ctx->stream, coeffs, seg_rows, seg_offsets, B, m, dt,
-                           cuboids, n_cuboids, audit, hit_rows, first_hit);
-    else
-        hipLaunchKernelGGL((minsnap_audit_kernel<kLanes, false>), grid, block, 0, ctx->stream, coeffs, seg_rows, seg_offsets, B, m, dt,
-                           cuboids, n_cuboids, audit, hit_rows, first_hit);
-}
-
 }  // namespace
 
 int uavac_launch_audit(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                        double dt, const double *cuboids, int n_cuboids, double *audit, int32_t *hit_rows, int32_t *first_hit) {
-    if (ctx->audit_lanes == 64) launch<64>(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, cuboids, n_cuboids, audit, hit_rows, first_hit);
-    else launch<16>(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, cuboids, n_cuboids, audit, hit_rows, first_hit);
-    UAVAC_HIP(ctx, hipGetLastError());
-    return UAVAC_OK;
+    const size_t lds = (size_t)n_cuboids * (6 * sizeof(double) + 2 * sizeof(int) * 64 * kWaves);      // 16 cuboids: 33.5 KB
+    return launch_by_lanes<kWaves>(ctx, B, [&](auto lanes, dim3 grid, dim3 block) {
+        if (n_cuboids > 0)
+            hipLaunchKernelGGL((minsnap_audit_kernel<lanes(), true>), grid, block, lds, ctx->stream, coeffs, seg_rows, seg_offsets, B, m, dt,
+                               cuboids, n_cuboids, audit, hit_rows, first_hit);
+        else
+            hipLaunchKernelGGL((minsnap_audit_kernel<lanes(), false>), grid, block, 0, ctx->stream, coeffs, seg_rows, seg_offsets, B, m, dt,
+                               cuboids, n_cuboids, audit, hit_rows, first_hit);
+    });
 }

@@ -7,10 +7,10 @@
 // the vertical acceleration of the same row, binds long before max_horiz_accel does, and divides by g - az, which a fast plan can drive
 // through zero.  The flight side has these columns (flown_audit.hip: bank_x, bank_y, body_rate, clearance); this is their plan side.
 //
-// Shape of minsnap_audit.hip: a group of 16 or 64 lanes per mission (mission_walk.h, the audit's own option "audit_lanes") walks exactly
-// the sampler's rows -- row r of segment s at t = (r - first row of s) * dt --, a lane keeps its segment's 24 coefficients in registers,
-// and the group reduces at the end: max, min, integer add and a lexicographic minimum of (d2, row), all exact and independent of order,
-// so the outputs depend neither on the lanes per mission nor on the launch shape or the batch split.
+// Shape: the row walk of row_walk.h -- a group of 16 or 64 lanes per mission (the option "audit_lanes") walks exactly the sampler's
+// rows -- and the group reduces at the end: max, min, integer add and a lexicographic minimum of (d2, row), all exact and independent
+// of order.  Of that header's pieces this kernel takes all but each_row: the loop stands here in the kernel's own text, because the
+// sixteen-cuboid launches measured slower through the lambda (profiles/NOTES.md R20).
 //
 // ROUNDING (part of the contract, include/uavac.h): position, velocity and acceleration are the sampler's (the fma chains of
 // minsnap_eval_row), the jerk is that of minsnap_eval_jerk_snap; everything formed from them is separately rounded -- contraction is off
@@ -21,7 +21,7 @@
 // NaN demands, NaN clearances, every index -1 and no inverted row.  A singular plan never looks feasible.
 
 #include "uavac_internal.h"
-#include "mission_walk.h"
+#include "row_walk.h"
 
 #include <cmath>
 #include <limits>
@@ -82,15 +82,6 @@ __device__ __forceinline__ double gap2(const double *x, double px, double py, do
     return (ex * ex + ey * ey) + ez * ez;
 }
 
-// 0 when all twelve are finite, NaN otherwise (0 * inf and 0 * NaN are NaN; the sum of finite zeros is 0)
-__device__ __forceinline__ double nonfinite_probe(const double p[3], const double v[3], const double a[3], const double j[3]) {
-    double z = 0.0 * p[0];
-    z = fma(0.0, p[1], z); z = fma(0.0, p[2], z);
-#pragma unroll
-    for (int x = 0; x < 3; ++x) { z = fma(0.0, v[x], z); z = fma(0.0, a[x], z); z = fma(0.0, j[x], z); }
-    return z;
-}
-
 // kLanes (16 or 64) lanes per mission, 64 / kLanes missions per wavefront.  BOXES: cuboids were given.
 // Dynamic LDS (BOXES only): the cuboids [n_cuboids][6] -- the same for every lane, so a read is one broadcast -- then every lane's own
 // smallest d2 per cuboid, [n_cuboids][threads] f64, and the row that attained it, [n_cuboids][threads] i32.  They live there for the
@@ -107,21 +98,14 @@ __global__ void __launch_bounds__(64 * kWaves) minsnap_demand_kernel(
     double *near2 = lds + 6 * n_cuboids + threadIdx.x;                                    // [n_cuboids][kThreads], this lane's column
     int *near_row = reinterpret_cast<int *>(lds + (6 + kThreads) * n_cuboids) + threadIdx.x;      // [n_cuboids][kThreads]
 
-    const LaneGroup<kLanes, kWaves> G(B);                    // (dead groups shadow the last mission, walk nothing and write nothing)
-    const int b = G.b, l = G.l;
-    const bool live = G.live;
-    const Mission M = mission_of(seg_offsets, G.shadow, m);
-    const int mb = M.m;
-    const int32_t *rows_of = seg_rows + M.s0;
-    const double *cm = coeffs + (size_t)M.s0 * 24;
-
-    long long total = 0;                                     // the mission's rows: what the sampler's row offsets give it
-    for (int s = 0; s < mb; ++s) total += rows_of[s];
-    const long long n_rows = live ? total : 0;
+    const RowWalk<kLanes, kWaves> W(coeffs, seg_rows, seg_offsets, B, m);
+    const int b = W.b, l = W.l;
+    const bool live = W.live;
+    const long long total = W.total, n_rows = W.n_rows;
 
     const double inf = std::numeric_limits<double>::infinity();
     if (BOXES) {
-        for (int i = threadIdx.x; i < n_cuboids * 6; i += kThreads) lds[i] = cuboids[i];
+        stage_cuboids<kThreads>(lds, cuboids, n_cuboids);
         // before any row: (+inf, the lane's first row) -- the lowest row wins a tie, also among rows that are all infinitely far
         for (int q = 0; q < n_cuboids; ++q) { near2[q * kThreads] = inf; near_row[q * kThreads] = l < n_rows ? l : kNoRow; }
         __syncthreads();
@@ -131,6 +115,12 @@ __global__ void __launch_bounds__(64 * kWaves) minsnap_demand_kernel(
     double bad = 0.0;                                        // becomes NaN with the first non-finite sample
     int inv_count = 0, inv_first = kNoRow;
 
+    // RowWalk::each_row's loop, kept as text: through the lambda the launches with sixteen cuboids measured 1.3 % (16 lanes) and 2.2 %
+    // (64 lanes) slower at equal registers and instruction count -- the cuboid loop lands four bytes later (profiles/NOTES.md R20).  A
+    // change to the walk is made there AND here.
+    const int mb = W.mb;
+    const int32_t *rows_of = W.rows_of;
+    const double *cm = W.cm;
     double c[24];                                            // coefficients of the segment this lane stands in
     int s = 0, loaded = -1, cnt = rows_of[0];                // this lane's segment, the one in `c`, its row count
     long long base = 0;                                      // ... and its first row
@@ -148,7 +138,7 @@ __global__ void __launch_bounds__(64 * kWaves) minsnap_demand_kernel(
         m_nmax = fmax(m_nmax, d.n2); m_nmin = fmin(m_nmin, d.n2);
         m_bx2 = fmax(m_bx2, d.bx2); m_by2 = fmax(m_by2, d.by2); m_w2 = fmax(m_w2, d.w2);
         if (d.inverted) { inv_count += 1; inv_first = min(inv_first, (int)r); }
-        bad += nonfinite_probe(p, v, a, j);
+        bad += nonfinite_probe(p[0], p[1], p[2], v[0], v[1], v[2], a[0], a[1], a[2], j[0], j[1], j[2]);
         if (BOXES) {
 #pragma nounroll
             for (int q = 0; q < n_cuboids; ++q) {            // (uniform trip count)
@@ -199,29 +189,18 @@ __global__ void __launch_bounds__(64 * kWaves) minsnap_demand_kernel(
     }
 }
 
-template <int kLanes>
-void launch(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt, double g,
-            const double *cuboids, int n_cuboids, double *demand, int32_t *idemand, double *clearance, int32_t *clearance_row) {
-    const int per_wg = kWaves * (64 / kLanes);
-    const dim3 grid((B + per_wg - 1) / per_wg), block(64 * kWaves);
-    const size_t lds = (size_t)n_cuboids * (6 * sizeof(double) + (sizeof(double) + sizeof(int)) * 64 * kWaves);      // 16 cuboids: 48.75 KB
-    if (n_cuboids > 0)
-        hipLaunchKernelGGL((minsnap_demand_kernel<kLanes, true>), grid, block, lds, ctx->stream, coeffs, seg_rows, seg_offsets, B, m, dt, g,
-                           cuboids, n_cuboids, demand, idemand, clearance, clearance_row);
-    else
-        hipLaunchKernelGGL((minsnap_demand_kernel<kLanes, false>), grid, block, 0, ctx->stream, coeffs, seg_rows, seg_offsets, B, m, dt, g,
-                           cuboids, n_cuboids, demand, idemand, clearance, clearance_row);
-}
-
 }  // namespace
 
 int uavac_launch_demand(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
                         double g, const double *cuboids, int n_cuboids, double *demand, int32_t *idemand, double *clearance,
                         int32_t *clearance_row) {
-    if (ctx->audit_lanes == 64)
-        launch<64>(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, g, cuboids, n_cuboids, demand, idemand, clearance, clearance_row);
-    else
-        launch<16>(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, g, cuboids, n_cuboids, demand, idemand, clearance, clearance_row);
-    UAVAC_HIP(ctx, hipGetLastError());
-    return UAVAC_OK;
+    const size_t lds = (size_t)n_cuboids * (6 * sizeof(double) + (sizeof(double) + sizeof(int)) * 64 * kWaves);      // 16 cuboids: 48.75 KB
+    return launch_by_lanes<kWaves>(ctx, B, [&](auto lanes, dim3 grid, dim3 block) {
+        if (n_cuboids > 0)
+            hipLaunchKernelGGL((minsnap_demand_kernel<lanes(), true>), grid, block, lds, ctx->stream, coeffs, seg_rows, seg_offsets, B, m, dt,
+                               g, cuboids, n_cuboids, demand, idemand, clearance, clearance_row);
+        else
+            hipLaunchKernelGGL((minsnap_demand_kernel<lanes(), false>), grid, block, 0, ctx->stream, coeffs, seg_rows, seg_offsets, B, m, dt,
+                               g, cuboids, n_cuboids, demand, idemand, clearance, clearance_row);
+    });
 }

@@ -15,9 +15,8 @@
 // exact and order-free.  Division by a positive constant is monotone under rounding, so the NUMERATORS are reduced and lane 0 divides
 // once per mission; no row is divided.
 //
-// Shape of minsnap_demand.hip without cuboids: a group of 16 or 64 lanes per mission (mission_walk.h, the option "audit_lanes") walks
-// exactly the sampler's rows, a lane keeps its segment's 24 coefficients in registers, four fmax accumulators start at -inf and the
-// group reduces them with fmax.  No LDS, no scratch.
+// Shape: the row walk of row_walk.h -- a group of 16 or 64 lanes per mission (the option "audit_lanes") walks exactly the sampler's
+// rows --, four fmax accumulators start at -inf and the group reduces them with fmax.  No LDS, no scratch.
 //
 // ROUNDING (part of the contract, include/uavac.h): position, velocity and acceleration are the sampler's (the fma chains of
 // minsnap_eval_row); every product, sum, difference, fmax and sqrt formed from them is ONE rounded operation -- contraction is off in
@@ -29,7 +28,7 @@
 
 #include "uavac_internal.h"
 #include "minsnap_eval.h"
-#include "mission_walk.h"
+#include "row_walk.h"
 
 #include <cmath>
 #include <limits>
@@ -68,55 +67,28 @@ __device__ __forceinline__ double factor_of(double numerator, double denominator
     return sqrt(fmax(numerator / denominator, 0.0));
 }
 
-// 0 when all nine are finite, NaN otherwise (0 * inf and 0 * NaN are NaN; the sum of finite zeros is 0)
-__device__ __forceinline__ double nonfinite_probe(double px, double py, double pz, double vx, double vy, double vz, double ax,
-                                                  double ay, double az) {
-    double z = 0.0 * px;
-    z = fma(0.0, py, z); z = fma(0.0, pz, z);
-    z = fma(0.0, vx, z); z = fma(0.0, vy, z); z = fma(0.0, vz, z);
-    z = fma(0.0, ax, z); z = fma(0.0, ay, z); z = fma(0.0, az, z);
-    return z;
-}
-
 // kLanes (16 or 64) lanes per mission, 64 / kLanes missions per wavefront.
 template <int kLanes>
 __global__ void __launch_bounds__(64 * kWaves) minsnap_need_kernel(
     const double *__restrict__ coeffs, const int32_t *__restrict__ seg_rows, const int64_t *__restrict__ seg_offsets, int B, int m,
     double dt, NeedLimits L, double *__restrict__ need) {
-    const LaneGroup<kLanes, kWaves> G(B);                    // (dead groups shadow the last mission, walk nothing and write nothing)
-    const int b = G.b, l = G.l;
-    const bool live = G.live;
-    const Mission M = mission_of(seg_offsets, G.shadow, m);
-    const int mb = M.m;
-    const int32_t *rows_of = seg_rows + M.s0;
-    const double *cm = coeffs + (size_t)M.s0 * 24;
-
-    long long total = 0;                                     // the mission's rows: what the sampler's row offsets give it
-    for (int s = 0; s < mb; ++s) total += rows_of[s];
-    const long long n_rows = live ? total : 0;
+    const RowWalk<kLanes, kWaves> W(coeffs, seg_rows, seg_offsets, B, m);
+    const int b = W.b, l = W.l;
+    const bool live = W.live;
+    const long long n_rows = W.n_rows;
 
     const double ninf = -std::numeric_limits<double>::infinity();
     double m_tilt = ninf, m_upright = ninf, m_hi = ninf, m_lo = ninf;
     double bad = 0.0;                                        // becomes NaN with the first non-finite sample
 
-    double c[24];                                            // coefficients of the segment this lane stands in
-    int s = 0, loaded = -1, cnt = rows_of[0];                // this lane's segment, the one in `c`, its row count
-    long long base = 0;                                      // ... and its first row
-    for (long long r = l; r < n_rows; r += kLanes) {
-        seek(rows_of, mb, r, s, base, cnt);
-        if (s != loaded) {
-#pragma unroll
-            for (int k = 0; k < 24; ++k) c[k] = cm[s * 24 + k];
-            loaded = s;
-        }
-        const double t = (double)(int)(r - base) * dt;
+    W.each_row(dt, [&](const double (&c)[24], double t, long long) {
         double px, py, pz, vx, vy, vz, ax, ay, az;
         minsnap_eval_row<1>(c, t, px, py, pz, vx, vy, vz, ax, ay, az);
         const RowNeed n = row_need(ax, ay, az, L);
         m_tilt = fmax(m_tilt, n.tilt); m_upright = fmax(m_upright, n.upright);
         m_hi = fmax(m_hi, n.hi); m_lo = fmax(m_lo, n.lo);
         bad += nonfinite_probe(px, py, pz, vx, vy, vz, ax, ay, az);
-    }
+    });
 
     // across the group: max -- exact whatever the order
     const auto peak = [](double x, double o) { return fmax(x, o); };
@@ -134,22 +106,11 @@ __global__ void __launch_bounds__(64 * kWaves) minsnap_need_kernel(
     }
 }
 
-template <int kLanes>
-void launch(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
-            const NeedLimits &L, double *need) {
-    const int per_wg = kWaves * (64 / kLanes);
-    hipLaunchKernelGGL((minsnap_need_kernel<kLanes>), dim3((B + per_wg - 1) / per_wg), dim3(64 * kWaves), 0, ctx->stream, coeffs, seg_rows,
-                       seg_offsets, B, m, dt, L, need);
-}
-
 }  // namespace
 
 int uavac_launch_need(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
                       const NeedLimits &limits, double *need) {
-    if (ctx->audit_lanes == 64)
-        launch<64>(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, limits, need);
-    else
-        launch<16>(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, limits, need);
-    UAVAC_HIP(ctx, hipGetLastError());
-    return UAVAC_OK;
+    return launch_by_lanes<kWaves>(ctx, B, [&](auto lanes, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((minsnap_need_kernel<lanes()>), grid, block, 0, ctx->stream, coeffs, seg_rows, seg_offsets, B, m, dt, limits, need);
+    });
 }

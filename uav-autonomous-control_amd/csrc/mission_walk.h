@@ -6,8 +6,12 @@
 //   group_reduce                one __shfl_xor tree over such a group
 //   block_inclusive_scan_256    the workgroup scan behind every per-mission total
 //   kMaxClock / clamped_start   the bound of the group clock and the start row inside it
-// Only indexing, the walk and the reductions: every kernel keeps its own loads and its own arithmetic (and its own contraction mode --
-// nothing here multiplies).  Two kernels measured slower with these pieces than with their own text and keep it (profiles/NOTES.md
+// and, in row_walk.h beside it (included only by the three kernels that walk a mission's sampled rows without writing them: the plan
+// audit, the plan demand, the slowdown need):
+//   RowWalk / each_row          the walk itself: seek, the 24 coefficients of the row's segment reloaded on a change, the row time
+//   nonfinite_probe, stage_cuboids, launch_by_lanes
+// Only indexing, the walk and the reductions: every kernel keeps its own arithmetic (and its own contraction mode -- nothing here
+// multiplies; row_walk.h multiplies the row time only) and, but for the row walk's coefficients, its own loads.  Two kernels measured slower with these pieces than with their own text and keep it (profiles/NOTES.md
 // R17-3): the cost kernel of minsnap_timeopt.hip takes mission_of only, minsnap_first_yaw.hip nothing.
 #pragma once
 

@@ -432,13 +432,7 @@ class Engine:
         plan = self._coeff_plan(plan)
         B = int(plan.B)
         kw = dict(device=self.device)
-        cub = None
-        n = 0
-        if obstacles is not None:
-            cub = self._dev(obstacles, torch.float64).reshape(-1, 6)
-            n = int(cub.shape[0])
-            if n > nat.AUDIT_MAX_CUBOIDS:
-                raise ValueError(f"{n} cuboids; at most {nat.AUDIT_MAX_CUBOIDS} per audit")
+        cub, n = (None, 0) if obstacles is None else self._cuboids(obstacles, "audit")
         block = torch.empty((nat.AUDIT_ROWS, B), dtype=torch.float64, **kw)
         hit_rows = torch.empty((n, B), dtype=torch.int32, **kw)
         first_hit = torch.empty((n, B), dtype=torch.int32, **kw)
