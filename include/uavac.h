@@ -174,7 +174,8 @@ int uavac_clock_probe_dev(uavac_ctx *ctx, int window_us, int64_t *stamps);
  * (default: sized from B and K) or 1 .. UAVAC_FLOWN_AUDIT_MAX_SPLIT = workgroups that share the ticks of one window of 64 vehicles in
  * uavac_flown_audit_dev (same results).  "conflict_slots": 0 (default: 64) or 1 .. 64 = j-tile slots per mission and discovery round
  * of the conflict lists (uavac_minsnap_conflict_offsets_dev, uavac_minsnap_conflicts_dev, uavac_flown_conflict_offsets_dev,
- * uavac_flown_conflicts_dev; same results, less scratch, more rounds).
+ * uavac_flown_conflicts_dev; same results, less scratch, more rounds).  "search_block": 0 (default: 64), 64, 128 or 256 = missions per
+ * block of uavac_minsnap_stagger_wide_dev and uavac_minsnap_layer_wide_dev (same results).
  * Defaults from the environment (UAVAC_ROLLOUT_ALIGN, UAVAC_YAW_GROUP, UAVAC_SAMPLER_WAVES, UAVAC_SAMPLER_GROUP) at uavac_create.
  * ONE option is not a tuning knob but part of the log layout: "log_pitch" = P doubles per log row,
  * 0 (default) = B.  With P >= B the rollouts write state_log [K][13][P] and cmd_log [K][12][P]
@@ -472,6 +473,27 @@ int uavac_minsnap_stagger_dev(uavac_ctx *ctx, const double *coeffs, const int32_
                               double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius,
                               int step, int max_steps, int32_t *istag);
 
+/* STAGGER FOR GROUPS OF ANY SIZE: uavac_minsnap_stagger_dev's rule without UAVAC_STAGGER_MAX_GROUP (csrc/minsnap_stagger_wide.hip,
+ * csrc/fleet_wide.h).  Every argument means what it means there, and istag [UAVAC_STAGGER_ROWS][B] holds the same integers: on a batch
+ * whose groups all fit the narrow call the two calls' outputs are equal, and for any group sizes they are exactly what NumPy gives on
+ * the sampled rows (uav_ac.scoring.stagger_from_rows(..., max_group = group_cap)).
+ * group_cap >= 1 is the caller's bound on the largest group: a group above it (its offsets are on the device) is not examined -- base
+ * start, -2 and 0 for all of its missions, sticky flag 0 --, as a group above UAVAC_STAGGER_MAX_GROUP is there.  group_offsets == NULL
+ * means one group of all B.
+ * HOW.  A group is cut into blocks of 64, 128 or 256 consecutive missions (option "search_block"; same results).  Per block two
+ * launches: a SEED kernel, parallel over the whole chip, computes for every candidate of the block's missions whether it meets a
+ * mission of an earlier block at its granted start -- one bit per (mission, candidate) in scratch --, then the narrow call's search
+ * decides the block with one workgroup per group, its candidates' "met somebody" bits starting from the seed.  A candidate is clear
+ * iff no partner decided before it is inside the radius at any clock row; an OR does not care how it is split, so the outputs depend
+ * neither on the block size nor on the launch shape.  2 ceil(min(group_cap, B) / block) launches (the pre-pass, a search per block, a
+ * seed per block but the first) and two memsets on the ctx stream, no host read; a launch for a block that no group has costs an empty launch, so give the smallest group_cap you can.
+ * Scratch from the ctx arena: 8 + 8 (max_steps / 64 + 1) bytes per mission and 8 per group; UAVAC_ENOMEM when it does not fit.
+ * UAVAC_EINVAL before anything is enqueued: everything uavac_minsnap_stagger_dev refuses but its group limit, group_cap < 1,
+ * group_offsets == NULL with B > group_cap. */
+int uavac_minsnap_stagger_wide_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                   double dt, const int64_t *group_offsets, int G, int group_cap, const int32_t *start_rows,
+                                   double radius, int step, int max_steps, int32_t *istag);
+
 /* DELAY AS A PLAN TRANSFORM: how start rows -- istag[0] of uavac_minsnap_stagger_dev, or any start_rows of the separation audit -- are
  * flown.  Mission b of the input (coeffs / times / seg_rows / seg_offsets / B / m / dt as in uavac_minsnap_audit_dev: seg_offsets NULL =
  * uniform, otherwise ragged with segment counts clamped to 1 .. m) has m_b segments and start row S_b = start_rows[b] (i32, device,
@@ -572,6 +594,24 @@ int uavac_minsnap_layer_obs_dev(uavac_ctx *ctx, const double *coeffs, const int3
                                 double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double delta_x,
                                 double delta_y, double delta_z, int max_steps, const double *cuboids, int n_cuboids, int32_t *ilayer,
                                 double *offsets);
+
+/* LAYER FOR GROUPS OF ANY SIZE: uavac_minsnap_layer_obs_dev's rule without UAVAC_LAYER_MAX_GROUP (csrc/minsnap_layer_wide.hip,
+ * csrc/fleet_wide.h), by the decomposition of uavac_minsnap_stagger_wide_dev: per block of 64, 128 or 256 missions (option
+ * "search_block"; same results) a seed kernel marks the candidate layers that meet a mission of an earlier block on its granted
+ * layer, then the narrow call's search decides the block.  The cuboids are the search's business alone: a blocked candidate is
+ * refused whatever its seed bit says, and `blocked` counts the refusals only.  Every argument means what it means in
+ * uavac_minsnap_layer_obs_dev, ilayer is [UAVAC_LAYER_OBS_ROWS][B] and offsets [B][3] as there, and on a batch whose groups all fit the
+ * narrow call the outputs are equal bit for bit; with n_cuboids = 0 (cuboids may be NULL) rows 0-2 and the offsets are
+ * uavac_minsnap_layer_dev's and row 3 is 0.  For any group sizes: exactly what NumPy gives on the sampled rows of the shifted plans
+ * (uav_ac.scoring.layer_obstacles_from_rows(..., max_group = group_cap)).
+ * group_cap, the launches, the scratch and UAVAC_ENOMEM as in uavac_minsnap_stagger_wide_dev; a group above group_cap reports 0 / -2 /
+ * 0 / 0 for all of its missions and raises sticky flag 0.
+ * UAVAC_EINVAL before anything is enqueued: everything uavac_minsnap_layer_obs_dev refuses but its group limit, group_cap < 1,
+ * group_offsets == NULL with B > group_cap. */
+int uavac_minsnap_layer_wide_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                 double dt, const int64_t *group_offsets, int G, int group_cap, const int32_t *start_rows, double radius,
+                                 double delta_x, double delta_y, double delta_z, int max_steps, const double *cuboids, int n_cuboids,
+                                 int32_t *ilayer, double *offsets);
 
 /* OFFSET AS A PLAN TRANSFORM: how the granted layers are flown and audited.  out_coeffs = coeffs (the same layout: [B][8 m][3] uniform
  * with seg_offsets == NULL, or [total_segments][8][3] ragged with seg_offsets [B+1]; total_segments is ignored for a uniform batch)

@@ -25,6 +25,12 @@
 // the sticky flag.  Every decision is a comparison d^2 < r^2 on the audit's arithmetic, the horizon only has to reach the row past
 // which both stand still (a longer one gives the same answer), so the outputs depend neither on the tile or chunk sizes nor on what
 // else is in the batch.
+//   fleet_search<Policy, true>   the BLOCK-WISE form (fleet_wide.h: groups of any size): a launch decides block k of every group --
+//                          `blk` consecutive missions -- and nothing else.  `granted[]`, the j-tiles and the walk are the block's;
+//                          `earlier` and the horizon come from the group's carry, which the launch of block k - 1 left in scratch;
+//                          what the missions of the blocks before did to the candidates arrives as the start value of `round_hit`
+//                          (the seed kernel of fleet_wide.h, one bit per candidate).  The narrow instantiations compile to what
+//                          they compiled to before the form existed: every difference is an `if constexpr`.
 #pragma once
 
 #include "fleet_clock.h"
@@ -74,6 +80,7 @@ struct OnLayer {
 //   start_of           the clock row at which a mission with base start si and that grant starts
 //   horizon            the row past which the mission on any candidate up to q_last, and everybody decided before (h_prev), holds a last row
 //   record             the outputs of mission i
+//   grants             row 0 of those outputs, where the grants of the missions decided by earlier LAUNCHES are read (fleet_wide.h)
 struct Delay {
     static constexpr bool kMoves = false, kObs = false;
     static constexpr int kMaxGroup = UAVAC_STAGGER_MAX_GROUP;
@@ -86,6 +93,7 @@ struct Delay {
     __device__ __forceinline__ void record(size_t B, int i, int granted, int steps, int earlier, int) const {
         istag[i] = granted; istag[B + i] = steps; istag[2 * B + i] = earlier;
     }
+    __device__ __forceinline__ const int32_t *grants() const { return istag; }
 };
 
 template <bool OBS>
@@ -105,18 +113,28 @@ struct OnLayers {
         double *o = offsets + 3 * (size_t)i;
         o[0] = layer_offset(granted, delta.x); o[1] = layer_offset(granted, delta.y); o[2] = layer_offset(granted, delta.z);
     }
+    __device__ __forceinline__ const int32_t *grants() const { return ilayer; }
 };
 using Layer = OnLayers<false>;
 using LayerObs = OnLayers<true>;
 
+// What a launch of the block-wise form knows beside the search's arguments (fleet_wide.h lays the scratch out and fills it).
+struct Block {
+    int k, blk, group_cap;                                   // the block's number; missions per block (a multiple of kTile, at most
+                                                             // kMaxGroup); the caller's bound on a group: a larger one is not examined
+    unsigned long long *seed;                                // [B][words]: bit l of seed[i][r] = candidate 64 r + l of mission i meets a
+    int words;                                               // mission of an earlier block of its group
+    int32_t *carry;                                          // [groups][2]: the included missions decided so far, and their horizon
+};
+
 // ------------------------------------------------------------------------------------------------------------------ the decisions
 // (the body of a __global__ kernel of kThreads threads and one workgroup per group: see the head of this file)
-template <class Policy>
+template <class Policy, bool WIDE = false>
 __device__ __forceinline__ void fleet_search(const Policy pol, const double *__restrict__ coeffs, const int32_t *__restrict__ seg_rows,
                                              const int64_t *__restrict__ seg_offsets, int B, int m, double dt,
                                              const int64_t *__restrict__ group_offsets, const int32_t *__restrict__ n_rows,
                                              const int32_t *__restrict__ start, double r2, int max_steps, const double *__restrict__ cuboids,
-                                             int n_cuboids, int32_t *__restrict__ flags) {
+                                             int n_cuboids, int32_t *__restrict__ flags, const Block wide = {}) {
     constexpr bool OBS = Policy::kObs;
     __shared__ double tile[kWaves * kRegion];
     __shared__ int granted[Policy::kMaxGroup];               // what was decided so far, by position in the group
@@ -128,9 +146,14 @@ __device__ __forceinline__ void fleet_search(const Policy pol, const double *__r
     int g0, g1;
     group_range(group_offsets, blockIdx.x, B, g0, g1);
     if (g1 == g0) return;
-    if (g1 - g0 > Policy::kMaxGroup) {                       // cannot be refused by the host: its missions stay "not examined", and flag 0
+    if (g1 - g0 > (WIDE ? wide.group_cap : Policy::kMaxGroup)) {       // cannot be refused by the host: its missions stay "not examined", and flag 0
         if (threadIdx.x == 0) atomicOr(&flags[0], 1);
         return;
+    }
+    int b0 = g0, b1 = g1;                                    // the missions this launch decides; WIDE: block k of the group, if it has one
+    if constexpr (WIDE) {
+        b0 = g0 + wide.k * wide.blk; b1 = min(g1, b0 + wide.blk);
+        if (b0 >= g1) return;
     }
     const int nc = OBS ? min(max(n_cuboids, 0), kMaxCuboids) : 0;      // (the host refuses anything else: LDS is never left)
     if (OBS) {                                               // (visible to everybody behind the first barrier of the first round)
@@ -140,10 +163,14 @@ __device__ __forceinline__ void fleet_search(const Policy pol, const double *__r
 
     int turn = 0;
     int h_prev = 0, earlier = 0;                             // the row past which every decided mission holds its last row; how many there are
-    for (int i = g0; i < g1; ++i) {                          // (uniform: every thread walks the same missions and takes the same decisions)
+    if constexpr (WIDE) {                                    // (what the launch of the block before left; zeros ahead of block 0)
+        earlier = __builtin_amdgcn_readfirstlane(wide.carry[2 * blockIdx.x]);
+        h_prev = __builtin_amdgcn_readfirstlane(wide.carry[2 * blockIdx.x + 1]);
+    }
+    for (int i = b0; i < b1; ++i) {                          // (uniform: every thread walks the same missions and takes the same decisions)
         const int ni = __builtin_amdgcn_readfirstlane(n_rows[i]), si = __builtin_amdgcn_readfirstlane(start[i]);
         if (ni == 0) {                                       // excluded: nobody is checked against it (its record is the pre-pass's)
-            if (threadIdx.x == 0) granted[i - g0] = pol.grant(si, 0);
+            if (threadIdx.x == 0) granted[i - b0] = pol.grant(si, 0);
             continue;
         }
         const bool search = OBS || earlier > 0;              // without cuboids the first included mission of a group stays as it is
@@ -152,7 +179,7 @@ __device__ __forceinline__ void fleet_search(const Policy pol, const double *__r
             const Mission Mi = mission_of(seg_offsets, i, m);
             const int32_t *irows = seg_rows + Mi.s0;
             const double *icm = coeffs + (size_t)Mi.s0 * 24;
-            const int n_tiles = (OBS && earlier == 0) ? 0 : (i - g0 + kTile - 1) / kTile;     // (nobody before it: the cuboids alone decide)
+            const int n_tiles = (OBS && earlier == 0) ? 0 : (i - b0 + kTile - 1) / kTile;     // (nobody before it: the cuboids alone decide)
             for (int q0 = 0; q0 <= max_steps && steps < 0; q0 += kTile) {
                 const int n_live = min(kTile, max_steps - q0 + 1);                    // candidates of this round (the lanes past them shadow the last)
                 const unsigned long long live = n_live == kTile ? ~0ull : (1ull << n_live) - 1ull;
@@ -162,8 +189,8 @@ __device__ __forceinline__ void fleet_search(const Policy pol, const double *__r
                 turn ^= 1;
                 unsigned long long &round_hit = round_hits[turn];
                 unsigned long long &round_block = round_blocks[OBS ? turn : 0];
-                if (threadIdx.x == 0) {
-                    round_hit = 0;
+                if (threadIdx.x == 0) {                      // (WIDE: the candidates that a mission of an earlier block is in the way of)
+                    round_hit = WIDE ? wide.seed[(size_t)i * wide.words + q0 / kTile] & live : 0;
                     if (OBS) round_block = 0;
                 }
                 __syncthreads();                             // (also: `granted` of the previous mission is visible from here)
@@ -190,7 +217,7 @@ __device__ __forceinline__ void fleet_search(const Policy pol, const double *__r
                 bool hit = false;
                 unsigned long long told = 0;                 // what this wavefront has put into round_hit
                 for (int t = 0; t < n_tiles; ++t) {
-                    const int j0 = g0 + t * kTile;
+                    const int j0 = b0 + t * kTile;
                     const int n_val = min(kTile, i - j0);    // partners of this tile: the missions before i
                     const int n_pad = (n_val + kUnroll - 1) / kUnroll * kUnroll;
                     const bool jvalid = lane < n_val;
@@ -198,7 +225,7 @@ __device__ __forceinline__ void fleet_search(const Policy pol, const double *__r
                     const Mission Mj = mission_of(seg_offsets, jb, m);
                     const int32_t *jrows = seg_rows + Mj.s0;
                     const double *jcm = coeffs + (size_t)Mj.s0 * 24;
-                    const int nj = jvalid ? n_rows[jb] : 0, sb = start[jb], gj = granted[jb - g0];
+                    const int nj = jvalid ? n_rows[jb] : 0, sb = start[jb], gj = granted[jb - b0];
                     const int sj = pol.start_of(sb, gj);
                     int js = 0, jbase = 0, jcnt = jrows[0];
                     int is = 0, ibase = 0, icnt = irows[0];
@@ -230,16 +257,19 @@ __device__ __forceinline__ void fleet_search(const Policy pol, const double *__r
         }
         const int gi = pol.grant(si, max(steps, 0));         // (unresolved: the mission as it is)
         if (threadIdx.x == 0) {
-            granted[i - g0] = gi;
+            granted[i - b0] = gi;
             pol.record((size_t)B, i, gi, steps, earlier, blocked);
         }
         h_prev = max(h_prev, pol.start_of(si, gi) + ni);
         ++earlier;
     }
+    if constexpr (WIDE) {                                    // for the launches of block k + 1
+        if (threadIdx.x == 0) { wide.carry[2 * blockIdx.x] = earlier; wide.carry[2 * blockIdx.x + 1] = h_prev; }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the layers' kernels
-// (needed by two object files, minsnap_layer.o and minsnap_layer_obs.o, hence here; stagger's are in minsnap_stagger.hip)
+// (needed by two object files, minsnap_layer.o and minsnap_layer_obs.o, hence here; stagger's are in minsnap_stagger.hip and stagger_prepass.h)
 // The pre-pass (fleet_clock.h) and the record of a mission that is never examined -- layer 0 / -2 / 0, OBS: blocked 0, and the offset
 // of layer 0 -- which the decision kernel overwrites for everybody it decides.
 template <bool OBS>

@@ -16,21 +16,11 @@
 // The structure of the search, its rounding and why its outputs depend on nothing but the contract are described there.
 
 #include "fleet_search.h"
+#include "stagger_prepass.h"
 
 namespace {
 
-// ------------------------------------------------------------------------------------------------------------------ pre-pass
-// (fleet_clock.h) and the record of a mission that is never examined, until the decision kernel says otherwise
-__global__ void __launch_bounds__(kThreads) stagger_prepass_kernel(const double *__restrict__ coeffs, const int32_t *__restrict__ seg_rows,
-                                                                   const int64_t *__restrict__ seg_offsets, int B, int m,
-                                                                   const int32_t *__restrict__ start_rows, int32_t *__restrict__ n_rows,
-                                                                   int32_t *__restrict__ start, int32_t *__restrict__ istag,
-                                                                   int32_t *__restrict__ flags) {
-    int b, s;
-    if (!prepass_mission(coeffs, seg_rows, seg_offsets, B, m, start_rows, n_rows, start, flags, b, s)) return;
-    istag[b] = s; istag[(size_t)B + b] = -2; istag[2 * (size_t)B + b] = 0;
-}
-
+// (the pre-pass is stagger_prepass.h's: the block-wise form, minsnap_stagger_wide.hip, launches it too)
 // ------------------------------------------------------------------------------------------------------------------ the decisions
 __global__ void __launch_bounds__(kThreads, 3) minsnap_stagger_kernel(
     const double *__restrict__ coeffs, const int32_t *__restrict__ seg_rows, const int64_t *__restrict__ seg_offsets, int B, int m, double dt,

@@ -279,8 +279,8 @@ int plan_chain(uavac_ctx *ctx, const double *wp, int B, int m, Vel velocity, dou
 // The options of uavac_set_option: where each is kept, which values it takes and what a refusal says.
 //   kOneOf   one of the values a[] (zero ends the list: no set here holds it)      kClamp   every value is taken, clamped into a[0] .. a[1]
 //   kRange   a[0] <= value <= a[1]                                                kBool    every value is taken: 0 or not
-//   kPad8    kRange, rounded down to a multiple of 8
-enum class Rule { kOneOf, kRange, kClamp, kBool, kPad8 };
+//   kPad8    kRange, rounded down to a multiple of 8                                   kAutoOr  0 (automatic), or kOneOf
+enum class Rule { kOneOf, kRange, kClamp, kBool, kPad8, kAutoOr };
 struct Option {
     const char *name;
     int uavac_ctx::*field;
@@ -294,6 +294,7 @@ const Option kOptions[] = {
     {"audit_lanes", &uavac_ctx::audit_lanes, Rule::kOneOf, {16, 64}, "audit_lanes is 16 or 64"},
     {"separation_split", &uavac_ctx::separation_split, Rule::kRange, {0, UAVAC_SEP_MAX_SPLIT},
      "separation_split is 0 (automatic) or 1 .. UAVAC_SEP_MAX_SPLIT"},
+    {"search_block", &uavac_ctx::search_block, Rule::kAutoOr, {64, 128, 256}, "search_block is 0 (default), 64, 128 or 256"},
     {"conflict_slots", &uavac_ctx::conflict_slots, Rule::kRange, {0, 64}, "conflict_slots is 0 (automatic) or 1 .. 64"},
     {"flown_audit_split", &uavac_ctx::flown_audit_split, Rule::kRange, {0, UAVAC_FLOWN_AUDIT_MAX_SPLIT},
      "flown_audit_split is 0 (automatic) or 1 .. UAVAC_FLOWN_AUDIT_MAX_SPLIT"},
@@ -324,7 +325,7 @@ bool apply_option(uavac_ctx *ctx, const Option &o, int value) {
     bool listed = false;
     for (int v : o.a) listed |= v != 0 && v == value;
     const bool ranged = o.rule == Rule::kRange || o.rule == Rule::kPad8;
-    if ((o.rule == Rule::kOneOf && !listed) || (ranged && (value < o.a[0] || value > o.a[1]))) return false;
+    if ((o.rule == Rule::kOneOf && !listed) || (o.rule == Rule::kAutoOr && value != 0 && !listed) || (ranged && (value < o.a[0] || value > o.a[1]))) return false;
     if (o.rule == Rule::kPad8) value &= ~7;
     if (o.rule == Rule::kClamp) value = value < o.a[0] ? o.a[0] : (value > o.a[1] ? o.a[1] : value);
     if (o.rule == Rule::kBool) value = value ? 1 : 0;
@@ -968,17 +969,41 @@ int uavac_minsnap_conflicts_dev(uavac_ctx *ctx, const double *coeffs, const int3
                                   pair_d, pair_i);
 }
 
-int uavac_minsnap_stagger_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
-                              double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, int step,
-                              int max_steps, int32_t *istag) {
-    UAVAC_ENTER(ctx);
+// what uavac_minsnap_stagger_dev and uavac_minsnap_stagger_wide_dev refuse alike
+static int check_stagger_args(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, int B, int m, double dt, const int64_t *group_offsets,
+                              int G, double radius, int step, int max_steps, const int32_t *istag) {
     if (int rc = check_pair_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, istag != nullptr)) return rc;
     if (step < 1) return uavac_fail(ctx, UAVAC_EINVAL, "step must be >= 1");
     if (max_steps < 0 || max_steps > UAVAC_STAGGER_MAX_STEPS) return uavac_fail(ctx, UAVAC_EINVAL, "max_steps must be in [0, UAVAC_STAGGER_MAX_STEPS]");
     if ((long long)step * max_steps > (1LL << 29)) return uavac_fail(ctx, UAVAC_EINVAL, "step * max_steps must not exceed 2^29 rows");
+    return UAVAC_OK;
+}
+
+int uavac_minsnap_stagger_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                              double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, int step,
+                              int max_steps, int32_t *istag) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_stagger_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, step, max_steps, istag)) return rc;
     if (!group_offsets && B > UAVAC_STAGGER_MAX_GROUP)
         return uavac_fail(ctx, UAVAC_EINVAL, "one group of all B: B must not exceed UAVAC_STAGGER_MAX_GROUP");
     return uavac_launch_stagger(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, step, max_steps, istag);
+}
+
+// what the two block-wise searches refuse beside their narrow calls' lists
+static int check_group_cap(uavac_ctx *ctx, int B, const int64_t *group_offsets, int group_cap) {
+    if (group_cap < 1) return uavac_fail(ctx, UAVAC_EINVAL, "group_cap must be >= 1");
+    if (!group_offsets && B > group_cap) return uavac_fail(ctx, UAVAC_EINVAL, "one group of all B: B must not exceed group_cap");
+    return UAVAC_OK;
+}
+
+int uavac_minsnap_stagger_wide_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                   double dt, const int64_t *group_offsets, int G, int group_cap, const int32_t *start_rows, double radius,
+                                   int step, int max_steps, int32_t *istag) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_stagger_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, step, max_steps, istag)) return rc;
+    if (int rc = check_group_cap(ctx, B, group_offsets, group_cap)) return rc;
+    return uavac_launch_stagger_wide(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, group_cap, start_rows, radius, step,
+                                     max_steps, istag);
 }
 
 int uavac_minsnap_delay_offsets_dev(uavac_ctx *ctx, const int64_t *seg_offsets, int B, int m, const int32_t *start_rows,
@@ -1002,14 +1027,14 @@ int uavac_minsnap_delay_dev(uavac_ctx *ctx, const double *coeffs, const double *
                               out_seg_rows);
 }
 
-// what uavac_minsnap_layer_dev and uavac_minsnap_layer_obs_dev refuse alike
+// what uavac_minsnap_layer_dev and uavac_minsnap_layer_obs_dev refuse alike, and uavac_minsnap_layer_wide_dev (`wide`) but for the group limit
 static int check_layer_args(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, int B, int m, double dt, const int64_t *group_offsets,
                             int G, double radius, double delta_x, double delta_y, double delta_z, int max_steps, const int32_t *ilayer,
-                            const double *offsets) {
+                            const double *offsets, bool wide = false) {
     if (int rc = check_pair_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, ilayer && offsets)) return rc;
     if (!std::isfinite(delta_x) || !std::isfinite(delta_y) || !std::isfinite(delta_z)) return uavac_fail(ctx, UAVAC_EINVAL, "delta must be finite");
     if (max_steps < 0 || max_steps > UAVAC_LAYER_MAX_STEPS) return uavac_fail(ctx, UAVAC_EINVAL, "max_steps must be in [0, UAVAC_LAYER_MAX_STEPS]");
-    if (!group_offsets && B > UAVAC_LAYER_MAX_GROUP)
+    if (!wide && !group_offsets && B > UAVAC_LAYER_MAX_GROUP)
         return uavac_fail(ctx, UAVAC_EINVAL, "one group of all B: B must not exceed UAVAC_LAYER_MAX_GROUP");
     return UAVAC_OK;
 }
@@ -1035,6 +1060,21 @@ int uavac_minsnap_layer_obs_dev(uavac_ctx *ctx, const double *coeffs, const int3
     if (n_cuboids > 0 && !cuboids) return uavac_fail(ctx, UAVAC_EINVAL, "cuboids must be given when n_cuboids > 0");
     return uavac_launch_layer_obs(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, radius, delta_x, delta_y, delta_z,
                                   max_steps, cuboids, n_cuboids, ilayer, offsets);
+}
+
+int uavac_minsnap_layer_wide_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                 double dt, const int64_t *group_offsets, int G, int group_cap, const int32_t *start_rows, double radius,
+                                 double delta_x, double delta_y, double delta_z, int max_steps, const double *cuboids, int n_cuboids,
+                                 int32_t *ilayer, double *offsets) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_layer_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, delta_x, delta_y, delta_z, max_steps, ilayer, offsets,
+                                  true))
+        return rc;
+    if (int rc = check_n_cuboids(ctx, n_cuboids)) return rc;
+    if (n_cuboids > 0 && !cuboids) return uavac_fail(ctx, UAVAC_EINVAL, "cuboids must be given when n_cuboids > 0");
+    if (int rc = check_group_cap(ctx, B, group_offsets, group_cap)) return rc;
+    return uavac_launch_layer_wide(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, group_cap, start_rows, radius, delta_x, delta_y,
+                                   delta_z, max_steps, cuboids, n_cuboids, ilayer, offsets);
 }
 
 int uavac_minsnap_shift_dev(uavac_ctx *ctx, const double *coeffs, const int64_t *seg_offsets, int B, int m, int64_t total_segments,

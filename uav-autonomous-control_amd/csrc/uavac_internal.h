@@ -35,6 +35,7 @@ struct uavac_ctx {
     int yaw_group = 8;               // tuning: chunks of the sampler's dense yaw column that leave together (1, 4, 8, 16)
     int audit_lanes = 16;            // tuning: lanes of a wavefront that walk one mission in the plan audit: 16 or 64 (minsnap_audit.hip; same results)
     int separation_split = 0;        // tuning: workgroups that share the j-tiles of one window of the separation audits (minsnap_separation.hip, flown_separation.hip; same results); 0 = sized from the batch
+    int search_block = 0;            // tuning: missions per block of the block-wise prioritised search (fleet_wide.h; same results): 64, 128, 256; 0 = the default there
     int conflict_slots = 0;          // tuning: j-tile slots per mission and round of the conflict list's discovery (minsnap_conflicts.hip; same results); 0 = 64
     int flown_audit_split = 0;       // tuning: workgroups that share the ticks of one window of the flown audit (flown_audit.hip; same results); 0 = sized from the batch
     int timeopt_chunk = 0;          // tuning: missions per chunk of the duration optimisation (minsnap_timeopt.hip; same results); 0 = sized from UAVAC_TIMEOPT_SCRATCH_BYTES
@@ -272,6 +273,15 @@ int uavac_launch_delay(uavac_ctx *ctx, const double *coeffs, const double *times
 int uavac_launch_layer(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
                        const int64_t *group_offsets, int G, const int32_t *start_rows, double radius, double delta_x, double delta_y,
                        double delta_z, int max_steps, int32_t *ilayer, double *offsets);
+// the two searches for groups of any size up to group_cap (minsnap_stagger_wide.hip, minsnap_layer_wide.hip: the block-wise form of
+// fleet_wide.h); outputs as uavac_launch_stagger's and uavac_launch_layer_obs's; scratch, the seed words included, from the ctx arena
+int uavac_launch_stagger_wide(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
+                              const int64_t *group_offsets, int G, int group_cap, const int32_t *start_rows, double radius, int step,
+                              int max_steps, int32_t *istag);
+int uavac_launch_layer_wide(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
+                            const int64_t *group_offsets, int G, int group_cap, const int32_t *start_rows, double radius, double delta_x,
+                            double delta_y, double delta_z, int max_steps, const double *cuboids, int n_cuboids, int32_t *ilayer,
+                            double *offsets);
 int uavac_launch_shift(uavac_ctx *ctx, const double *coeffs, const int64_t *seg_offsets, int B, int m, int64_t total_segments,
                        const double *offsets, double *out_coeffs);
 // the same search, refusing every layer on which a row of the mission's own lies inside a cuboid (minsnap_layer_obs.hip): cuboids

@@ -142,7 +142,7 @@ FROM_LDS = "from the LDS the kernel ends up with"
 # the row speaks of those alone.  `limit`, the most vector registers a kernel may take: a number; {kernel: number}; a function
 # of the kernel's template arguments; or FROM_LDS -- workgroups of four waves, so min(8, 160 KiB // LDS) workgroups per CU are
 # as many waves per SIMD, and the kernel must fit the allocation that still runs that many; a decision kernel of the layer
-# search must keep three workgroups per CU.  No kernel may spill a vector register; with `scratch_free` none may use scratch
+# search, and of the block-wise searches, must keep three workgroups per CU.  No kernel may spill a vector register; with `scratch_free` none may use scratch
 # memory at all (zero private-segment bytes).
 Budget = collections.namedtuple("Budget", "key obj noun kernels limit extra at_least scratch_free", defaults=(0, None, True))
 BUDGETS = (
@@ -205,7 +205,15 @@ BUDGETS = (
     # the same search refusing layers that put a mission into a cuboid, the two instantiations with cuboids (built: 50976 B of
     # LDS -- 768 B of cuboids, two more words -- hence still three workgroups per CU, at 142; the pre-pass 14)
     Budget("layer_obs_kernels", "minsnap_layer_obs.o", "obstacle-aware layer", ("layer_prepass_kernel", "minsnap_layer_kernel"), FROM_LDS),
+    # the two searches for groups of any size (csrc/fleet_wide.h): the block search is the decision kernel above and keeps its three
+    # workgroups per CU; the seed kernel holds the 48 KB tile and two words, hence three as well and <= 168 (built: stagger 142
+    # and 127, layer 151 and 144 -- the seed first; the pre-passes 14)
+    Budget("stagger_wide_kernels", "minsnap_stagger_wide.o", "wide stagger",
+           ("stagger_prepass_kernel", "wide_stagger_seed_kernel", "wide_stagger_kernel"), FROM_LDS),
+    Budget("layer_wide_kernels", "minsnap_layer_wide.o", "wide layer", ("layer_prepass_kernel", "wide_layer_seed_kernel", "wide_layer_kernel"),
+           FROM_LDS),
 )
+DECISION_KERNELS = ("minsnap_layer_kernel", "wide_layer_kernel", "wide_stagger_kernel")      # FROM_LDS: these keep three workgroups per CU
 COUNTED = ("rollout_registers", "planning_registers")      # `run_all` reports these as a number of kernels, the others as {kernel: VGPRs}
 
 # The object files that have no budget, and why not.
@@ -232,7 +240,7 @@ def vgpr_limit(rule, k: Kernel):
     if rule is FROM_LDS:
         lds = k.group_segment_fixed_size
         waves = min(8, LDS_BYTES_PER_CU // lds) if lds else 8
-        if "minsnap_layer_kernel" in k.name and waves < 3:
+        if any(name in k.name for name in DECISION_KERNELS) and waves < 3:
             return f"{lds} bytes of LDS: fewer than three workgroups per CU"
         return VGPRS_AT_WAVES_PER_SIMD.get(waves, 0)           # (a workgroup that does not fit a CU at all: limit 0)
     return rule
@@ -296,6 +304,8 @@ def check_flown_conflict_kernels(): return vgprs(check_budgets("flown_conflict_k
 def check_flown_audit_kernels(): return vgprs(check_budgets("flown_audit_kernels"))                     # noqa: E704
 def check_layer_kernels(): return vgprs(check_budgets("layer_kernels"))                                 # noqa: E704
 def check_layer_obs_kernels(): return vgprs(check_budgets("layer_obs_kernels"))                         # noqa: E704
+def check_stagger_wide_kernels(): return vgprs(check_budgets("stagger_wide_kernels"))                   # noqa: E704
+def check_layer_wide_kernels(): return vgprs(check_budgets("layer_wide_kernels"))                       # noqa: E704
 TIMEOPT_KERNELS = next(row.kernels for row in BUDGETS if row.key == "timeopt_kernels")
 FLOWN_CONFLICT_KERNELS = next(row.kernels for row in BUDGETS if row.key == "flown_conflict_kernels")
 

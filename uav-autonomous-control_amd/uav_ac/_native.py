@@ -31,6 +31,7 @@ FLOWN_AUDIT_ROWS, FLOWN_AUDIT_MAX_SPLIT = 8, 64      # the plan audit of a fligh
 STAGGER_ROWS, STAGGER_MAX_STEPS, STAGGER_MAX_GROUP = 3, 1023, 256      # start delays (include/uavac.h uavac_minsnap_stagger_dev)
 LAYER_ROWS, LAYER_MAX_STEPS, LAYER_MAX_GROUP = 3, 1023, 256            # offset layers (include/uavac.h uavac_minsnap_layer_dev)
 LAYER_OBS_ROWS = 4                                                     # ... that keep out of cuboids (uavac_minsnap_layer_obs_dev)
+SEARCH_BLOCKS = (64, 128, 256)                                         # option "search_block" of the searches for groups of any size (0: the default)
 VERSION = 310
 GROUND_IN_CONTACT, GROUND_TAKEN_OFF, GROUND_HIT_AFTER_TAKEOFF = 1, 2, 4       # istate row 3 (include/uavac.h)
 
@@ -104,12 +105,16 @@ _SIGNATURES = {
     "uavac_minsnap_conflicts_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, C.c_double, _P, C.c_int64, _P,
                                               _P]),
     "uavac_minsnap_stagger_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, C.c_double, C.c_int, C.c_int, _P]),
+    "uavac_minsnap_stagger_wide_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, C.c_int, _P, C.c_double, C.c_int,
+                                                 C.c_int, _P]),
     "uavac_minsnap_delay_offsets_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "uavac_minsnap_delay_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P, _P]),
     "uavac_minsnap_layer_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, C.c_double, C.c_double, C.c_double,
                                           C.c_double, C.c_int, _P, _P]),
     "uavac_minsnap_layer_obs_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, C.c_double, C.c_double, C.c_double,
                                               C.c_double, C.c_int, _P, C.c_int, _P, _P]),
+    "uavac_minsnap_layer_wide_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, C.c_int, _P, C.c_double, C.c_double,
+                                               C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P]),
     "uavac_minsnap_shift_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int64, _P, _P]),
     "uavac_minsnap_take_offsets_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P]),
     "uavac_minsnap_take_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),

@@ -404,6 +404,25 @@ class Engine:
             raise ValueError("group offsets hold at least two entries")
         return go, G
 
+    def _group_cap(self, groups, B: int, group_cap=None) -> int:
+        """The `group_cap` of the searches for groups of any size (`wide=True`): the largest group where the sizes are known without a
+        sync -- `groups` None, a group size, or offsets on the host; a `group_cap` below it is a ValueError --, for offsets that are a
+        device tensor the caller's `group_cap`, else B."""
+        if group_cap is not None and int(group_cap) < 1:
+            raise ValueError("group_cap must be >= 1")
+        if hasattr(groups, "is_cuda") and groups.is_cuda:
+            return B if group_cap is None else int(group_cap)
+        if groups is None:
+            largest = B
+        elif isinstance(groups, (int, np.integer)):
+            largest = min(int(groups), B)
+        else:
+            sizes = np.diff(np.asarray(groups.numpy() if hasattr(groups, "numpy") else groups, dtype=np.int64).reshape(-1))
+            largest = max(int(sizes.max()) if sizes.size else 1, 1)
+        if group_cap is not None and int(group_cap) < largest:
+            raise ValueError(f"a group of {largest} missions; group_cap is {int(group_cap)}")
+        return largest
+
     def _start_rows(self, start_rows, B: int):
         """One start row per mission -> (B,) i32 on the device."""
         start = self._dev(start_rows, self._torch.int32).reshape(-1)
@@ -545,7 +564,7 @@ class Engine:
         return self._conflict_list("uavac_minsnap_conflict_offsets_dev", "uavac_minsnap_conflicts_dev", pair_args, B)
 
     def stagger(self, plan, radius: float, groups=None, start_rows=None, step: int = 1, max_steps: int = 255,
-                priority=None) -> StaggerResult:
+                priority=None, wide: bool = False, group_cap=None) -> StaggerResult:
         """Prioritised deconfliction by start delay (`uavac_minsnap_stagger_dev`): the call that acts on `Engine.separation`'s
         verdict.  Within a group the missions are taken in ascending batch index -- the lowest index is never delayed --, and each
         gets the smallest start `start_rows[b] + q * step`, q = 0 .. `max_steps`, that keeps it outside `radius` of every mission
@@ -563,11 +582,19 @@ class Engine:
         (`uavac_fleet_order_dev`, `uav_ac.scoring.priority_order`) --, and "the lowest index is never delayed" becomes "the first of its
         group's order".  A composition: the search runs unchanged on `Engine.take(plan, order)` with `start_rows[order]`, and its answers
         are gathered back, so the result is in the caller's batch order and is exactly `stagger_from_rows` on `take_rows(rows,
-        row_offsets, order)` mapped back with `rank`; the one host read is `Engine.take`'s.  None: the call as it always was."""
+        row_offsets, order)` mapped back with `rank`; the one host read is `Engine.take`'s.  None: the call as it always was.
+        `wide=True`: groups of ANY size (`uavac_minsnap_stagger_wide_dev`): the same rule and the same integers -- exactly
+        `stagger_from_rows(..., max_group=group_cap)` --, decided block by block: per block of 64 missions (ctx option "search_block": 64, 128, 256; same results)
+        a chip-wide kernel marks the candidates that meet a mission of an earlier block, then the search above decides the block.
+        `group_cap` bounds the largest group: it is taken from `groups` when they are None, an int or on the host; for offsets that are
+        a device tensor it is the caller's value, else B -- which costs ceil(B / block) pairs of mostly empty launches, so give it --,
+        and a group above it reports steps = -2 and raises sticky flag 0.  `priority` composes unchanged.  `wide=False`: the call as it
+        always was, `group_cap` is not looked at."""
         if priority is not None:
             B = int(self._coeff_plan(plan).B)
-            order, rank, start = self._priority_order(priority, groups, B, nat.STAGGER_MAX_GROUP, start_rows)
-            return self._stagger_back(self.stagger(self.take(plan, order), radius, groups, start, step, max_steps), rank)
+            order, rank, start = self._priority_order(priority, groups, B, None if wide else nat.STAGGER_MAX_GROUP, start_rows)
+            return self._stagger_back(self.stagger(self.take(plan, order), radius, groups, start, step, max_steps, wide=wide,
+                                                   group_cap=group_cap), rank)
         torch = self._torch
         plan = self._coeff_plan(plan)
         B = int(plan.B)
@@ -578,10 +605,15 @@ class Engine:
             raise ValueError(f"max_steps must be in 0 .. {nat.STAGGER_MAX_STEPS}")
         if step * max_steps > 2 ** 29:
             raise ValueError("step * max_steps must not exceed 2^29 rows")
-        go, G = self._groups(groups, B, nat.STAGGER_MAX_GROUP)
+        cap = self._group_cap(groups, B, group_cap) if wide else None
+        go, G = self._groups(groups, B, None if wide else nat.STAGGER_MAX_GROUP)
         start = None if start_rows is None else self._start_rows(start_rows, B)
         block = torch.empty((nat.STAGGER_ROWS, B), dtype=torch.int32, device=self.device)
         self._bind_stream()
+        if wide:
+            self.ctx.call("uavac_minsnap_stagger_wide_dev", *self._plan_args(plan), _ptr(go), G, cap, _ptr(start), float(radius), step,
+                          max_steps, _ptr(block))
+            return StaggerResult(*block.unbind(0), block)
         self.ctx.call("uavac_minsnap_stagger_dev", *self._plan_args(plan), _ptr(go), G, _ptr(start), float(radius), step, max_steps,
                       _ptr(block))
         return StaggerResult(*block.unbind(0), block)
@@ -631,7 +663,7 @@ class Engine:
         return self.sample_rows(out) if rows else out
 
     def layer(self, plan, radius: float, groups=None, start_rows=None, delta=(0.0, 0.0, -0.5), max_steps: int = 63,
-              obstacles=None, priority=None) -> LayerResult:
+              obstacles=None, priority=None, wide: bool = False, group_cap=None) -> LayerResult:
         """Prioritised deconfliction by offset (`uavac_minsnap_layer_dev`): the second lever on `Engine.separation`'s verdict, for the
         conflicts that waiting cannot resolve (a shared first or last waypoint, a crossing of a busy region).  `start_rows` are FIXED
         starts -- `StaggerResult.start_rows`, for instance; nobody is delayed by this call.  Within a group the missions are taken in
@@ -657,11 +689,15 @@ class Engine:
         first of its group's order"; the search runs unchanged on `Engine.take(plan, order)` with `start_rows[order]`, and `block`
         (column-wise) and `offsets` (row-wise) are gathered back into the caller's batch order.  Exactly `layer_from_rows` /
         `layer_obstacles_from_rows` on `take_rows(...)` of the shifted plans' rows, mapped back with `rank`.  The one host read is
-        `Engine.take`'s.  None: the call as it always was."""
+        `Engine.take`'s.  None: the call as it always was.
+        `wide=True`, `group_cap`: groups of any size (`uavac_minsnap_layer_wide_dev`), as in `Engine.stagger`: the same rule, exactly
+        `layer_obstacles_from_rows(..., max_group=group_cap)`.  The one kernel is the search with obstacles: `result.block` is (4, B)
+        whether `obstacles` are given or not, and without them `blocked` is all 0 and rows 0-2 are `layer_from_rows`'."""
         if priority is not None:
             B = int(self._coeff_plan(plan).B)
-            order, rank, start = self._priority_order(priority, groups, B, nat.LAYER_MAX_GROUP, start_rows)
-            return self._layer_back(self.layer(self.take(plan, order), radius, groups, start, delta, max_steps, obstacles), rank)
+            order, rank, start = self._priority_order(priority, groups, B, None if wide else nat.LAYER_MAX_GROUP, start_rows)
+            return self._layer_back(self.layer(self.take(plan, order), radius, groups, start, delta, max_steps, obstacles, wide=wide,
+                                               group_cap=group_cap), rank)
         torch = self._torch
         plan = self._coeff_plan(plan)
         B = int(plan.B)
@@ -671,9 +707,17 @@ class Engine:
         d = np.asarray(delta.detach().cpu().numpy() if hasattr(delta, "detach") else delta, dtype=np.float64).reshape(-1)
         if d.size != 3 or not np.isfinite(d).all():
             raise ValueError("delta must be three finite numbers")
-        go, G = self._groups(groups, B, nat.LAYER_MAX_GROUP)
+        cap = self._group_cap(groups, B, group_cap) if wide else None
+        go, G = self._groups(groups, B, None if wide else nat.LAYER_MAX_GROUP)
         start = None if start_rows is None else self._start_rows(start_rows, B)
         offsets = torch.empty((B, 3), dtype=torch.float64, device=self.device)
+        if wide:
+            cub, n = (None, 0) if obstacles is None else self._cuboids(obstacles, "search")
+            block = torch.empty((nat.LAYER_OBS_ROWS, B), dtype=torch.int32, device=self.device)
+            self._bind_stream()
+            self.ctx.call("uavac_minsnap_layer_wide_dev", *self._plan_args(plan), _ptr(go), G, cap, _ptr(start), float(radius), float(d[0]),
+                          float(d[1]), float(d[2]), max_steps, _ptr(cub) if n else None, n, _ptr(block), _ptr(offsets))
+            return LayerResult(*block[:nat.LAYER_ROWS].unbind(0), block, offsets)
         if obstacles is not None:
             cub, n = self._cuboids(obstacles, "search")
             block = torch.empty((nat.LAYER_OBS_ROWS, B), dtype=torch.int32, device=self.device)
@@ -864,7 +908,8 @@ class Engine:
 
     def _priority_order(self, priority, groups, B: int, max_group: int, start_rows):
         """The front of the `priority=` forms: the within-group order of `priority` (`uavac_fleet_order_dev`) -> (order, rank, the start
-        rows in slot order or None), device tensors.  The groups are checked against `max_group` here, before anything is copied."""
+        rows in slot order or None), device tensors.  The groups are checked against `max_group` (None: no limit, the `wide` forms) here,
+        before anything is copied."""
         torch = self._torch
         pr = self._dev(priority, torch.float64).reshape(-1)
         if pr.numel() != B:
@@ -891,7 +936,7 @@ class Engine:
         return LayerResult(*block[:nat.LAYER_ROWS].unbind(0), block, res.offsets[at].contiguous())
 
     def deconflict(self, plan, radius: float, groups=None, obstacles=None, start_rows=None, step: int = 1, max_delay_steps: int = 255,
-                   delta=(0.0, 0.0, -0.5), max_layers: int = 63, priority=None) -> DeconflictResult:
+                   delta=(0.0, 0.0, -0.5), max_layers: int = 63, priority=None, wide: bool = False, group_cap=None) -> DeconflictResult:
         """The fleet chain as one call: stagger -> layer -> shift -> delay.  `Engine.stagger(plan, radius, groups, start_rows, step,
         max_delay_steps)` makes missions wait; `Engine.layer(plan, radius, groups, start_rows=stagger.start_rows, delta=delta,
         max_steps=max_layers, obstacles=obstacles)` moves, at the granted starts, the ones that waiting cannot clear -- and, with
@@ -917,18 +962,23 @@ class Engine:
         WHAT STAYS UNRESOLVED: `eng.take(plan, ~result.resolved)` takes those missions out to look at them; re-plan them from your own
         waypoints (`plan_ragged` / `plan_collision_free`: `waypoints` is None after a transform, so the caller keeps them),
         `eng.put(plan, ~result.resolved, replanned)` puts them back, and `deconflict` runs again -- with a priority that takes them
-        first if they are to win this time."""
+        first if they are to win this time.
+        `wide=True`, `group_cap`: groups of any size; both searches run as `Engine.stagger(..., wide=True, group_cap=group_cap)` and
+        `Engine.layer(..., wide=True, group_cap=group_cap)`, and the guarantees above hold unchanged."""
+        w = dict(wide=wide, group_cap=group_cap)
         if priority is not None:
             B = int(self._coeff_plan(plan).B)
-            order, rank, start = self._priority_order(priority, groups, B, min(nat.STAGGER_MAX_GROUP, nat.LAYER_MAX_GROUP), start_rows)
+            order, rank, start = self._priority_order(priority, groups, B, None if wide else min(nat.STAGGER_MAX_GROUP, nat.LAYER_MAX_GROUP),
+                                                      start_rows)
             taken = self.take(plan, order)
-            stag = self.stagger(taken, radius, groups=groups, start_rows=start, step=step, max_steps=max_delay_steps)
-            lay = self.layer(taken, radius, groups=groups, start_rows=stag.start_rows, delta=delta, max_steps=max_layers, obstacles=obstacles)
+            stag = self.stagger(taken, radius, groups=groups, start_rows=start, step=step, max_steps=max_delay_steps, **w)
+            lay = self.layer(taken, radius, groups=groups, start_rows=stag.start_rows, delta=delta, max_steps=max_layers, obstacles=obstacles,
+                             **w)
             stag, lay = self._stagger_back(stag, rank), self._layer_back(lay, rank)
             flown = self.delay(self.shift(plan, lay.offsets), stag.start_rows)
             return DeconflictResult(flown, stag, lay, lay.steps >= 0)
-        stag = self.stagger(plan, radius, groups=groups, start_rows=start_rows, step=step, max_steps=max_delay_steps)
-        lay = self.layer(plan, radius, groups=groups, start_rows=stag.start_rows, delta=delta, max_steps=max_layers, obstacles=obstacles)
+        stag = self.stagger(plan, radius, groups=groups, start_rows=start_rows, step=step, max_steps=max_delay_steps, **w)
+        lay = self.layer(plan, radius, groups=groups, start_rows=stag.start_rows, delta=delta, max_steps=max_layers, obstacles=obstacles, **w)
         flown = self.delay(self.shift(plan, lay.offsets), stag.start_rows)
         return DeconflictResult(flown, stag, lay, lay.steps >= 0)
 

@@ -313,6 +313,15 @@ def _inside_any(own, partners, r2) -> bool:
         return bool(((dx * dx + dy * dy) + dz * dz < r2).any())
 
 
+def _max_group(max_group, narrow) -> int:
+    """the group limit of a search rule: the narrow call's constant, or the caller's number (>= 1)"""
+    if max_group is None:
+        return narrow
+    if int(max_group) < 1:
+        raise ValueError("max_group must be >= 1")
+    return int(max_group)
+
+
 def _prioritised_search(N, included, go, max_group, max_steps, pos, start, r2, blocked=None):
     """The search the stagger and the layer rules share.  Candidate q of mission i stands at the positions pos(i, q) (N_i, 3) from
     start row start(i, q) on; per group the included missions in ascending index examine q = 0 .. max_steps against the GRANTED
@@ -893,7 +902,7 @@ def delay_rows(rows, row_offsets, start_rows, first_yaw):
 STAG_START, STAG_STEPS, STAG_EARLIER = range(nat.STAGGER_ROWS)                                   # istag rows (include/uavac.h)
 
 
-def stagger_from_rows(rows, row_offsets, radius, group_offsets=None, start_rows=None, step=1, max_steps=255):
+def stagger_from_rows(rows, row_offsets, radius, group_offsets=None, start_rows=None, step=1, max_steps=255, max_group=None):
     """Prioritised deconfliction by start delay, decided on SAMPLED rows -- the SPECIFICATION of `uavac_minsnap_stagger_dev`
     (csrc/minsnap_stagger.hip), which is tested against it exactly.  NumPy on the host.
     `rows`, `row_offsets`, `radius`, `group_offsets` as `separation_from_rows` takes them, and the clock, the excluded missions and
@@ -908,6 +917,8 @@ def stagger_from_rows(rows, row_offsets, radius, group_offsets=None, start_rows=
     candidate is granted: T_i = s, steps = q; if none is clear the mission is unresolved: steps = -1, T_i = S_i, and it remains a
     partner for every later mission.  An excluded mission, and every mission of a group of more than STAGGER_MAX_GROUP, is not
     examined: its clamped base start, steps = -2, earlier = 0; nobody is checked against an excluded mission.
+    `max_group`: a number sets that limit instead -- the SPECIFICATION of `uavac_minsnap_stagger_wide_dev` with `group_cap` = max_group
+    (the rule itself has no size limit); None = STAGGER_MAX_GROUP.
     -> istag (STAGGER_ROWS, B) i32: the granted start row; steps; earlier (how many missions it was checked against)."""
     rows = _host(rows)
     ro = _host_i64(row_offsets)
@@ -921,7 +932,7 @@ def stagger_from_rows(rows, row_offsets, radius, group_offsets=None, start_rows=
     N = np.diff(ro)
     pos = [rows[ro[b]:ro[b + 1], 0:3] for b in range(B)]
     # the candidate is a start row: the mission's own rows from S_i + q * step on, up to the horizon of that candidate
-    steps, earlier, _ = _prioritised_search(N, _included(pos.__getitem__, N), go, nat.STAGGER_MAX_GROUP, max_steps, lambda i, q: pos[i],
+    steps, earlier, _ = _prioritised_search(N, _included(pos.__getitem__, N), go, _max_group(max_group, nat.STAGGER_MAX_GROUP), max_steps, lambda i, q: pos[i],
                                             lambda i, q: int(S[i]) + q * step, radius * radius)
     istag = np.zeros((nat.STAGGER_ROWS, B), dtype=np.int32)
     istag[STAG_START], istag[STAG_STEPS], istag[STAG_EARLIER] = S + np.maximum(steps, 0) * step, steps, earlier
@@ -975,7 +986,7 @@ def shift_coeffs(coeffs, seg_offsets_or_m, offsets):
     return co
 
 
-def layer_from_rows(rows_at, row_offsets, radius, group_offsets=None, start_rows=None, max_steps=63):
+def layer_from_rows(rows_at, row_offsets, radius, group_offsets=None, start_rows=None, max_steps=63, max_group=None):
     """Prioritised deconfliction by offset layers, decided on SAMPLED rows -- the SPECIFICATION of `uavac_minsnap_layer_dev`
     (csrc/minsnap_layer.hip), which is tested against it exactly.  NumPy on the host.
     `rows_at(q)` -> the (N, >= 3) rows of the WHOLE batch with every mission on layer q, i.e. of the plan with fl(q * delta) added to
@@ -990,15 +1001,18 @@ def layer_from_rows(rows_at, row_offsets, radius, group_offsets=None, start_rows
     N_j)) the two are not inside the radius.  The first clear candidate is granted: L_i = steps = q; if none is clear the mission is
     unresolved: steps = -1, L_i = 0, and it remains a partner for every later mission.  An excluded mission, and every mission of a
     group of more than LAYER_MAX_GROUP, is not examined: layer 0, steps = -2, earlier = 0; nobody is checked against an excluded one.
+    `max_group`: a number sets that limit instead (`uavac_minsnap_layer_wide_dev` without cuboids, `group_cap` = max_group); None =
+    LAYER_MAX_GROUP.
     -> ilayer (LAYER_ROWS, B) i32: the granted layer; steps; earlier (how many missions it was checked against)."""
-    return _layer_search(rows_at, row_offsets, radius, (), group_offsets, start_rows, max_steps)[:nat.LAYER_ROWS]
+    return _layer_search(rows_at, row_offsets, radius, (), group_offsets, start_rows, max_steps, max_group)[:nat.LAYER_ROWS]
 
 
-def layer_obstacles_from_rows(rows_at, row_offsets, radius, cuboids, group_offsets=None, start_rows=None, max_steps=63):
+def layer_obstacles_from_rows(rows_at, row_offsets, radius, cuboids, group_offsets=None, start_rows=None, max_steps=63, max_group=None):
     """`layer_from_rows` with obstacles -- the SPECIFICATION of `uavac_minsnap_layer_obs_dev` (csrc/minsnap_layer_obs.hip), which is
     tested against it exactly.  NumPy on the host.  `rows_at`, `row_offsets`, `radius`, `group_offsets`, `start_rows`, `max_steps` as
     `layer_from_rows` takes them, and the clock, the excluded missions (judged on layer 0), the clamped starts, `LAYER_MAX_GROUP` and
-    the distance arithmetic are the same.  `cuboids` (n, 6): xmin xmax ymin ymax zmin zmax, 0 <= n <= AUDIT_MAX_CUBOIDS.
+    the distance arithmetic are the same.  `cuboids` (n, 6): xmin xmax ymin ymax zmin zmax, 0 <= n <= AUDIT_MAX_CUBOIDS.  `max_group`: a
+    number sets the group limit instead -- the SPECIFICATION of `uavac_minsnap_layer_wide_dev` with `group_cap` = max_group.
 
     The differences, and only these.  Candidate q of mission i is BLOCKED when any of the mission's own rows
     rows_at(q)[ro[i]:ro[i + 1], 0:3] lies inside any cuboid by the audit's inclusive test (x >= xmin and x <= xmax and ...: a NaN bound
@@ -1010,10 +1024,10 @@ def layer_obstacles_from_rows(rows_at, row_offsets, radius, cuboids, group_offse
     -> ilayer (LAYER_OBS_ROWS, B) i32: rows 0-2 as `layer_from_rows`; row 3 `blocked` = how many of the candidates q = 0 .. steps - 1
     (0 .. max_steps when unresolved) a cuboid refused, 0 for a mission that was not examined.  With n = 0 rows 0-2 equal
     `layer_from_rows` exactly and row 3 is zero."""
-    return _layer_search(rows_at, row_offsets, radius, cuboids, group_offsets, start_rows, max_steps)
+    return _layer_search(rows_at, row_offsets, radius, cuboids, group_offsets, start_rows, max_steps, max_group)
 
 
-def _layer_search(rows_at, row_offsets, radius, cuboids, group_offsets, start_rows, max_steps):
+def _layer_search(rows_at, row_offsets, radius, cuboids, group_offsets, start_rows, max_steps, max_group=None):
     """Both layer rules -> ilayer (LAYER_OBS_ROWS, B) i32.  Without cuboids nothing is ever blocked and rows 0-2 are `layer_from_rows`."""
     ro = _host_i64(row_offsets)
     B = len(ro) - 1
@@ -1044,7 +1058,7 @@ def _layer_search(rows_at, row_offsets, radius, cuboids, group_offsets, start_ro
                     return True
         return False
 
-    steps, earlier, blocked = _prioritised_search(N, _included(lambda b: pos(b, 0), N), go, nat.LAYER_MAX_GROUP, max_steps, pos,
+    steps, earlier, blocked = _prioritised_search(N, _included(lambda b: pos(b, 0), N), go, _max_group(max_group, nat.LAYER_MAX_GROUP), max_steps, pos,
                                                   lambda b, q: int(S[b]), radius * radius, is_blocked if len(cub) else None)
     ilayer = np.zeros((nat.LAYER_OBS_ROWS, B), dtype=np.int32)
     ilayer[LAYER_LAYER], ilayer[LAYER_STEPS], ilayer[LAYER_EARLIER], ilayer[LAYER_BLOCKED] = np.maximum(steps, 0), steps, earlier, blocked
