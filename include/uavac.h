@@ -674,6 +674,59 @@ int uavac_minsnap_take_dev(uavac_ctx *ctx, const double *coeffs, const double *t
 int uavac_fleet_order_dev(uavac_ctx *ctx, const double *priority, const int64_t *group_offsets, int G, int B, int32_t *order,
                           int32_t *rank);
 
+/* ENVELOPE: every mission's SWEPT BOX, per mission, WITHOUT sampling its rows -- what the split of a fleet into independent airspaces
+ * (uavac_fleet_airspaces_dev below) starts from.  One kernel walks every mission's rows as the plan audit does
+ * (csrc/minsnap_envelope.hip) and stores none of them.  coeffs / seg_rows / seg_offsets / B / m / dt as in uavac_minsnap_audit_dev
+ * (seg_offsets NULL = uniform, otherwise ragged with segment counts clamped to 1 .. m).
+ *   reach [B][3] f64 (device) or NULL: an offset per mission whose plan is covered as well, e.g. fl(max_steps * delta) of a layer search
+ *   env   [B][6] f64 (device): lo x, lo y, lo z, hi x, hi y, hi z -- the minimum and the maximum, per axis, of the positions the sampler
+ *         writes for the mission and, with reach, of the positions it writes for the mission shifted by reach[b]
+ *         (uavac_minsnap_shift_dev) too: the hull of both.
+ * ROUNDING is part of the contract.  Positions by the sampler's fma chain, hence the bits of the rows; the shifted side from c0' =
+ * fl(c0 + reach[b][a]) in every segment -- a rounded sum of its own, then the same chain: the two roundings of uavac_minsnap_shift_dev,
+ * which also leaves a mission alone whose three reach components are all +-0.  Minimum and maximum are exact and independent of order,
+ * so the result does not depend on the launch shape (option "audit_lanes": 16 or 64 lanes per mission, same results); -0.0 and +0.0
+ * are the same number here: the contract is equality as numbers, NaN in the same places (uav_ac.scoring.envelope_from_rows on the
+ * sampled rows).  A mission without rows, or with ANY position that is not finite on either side, reports NaN in all six.
+ * WHY A BOX IS ENOUGH.  Rounded subtraction, multiplication and addition are monotone, the chain ends per axis with fma(p, t, c0), which
+ * is monotone in c0, and a layer's coefficient fl(c0 + fl(q * delta_a)) is monotone in q: every row of every layer q = 0 .. max_steps
+ * lies, per axis, between the mission's rows on layer 0 and on layer max_steps, inside the box with reach = fl(max_steps * delta).  Hold
+ * rows and the rows a mission waits on before its start are its own first and last rows.  So if fl(lo_i - hi_j) >= radius on some axis,
+ * every d^2 a search can compute for the pair is >= radius * radius, whatever the starts and the granted layers: never inside.
+ * Exactly env [B][6] is written, nothing is read back, one kernel on the ctx stream.
+ * UAVAC_EINVAL before anything is enqueued: no context, a NULL coeffs / seg_rows / env, B < 1, m outside 1 .. UAVAC_MAX_SEGMENTS, dt not
+ * positive and finite. */
+int uavac_minsnap_envelope_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                               double dt, const double *reach, double *env);
+
+/* AIRSPACES: a fleet split into groups of missions that can never meet.  The prioritised searches (uavac_minsnap_stagger_dev,
+ * uavac_minsnap_layer_dev and their _obs / _wide forms) cost the square of a group's size, and `group_offsets` is the only lever on it;
+ * this call computes the finest split that changes no answer.  A mission's greedy decision depends only on earlier missions that can
+ * come inside the radius of it; those are all in its connected component of the graph below; so the unchanged search, run per
+ * component on the missions in their original relative order, gives every mission the start / steps / layer / blocked that the search
+ * over the whole group gives (`earlier` becomes the count within the component).  csrc/fleet_airspaces.hip;
+ * uav_ac.scoring.airspaces_from_envelopes states the rule in NumPy, round for round.
+ *   env [B][6] f64 (device): the boxes of uavac_minsnap_envelope_dev.  group_offsets [G + 1] i64 / G as in uavac_fleet_order_dev,
+ *   clamped to the batch in the same way (NULL: one group of all B); a mission that no group holds is linked to nobody.
+ *   labels [B] i32 (device), info [2] i32 (device).
+ * THE LINK.  Missions i != j of the same group are linked iff on all three axes fl(lo_i - hi_j) < radius and fl(lo_j - hi_i) < radius:
+ * one rounded subtraction each, nothing contracted, strictly less -- a gap of exactly the radius is no link, radius 0 links boxes that
+ * overlap by more than a face, and a box with a NaN links to nobody.
+ * ONE ROUND, on whole arrays (double-buffered, so it is reproducible):  m[i] = min(lab[i], min of lab[j] over the linked j);
+ * lab'[i] = m[m[i]].  The first round starts from lab[i] = i; with resume = 1 from `labels` as given (the output of an earlier call
+ * on the same boxes; a value outside 0 .. B - 1 is read as the nearest index).  The call enqueues at most `rounds` rounds, and a round
+ * whose predecessor changed nothing exits at once: no workgroup waits for another, there is no grid-wide barrier.
+ *   info[0] = how many rounds of this call changed a label;  info[1] = 1 iff the last round that ran changed nothing.
+ * With info[1] = 1 the labels are FINAL: labels[b] is the lowest batch index of b's component -- unique, so it depends neither on the
+ * launch shape nor on how the rounds were split over calls.  With info[1] = 0 they describe a FINER partition than the components:
+ * call again with resume = 1, and NEVER hand such labels to a search -- its answers would not be the group's.
+ * Cost per round: the sum of g^2 box tests over the groups, one lane per mission, the partners through LDS tiles; two launches per
+ * round and two more per call; scratch (B + rounds words) from the ctx arena.  Exactly labels [B] and info [2] are written.
+ * UAVAC_EINVAL before anything is enqueued: no context, a NULL env / labels / info, B < 1, G < 1 when group_offsets != NULL, radius
+ * negative or not finite, rounds < 1, resume outside {0, 1}.  UAVAC_ENOMEM / UAVAC_EHIP when the scratch cannot be had. */
+int uavac_fleet_airspaces_dev(uavac_ctx *ctx, const double *env, const int64_t *group_offsets, int G, int B, double radius, int rounds,
+                              int resume, int32_t *labels, int32_t *info);
+
 /* FLOWN SEPARATION: the separation audit of a FLIGHT.  uavac_minsnap_separation_dev speaks about plans; the vehicles track them with an
  * error.  This call reads the positions in a rollout's state log and reports, in the same terms and with the same exactness, how close
  * the vehicles came (csrc/flown_separation.hip): nothing is read back, everything is enqueued on the ctx stream, scratch from the arena.

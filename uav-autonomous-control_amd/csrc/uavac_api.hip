@@ -931,6 +931,15 @@ int uavac_minsnap_demand_dev(uavac_ctx *ctx, const double *coeffs, const int32_t
                                clearance_row);
 }
 
+int uavac_minsnap_envelope_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                               double dt, const double *reach, double *env) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_plan_args(ctx, coeffs, B, m)) return rc;
+    if (!seg_rows || !env) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (int rc = check_dt_positive(ctx, dt)) return rc;
+    return uavac_launch_envelope(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, reach, env);
+}
+
 // what the fleet's pair calls (separation, stagger, layer) refuse alike, in this order; `outputs`: every output pointer of the call is there
 static int check_pair_args(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, int B, int m, double dt, const int64_t *group_offsets,
                            int G, double radius, bool outputs) {
@@ -1115,6 +1124,18 @@ int uavac_fleet_order_dev(uavac_ctx *ctx, const double *priority, const int64_t 
     if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
     if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
     return uavac_launch_fleet_order(ctx, priority, group_offsets, G, B, order, rank);
+}
+
+int uavac_fleet_airspaces_dev(uavac_ctx *ctx, const double *env, const int64_t *group_offsets, int G, int B, double radius, int rounds,
+                              int resume, int32_t *labels, int32_t *info) {
+    UAVAC_ENTER(ctx);
+    if (!env || !labels || !info) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer");
+    if (B < 1) return uavac_fail(ctx, UAVAC_EINVAL, "B must be >= 1");
+    if (group_offsets && G < 1) return uavac_fail(ctx, UAVAC_EINVAL, "G must be >= 1 when group_offsets are given");
+    if (!std::isfinite(radius) || radius < 0.0) return uavac_fail(ctx, UAVAC_EINVAL, "radius must be finite and >= 0");
+    if (rounds < 1) return uavac_fail(ctx, UAVAC_EINVAL, "rounds must be >= 1");
+    if (resume != 0 && resume != 1) return uavac_fail(ctx, UAVAC_EINVAL, "resume is 0 or 1");
+    return uavac_launch_fleet_airspaces(ctx, env, group_offsets, G, B, radius, rounds, resume, labels, info);
 }
 
 // what the flown separation audit and the flown conflict list refuse alike; `outputs`: the call's required output pointers are there

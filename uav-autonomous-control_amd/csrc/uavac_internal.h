@@ -368,3 +368,11 @@ int uavac_launch_take(uavac_ctx *ctx, const double *coeffs, const double *times,
 // priorities into a within-group order (minsnap_take.hip): order [B] = the mission in every slot, rank [B] its inverse
 int uavac_launch_fleet_order(uavac_ctx *ctx, const double *priority, const int64_t *group_offsets, int G, int B, int32_t *order,
                              int32_t *rank);
+// a mission's swept box without the rows (minsnap_envelope.hip): env [B][6] = lo x y z, hi x y z over the sampler's positions and, with
+// reach [B][3] (device, may be NULL), over those of the plan with c0' = fl(c0 + reach[b]) as well
+int uavac_launch_envelope(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                          double dt, const double *reach, double *env);
+// the connected components of "boxes nearer than the radius", per group (fleet_airspaces.hip): labels [B] = the lowest batch index of
+// the mission's component once converged, info [2] = {rounds that changed a label, converged}; scratch from the ctx arena
+int uavac_launch_fleet_airspaces(uavac_ctx *ctx, const double *env, const int64_t *group_offsets, int G, int B, double radius, int rounds,
+                                 int resume, int32_t *labels, int32_t *info);

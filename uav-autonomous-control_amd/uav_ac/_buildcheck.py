@@ -163,6 +163,9 @@ BUDGETS = (
     # the slowdown factors of the tilt and thrust limits: the audit's shape and budget, no LDS (built: 112 and 120 at 64 and 16 lanes
     # per mission, no scratch memory)
     Budget("planning_registers", "minsnap_need.o", "plan-need", ("minsnap_need_kernel",), 168, at_least=2),
+    # the swept boxes: the audit's shape and budget, no LDS (built: 82 and 90 at 64 and 16 lanes per mission, 88 and 102
+    # with a reach, no scratch memory)
+    Budget("planning_registers", "minsnap_envelope.o", "plan-envelope", ("minsnap_envelope_kernel",), 168, at_least=4),
     # the solve with boundary derivatives, uniform and ragged: two waves per SIMD (built: 211 / 217)
     Budget("planning_registers", "minsnap_solve_bc.o", "boundary-solve", ("minsnap_solve_bc_kernel",), 256, extra=1),
     # plans from given durations, the snap cost, the duration optimisation's bookkeeping: loops over a mission's segments that keep
@@ -187,6 +190,10 @@ BUDGETS = (
     # missions selected and reordered, priorities into a within-group order: two plain copies and a count over 2 KB LDS tiles
     # of keys, eight waves per SIMD (built: 24, 28 and 18)
     Budget("take_kernels", "minsnap_take.o", "take", ("take_counts_kernel", "minsnap_take_kernel", "fleet_order_kernel"), 64),
+    # independent airspaces from the boxes: the link kernel's 13 KB tile of boxes and labels, eight waves per SIMD like the order
+    # kernel it is shaped after (built: 40, the others 3 .. 6)
+    Budget("airspace_kernels", "fleet_airspaces.o", "airspace",
+           ("airspace_begin_kernel", "airspace_link_kernel", "airspace_jump_kernel", "airspace_info_kernel"), 64),
     # the separation the fleet flew, from a state log: the 48 KB tile like the plan audit's (built: 143, the merge 18)
     Budget("flown_separation_kernels", "flown_separation.o", "flown-separation", ("flown_separation_kernel", "flown_merge_kernel"), 168),
     # the conflict list of a flight: the discovery keeps the 48 KB tile (built: 114); the measure keeps 48 log values per lane
@@ -299,6 +306,7 @@ def check_conflict_kernels(): return vgprs(check_budgets("conflict_kernels"))   
 def check_stagger_kernels(): return vgprs(check_budgets("stagger_kernels"))                             # noqa: E704
 def check_delay_kernels(): return vgprs(check_budgets("delay_kernels"))                                 # noqa: E704
 def check_take_kernels(): return vgprs(check_budgets("take_kernels"))                                   # noqa: E704
+def check_airspace_kernels(): return vgprs(check_budgets("airspace_kernels"))                           # noqa: E704
 def check_flown_separation_kernels(): return vgprs(check_budgets("flown_separation_kernels"))           # noqa: E704
 def check_flown_conflict_kernels(): return vgprs(check_budgets("flown_conflict_kernels"))               # noqa: E704
 def check_flown_audit_kernels(): return vgprs(check_budgets("flown_audit_kernels"))                     # noqa: E704

@@ -99,6 +99,7 @@ _SIGNATURES = {
                                           C.c_int64, _P, _P]),
     "uavac_minsnap_first_yaw_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P]),
     "uavac_minsnap_audit_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, _P, _P]),
+    "uavac_minsnap_envelope_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P]),
     "uavac_minsnap_demand_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, C.c_double, _P, C.c_int, _P, _P, _P, _P]),
     "uavac_minsnap_separation_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, C.c_double, _P, _P]),
     "uavac_minsnap_conflict_offsets_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, C.c_double, _P]),
@@ -119,6 +120,7 @@ _SIGNATURES = {
     "uavac_minsnap_take_offsets_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P]),
     "uavac_minsnap_take_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "uavac_fleet_order_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "uavac_fleet_airspaces_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _P, _P]),
     "uavac_flown_separation_dev": (C.c_int,[_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, C.c_double, _P, _P]),
     "uavac_flown_conflict_offsets_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, C.c_double, _P]),
     "uavac_flown_conflicts_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, C.c_double, _P, C.c_int64, _P, _P]),

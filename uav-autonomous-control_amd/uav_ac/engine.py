@@ -12,8 +12,8 @@ from typing import Optional
 import numpy as np
 
 from . import _native as nat
-from .plans import (ConflictList, DeconflictResult, FlightAudit, LayerResult, Plan, PlanAudit, PlanDemand, PlanNeed, RaggedBatch,  # noqa: F401
-                    RaggedPlan, RetimeResult, RRTDeviceBatch, Segments, SeparationAudit, StaggerResult, TimeOptResult, _ptr, segments,
+from .plans import (Airspaces, ConflictList, DeconflictResult, FlightAudit, LayerResult, Plan, PlanAudit, PlanDemand, PlanEnvelope,  # noqa: F401
+                    PlanNeed, RaggedBatch, RaggedPlan, RetimeResult, RRTDeviceBatch, Segments, SeparationAudit, StaggerResult, TimeOptResult, _ptr, segments,
                     uniform_offsets)  # (the plans and result records live in uav_ac/plans.py; every name is re-exported here)
 
 
@@ -564,7 +564,7 @@ class Engine:
         return self._conflict_list("uavac_minsnap_conflict_offsets_dev", "uavac_minsnap_conflicts_dev", pair_args, B)
 
     def stagger(self, plan, radius: float, groups=None, start_rows=None, step: int = 1, max_steps: int = 255,
-                priority=None, wide: bool = False, group_cap=None) -> StaggerResult:
+                priority=None, wide: bool = False, group_cap=None, airspaces: bool = False) -> StaggerResult:
         """Prioritised deconfliction by start delay (`uavac_minsnap_stagger_dev`): the call that acts on `Engine.separation`'s
         verdict.  Within a group the missions are taken in ascending batch index -- the lowest index is never delayed --, and each
         gets the smallest start `start_rows[b] + q * step`, q = 0 .. `max_steps`, that keeps it outside `radius` of every mission
@@ -589,7 +589,19 @@ class Engine:
         `group_cap` bounds the largest group: it is taken from `groups` when they are None, an int or on the host; for offsets that are
         a device tensor it is the caller's value, else B -- which costs ceil(B / block) pairs of mostly empty launches, so give it --,
         and a group above it reports steps = -2 and raises sticky flag 0.  `priority` composes unchanged.  `wide=False`: the call as it
-        always was, `group_cap` is not looked at."""
+        always was, `group_cap` is not looked at.
+        `airspaces=True`: the same answers for groups of any size at the cost of the airspaces' sizes, not the groups'.  The groups are
+        split into the airspaces of `Engine.airspaces(plan, radius, groups)` -- missions in different ones can never meet, whatever
+        their starts --, and a composition like `priority=`'s runs the unchanged search per airspace: `Engine.take(plan, order)`, the
+        search on the airspace offsets, the answers gathered back with `rank`.  `start_rows` and `steps` are exactly those of
+        `wide=True` on the caller's groups (`stagger_from_rows(..., max_group=B)`); `earlier` counts WITHIN THE AIRSPACE.  The size
+        limits now apply to airspaces, not groups: the narrow call when the largest airspace holds at most `STAGGER_MAX_GROUP`
+        missions, else the block-wise one with `group_cap` = that size; `wide` and `group_cap` are not looked at.  With `priority` the
+        order within an airspace is the priority's.  Host reads: `Engine.airspaces`' and `Engine.take`'s.  False: exactly the native
+        calls made without the keyword."""
+        if airspaces:
+            taken, rank, start, route = self._airspace_front(plan, radius, groups, None, priority, start_rows)
+            return self._stagger_back(self.stagger(taken, radius, start_rows=start, step=step, max_steps=max_steps, **route), rank)
         if priority is not None:
             B = int(self._coeff_plan(plan).B)
             order, rank, start = self._priority_order(priority, groups, B, None if wide else nat.STAGGER_MAX_GROUP, start_rows)
@@ -663,7 +675,7 @@ class Engine:
         return self.sample_rows(out) if rows else out
 
     def layer(self, plan, radius: float, groups=None, start_rows=None, delta=(0.0, 0.0, -0.5), max_steps: int = 63,
-              obstacles=None, priority=None, wide: bool = False, group_cap=None) -> LayerResult:
+              obstacles=None, priority=None, wide: bool = False, group_cap=None, airspaces: bool = False) -> LayerResult:
         """Prioritised deconfliction by offset (`uavac_minsnap_layer_dev`): the second lever on `Engine.separation`'s verdict, for the
         conflicts that waiting cannot resolve (a shared first or last waypoint, a crossing of a busy region).  `start_rows` are FIXED
         starts -- `StaggerResult.start_rows`, for instance; nobody is delayed by this call.  Within a group the missions are taken in
@@ -692,7 +704,16 @@ class Engine:
         `Engine.take`'s.  None: the call as it always was.
         `wide=True`, `group_cap`: groups of any size (`uavac_minsnap_layer_wide_dev`), as in `Engine.stagger`: the same rule, exactly
         `layer_obstacles_from_rows(..., max_group=group_cap)`.  The one kernel is the search with obstacles: `result.block` is (4, B)
-        whether `obstacles` are given or not, and without them `blocked` is all 0 and rows 0-2 are `layer_from_rows`'."""
+        whether `obstacles` are given or not, and without them `blocked` is all 0 and rows 0-2 are `layer_from_rows`'.
+        `airspaces=True`: as in `Engine.stagger`, with the airspaces of `Engine.airspaces(plan, radius, groups, reach=max_steps * delta)`:
+        the boxes cover every layer 0 .. `max_steps`, so missions in different airspaces can never meet whatever layers they are
+        granted.  `layers`, `steps`, `blocked` and `offsets` are exactly those of `wide=True` on the caller's groups; `earlier` counts
+        within the airspace; the limit `LAYER_MAX_GROUP` applies to airspaces (above it the block-wise search with `group_cap` = the
+        largest airspace, whose block is (4, B); below it the narrow calls, (3, B) without `obstacles`)."""
+        if airspaces:
+            taken, rank, start, route = self._airspace_front(plan, radius, groups, self._layer_reach(delta, max_steps), priority, start_rows)
+            return self._layer_back(self.layer(taken, radius, start_rows=start, delta=delta, max_steps=max_steps, obstacles=obstacles, **route),
+                                    rank)
         if priority is not None:
             B = int(self._coeff_plan(plan).B)
             order, rank, start = self._priority_order(priority, groups, B, None if wide else nat.LAYER_MAX_GROUP, start_rows)
@@ -906,6 +927,106 @@ class Engine:
         sel[at] = B + np.arange(n, dtype=np.int64)
         return self.take(self.concat([plan, other]), sel, rows=rows)
 
+    def envelope(self, plan, reach=None) -> PlanEnvelope:
+        """Every mission's swept box without sampling its rows (`uavac_minsnap_envelope_dev`): the minimum and the maximum per axis of
+        the positions the sampler writes -- as numbers exactly `uav_ac.scoring.envelope_from_rows` on the sampled rows.  `reach`: None, a
+        (3,) vector for every mission or a (B, 3) array or tensor: the box is then the hull of the plan's rows and of the rows of
+        `Engine.shift(plan, reach)`, and holds every layer in between (`reach = max_steps * delta` of a layer search).  `plan`: what
+        `Engine.audit` takes.  A mission without rows or with a position that is not finite reports NaN in all six.  Never reads
+        `plan.traj`; stream-ordered, no sync."""
+        torch = self._torch
+        plan = self._coeff_plan(plan)
+        B = int(plan.B)
+        r = None
+        if reach is not None:
+            r = self._dev(reach, torch.float64)
+            if r.numel() == 3:
+                r = r.reshape(1, 3).expand(B, 3)
+            elif r.numel() != 3 * B or (r.dim() == 2 and tuple(r.shape) != (B, 3)):
+                raise ValueError(f"reach is (3,) or ({B}, 3), got {tuple(r.shape)}")
+            r = r.reshape(B, 3).contiguous()
+        block = torch.empty((B, 6), dtype=torch.float64, device=self.device)
+        self._bind_stream()
+        self.ctx.call("uavac_minsnap_envelope_dev", *self._plan_args(plan), _ptr(r), _ptr(block))
+        return PlanEnvelope(block[:, :3], block[:, 3:], block)
+
+    def airspaces(self, plan, radius: float, groups=None, reach=None, rounds: int = 32) -> Airspaces:
+        """The fleet split into groups of missions that can never come inside `radius` of each other, whatever their starts -- and,
+        with `reach` = max_steps * delta, whatever layers 0 .. max_steps they are granted: the connected components, within each of
+        the caller's `groups`, of "the swept boxes are nearer than `radius` on every axis" (`uavac_fleet_airspaces_dev` on
+        `Engine.envelope(plan, reach)`; `uav_ac.scoring.airspaces_from_envelopes`).  The prioritised searches run per airspace, on
+        the missions in their original relative order, give every mission the answer of the search over its whole group:
+        `Engine.stagger / layer / deconflict(..., airspaces=True)` do that.
+        A chain on the device: the boxes, the labels (`rounds` rounds per call), `uavac_fleet_order_dev` with the labels as
+        priorities (exact in float64; stable, so an airspace keeps its order), the boundaries where the label changes.  ONE small
+        host read covers the labelling's verdict and the boundaries, on the footing of `Engine.take`'s; while the labels are not final
+        the labelling is called again where it stopped and the read repeated -- labels that are not final never leave this call.
+        `plan` and `groups` as `Engine.stagger` takes them (any group size).  -> Airspaces."""
+        torch = self._torch
+        plan = self._coeff_plan(plan)
+        B = int(plan.B)
+        radius, rounds = float(radius), int(rounds)
+        if not (np.isfinite(radius) and radius >= 0.0):
+            raise ValueError("radius must be finite and >= 0")
+        if rounds < 1:
+            raise ValueError("rounds must be >= 1")
+        go, G = self._groups(groups, B)
+        env = self.envelope(plan, reach)
+        kw = dict(dtype=torch.int32, device=self.device)
+        labels, order, rank = (torch.empty((B,), **kw) for _ in range(3))
+        tail = torch.empty((2 + B,), **kw)                               # info, and behind it: does an airspace begin in this slot?
+        self._bind_stream()
+        changed, resume = 0, 0
+        while True:
+            self.ctx.call("uavac_fleet_airspaces_dev", _ptr(env.block), _ptr(go), G, B, radius, rounds, resume, _ptr(labels), _ptr(tail))
+            keys = labels.to(torch.float64)
+            self.ctx.call("uavac_fleet_order_dev", _ptr(keys), _ptr(go), G, B, _ptr(order), _ptr(rank))
+            sorted_labels = labels[order.long()]
+            tail[2] = 1
+            tail[3:] = (sorted_labels[1:] != sorted_labels[:-1]).to(torch.int32)
+            host = tail.cpu().numpy()                                    # the one read (per labelling call)
+            changed += int(host[0])
+            if host[1]:
+                break
+            resume = 1
+        offsets_host = np.concatenate([np.flatnonzero(host[2:]), [B]]).astype(np.int64)
+        sizes = np.diff(offsets_host)
+        return Airspaces(labels, order, rank, torch.as_tensor(offsets_host).to(self.device), offsets_host, sizes, int(sizes.max()), changed)
+
+    NARROW_SEARCH = min(nat.STAGGER_MAX_GROUP, nat.LAYER_MAX_GROUP)     # the largest airspace the narrow searches take
+
+    @staticmethod
+    def _layer_reach(delta, max_steps) -> np.ndarray:
+        """The reach of a layer search, fl(max_steps * delta) per axis: what `airspaces` needs to cover every layer 0 .. max_steps."""
+        max_steps = int(max_steps)
+        if not (0 <= max_steps <= nat.LAYER_MAX_STEPS):
+            raise ValueError(f"max_steps must be in 0 .. {nat.LAYER_MAX_STEPS}")
+        d = np.asarray(delta.detach().cpu().numpy() if hasattr(delta, "detach") else delta, dtype=np.float64).reshape(-1)
+        if d.size != 3 or not np.isfinite(d).all():
+            raise ValueError("delta must be three finite numbers")
+        return np.float64(max_steps) * d
+
+    def _airspace_front(self, plan, radius, groups, reach, priority, start_rows):
+        """The front of the `airspaces=True` forms -> (the plan taken in airspace order, rank, the start rows in slot order or None, the
+        searches' `groups` / `wide` / `group_cap`).  With a `priority` two stable passes: the order by priority within the caller's
+        groups, then that order by label -- within an airspace the order is the priority's, ties to the earlier slot."""
+        torch = self._torch
+        plan = self._coeff_plan(plan)
+        B = int(plan.B)
+        asp = self.airspaces(plan, radius, groups, reach)
+        order, rank = asp.order, asp.rank
+        if priority is not None:
+            by_priority, slot_of, _ = self._priority_order(priority, groups, B, None, None)
+            go, G = self._groups(groups, B)
+            keys = asp.labels[by_priority.long()].to(torch.float64)
+            by_label, slot_then = (torch.empty((B,), dtype=torch.int32, device=self.device) for _ in range(2))
+            self._bind_stream()
+            self.ctx.call("uavac_fleet_order_dev", _ptr(keys), _ptr(go), G, B, _ptr(by_label), _ptr(slot_then))
+            order, rank = by_priority[by_label.long()].contiguous(), slot_then[slot_of.long()].contiguous()
+        start = None if start_rows is None else self._start_rows(start_rows, B)[order.long()]
+        wide = asp.largest > self.NARROW_SEARCH
+        return self.take(plan, order), rank, start, dict(groups=asp.offsets, wide=wide, group_cap=asp.largest if wide else None)
+
     def _priority_order(self, priority, groups, B: int, max_group: int, start_rows):
         """The front of the `priority=` forms: the within-group order of `priority` (`uavac_fleet_order_dev`) -> (order, rank, the start
         rows in slot order or None), device tensors.  The groups are checked against `max_group` (None: no limit, the `wide` forms) here,
@@ -936,7 +1057,8 @@ class Engine:
         return LayerResult(*block[:nat.LAYER_ROWS].unbind(0), block, res.offsets[at].contiguous())
 
     def deconflict(self, plan, radius: float, groups=None, obstacles=None, start_rows=None, step: int = 1, max_delay_steps: int = 255,
-                   delta=(0.0, 0.0, -0.5), max_layers: int = 63, priority=None, wide: bool = False, group_cap=None) -> DeconflictResult:
+                   delta=(0.0, 0.0, -0.5), max_layers: int = 63, priority=None, wide: bool = False, group_cap=None,
+                   airspaces: bool = False) -> DeconflictResult:
         """The fleet chain as one call: stagger -> layer -> shift -> delay.  `Engine.stagger(plan, radius, groups, start_rows, step,
         max_delay_steps)` makes missions wait; `Engine.layer(plan, radius, groups, start_rows=stagger.start_rows, delta=delta,
         max_steps=max_layers, obstacles=obstacles)` moves, at the granted starts, the ones that waiting cannot clear -- and, with
@@ -964,7 +1086,19 @@ class Engine:
         `eng.put(plan, ~result.resolved, replanned)` puts them back, and `deconflict` runs again -- with a priority that takes them
         first if they are to win this time.
         `wide=True`, `group_cap`: groups of any size; both searches run as `Engine.stagger(..., wide=True, group_cap=group_cap)` and
-        `Engine.layer(..., wide=True, group_cap=group_cap)`, and the guarantees above hold unchanged."""
+        `Engine.layer(..., wide=True, group_cap=group_cap)`, and the guarantees above hold unchanged.
+        `airspaces=True`: both searches per airspace, as `Engine.stagger` and `Engine.layer` describe it.  The airspaces are computed
+        ONCE, with `reach` = `max_layers` * `delta` -- boxes that cover the layers cover the starts too --, both searches run on one
+        `Engine.take(plan, order)`, and `plan` is built from the caller's plan as in the `priority=` form: the same `stagger.start_rows`
+        / `steps`, `layer.layers` / `steps` / `blocked` / `offsets`, `resolved` and `plan`, bit for bit, as `wide=True` gives;
+        `earlier` counts within the airspace, and the size limits apply to airspaces."""
+        if airspaces:
+            taken, rank, start, route = self._airspace_front(plan, radius, groups, self._layer_reach(delta, max_layers), priority, start_rows)
+            stag = self.stagger(taken, radius, start_rows=start, step=step, max_steps=max_delay_steps, **route)
+            lay = self.layer(taken, radius, start_rows=stag.start_rows, delta=delta, max_steps=max_layers, obstacles=obstacles, **route)
+            stag, lay = self._stagger_back(stag, rank), self._layer_back(lay, rank)
+            flown = self.delay(self.shift(plan, lay.offsets), stag.start_rows)
+            return DeconflictResult(flown, stag, lay, lay.steps >= 0)
         w = dict(wide=wide, group_cap=group_cap)
         if priority is not None:
             B = int(self._coeff_plan(plan).B)

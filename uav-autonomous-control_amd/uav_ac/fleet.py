@@ -27,7 +27,7 @@ def _torch():
 
 def _ptr(t) -> _P:
     return _P(0 if t is None else t.data_ptr())
-from .engine import ConflictList, DeconflictResult, Engine, FlightAudit, Plan, LayerResult, PlanAudit, PlanDemand, PlanNeed, RaggedBatch, RaggedPlan, RetimeResult, RRTDeviceBatch, SeparationAudit, StaggerResult, TimeOptResult  # noqa: F401  (re-exported)
+from .engine import Airspaces, ConflictList, DeconflictResult, Engine, FlightAudit, Plan, LayerResult, PlanAudit, PlanDemand, PlanEnvelope, PlanNeed, RaggedBatch, RaggedPlan, RetimeResult, RRTDeviceBatch, SeparationAudit, StaggerResult, TimeOptResult  # noqa: F401  (re-exported)
 from .sharding import (DEFAULT_TICK_TABLE, balanced_root_share, candidate_shard_sizes, gather_layout,  # noqa: F401
                        measure_tick_table, shard_bounds, shard_sizes)
 from .comm import RcclComm  # noqa: F401

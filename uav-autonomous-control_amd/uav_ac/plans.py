@@ -321,6 +321,30 @@ class LayerResult:
 
 
 @dataclass
+class PlanEnvelope:
+    """Every mission's swept box (`Engine.envelope`, include/uavac.h uavac_minsnap_envelope_dev): device tensors, the minimum and the
+    maximum per axis of the positions the sampler writes -- with a reach, of the shifted plan's as well.  NaN in all six for a mission
+    without rows or with a position that is not finite."""
+    lo: "object"             # (B, 3) f64
+    hi: "object"             # (B, 3) f64
+    block: "object" = None   # the [B][6] block the two above are views of
+
+
+@dataclass
+class Airspaces:
+    """A fleet split into groups that can never meet (`Engine.airspaces`, include/uavac.h uavac_fleet_airspaces_dev): the connected
+    components of "swept boxes nearer than the radius", per caller group, and the order that puts each of them side by side."""
+    labels: "object"         # (B,) i32, device: the lowest batch index of the mission's airspace (final: the engine resumes until they are)
+    order: "object"          # (B,) i32, device: the mission in every slot -- sorted by label within each caller group, stably
+    rank: "object"           # (B,) i32, device: its inverse, rank[order[s]] = s
+    offsets: "object"        # (A + 1,) i64, device: airspace a holds the slots [offsets[a], offsets[a + 1]) -- what the searches take as groups
+    offsets_host: np.ndarray  # the same on the host
+    sizes_host: np.ndarray   # (A,) i64, host: diff(offsets_host)
+    largest: int             # the largest airspace: at most 256 takes the narrow searches, more the wide ones with group_cap = largest
+    rounds: int              # labelling rounds that changed a label
+
+
+@dataclass
 class DeconflictResult:
     """What `Engine.deconflict` returns: the plan to fly and the two searches it was made from."""
     plan: "object"           # rows-free RaggedBatch: delay(shift(plan, layer.offsets), stagger.start_rows)

@@ -31,6 +31,9 @@ valid ticks, flown peaks, and per cuboid hits and closest approach --, and `flig
 `demand_from_rows` states what a plan ASKS of the vehicle -- specific thrust, bank, roll / pitch rate, rows that ask for thrust downward,
 and per cuboid the planned clearance: the rule of `Engine.demand` (uavac_minsnap_demand_dev) on sampled rows and jerk --,
 `demand_feasibility` judges it against what the vehicle can give, and `audit_gap` sets it beside the flight audit of the same missions.
+`envelope_from_rows` states every mission's swept box (`Engine.envelope`, uavac_minsnap_envelope_dev), `airspaces_from_envelopes` the
+split of a fleet into groups whose boxes can never come within a radius of each other, round for round (`Engine.airspaces`,
+uavac_fleet_airspaces_dev), and `airspace_order` the order that puts each of them side by side: what `airspaces=True` on the searches runs on.
 """
 from __future__ import annotations
 
@@ -1178,3 +1181,90 @@ def priority_order(priority, group_offsets=None):
     rank = np.empty(B, dtype=np.int32)
     rank[order] = np.arange(B, dtype=np.int32)
     return order, rank
+
+
+def envelope_from_rows(rows, row_offsets, rows_reach=None):
+    """Every mission's swept box on SAMPLED rows -- the SPECIFICATION of `uavac_minsnap_envelope_dev` (csrc/minsnap_envelope.hip),
+    which is tested against it as numbers.  NumPy on the host.
+    `rows` (N, >= 3) and `row_offsets` (B + 1,) as `separation_from_rows` takes them.  `rows_reach` (N, >= 3) or None: the rows of the
+    same plan with an offset added to c0 of every segment (`Engine.shift(plan, reach)`: the same row counts); the box is then the hull
+    of both.
+    -> (lo, hi), (B, 3) f64 each: the minimum and the maximum of the mission's positions per axis.  A mission without rows, or with a
+    position that is not finite on either side, gets NaN in all six."""
+    rows = _host(rows)
+    ro = _host_i64(row_offsets)
+    B = len(ro) - 1
+    sides = [rows[:, 0:3]] if rows_reach is None else [rows[:, 0:3], _host(rows_reach)[:, 0:3]]
+    if any(len(p) != len(sides[0]) for p in sides):
+        raise ValueError("rows_reach holds one row per row of rows")
+    lo, hi = np.full((B, 3), np.nan), np.full((B, 3), np.nan)
+    for b in range(B):
+        p = np.concatenate([s[ro[b]:ro[b + 1]] for s in sides])
+        if len(p) and np.isfinite(p).all():
+            lo[b], hi[b] = p.min(axis=0), p.max(axis=0)
+    return lo, hi
+
+
+def airspaces_from_envelopes(lo, hi, radius, group_offsets=None, rounds=None, labels=None):
+    """Independent airspaces from swept boxes -- the SPECIFICATION of `uavac_fleet_airspaces_dev` (csrc/fleet_airspaces.hip), which is
+    tested against it exactly, the round count included.  NumPy on the host.
+    `lo`, `hi` (B, 3): the boxes (`envelope_from_rows`).  `group_offsets` (G + 1,) or None = one group of all B, every entry clamped
+    as `priority_order` clamps it; a mission that no group holds is linked to nobody.
+    THE LINK.  Missions i != j of the same group are linked iff on all three axes lo_i - hi_j < radius and lo_j - hi_i < radius (each
+    difference one rounded subtraction, the comparison strict): two boxes that are `radius` apart on some axis are not linked, and
+    neither is a box that holds a NaN, to anybody.
+    ONE ROUND, on whole arrays: m[i] = min(lab[i], min of lab[j] over the linked j); lab'[i] = m[m[i]] (the pointer jump).  The first
+    round starts from lab[i] = i, or from `labels` (B,) when they are given (a resumed call).  At most `rounds` rounds are run (None:
+    as many as it takes); the first round that changes nothing is the last one run.
+    -> (labels (B,) i32, the number of rounds that changed a label, converged: the last round run changed nothing).  Once converged,
+    labels[b] is the lowest batch index of b's connected component; before that the labels describe a FINER partition than the
+    components and must not be used for anything but a resumed call."""
+    lo, hi = _host(lo).reshape(-1, 3), _host(hi).reshape(-1, 3)
+    B = len(lo)
+    if len(hi) != B:
+        raise ValueError("one lo and one hi per mission")
+    radius = _radius(radius)
+    if rounds is not None and int(rounds) < 1:
+        raise ValueError("rounds must be >= 1")
+    go = np.array([0, B], dtype=np.int64) if group_offsets is None else _host_i64(group_offsets)
+    if len(go) < 2:
+        raise ValueError("group offsets hold at least two entries")
+    lab = np.arange(B, dtype=np.int64) if labels is None else np.clip(_host_i64(labels), 0, max(B - 1, 0))
+    if len(lab) != B:
+        raise ValueError("one label per mission")
+    linked = []                                                                       # per group: (g0, g1, the (g, g) link matrix)
+    for g in range(len(go) - 1):
+        g0 = int(min(max(go[g], 0), B))
+        g1 = int(min(max(go[g + 1], g0), B))
+        if g1 - g0 < 2:
+            continue
+        with np.errstate(invalid="ignore", over="ignore"):
+            gap = lo[g0:g1, None, :] - hi[None, g0:g1, :]                             # gap[i, j] = lo_i - hi_j
+            link = (gap < radius).all(axis=2)
+        link = link & link.T
+        np.fill_diagonal(link, False)
+        linked.append((g0, g1, link))
+    changed, converged = 0, False
+    while rounds is None or changed < int(rounds):
+        m = lab.copy()
+        for g0, g1, link in linked:
+            m[g0:g1] = np.minimum(m[g0:g1], np.where(link, lab[None, g0:g1], B).min(axis=1))
+        new = m[m]
+        if np.array_equal(new, lab):
+            converged = True
+            break
+        lab, changed = new, changed + 1
+    return lab.astype(np.int32), changed, converged
+
+
+def airspace_order(labels, group_offsets=None):
+    """Missions sorted by airspace within each caller group: `priority_order(labels, group_offsets)` -- stable, so the missions of an
+    airspace keep their relative order -- and the boundaries where the label changes.  What `Engine.airspaces` computes on the device
+    (`uavac_fleet_order_dev` with the labels as priorities, exact in float64).
+    -> (order, rank, airspace_offsets): order and rank (B,) i32 as `priority_order` gives them; airspace_offsets (A + 1,) i64 ascending
+    from 0 to B, airspace a holds the slots [airspace_offsets[a], airspace_offsets[a + 1]) of `order`."""
+    lab = _host_i64(labels)
+    order, rank = priority_order(lab.astype(np.float64), group_offsets)
+    sorted_lab = lab[order]
+    starts = np.flatnonzero(np.concatenate([[True], sorted_lab[1:] != sorted_lab[:-1]])) if len(lab) else np.zeros(0, dtype=np.int64)
+    return order, rank, np.concatenate([starts, [len(lab)]]).astype(np.int64)
