@@ -613,6 +613,83 @@ int uavac_minsnap_layer_wide_dev(uavac_ctx *ctx, const double *coeffs, const int
                                  double delta_x, double delta_y, double delta_z, int max_steps, const double *cuboids, int n_cuboids,
                                  int32_t *ilayer, double *offsets);
 
+/* AGAINST COMMITTED TRAFFIC THAT NEVER MOVES: the audit and the two searches for new missions that are fitted around missions which
+ * have already been granted a start and a layer, or are in the air (csrc/minsnap_separation_against.hip,
+ * csrc/minsnap_stagger_against.hip, csrc/minsnap_layer_against.hip, csrc/fleet_against.h).  From coefficients and row counts alone:
+ * no row is written, nothing is read back, everything is enqueued on the ctx stream, scratch comes from the ctx arena.
+ * THE TRAFFIC is a second plan with its own arguments, in every one of the three calls the seven behind G: t_coeffs / t_seg_rows /
+ * t_seg_offsets / Bt / mt like coeffs / seg_rows / seg_offsets / B / m of uavac_minsnap_separation_dev (t_seg_offsets NULL = uniform
+ * with mt segments each, otherwise ragged with segment counts clamped to 1 .. mt), t_group_offsets [G + 1] i64 or NULL, t_start_rows
+ * [Bt] i32 or NULL = all 0.  It shares dt and G with the plan.
+ * CLOCK.  One row clock per group for both sides: a mission of the plan with start s and a traffic mission with start t_start_rows[j]
+ * stand at their own rows clamp(k - start, 0, N - 1) -- each waits on its first row before its start and holds its last row after
+ * its end.  The horizon covers both sides: H_g = max(S + N) over the included missions of the plan's group g AND of the traffic's.
+ * GROUPS.  Group g of the plan meets group g of the traffic and nobody else's.  group_offsets and t_group_offsets are both NULL -- one
+ * group each: all B against all Bt -- or both given, G + 1 entries each, ascending from 0 to B and from 0 to Bt; a group of either side
+ * may be empty.  Offsets are clamped to the batch they index, as everywhere.
+ * EXCLUDED MISSIONS, on either side: no rows, a coefficient that is not finite, or more than 2^29 rows.  Excluded traffic is
+ * nobody's partner and is counted nowhere.  A TRAFFIC MISSION STANDS AS PLANNED at its start row: it has no candidate and no layer,
+ * is never examined and never written -- no call writes to any of the traffic's arrays or has an output row for it.
+ * ROUNDING is uavac_minsnap_separation_dev's: positions by the sampler's fma chain, d^2 = (dx * dx + dy * dy) + dz * dz without
+ * contraction, r^2 = radius * radius rounded once, inside means d^2 < r^2 strictly.
+ * BAD INPUTS.  Start rows of either side outside 0 .. 2^29 are clamped and raise sticky flag 0 (uavac_take_flags), and so does a
+ * mission of more than 2^29 rows, which is excluded.  UAVAC_EINVAL before anything is enqueued: what the call without traffic
+ * refuses (below, per call), then a NULL t_coeffs or t_seg_rows, Bt < 1, mt outside 1 .. UAVAC_MAX_SEGMENTS, offsets given on one
+ * side only (group_offsets == NULL xor t_group_offsets == NULL).
+ *
+ * uavac_minsnap_separation_against_dev: THE CROSS AUDIT.  For every mission of the plan the closest approach to any included traffic
+ * mission of its group on the shared clock.  Missions of the plan are never compared with each other.  sep [B] f64 and isep
+ * [UAVAC_SEP_ROWS][B] i32 have the layout of uavac_minsnap_separation_dev with these meanings: sep the minimum distance; row 0 partner
+ * = the TRAFFIC batch index (0 .. Bt - 1); 1 the clock row of the minimum; 2 conflicts = the number of traffic missions that come
+ * inside the radius; 3 the first clock row with one inside (-1: none); 4 compared = the included traffic missions of the group.  The
+ * same arithmetic and ties: the lexicographic minimum of (d^2, row, partner), one correctly rounded sqrt last, strict <.  A mission
+ * whose group has no included traffic reports +inf, -1, -1, 0, -1, 0; an excluded mission of the plan NaN, -1, -1, 0, -1, 0.  Bit for
+ * bit what NumPy gives on the sampled rows (uav_ac.scoring.separation_against_rows), whatever the launch shape (option
+ * "separation_split").  Refuses what uavac_minsnap_separation_dev refuses (required pointers: coeffs, seg_rows, sep, isep).  Scratch:
+ * that call's, plus 8 bytes per traffic mission.  Cost: plan missions x traffic missions of the group x horizon.
+ *
+ * uavac_minsnap_stagger_against_dev: uavac_minsnap_stagger_wide_dev's rule and outputs -- group_cap, start_rows (the BASE starts),
+ * step, max_steps and istag [UAVAC_STAGGER_ROWS][B] mean what they mean there, and group_cap bounds the PLAN's missions of a group
+ * -- with ONE MORE CLAUSE IN "CLEAR": candidate q of mission i is clear iff it is outside the radius of every included mission j < i
+ * of its group at its granted start T_j AND of every included traffic mission of its group at that mission's start, at every clock
+ * row below the horizon, which covers the traffic's ends too.  earlier (row 2) counts the included traffic of the group PLUS the
+ * included plan missions before it.  The first included mission of a group is examined whenever its group has included traffic (in
+ * uavac_minsnap_stagger_wide_dev it never is).  A group without included traffic gives exactly that call's answers.  Exactly what
+ * NumPy gives on the sampled rows (uav_ac.scoring.stagger_against_rows(..., max_group = group_cap)), whatever the block size.
+ * WHAT THE RESULT GUARANTEES: uavac_minsnap_separation_against_dev with start_rows = istag[0] reports conflicts == 0 for every
+ * RESOLVED mission, and uavac_minsnap_separation_dev on the plan alone finds no pair of resolved missions inside the radius.  Two
+ * traffic missions that conflict with each other stay as they are: this call decides nothing about them.
+ * HOW.  The traffic is a virtual earlier block of the block-wise search (csrc/fleet_wide.h): behind the two pre-passes and the
+ * memsets one small kernel fills every group's carry with the traffic's count and horizon, and ONE seed kernel over all B missions,
+ * parallel over the chip, ORs into the seed words what the traffic does to every candidate 0 .. max_steps; then the seed / search
+ * launches per block as there, unchanged.  Three launches more than that call.  Refuses what uavac_minsnap_stagger_wide_dev refuses.
+ * Scratch: that call's, plus 8 bytes per traffic mission; UAVAC_ENOMEM with a message when it does not fit.  Cost: the seed is
+ * missions x (max_steps / 64 + 1) rounds x traffic of the group x horizon, a round ending early once all its candidates are hit.
+ *
+ * uavac_minsnap_layer_against_dev: the same extension of uavac_minsnap_layer_wide_dev -- the cuboid policy: every included mission
+ * is examined, a blocked candidate is refused before anybody is compared; ilayer is [UAVAC_LAYER_OBS_ROWS][B], offsets [B][3], cuboids
+ * may be NULL with n_cuboids = 0.  start_rows are FIXED starts.  A traffic mission is compared AS IT IS, on no layer: a caller who has
+ * layered the traffic passes the shifted plan (uavac_minsnap_shift_dev).  earlier counts the included traffic plus the included plan
+ * missions before it; a group without included traffic gives exactly uavac_minsnap_layer_wide_dev's answers.  Exactly what NumPy
+ * gives (uav_ac.scoring.layer_against_rows(..., max_group = group_cap)).  Refuses what uavac_minsnap_layer_wide_dev refuses.  Launches,
+ * scratch and UAVAC_ENOMEM as in uavac_minsnap_stagger_against_dev. */
+int uavac_minsnap_separation_against_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B,
+                                         int m, double dt, const int64_t *group_offsets, int G, const double *t_coeffs,
+                                         const int32_t *t_seg_rows, const int64_t *t_seg_offsets, int Bt, int mt,
+                                         const int64_t *t_group_offsets, const int32_t *t_start_rows, const int32_t *start_rows,
+                                         double radius, double *sep, int32_t *isep);
+int uavac_minsnap_stagger_against_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                      double dt, const int64_t *group_offsets, int G, const double *t_coeffs, const int32_t *t_seg_rows,
+                                      const int64_t *t_seg_offsets, int Bt, int mt, const int64_t *t_group_offsets,
+                                      const int32_t *t_start_rows, int group_cap, const int32_t *start_rows, double radius, int step,
+                                      int max_steps, int32_t *istag);
+int uavac_minsnap_layer_against_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                    double dt, const int64_t *group_offsets, int G, const double *t_coeffs, const int32_t *t_seg_rows,
+                                    const int64_t *t_seg_offsets, int Bt, int mt, const int64_t *t_group_offsets,
+                                    const int32_t *t_start_rows, int group_cap, const int32_t *start_rows, double radius, double delta_x,
+                                    double delta_y, double delta_z, int max_steps, const double *cuboids, int n_cuboids, int32_t *ilayer,
+                                    double *offsets);
+
 /* OFFSET AS A PLAN TRANSFORM: how the granted layers are flown and audited.  out_coeffs = coeffs (the same layout: [B][8 m][3] uniform
  * with seg_offsets == NULL, or [total_segments][8][3] ragged with seg_offsets [B+1]; total_segments is ignored for a uniform batch)
  * with c0'[a] = fl(c0[a] + offsets[b][a]) in every segment of mission b; c1 .. c7 are copied bit for bit, and so is every segment of a

@@ -116,25 +116,32 @@ __device__ __forceinline__ void fleet_seed(const Policy pol, const double *__res
 // Scratch from the ctx arena: the pre-pass's row totals and clamped starts, B x words seed words, two ints of carry per group.
 // `prepass(n_rows, start)` launches the policy's pre-pass, `seed(grid, n_rows, start, block)` and `search(grid, n_rows, start, block)` its
 // two kernels; everything goes to the ctx stream.
-template <class Prepass, class Seed, class Search>
+// TRAFFIC (fleet_against.h: Bt > 0 missions of another plan that count as decided before block 0): their row totals and starts are
+// two more pieces of the scratch; `traffic_prepass(t_n_rows, t_start)` is launched behind the pre-pass, `traffic_seed(t_n_rows,
+// t_start, n_rows, start, block)` between the memsets and block 0 -- it fills the carries and ORs into the seed words.
+template <class Prepass, class Seed, class Search, class TrafficPrepass, class TrafficSeed>
 int launch_wide_search(uavac_ctx *ctx, int B, const int64_t *group_offsets, int G, int group_cap, int max_steps, Prepass prepass, Seed seed,
-                       Search search) {
+                       Search search, int Bt, TrafficPrepass traffic_prepass, TrafficSeed traffic_seed) {
     const int groups = group_offsets ? G : 1;
     const int blk = ctx->search_block ? ctx->search_block : kWideBlock;
     const int words = max_steps / kTile + 1;
     const int blocks = (std::min(group_cap, B) + blk - 1) / blk;  // (no group is larger than the batch)
     if ((long long)groups * blk > 0x7fffffffLL) return uavac_fail(ctx, UAVAC_EINVAL, "too many groups for the block-wise search: G * block above 2^31 - 1");
-    int32_t *n_rows = nullptr, *start = nullptr, *carry = nullptr;
+    int32_t *n_rows = nullptr, *start = nullptr, *carry = nullptr, *t_n_rows = nullptr, *t_start = nullptr;
     unsigned long long *words_of = nullptr;
     Scratch s(ctx);
     s.want(&n_rows, B); s.want(&start, B); s.want(&words_of, (size_t)B * words); s.want(&carry, 2 * (size_t)groups);
+    if (Bt > 0) { s.want(&t_n_rows, Bt); s.want(&t_start, Bt); }
     if (s.commit()) {
         (void)hipGetLastError();
-        return uavac_fail(ctx, UAVAC_ENOMEM, "the block-wise search's scratch (8 + 8 (max_steps / 64 + 1) bytes per mission, 8 per group) does not fit on the device");
+        return uavac_fail(ctx, UAVAC_ENOMEM, Bt > 0 ? "the search's scratch (8 + 8 (max_steps / 64 + 1) bytes per mission, 8 per group, 8 per traffic mission) does not fit on the device"
+                                                    : "the block-wise search's scratch (8 + 8 (max_steps / 64 + 1) bytes per mission, 8 per group) does not fit on the device");
     }
     prepass(n_rows, start);
+    if (Bt > 0) traffic_prepass(t_n_rows, t_start);
     UAVAC_HIP(ctx, hipMemsetAsync(words_of, 0, (size_t)B * words * sizeof(unsigned long long), ctx->stream));
     UAVAC_HIP(ctx, hipMemsetAsync(carry, 0, 2 * (size_t)groups * sizeof(int32_t), ctx->stream));
+    if (Bt > 0) traffic_seed(t_n_rows, t_start, n_rows, start, Block{0, blk, group_cap, words_of, words, carry});
     for (int k = 0; k < blocks; ++k) {
         const Block block{k, blk, group_cap, words_of, words, carry};
         if (k > 0) {                                         // shares per mission: enough workgroups for the chip, at most one per j-tile
@@ -147,6 +154,14 @@ int launch_wide_search(uavac_ctx *ctx, int B, const int64_t *group_offsets, int 
     }
     UAVAC_HIP(ctx, hipGetLastError());
     return UAVAC_OK;
+}
+
+// (without traffic: the two calls for groups of any size)
+template <class Prepass, class Seed, class Search>
+int launch_wide_search(uavac_ctx *ctx, int B, const int64_t *group_offsets, int G, int group_cap, int max_steps, Prepass prepass, Seed seed,
+                       Search search) {
+    return launch_wide_search(ctx, B, group_offsets, G, group_cap, max_steps, prepass, seed, search, 0, [](int32_t *, int32_t *) {},
+                              [](int32_t *, int32_t *, const int32_t *, const int32_t *, Block) {});
 }
 
 }  // namespace

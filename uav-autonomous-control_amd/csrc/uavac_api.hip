@@ -1086,6 +1086,61 @@ int uavac_minsnap_layer_wide_dev(uavac_ctx *ctx, const double *coeffs, const int
                                    delta_z, max_steps, cuboids, n_cuboids, ilayer, offsets);
 }
 
+// what the three calls against traffic refuse about the traffic's side, behind their own calls' lists
+static int check_traffic_args(uavac_ctx *ctx, const int64_t *group_offsets, const double *t_coeffs, const int32_t *t_seg_rows, int Bt, int mt,
+                              const int64_t *t_group_offsets) {
+    if (!t_coeffs || !t_seg_rows) return uavac_fail(ctx, UAVAC_EINVAL, "null pointer (traffic)");
+    if (Bt < 1) return uavac_fail(ctx, UAVAC_EINVAL, "Bt must be >= 1");
+    if (mt < 1 || mt > UAVAC_MAX_SEGMENTS) return uavac_fail(ctx, UAVAC_EINVAL, "mt must be in [1, UAVAC_MAX_SEGMENTS]");
+    if (!group_offsets != !t_group_offsets)
+        return uavac_fail(ctx, UAVAC_EINVAL, "group_offsets and t_group_offsets go together: both or none");
+    return UAVAC_OK;
+}
+
+int uavac_minsnap_separation_against_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B,
+                                         int m, double dt, const int64_t *group_offsets, int G, const double *t_coeffs,
+                                         const int32_t *t_seg_rows, const int64_t *t_seg_offsets, int Bt, int mt,
+                                         const int64_t *t_group_offsets, const int32_t *t_start_rows, const int32_t *start_rows,
+                                         double radius, double *sep, int32_t *isep) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_pair_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, sep && isep)) return rc;
+    if (int rc = check_traffic_args(ctx, group_offsets, t_coeffs, t_seg_rows, Bt, mt, t_group_offsets)) return rc;
+    return uavac_launch_separation_against(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, t_coeffs, t_seg_rows,
+                                           t_seg_offsets, Bt, mt, t_group_offsets, t_start_rows, radius, sep, isep);
+}
+
+int uavac_minsnap_stagger_against_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                      double dt, const int64_t *group_offsets, int G, const double *t_coeffs, const int32_t *t_seg_rows,
+                                      const int64_t *t_seg_offsets, int Bt, int mt, const int64_t *t_group_offsets,
+                                      const int32_t *t_start_rows, int group_cap, const int32_t *start_rows, double radius, int step,
+                                      int max_steps, int32_t *istag) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_stagger_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, step, max_steps, istag)) return rc;
+    if (int rc = check_group_cap(ctx, B, group_offsets, group_cap)) return rc;
+    if (int rc = check_traffic_args(ctx, group_offsets, t_coeffs, t_seg_rows, Bt, mt, t_group_offsets)) return rc;
+    return uavac_launch_stagger_against(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, group_cap, start_rows, t_coeffs,
+                                        t_seg_rows, t_seg_offsets, Bt, mt, t_group_offsets, t_start_rows, radius, step, max_steps, istag);
+}
+
+int uavac_minsnap_layer_against_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                    double dt, const int64_t *group_offsets, int G, const double *t_coeffs, const int32_t *t_seg_rows,
+                                    const int64_t *t_seg_offsets, int Bt, int mt, const int64_t *t_group_offsets,
+                                    const int32_t *t_start_rows, int group_cap, const int32_t *start_rows, double radius, double delta_x,
+                                    double delta_y, double delta_z, int max_steps, const double *cuboids, int n_cuboids, int32_t *ilayer,
+                                    double *offsets) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_layer_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, delta_x, delta_y, delta_z, max_steps, ilayer, offsets,
+                                  true))
+        return rc;
+    if (int rc = check_n_cuboids(ctx, n_cuboids)) return rc;
+    if (n_cuboids > 0 && !cuboids) return uavac_fail(ctx, UAVAC_EINVAL, "cuboids must be given when n_cuboids > 0");
+    if (int rc = check_group_cap(ctx, B, group_offsets, group_cap)) return rc;
+    if (int rc = check_traffic_args(ctx, group_offsets, t_coeffs, t_seg_rows, Bt, mt, t_group_offsets)) return rc;
+    return uavac_launch_layer_against(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, group_cap, start_rows, t_coeffs, t_seg_rows,
+                                      t_seg_offsets, Bt, mt, t_group_offsets, t_start_rows, radius, delta_x, delta_y, delta_z, max_steps, cuboids,
+                                      n_cuboids, ilayer, offsets);
+}
+
 int uavac_minsnap_shift_dev(uavac_ctx *ctx, const double *coeffs, const int64_t *seg_offsets, int B, int m, int64_t total_segments,
                             const double *offsets, double *out_coeffs) {
     UAVAC_ENTER(ctx);

@@ -282,6 +282,21 @@ int uavac_launch_layer_wide(uavac_ctx *ctx, const double *coeffs, const int32_t 
                             const int64_t *group_offsets, int G, int group_cap, const int32_t *start_rows, double radius, double delta_x,
                             double delta_y, double delta_z, int max_steps, const double *cuboids, int n_cuboids, int32_t *ilayer,
                             double *offsets);
+// the same two searches and the audit AGAINST TRAFFIC, a second plan (t_*) that never moves (minsnap_stagger_against.hip,
+// minsnap_layer_against.hip: fleet_against.h; minsnap_separation_against.hip); outputs as the wide searches' and the audit's
+int uavac_launch_stagger_against(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
+                                 const int64_t *group_offsets, int G, int group_cap, const int32_t *start_rows, const double *t_coeffs,
+                                 const int32_t *t_seg_rows, const int64_t *t_seg_offsets, int Bt, int mt, const int64_t *t_group_offsets,
+                                 const int32_t *t_start_rows, double radius, int step, int max_steps, int32_t *istag);
+int uavac_launch_layer_against(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m, double dt,
+                               const int64_t *group_offsets, int G, int group_cap, const int32_t *start_rows, const double *t_coeffs,
+                               const int32_t *t_seg_rows, const int64_t *t_seg_offsets, int Bt, int mt, const int64_t *t_group_offsets,
+                               const int32_t *t_start_rows, double radius, double delta_x, double delta_y, double delta_z, int max_steps,
+                               const double *cuboids, int n_cuboids, int32_t *ilayer, double *offsets);
+int uavac_launch_separation_against(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                    double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, const double *t_coeffs,
+                                    const int32_t *t_seg_rows, const int64_t *t_seg_offsets, int Bt, int mt, const int64_t *t_group_offsets,
+                                    const int32_t *t_start_rows, double radius, double *sep, int32_t *isep);
 int uavac_launch_shift(uavac_ctx *ctx, const double *coeffs, const int64_t *seg_offsets, int B, int m, int64_t total_segments,
                        const double *offsets, double *out_coeffs);
 // the same search, refusing every layer on which a row of the mission's own lies inside a cuboid (minsnap_layer_obs.hip): cuboids

@@ -219,8 +219,20 @@ BUDGETS = (
            ("stagger_prepass_kernel", "wide_stagger_seed_kernel", "wide_stagger_kernel"), FROM_LDS),
     Budget("layer_wide_kernels", "minsnap_layer_wide.o", "wide layer", ("layer_prepass_kernel", "wide_layer_seed_kernel", "wide_layer_kernel"),
            FROM_LDS),
+    # the same searches against traffic that never moves (csrc/fleet_against.h): the two kernels above, and the traffic's seed
+    # kernel, which holds the 48 KB tile and two words like the block seed, hence three workgroups per CU and <= 168; the two
+    # pre-passes and the carry (32 B) run eight waves per SIMD
+    Budget("stagger_against_kernels", "minsnap_stagger_against.o", "stagger against traffic",
+           ("stagger_prepass_kernel", "traffic_prepass_kernel", "traffic_carry_kernel", "against_stagger_seed_kernel", "wide_stagger_seed_kernel",
+            "wide_stagger_kernel"), FROM_LDS),
+    Budget("layer_against_kernels", "minsnap_layer_against.o", "layer against traffic",
+           ("layer_prepass_kernel", "traffic_prepass_kernel", "traffic_carry_kernel", "against_layer_seed_kernel", "wide_layer_seed_kernel",
+            "wide_layer_kernel"), FROM_LDS),
+    # the cross audit: the plan audit's pair kernel with its partners taken from the traffic, the 48 KB tile, three workgroups per CU
+    Budget("separation_against_kernels", "minsnap_separation_against.o", "cross-audit",
+           ("against_prepass_kernel", "separation_against_kernel", "against_merge_kernel"), FROM_LDS),
 )
-DECISION_KERNELS = ("minsnap_layer_kernel", "wide_layer_kernel", "wide_stagger_kernel")      # FROM_LDS: these keep three workgroups per CU
+DECISION_KERNELS =("minsnap_layer_kernel", "wide_layer_kernel", "wide_stagger_kernel")      # FROM_LDS: these keep three workgroups per CU
 COUNTED = ("rollout_registers", "planning_registers")      # `run_all` reports these as a number of kernels, the others as {kernel: VGPRs}
 
 # The object files that have no budget, and why not.
@@ -314,6 +326,9 @@ def check_layer_kernels(): return vgprs(check_budgets("layer_kernels"))         
 def check_layer_obs_kernels(): return vgprs(check_budgets("layer_obs_kernels"))                         # noqa: E704
 def check_stagger_wide_kernels(): return vgprs(check_budgets("stagger_wide_kernels"))                   # noqa: E704
 def check_layer_wide_kernels(): return vgprs(check_budgets("layer_wide_kernels"))                       # noqa: E704
+def check_stagger_against_kernels(): return vgprs(check_budgets("stagger_against_kernels"))             # noqa: E704
+def check_layer_against_kernels(): return vgprs(check_budgets("layer_against_kernels"))                 # noqa: E704
+def check_separation_against_kernels(): return vgprs(check_budgets("separation_against_kernels"))       # noqa: E704
 TIMEOPT_KERNELS = next(row.kernels for row in BUDGETS if row.key == "timeopt_kernels")
 FLOWN_CONFLICT_KERNELS = next(row.kernels for row in BUDGETS if row.key == "flown_conflict_kernels")
 

@@ -116,6 +116,14 @@ _SIGNATURES = {
                                               C.c_double, C.c_int, _P, C.c_int, _P, _P]),
     "uavac_minsnap_layer_wide_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, C.c_int, _P, C.c_double, C.c_double,
                                                C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P]),
+    # against traffic: the seven arguments of the second plan (t_coeffs, t_seg_rows, t_seg_offsets, Bt, mt, t_group_offsets, t_start_rows) behind G
+    "uavac_minsnap_separation_against_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int,
+                                                       _P, _P, _P, C.c_double, _P, _P]),
+    "uavac_minsnap_stagger_against_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P,
+                                                    _P, C.c_int, _P, C.c_double, C.c_int, C.c_int, _P]),
+    "uavac_minsnap_layer_against_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P,
+                                                  _P, C.c_int, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P,
+                                                  _P]),
     "uavac_minsnap_shift_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int64, _P, _P]),
     "uavac_minsnap_take_offsets_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P]),
     "uavac_minsnap_take_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),

@@ -518,6 +518,43 @@ class Engine:
         B, held, pair_args = self._pair_args(plan, radius, groups, start_rows)      # (`held` keeps the pointers' tensors alive)
         return self._separation_audit("uavac_minsnap_separation_dev", pair_args, B)
 
+    def _traffic_args(self, plan, traffic, traffic_groups, traffic_start_rows, go, G: int):
+        """The TRAFFIC of the calls against committed traffic -> (the tensors behind the pointers, the seven arguments of the C calls:
+        t_coeffs, t_seg_rows, t_seg_offsets, Bt, mt, t_group_offsets, t_start_rows).  `traffic`: what `Engine.audit` takes, on the
+        plan's dt; `traffic_groups` like `groups`, with as many groups as the plan has (`go`, `G`: the plan's, from `_groups`) -- both
+        None, or both given; `traffic_start_rows` (Bt,) or None.  Anything else is a ValueError."""
+        traffic = self._coeff_plan(traffic)
+        if float(traffic.dt) != float(plan.dt):
+            raise ValueError(f"the traffic's dt ({float(traffic.dt)}) is not the plan's ({float(plan.dt)}): their rows would not share a clock")
+        Bt = int(traffic.B)
+        tgo, Gt = self._groups(traffic_groups, Bt)
+        if (go is None) != (tgo is None) or G != Gt:
+            raise ValueError(f"the plan has {G if go is not None else 1} group(s), the traffic {Gt if tgo is not None else 1}: `groups` and "
+                             "`traffic_groups` are both None or hold the same number of groups")
+        tstart = None if traffic_start_rows is None else self._start_rows(traffic_start_rows, Bt)
+        t = segments(traffic)
+        return (traffic, tgo, tstart), (_ptr(traffic.coeffs), _ptr(traffic.seg_rows), _ptr(t.so), t.B, t.m, _ptr(tgo), _ptr(tstart))
+
+    def separation_against(self, plan, traffic, radius: float, groups=None, traffic_groups=None, start_rows=None,
+                           traffic_start_rows=None) -> SeparationAudit:
+        """The plan's missions audited against ANOTHER plan, committed `traffic` (`uavac_minsnap_separation_against_dev`): per mission
+        of `plan` the closest approach to any traffic mission of its group, to which one (`partner` is the TRAFFIC batch index) and at
+        which row of the shared clock, how many traffic missions come inside `radius` and when the first one does; `compared` is the
+        included traffic of its group.  Missions of `plan` are never compared with each other (`Engine.separation` does that).  Bit
+        for bit what NumPy gives on the sampled rows (`uav_ac.scoring.separation_against_rows`).  `plan`, `groups`, `start_rows` as
+        `Engine.separation` takes them; `traffic` likewise, with the same `dt` (otherwise ValueError), `traffic_start_rows` (Bt,) or
+        None; `traffic_groups` like `groups`: group g of the plan meets group g of the traffic, so both are None (all against all) or
+        both hold the same number of groups, otherwise ValueError.  The horizon covers both sides.  A mission whose group has no
+        traffic reports +inf / -1 / -1 / 0 / -1 / 0.  Never reads `traj`; stream-ordered, no sync.  This is the audit that confirms
+        `Engine.stagger / layer / deconflict(..., traffic=)`."""
+        plan = self._coeff_plan(plan)
+        B = int(plan.B)
+        go, G = self._groups(groups, B)
+        start = None if start_rows is None else self._start_rows(start_rows, B)
+        held, targs = self._traffic_args(plan, traffic, traffic_groups, traffic_start_rows, go, G)      # (`held` keeps the pointers' tensors alive)
+        return self._separation_audit("uavac_minsnap_separation_against_dev",
+                                      (*self._plan_args(plan), _ptr(go), G, *targs, _ptr(start), float(radius)), B)
+
     def _separation_audit(self, call: str, args, B: int) -> SeparationAudit:
         """The planned or the flown separation audit: `call` on its leading arguments `args`, into a fresh result."""
         torch = self._torch
@@ -564,7 +601,8 @@ class Engine:
         return self._conflict_list("uavac_minsnap_conflict_offsets_dev", "uavac_minsnap_conflicts_dev", pair_args, B)
 
     def stagger(self, plan, radius: float, groups=None, start_rows=None, step: int = 1, max_steps: int = 255,
-                priority=None, wide: bool = False, group_cap=None, airspaces: bool = False) -> StaggerResult:
+                priority=None, wide: bool = False, group_cap=None, airspaces: bool = False, traffic=None, traffic_groups=None,
+                traffic_start_rows=None) -> StaggerResult:
         """Prioritised deconfliction by start delay (`uavac_minsnap_stagger_dev`): the call that acts on `Engine.separation`'s
         verdict.  Within a group the missions are taken in ascending batch index -- the lowest index is never delayed --, and each
         gets the smallest start `start_rows[b] + q * step`, q = 0 .. `max_steps`, that keeps it outside `radius` of every mission
@@ -598,15 +636,33 @@ class Engine:
         limits now apply to airspaces, not groups: the narrow call when the largest airspace holds at most `STAGGER_MAX_GROUP`
         missions, else the block-wise one with `group_cap` = that size; `wide` and `group_cap` are not looked at.  With `priority` the
         order within an airspace is the priority's.  Host reads: `Engine.airspaces`' and `Engine.take`'s.  False: exactly the native
-        calls made without the keyword."""
+        calls made without the keyword.
+        `traffic`: committed missions that NEVER MOVE (`uavac_minsnap_stagger_against_dev`) -- a second plan (what `Engine.audit`
+        takes, on the same `dt`) whose missions have been granted their starts and layers, or are in the air, and around which the
+        missions of `plan` are fitted.  A traffic mission stands as planned at `traffic_start_rows[j]` (None: all 0); `traffic_groups`
+        like `groups`: group g of the plan meets group g of the traffic, so both are None or hold the same number of groups.  One
+        more clause in "clear": the candidate is also outside `radius` of every traffic mission of its group over the whole shared
+        clock; `earlier` counts the group's traffic plus the plan's missions before it, and the first mission of a group is examined
+        whenever its group has traffic.  Exactly `uav_ac.scoring.stagger_against_rows(..., max_group=group_cap)`; a group without
+        traffic answers as `wide=True` does.  Always the block-wise form: `wide` is not looked at, `group_cap` works as for
+        `wide=True`, and the cost is arrivals x (traffic + earlier arrivals), not all x all.  Nothing of the traffic is decided or
+        written: two traffic missions that conflict with each other stay as they are.  `priority` composes as before -- the plan is
+        taken in order, the traffic is untouched.  Confirm with `Engine.separation_against(plan, traffic, radius, ...,
+        start_rows=result.start_rows)`.  `airspaces=True` together with `traffic` is a ValueError (airspaces are not labelled across
+        two plans), and so are a different `dt` and group counts that do not match.  None: exactly the native calls made without
+        the keyword."""
+        against = dict(traffic=traffic, traffic_groups=traffic_groups, traffic_start_rows=traffic_start_rows)
         if airspaces:
+            if traffic is not None:
+                raise ValueError("airspaces=True does not take traffic: airspaces are not labelled across two plans")
             taken, rank, start, route = self._airspace_front(plan, radius, groups, None, priority, start_rows)
             return self._stagger_back(self.stagger(taken, radius, start_rows=start, step=step, max_steps=max_steps, **route), rank)
+        wide = wide or traffic is not None
         if priority is not None:
             B = int(self._coeff_plan(plan).B)
             order, rank, start = self._priority_order(priority, groups, B, None if wide else nat.STAGGER_MAX_GROUP, start_rows)
             return self._stagger_back(self.stagger(self.take(plan, order), radius, groups, start, step, max_steps, wide=wide,
-                                                   group_cap=group_cap), rank)
+                                                   group_cap=group_cap, **against), rank)
         torch = self._torch
         plan = self._coeff_plan(plan)
         B = int(plan.B)
@@ -621,6 +677,12 @@ class Engine:
         go, G = self._groups(groups, B, None if wide else nat.STAGGER_MAX_GROUP)
         start = None if start_rows is None else self._start_rows(start_rows, B)
         block = torch.empty((nat.STAGGER_ROWS, B), dtype=torch.int32, device=self.device)
+        if traffic is not None:
+            held, targs = self._traffic_args(plan, traffic, traffic_groups, traffic_start_rows, go, G)      # (`held` keeps the tensors alive)
+            self._bind_stream()
+            self.ctx.call("uavac_minsnap_stagger_against_dev", *self._plan_args(plan), _ptr(go), G, *targs, cap, _ptr(start), float(radius),
+                          step, max_steps, _ptr(block))
+            return StaggerResult(*block.unbind(0), block)
         self._bind_stream()
         if wide:
             self.ctx.call("uavac_minsnap_stagger_wide_dev", *self._plan_args(plan), _ptr(go), G, cap, _ptr(start), float(radius), step,
@@ -675,7 +737,8 @@ class Engine:
         return self.sample_rows(out) if rows else out
 
     def layer(self, plan, radius: float, groups=None, start_rows=None, delta=(0.0, 0.0, -0.5), max_steps: int = 63,
-              obstacles=None, priority=None, wide: bool = False, group_cap=None, airspaces: bool = False) -> LayerResult:
+              obstacles=None, priority=None, wide: bool = False, group_cap=None, airspaces: bool = False, traffic=None,
+              traffic_groups=None, traffic_start_rows=None) -> LayerResult:
         """Prioritised deconfliction by offset (`uavac_minsnap_layer_dev`): the second lever on `Engine.separation`'s verdict, for the
         conflicts that waiting cannot resolve (a shared first or last waypoint, a crossing of a busy region).  `start_rows` are FIXED
         starts -- `StaggerResult.start_rows`, for instance; nobody is delayed by this call.  Within a group the missions are taken in
@@ -709,16 +772,26 @@ class Engine:
         the boxes cover every layer 0 .. `max_steps`, so missions in different airspaces can never meet whatever layers they are
         granted.  `layers`, `steps`, `blocked` and `offsets` are exactly those of `wide=True` on the caller's groups; `earlier` counts
         within the airspace; the limit `LAYER_MAX_GROUP` applies to airspaces (above it the block-wise search with `group_cap` = the
-        largest airspace, whose block is (4, B); below it the narrow calls, (3, B) without `obstacles`)."""
+        largest airspace, whose block is (4, B); below it the narrow calls, (3, B) without `obstacles`).
+        `traffic`, `traffic_groups`, `traffic_start_rows`: committed missions that never move (`uavac_minsnap_layer_against_dev`), as
+        in `Engine.stagger`: a candidate layer must also be outside `radius` of every traffic mission of its group, which is compared
+        AS IT IS, on no layer, at its own start row -- pass the plan the traffic flies, shifted and delayed if it was.  Exactly
+        `uav_ac.scoring.layer_against_rows(..., max_group=group_cap)`; always the block-wise form with the cuboid policy (`block` is
+        (4, B), `wide` is not looked at); `earlier` counts the group's traffic too; `priority` composes unchanged; `airspaces=True`
+        with `traffic`, another `dt` and group counts that do not match are ValueErrors."""
+        against = dict(traffic=traffic, traffic_groups=traffic_groups, traffic_start_rows=traffic_start_rows)
         if airspaces:
+            if traffic is not None:
+                raise ValueError("airspaces=True does not take traffic: airspaces are not labelled across two plans")
             taken, rank, start, route = self._airspace_front(plan, radius, groups, self._layer_reach(delta, max_steps), priority, start_rows)
             return self._layer_back(self.layer(taken, radius, start_rows=start, delta=delta, max_steps=max_steps, obstacles=obstacles, **route),
                                     rank)
+        wide = wide or traffic is not None
         if priority is not None:
             B = int(self._coeff_plan(plan).B)
             order, rank, start = self._priority_order(priority, groups, B, None if wide else nat.LAYER_MAX_GROUP, start_rows)
             return self._layer_back(self.layer(self.take(plan, order), radius, groups, start, delta, max_steps, obstacles, wide=wide,
-                                               group_cap=group_cap), rank)
+                                               group_cap=group_cap, **against), rank)
         torch = self._torch
         plan = self._coeff_plan(plan)
         B = int(plan.B)
@@ -735,6 +808,12 @@ class Engine:
         if wide:
             cub, n = (None, 0) if obstacles is None else self._cuboids(obstacles, "search")
             block = torch.empty((nat.LAYER_OBS_ROWS, B), dtype=torch.int32, device=self.device)
+            if traffic is not None:
+                held, targs = self._traffic_args(plan, traffic, traffic_groups, traffic_start_rows, go, G)      # (`held` keeps the tensors alive)
+                self._bind_stream()
+                self.ctx.call("uavac_minsnap_layer_against_dev", *self._plan_args(plan), _ptr(go), G, *targs, cap, _ptr(start), float(radius),
+                              float(d[0]), float(d[1]), float(d[2]), max_steps, _ptr(cub) if n else None, n, _ptr(block), _ptr(offsets))
+                return LayerResult(*block[:nat.LAYER_ROWS].unbind(0), block, offsets)
             self._bind_stream()
             self.ctx.call("uavac_minsnap_layer_wide_dev", *self._plan_args(plan), _ptr(go), G, cap, _ptr(start), float(radius), float(d[0]),
                           float(d[1]), float(d[2]), max_steps, _ptr(cub) if n else None, n, _ptr(block), _ptr(offsets))
@@ -1058,7 +1137,7 @@ class Engine:
 
     def deconflict(self, plan, radius: float, groups=None, obstacles=None, start_rows=None, step: int = 1, max_delay_steps: int = 255,
                    delta=(0.0, 0.0, -0.5), max_layers: int = 63, priority=None, wide: bool = False, group_cap=None,
-                   airspaces: bool = False) -> DeconflictResult:
+                   airspaces: bool = False, traffic=None, traffic_groups=None, traffic_start_rows=None) -> DeconflictResult:
         """The fleet chain as one call: stagger -> layer -> shift -> delay.  `Engine.stagger(plan, radius, groups, start_rows, step,
         max_delay_steps)` makes missions wait; `Engine.layer(plan, radius, groups, start_rows=stagger.start_rows, delta=delta,
         max_steps=max_layers, obstacles=obstacles)` moves, at the granted starts, the ones that waiting cannot clear -- and, with
@@ -1091,18 +1170,32 @@ class Engine:
         ONCE, with `reach` = `max_layers` * `delta` -- boxes that cover the layers cover the starts too --, both searches run on one
         `Engine.take(plan, order)`, and `plan` is built from the caller's plan as in the `priority=` form: the same `stagger.start_rows`
         / `steps`, `layer.layers` / `steps` / `blocked` / `offsets`, `resolved` and `plan`, bit for bit, as `wide=True` gives;
-        `earlier` counts within the airspace, and the size limits apply to airspaces."""
+        `earlier` counts within the airspace, and the size limits apply to airspaces.
+        `traffic`, `traffic_groups`, `traffic_start_rows`: NEWCOMERS AROUND COMMITTED TRAFFIC THAT NEVER MOVES -- the missions of an
+        earlier `deconflict` that have been granted their starts and layers, or are in the air.  The chain is the same: stagger
+        against the traffic, layer against the traffic at the granted starts, shift, delay -- `Engine.stagger(..., traffic=)` and
+        `Engine.layer(..., traffic=)`, always block-wise (`wide` is not looked at, `group_cap` as for `wide=True`).  `traffic` is the
+        plan the committed missions FLY (an earlier `result.plan`: shifted and delayed), with `traffic_start_rows` None, or any plan
+        with its start rows.  `result.plan` holds the NEWCOMERS ONLY, and nothing of the traffic is decided, moved or written -- two
+        committed missions that conflict with each other stay as they are, which a `priority=` on a re-run of everybody could not
+        promise.  `Engine.concat([traffic, result.plan])` is the new committed fleet.  GUARANTEES, in addition to those above:
+        `Engine.separation_against(result.plan, traffic, radius, groups, traffic_groups, traffic_start_rows=traffic_start_rows)`
+        reports `conflicts == 0` for every resolved mission.  `airspaces=True` with `traffic` is a ValueError (airspaces are not
+        labelled across two plans); so are a different `dt` and group counts that do not match."""
+        against = dict(traffic=traffic, traffic_groups=traffic_groups, traffic_start_rows=traffic_start_rows)
         if airspaces:
+            if traffic is not None:
+                raise ValueError("airspaces=True does not take traffic: airspaces are not labelled across two plans")
             taken, rank, start, route = self._airspace_front(plan, radius, groups, self._layer_reach(delta, max_layers), priority, start_rows)
             stag = self.stagger(taken, radius, start_rows=start, step=step, max_steps=max_delay_steps, **route)
             lay = self.layer(taken, radius, start_rows=stag.start_rows, delta=delta, max_steps=max_layers, obstacles=obstacles, **route)
             stag, lay = self._stagger_back(stag, rank), self._layer_back(lay, rank)
             flown = self.delay(self.shift(plan, lay.offsets), stag.start_rows)
             return DeconflictResult(flown, stag, lay, lay.steps >= 0)
-        w = dict(wide=wide, group_cap=group_cap)
+        w = dict(wide=wide or traffic is not None, group_cap=group_cap, **against)
         if priority is not None:
             B = int(self._coeff_plan(plan).B)
-            order, rank, start = self._priority_order(priority, groups, B, None if wide else min(nat.STAGGER_MAX_GROUP, nat.LAYER_MAX_GROUP),
+            order, rank, start = self._priority_order(priority, groups, B, None if w["wide"] else min(nat.STAGGER_MAX_GROUP, nat.LAYER_MAX_GROUP),
                                                       start_rows)
             taken = self.take(plan, order)
             stag = self.stagger(taken, radius, groups=groups, start_rows=start, step=step, max_steps=max_delay_steps, **w)

@@ -325,20 +325,23 @@ def _max_group(max_group, narrow) -> int:
     return int(max_group)
 
 
-def _prioritised_search(N, included, go, max_group, max_steps, pos, start, r2, blocked=None):
+def _prioritised_search(N, included, go, max_group, max_steps, pos, start, r2, blocked=None, committed=None):
     """The search the stagger and the layer rules share.  Candidate q of mission i stands at the positions pos(i, q) (N_i, 3) from
     start row start(i, q) on; per group the included missions in ascending index examine q = 0 .. max_steps against the GRANTED
     candidates of the missions decided before them (candidate 0 for an unresolved one), up to the horizon max(every partner's end,
     the candidate's own end).  `blocked(i, q)`: refused before anybody is compared -- and then the first of a group is examined too.
     pos is only called for a candidate that is compared with somebody, and for a partner's granted one.
+    `committed(g)`: the (key, candidate) pairs that count as decided before the group's first mission -- the TRAFFIC of the
+    `*_against_rows` rules; a key is B or above, N, pos and start know it, and it is never examined itself.  The group limit counts
+    the group's own missions only.
     -> steps (-2: not examined, -1: unresolved), earlier, refused candidates: (B,) each."""
-    B = len(N)
+    B = len(included)
     steps, earlier, refused = np.full(B, -2), np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
     for g in range(len(go) - 1):
         g0, g1 = int(go[g]), int(go[g + 1])
         if g1 - g0 > max_group:
             continue
-        done = []                                                                     # (mission, granted candidate) of the included missions decided so far
+        done = [] if committed is None else list(committed(g))                       # (mission, granted candidate) of the included missions decided so far
         for i in range(g0, g1):
             if not included[i]:
                 continue
@@ -942,6 +945,122 @@ def stagger_from_rows(rows, row_offsets, radius, group_offsets=None, start_rows=
     return istag
 
 
+def _traffic_side(traffic_rows, traffic_row_offsets, group_offsets, traffic_group_offsets, traffic_start_rows, go, upper=_MAX_CLOCK,
+                  longest=_MAX_CLOCK):
+    """The TRAFFIC of the `*_against_rows` rules, a second plan on sampled rows: `traffic_rows` (Nt, >= 3), `traffic_row_offsets`
+    (Bt + 1,) -- Bt may be 0 --, `traffic_start_rows` (Bt,) or None = all 0, clamped like the plan's, `traffic_group_offsets` (G + 1,)
+    ascending from 0 to Bt: group g of the plan meets group g of the traffic and nobody else's, so both sides give offsets, with the
+    same G, or neither does (one group each); anything else is a ValueError.
+    -> (pos: list of (N_j, 3), N (Bt,), S (Bt,), offsets (G + 1,), included (Bt,) bool)."""
+    rows = _host(traffic_rows)
+    rows = rows if rows.ndim == 2 else rows.reshape(-1, 3)                                # (no traffic at all: an empty array of any shape)
+    ro = _host_i64(traffic_row_offsets)
+    Bt = len(ro) - 1
+    if Bt < 0:
+        raise ValueError("traffic_row_offsets hold at least one entry")
+    if (group_offsets is None) != (traffic_group_offsets is None):
+        raise ValueError("group_offsets and traffic_group_offsets go together: both or none")
+    tgo = _group_offsets(traffic_group_offsets, Bt)
+    if len(tgo) != len(go):
+        raise ValueError(f"the plan has {len(go) - 1} groups, the traffic {len(tgo) - 1}")
+    S = _start_rows(traffic_start_rows, Bt, upper)
+    N = np.diff(ro)
+    pos = [rows[ro[b]:ro[b + 1], 0:3] for b in range(Bt)]
+    return pos, N, S, tgo, _included(pos.__getitem__, N, longest)
+
+
+def separation_against_rows(rows, row_offsets, traffic_rows, traffic_row_offsets, radius, group_offsets=None, traffic_group_offsets=None,
+                            start_rows=None, traffic_start_rows=None):
+    """The CROSS audit recomputed from sampled rows -- the SPECIFICATION of `uavac_minsnap_separation_against_dev`
+    (csrc/minsnap_separation_against.hip), which is tested against it bit for bit.  NumPy on the host.
+    `rows`, `row_offsets`, `radius`, `group_offsets`, `start_rows` as `separation_from_rows` takes them: the PLAN.  `traffic_rows`,
+    `traffic_row_offsets`, `traffic_group_offsets`, `traffic_start_rows`: the TRAFFIC, a second plan on the same dt (`_traffic_side`:
+    group g of the plan meets group g of the traffic; offsets on both sides or on neither).
+
+    Every mission of the plan is compared with every included traffic mission of its group, and with nobody else: never with another
+    mission of the plan.  The clock is `separation_from_rows`': a mission on either side stands at its own row clamp(k - S, 0, N - 1),
+    and k runs below the horizon H_g = max(S + N) over the included missions of BOTH sides of the group.  Excluded missions (no rows,
+    or a position that is not finite) as there: excluded traffic is nobody's partner and is not counted, an excluded plan mission
+    reports NaN / -1 / -1 / 0 / -1 / 0.  A plan mission whose group has no included traffic reports +inf / -1 / -1 / 0 / -1 / 0.
+    Arithmetic and ties as there: d^2 = (dx * dx + dy * dy) + dz * dz, the lexicographic minimum of (d^2, clock row, partner), one
+    sqrt last, inside means d^2 < r^2 strictly.
+    -> (sep (B,) f64, isep (SEP_ROWS, B) i32) with the layout of `separation_from_rows`: partner = the TRAFFIC batch index; the clock
+    row of the minimum; conflicts = the traffic missions that come inside the radius; the first clock row with one inside; compared =
+    the included traffic missions of the group."""
+    rows = _host(rows)
+    ro = _host_i64(row_offsets)
+    B = len(ro) - 1
+    radius = _radius(radius)
+    go = _group_offsets(group_offsets, B)
+    S = _start_rows(start_rows, B, upper=None)
+    r2 = radius * radius
+    N = np.diff(ro)
+    pos = [rows[ro[b]:ro[b + 1], 0:3] for b in range(B)]
+    included = _included(pos.__getitem__, N, longest=None)
+    tpos, tN, tS, tgo, tinc = _traffic_side(traffic_rows, traffic_row_offsets, group_offsets, traffic_group_offsets, traffic_start_rows, go,
+                                            upper=None, longest=None)
+    sep = np.full(B, np.nan)
+    isep = np.zeros((nat.SEP_ROWS, B), dtype=np.int32)
+    isep[[SEP_PARTNER, SEP_ROW, SEP_FIRST_CONFLICT]] = -1
+    for g in range(len(go) - 1):
+        members = [b for b in range(int(go[g]), int(go[g + 1])) if included[b]]
+        partners = [j for j in range(int(tgo[g]), int(tgo[g + 1])) if tinc[j]]
+        if not members:
+            continue
+        if not partners:
+            sep[members] = np.inf
+            continue
+        k = np.arange(int(max(max(S[b] + N[b] for b in members), max(tS[j] + tN[j] for j in partners))))
+        T = np.stack([_at(tpos[j], k, tS[j]) for j in partners])                         # (n, H, 3): where the traffic stands at clock row k
+        for b in members:
+            own = _at(pos[b], k, S[b])
+            dx, dy, dz = (own[:, c][:, None] - T[:, :, c].T for c in range(3))            # (H, n): rows first, partners ascending
+            d2 = (dx * dx + dy * dy) + dz * dz
+            row, j = divmod(int(np.argmin(d2)), len(partners))                           # the first minimum: lowest row, then lowest partner
+            sep[b] = np.sqrt(d2[row, j])
+            isep[SEP_PARTNER, b], isep[SEP_ROW, b], isep[SEP_COMPARED, b] = partners[j], row, len(partners)
+            inside = d2 < r2
+            isep[SEP_CONFLICTS, b] = int(inside.any(axis=0).sum())
+            hit_rows = np.flatnonzero(inside.any(axis=1))
+            isep[SEP_FIRST_CONFLICT, b] = hit_rows[0] if len(hit_rows) else -1
+    return sep, isep
+
+
+def stagger_against_rows(rows, row_offsets, traffic_rows, traffic_row_offsets, radius, group_offsets=None, traffic_group_offsets=None,
+                         start_rows=None, traffic_start_rows=None, step=1, max_steps=255, max_group=None):
+    """`stagger_from_rows` against committed TRAFFIC that never moves -- the SPECIFICATION of `uavac_minsnap_stagger_against_dev`
+    (csrc/minsnap_stagger_against.hip), which is tested against it exactly.  NumPy on the host.
+    The plan's arguments, the clock, the excluded missions, the arithmetic and the rule are `stagger_from_rows`', with `max_group` =
+    the call's `group_cap` (None: no limit but the batch -- the call is always block-wise; the limit counts the plan's missions of a
+    group only).  The traffic's are `separation_against_rows`': a second plan on the same dt whose group g meets the plan's group g.
+    A traffic mission stands as planned at its start row `traffic_start_rows[j]` (clamped to 0 .. 2^29): it has no candidates, is never
+    examined and never written; an excluded one is nobody's partner and is not counted.
+    ONE MORE CLAUSE IN "CLEAR": candidate q of mission i is clear iff it is outside the radius of every included mission j < i of its
+    group at its granted start AND of every included traffic mission of its group at that mission's start, at every clock row below
+    the horizon, which covers the traffic's ends too.  `earlier` counts the included traffic of the group plus the included plan
+    missions before it, and the first included mission of a group is examined whenever its group has included traffic.  A group
+    without included traffic gives exactly `stagger_from_rows(..., max_group=max_group)`.
+    -> istag (STAGGER_ROWS, B) i32, as `stagger_from_rows`."""
+    rows = _host(rows)
+    ro = _host_i64(row_offsets)
+    B = len(ro) - 1
+    radius, step, max_steps = _radius(float(radius)), int(step), int(max_steps)
+    if step < 1 or not (0 <= max_steps <= nat.STAGGER_MAX_STEPS) or step * max_steps > _MAX_CLOCK:
+        raise ValueError(f"step must be >= 1, max_steps in 0 .. {nat.STAGGER_MAX_STEPS}, step * max_steps at most 2^29")
+    go = _group_offsets(group_offsets, B)
+    S = _start_rows(start_rows, B)
+    N = np.diff(ro)
+    pos = [rows[ro[b]:ro[b + 1], 0:3] for b in range(B)]
+    tpos, tN, tS, tgo, tinc = _traffic_side(traffic_rows, traffic_row_offsets, group_offsets, traffic_group_offsets, traffic_start_rows, go)
+    steps, earlier, _ = _prioritised_search(
+        np.concatenate([N, tN]), _included(pos.__getitem__, N), go, _max_group(max_group, max(B, 1)), max_steps,
+        lambda i, q: pos[i] if i < B else tpos[i - B], lambda i, q: int(S[i]) + q * step if i < B else int(tS[i - B]), radius * radius,
+        committed=lambda g: [(B + j, 0) for j in range(int(tgo[g]), int(tgo[g + 1])) if tinc[j]])
+    istag = np.zeros((nat.STAGGER_ROWS, B), dtype=np.int32)
+    istag[STAG_START], istag[STAG_STEPS], istag[STAG_EARLIER] = S + np.maximum(steps, 0) * step, steps, earlier
+    return istag
+
+
 def stagger_ok(istag) -> dict:
     """A stagger result (`Engine.stagger` -> StaggerResult, anything with `steps`, or the [STAGGER_ROWS][B] block itself; tensors on
     any device or arrays) -> dict of (B,) bool host arrays: `resolved` (steps >= 0: a start was granted) and `examined` (steps !=
@@ -1030,8 +1149,28 @@ def layer_obstacles_from_rows(rows_at, row_offsets, radius, cuboids, group_offse
     return _layer_search(rows_at, row_offsets, radius, cuboids, group_offsets, start_rows, max_steps, max_group)
 
 
-def _layer_search(rows_at, row_offsets, radius, cuboids, group_offsets, start_rows, max_steps, max_group=None):
-    """Both layer rules -> ilayer (LAYER_OBS_ROWS, B) i32.  Without cuboids nothing is ever blocked and rows 0-2 are `layer_from_rows`."""
+def layer_against_rows(rows_at, row_offsets, traffic_rows, traffic_row_offsets, radius, cuboids=None, group_offsets=None,
+                       traffic_group_offsets=None, start_rows=None, traffic_start_rows=None, max_steps=63, max_group=None):
+    """`layer_obstacles_from_rows` against committed TRAFFIC that never moves -- the SPECIFICATION of
+    `uavac_minsnap_layer_against_dev` (csrc/minsnap_layer_against.hip), which is tested against it exactly.  NumPy on the host.
+    `rows_at`, `row_offsets`, `radius`, `cuboids` (None or zero rows: no obstacles), `group_offsets`, `start_rows`, `max_steps` as
+    `layer_obstacles_from_rows` takes them, and the rule is that one's -- the cuboid policy: every included mission is examined, a
+    blocked candidate is refused before anybody is compared --, with `max_group` = the call's `group_cap` (None: no limit but the
+    batch).  The traffic's arguments are `stagger_against_rows`'; a traffic mission is compared AS IT IS, on no layer, at its start
+    row (a caller who has layered the traffic passes the rows of the shifted plan), has no candidates and is never examined.
+    One more clause in "clear": the candidate is also outside the radius of every included traffic mission of its group, up to a
+    horizon that covers the traffic's ends too; `earlier` counts the included traffic of the group plus the included plan missions
+    before it.  A group without included traffic gives exactly `layer_obstacles_from_rows(..., max_group=max_group)`.
+    -> ilayer (LAYER_OBS_ROWS, B) i32, as `layer_obstacles_from_rows`."""
+    B = len(_host_i64(row_offsets)) - 1
+    return _layer_search(rows_at, row_offsets, radius, () if cuboids is None else cuboids, group_offsets, start_rows, max_steps,
+                         max(B, 1) if max_group is None else max_group,
+                         traffic=(traffic_rows, traffic_row_offsets, traffic_group_offsets, traffic_start_rows))
+
+
+def _layer_search(rows_at, row_offsets, radius, cuboids, group_offsets, start_rows, max_steps, max_group=None, traffic=None):
+    """Both layer rules -> ilayer (LAYER_OBS_ROWS, B) i32.  Without cuboids nothing is ever blocked and rows 0-2 are `layer_from_rows`.
+    `traffic`: (rows, row_offsets, group_offsets, start_rows) of `layer_against_rows`."""
     ro = _host_i64(row_offsets)
     B = len(ro) - 1
     radius, max_steps = float(radius), int(max_steps)
@@ -1050,7 +1189,17 @@ def _layer_search(rows_at, row_offsets, radius, cuboids, group_offsets, start_ro
     S = _start_rows(start_rows, B)
     N = np.diff(ro)
 
+    committed = None
+    if traffic is not None:                                                           # (keys B .. B + Bt - 1: as planned, at their own starts)
+        tpos, tN, tS, tgo, tinc = _traffic_side(traffic[0], traffic[1], group_offsets, traffic[2], traffic[3], go)
+        N, S = np.concatenate([N, tN]), np.concatenate([S, tS])
+
+        def committed(g):
+            return [(B + j, 0) for j in range(int(tgo[g]), int(tgo[g + 1])) if tinc[j]]
+
     def pos(b, q):                                                                    # the candidate is a layer: the mission's rows of rows_at(q)
+        if b >= B:
+            return tpos[b - B]
         return _host(rows_at(q))[ro[b]:ro[b + 1], 0:3]
 
     def is_blocked(b, q):
@@ -1061,8 +1210,8 @@ def _layer_search(rows_at, row_offsets, radius, cuboids, group_offsets, start_ro
                     return True
         return False
 
-    steps, earlier, blocked = _prioritised_search(N, _included(lambda b: pos(b, 0), N), go, _max_group(max_group, nat.LAYER_MAX_GROUP), max_steps, pos,
-                                                  lambda b, q: int(S[b]), radius * radius, is_blocked if len(cub) else None)
+    steps, earlier, blocked = _prioritised_search(N, _included(lambda b: pos(b, 0), N[:B]), go, _max_group(max_group, nat.LAYER_MAX_GROUP), max_steps, pos,
+                                                  lambda b, q: int(S[b]), radius * radius, is_blocked if len(cub) else None, committed)
     ilayer = np.zeros((nat.LAYER_OBS_ROWS, B), dtype=np.int32)
     ilayer[LAYER_LAYER], ilayer[LAYER_STEPS], ilayer[LAYER_EARLIER], ilayer[LAYER_BLOCKED] = np.maximum(steps, 0), steps, earlier, blocked
     return ilayer
