@@ -174,7 +174,8 @@ int uavac_clock_probe_dev(uavac_ctx *ctx, int window_us, int64_t *stamps);
  * (default: sized from B and K) or 1 .. UAVAC_FLOWN_AUDIT_MAX_SPLIT = workgroups that share the ticks of one window of 64 vehicles in
  * uavac_flown_audit_dev (same results).  "conflict_slots": 0 (default: 64) or 1 .. 64 = j-tile slots per mission and discovery round
  * of the conflict lists (uavac_minsnap_conflict_offsets_dev, uavac_minsnap_conflicts_dev, uavac_flown_conflict_offsets_dev,
- * uavac_flown_conflicts_dev; same results, less scratch, more rounds).  "search_block": 0 (default: 64), 64, 128 or 256 = missions per
+ * uavac_flown_conflicts_dev, and the two cross calls uavac_minsnap_conflict_against_offsets_dev, uavac_minsnap_conflicts_against_dev;
+ * same results, less scratch, more rounds).  "search_block": 0 (default: 64), 64, 128 or 256 = missions per
  * block of uavac_minsnap_stagger_wide_dev and uavac_minsnap_layer_wide_dev (same results).
  * Defaults from the environment (UAVAC_ROLLOUT_ALIGN, UAVAC_YAW_GROUP, UAVAC_SAMPLER_WAVES, UAVAC_SAMPLER_GROUP) at uavac_create.
  * ONE option is not a tuning knob but part of the log layout: "log_pitch" = P doubles per log row,
@@ -672,7 +673,45 @@ int uavac_minsnap_layer_wide_dev(uavac_ctx *ctx, const double *coeffs, const int
  * layered the traffic passes the shifted plan (uavac_minsnap_shift_dev).  earlier counts the included traffic plus the included plan
  * missions before it; a group without included traffic gives exactly uavac_minsnap_layer_wide_dev's answers.  Exactly what NumPy
  * gives (uav_ac.scoring.layer_against_rows(..., max_group = group_cap)).  Refuses what uavac_minsnap_layer_wide_dev refuses.  Launches,
- * scratch and UAVAC_ENOMEM as in uavac_minsnap_stagger_against_dev. */
+ * scratch and UAVAC_ENOMEM as in uavac_minsnap_stagger_against_dev.
+ *
+ * uavac_minsnap_conflict_against_offsets_dev, uavac_minsnap_conflicts_against_dev: THE CROSS CONFLICT LIST, the cross audit's conflict
+ * graph in CSR form (csrc/minsnap_conflicts_against.hip).  What uavac_minsnap_conflict_offsets_dev / uavac_minsnap_conflicts_dev are to
+ * uavac_minsnap_separation_dev, these two are to the cross audit: the same two calls in the same order (offsets -> read pair_offsets[B]
+ * -> allocate -> fill), pair_offsets [B + 1] i64, pair_d [capacity] f64 and pair_i [UAVAC_CONF_ROWS][capacity] i32 with the rows of
+ * CONFLICT LIST above.  Everything in this block applies -- clock, groups, excluded missions, rounding, bad inputs and their flags --
+ * and so does the conflict list's contract:
+ *   THE LIST.  Mission i of the PLAN lists every included traffic mission j of its group with d^2(i, j, k) < r^2 -- strictly -- at some
+ *   clock row k in [0, H_g), H_g over both sides, in ascending j; row 0, the partner, is the TRAFFIC batch index (0 .. Bt - 1).
+ *   Missions of the plan are never compared with each other.  An excluded plan mission lists nothing, excluded traffic is listed by
+ *   nobody, a group without included traffic lists nothing.
+ *   The fill repeats the discovery and relies on nothing the offsets call left behind.
+ *   BOUNDS.  An entry is written only inside the mission's slice, at or above 0 and below `capacity`.  Sticky flag 2 is raised when the
+ *   buffers end inside a slice; sticky flag 0 when a slice holds another number of entries than the mission has partners (what fits is
+ *   filled in ascending partner order, the rest of the slice is left as it was).  capacity == 0 with pair_d == pair_i == NULL is allowed.
+ *   Neither call writes to any array of either plan.
+ * WHAT THE RESULT GUARANTEES, on the same inputs as uavac_minsnap_separation_against_dev: diff(pair_offsets) == isep[2], the cross
+ * audit's conflicts.  The minimum of row 1 over a mission's entries == isep[3], its first_conflict.  For a mission with an entry the
+ * audit's (sep, row, partner) is the lexicographic minimum of (pair_d, row 4, partner) over its entries.  d^2 is bit-symmetric, so the
+ * list of the traffic against the plan (sides and groups swapped) is the transpose of this one, bit for bit
+ * (uav_ac.scoring.conflicts_transposed).  Every output is bit for bit what NumPy gives on the sampled rows
+ * (uav_ac.scoring.conflicts_against_rows), whatever the launch shape (options "separation_split" and "conflict_slots") or what else is
+ * in either batch: a group of both sides listed alone gives the same records with the partner indices shifted.
+ * UAVAC_EINVAL before anything is enqueued: what uavac_minsnap_separation_against_dev refuses for the two plans (required pointers:
+ * coeffs, seg_rows, pair_offsets; then the traffic's list above), then capacity < 0, pair_d or pair_i NULL with capacity > 0.
+ * Rounds: the discovery is repeated over the tile slots until ceil(Bt / 64) j-tiles, the most a traffic group can have, are covered.
+ * Scratch: the plan-side list's, plus 8 bytes per traffic mission.  Cost: each call about one cross audit; the fill adds entries x
+ * horizon. */
+int uavac_minsnap_conflict_against_offsets_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B,
+                                               int m, double dt, const int64_t *group_offsets, int G, const double *t_coeffs,
+                                               const int32_t *t_seg_rows, const int64_t *t_seg_offsets, int Bt, int mt,
+                                               const int64_t *t_group_offsets, const int32_t *t_start_rows, const int32_t *start_rows,
+                                               double radius, int64_t *pair_offsets);
+int uavac_minsnap_conflicts_against_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B,
+                                        int m, double dt, const int64_t *group_offsets, int G, const double *t_coeffs,
+                                        const int32_t *t_seg_rows, const int64_t *t_seg_offsets, int Bt, int mt,
+                                        const int64_t *t_group_offsets, const int32_t *t_start_rows, const int32_t *start_rows, double radius,
+                                        const int64_t *pair_offsets, int64_t capacity, double *pair_d, int32_t *pair_i);
 int uavac_minsnap_separation_against_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B,
                                          int m, double dt, const int64_t *group_offsets, int G, const double *t_coeffs,
                                          const int32_t *t_seg_rows, const int64_t *t_seg_offsets, int Bt, int mt,

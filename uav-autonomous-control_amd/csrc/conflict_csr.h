@@ -150,6 +150,17 @@ inline void shape_of(const uavac_ctx *ctx, int B, const int64_t *group_offsets, 
     s.rounds = (most + s.slots - 1) / s.slots;
 }
 
+// The same for a list whose partners are ANOTHER batch of Bt vehicles (minsnap_conflicts_against.hip): the windows and the shares are
+// the caller's, and the most j-tiles a group can have is ceil(Bt / 64), the partners' side, not the owners'.
+inline void shape_of_sides(const uavac_ctx *ctx, int windows, int P, int Bt, Shape &s) {
+    s.windows = windows;
+    s.P = P;
+    const int most = (Bt + kTile - 1) / kTile;               // j-tiles of the largest partner group there can be
+    s.slots = ctx->conflict_slots > 0 ? ctx->conflict_slots : kMaxSlots;
+    s.slots = s.slots > most ? most : s.slots;
+    s.rounds = (most + s.slots - 1) / s.slots;
+}
+
 // count, words and owner on the caller's Scratch, beside the caller's own pieces
 inline void shape_want(Scratch &scratch, Shape &s, int B, long long capacity) {
     scratch.want(&s.count, (size_t)B);

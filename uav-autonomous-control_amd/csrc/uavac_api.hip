@@ -1109,6 +1109,32 @@ int uavac_minsnap_separation_against_dev(uavac_ctx *ctx, const double *coeffs, c
                                            t_seg_offsets, Bt, mt, t_group_offsets, t_start_rows, radius, sep, isep);
 }
 
+int uavac_minsnap_conflict_against_offsets_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B,
+                                               int m, double dt, const int64_t *group_offsets, int G, const double *t_coeffs,
+                                               const int32_t *t_seg_rows, const int64_t *t_seg_offsets, int Bt, int mt,
+                                               const int64_t *t_group_offsets, const int32_t *t_start_rows, const int32_t *start_rows,
+                                               double radius, int64_t *pair_offsets) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_pair_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, pair_offsets != nullptr)) return rc;
+    if (int rc = check_traffic_args(ctx, group_offsets, t_coeffs, t_seg_rows, Bt, mt, t_group_offsets)) return rc;
+    return uavac_launch_conflict_against_offsets(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, t_coeffs,
+                                                 t_seg_rows, t_seg_offsets, Bt, mt, t_group_offsets, t_start_rows, radius, pair_offsets);
+}
+
+int uavac_minsnap_conflicts_against_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B,
+                                        int m, double dt, const int64_t *group_offsets, int G, const double *t_coeffs,
+                                        const int32_t *t_seg_rows, const int64_t *t_seg_offsets, int Bt, int mt,
+                                        const int64_t *t_group_offsets, const int32_t *t_start_rows, const int32_t *start_rows, double radius,
+                                        const int64_t *pair_offsets, int64_t capacity, double *pair_d, int32_t *pair_i) {
+    UAVAC_ENTER(ctx);
+    if (int rc = check_pair_args(ctx, coeffs, seg_rows, B, m, dt, group_offsets, G, radius, pair_offsets != nullptr)) return rc;
+    if (int rc = check_traffic_args(ctx, group_offsets, t_coeffs, t_seg_rows, Bt, mt, t_group_offsets)) return rc;
+    if (capacity < 0) return uavac_fail(ctx, UAVAC_EINVAL, "capacity must be >= 0");
+    if (capacity > 0 && (!pair_d || !pair_i)) return uavac_fail(ctx, UAVAC_EINVAL, "pair_d and pair_i are required when capacity > 0");
+    return uavac_launch_conflicts_against(ctx, coeffs, seg_rows, seg_offsets, B, m, dt, group_offsets, G, start_rows, t_coeffs, t_seg_rows,
+                                          t_seg_offsets, Bt, mt, t_group_offsets, t_start_rows, radius, pair_offsets, capacity, pair_d, pair_i);
+}
+
 int uavac_minsnap_stagger_against_dev(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
                                       double dt, const int64_t *group_offsets, int G, const double *t_coeffs, const int32_t *t_seg_rows,
                                       const int64_t *t_seg_offsets, int Bt, int mt, const int64_t *t_group_offsets,

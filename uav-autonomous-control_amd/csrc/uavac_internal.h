@@ -297,6 +297,17 @@ int uavac_launch_separation_against(uavac_ctx *ctx, const double *coeffs, const 
                                     double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, const double *t_coeffs,
                                     const int32_t *t_seg_rows, const int64_t *t_seg_offsets, int Bt, int mt, const int64_t *t_group_offsets,
                                     const int32_t *t_start_rows, double radius, double *sep, int32_t *isep);
+// the cross audit's conflict graph in CSR form (minsnap_conflicts_against.hip): pair_offsets [B + 1], then pair_d [capacity] and pair_i
+// [UAVAC_CONF_ROWS][capacity] with TRAFFIC batch indices as partners; scratch from the ctx arena
+int uavac_launch_conflict_against_offsets(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B,
+                                          int m, double dt, const int64_t *group_offsets, int G, const int32_t *start_rows,
+                                          const double *t_coeffs, const int32_t *t_seg_rows, const int64_t *t_seg_offsets, int Bt, int mt,
+                                          const int64_t *t_group_offsets, const int32_t *t_start_rows, double radius, int64_t *pair_offsets);
+int uavac_launch_conflicts_against(uavac_ctx *ctx, const double *coeffs, const int32_t *seg_rows, const int64_t *seg_offsets, int B, int m,
+                                   double dt, const int64_t *group_offsets, int G, const int32_t *start_rows, const double *t_coeffs,
+                                   const int32_t *t_seg_rows, const int64_t *t_seg_offsets, int Bt, int mt, const int64_t *t_group_offsets,
+                                   const int32_t *t_start_rows, double radius, const int64_t *pair_offsets, int64_t capacity, double *pair_d,
+                                   int32_t *pair_i);
 int uavac_launch_shift(uavac_ctx *ctx, const double *coeffs, const int64_t *seg_offsets, int B, int m, int64_t total_segments,
                        const double *offsets, double *out_coeffs);
 // the same search, refusing every layer on which a row of the mission's own lies inside a cuboid (minsnap_layer_obs.hip): cuboids

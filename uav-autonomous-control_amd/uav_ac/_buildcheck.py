@@ -231,6 +231,12 @@ BUDGETS = (
     # the cross audit: the plan audit's pair kernel with its partners taken from the traffic, the 48 KB tile, three workgroups per CU
     Budget("separation_against_kernels", "minsnap_separation_against.o", "cross-audit",
            ("against_prepass_kernel", "separation_against_kernel", "against_merge_kernel"), FROM_LDS),
+    # the cross audit's conflict list: the discovery is the cross audit's loop nest keeping bits only, the measure walks one mission of
+    # either plan; both keep the 48 KB tile (three workgroups per CU, <= 168); the pre-pass, the counts and the list of conflict_csr.h
+    # run eight waves per SIMD (<= 64)
+    Budget("cross_conflict_kernels", "minsnap_conflicts_against.o", "cross-conflict-list",
+           ("conflict_against_prepass_kernel", "conflict_against_discover_kernel", "conflict_count_kernel", "conflict_list_kernel",
+            "conflict_against_measure_kernel"), FROM_LDS),
 )
 DECISION_KERNELS =("minsnap_layer_kernel", "wide_layer_kernel", "wide_stagger_kernel")      # FROM_LDS: these keep three workgroups per CU
 COUNTED = ("rollout_registers", "planning_registers")      # `run_all` reports these as a number of kernels, the others as {kernel: VGPRs}
@@ -329,6 +335,7 @@ def check_layer_wide_kernels(): return vgprs(check_budgets("layer_wide_kernels")
 def check_stagger_against_kernels(): return vgprs(check_budgets("stagger_against_kernels"))             # noqa: E704
 def check_layer_against_kernels(): return vgprs(check_budgets("layer_against_kernels"))                 # noqa: E704
 def check_separation_against_kernels(): return vgprs(check_budgets("separation_against_kernels"))       # noqa: E704
+def check_cross_conflict_kernels(): return vgprs(check_budgets("cross_conflict_kernels"))               # noqa: E704
 TIMEOPT_KERNELS = next(row.kernels for row in BUDGETS if row.key == "timeopt_kernels")
 FLOWN_CONFLICT_KERNELS = next(row.kernels for row in BUDGETS if row.key == "flown_conflict_kernels")
 

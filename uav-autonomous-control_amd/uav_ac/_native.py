@@ -119,6 +119,10 @@ _SIGNATURES = {
     # against traffic: the seven arguments of the second plan (t_coeffs, t_seg_rows, t_seg_offsets, Bt, mt, t_group_offsets, t_start_rows) behind G
     "uavac_minsnap_separation_against_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int,
                                                        _P, _P, _P, C.c_double, _P, _P]),
+    "uavac_minsnap_conflict_against_offsets_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, _P, _P, C.c_int,
+                                                             C.c_int, _P, _P, _P, C.c_double, _P]),
+    "uavac_minsnap_conflicts_against_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int,
+                                                      _P, _P, _P, C.c_double, _P, C.c_int64, _P, _P]),
     "uavac_minsnap_stagger_against_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P,
                                                     _P, C.c_int, _P, C.c_double, C.c_int, C.c_int, _P]),
     "uavac_minsnap_layer_against_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P,

@@ -600,6 +600,28 @@ class Engine:
         B, held, pair_args = self._pair_args(plan, radius, groups, start_rows)      # (`held` keeps the pointers' tensors alive)
         return self._conflict_list("uavac_minsnap_conflict_offsets_dev", "uavac_minsnap_conflicts_dev", pair_args, B)
 
+    def conflicts_against(self, plan, traffic, radius: float, groups=None, traffic_groups=None, start_rows=None,
+                          traffic_start_rows=None) -> ConflictList:
+        """Every traffic mission that `Engine.separation_against` counts as a conflict of a plan mission, with when and how near
+        (`uavac_minsnap_conflict_against_offsets_dev`, `uavac_minsnap_conflicts_against_dev`): mission i of `plan` lists each mission
+        of its group's committed `traffic` that comes inside `radius` at some row of the shared clock, in ascending TRAFFIC batch
+        index (`partner`), with the first and the last row inside, the number of rows inside, and the pair's closest approach and its
+        row -- bit for bit what NumPy gives on the sampled rows (`uav_ac.scoring.conflicts_against_rows`).  Every argument as
+        `Engine.separation_against` takes it, with its ValueErrors (another `dt`, unmatched groups), and on the same inputs
+        diff(offsets) is its `conflicts`, the least `first_row` of a mission its `first_conflict`, and its (min_distance, row,
+        partner) the least (min_distance, min_row, partner) of the mission's entries.  Missions of `plan` are never compared with
+        each other (`Engine.conflicts` does that).  `uav_ac.scoring.conflicts_transposed(cl, traffic.B)` is the same list seen from
+        the traffic's side.  Never reads `traj`, writes to neither plan.  ONE small host read: the number of entries, to size the
+        result; without entries the second launch is skipped.  After `Engine.deconflict(..., traffic=)` this names the committed
+        missions that stand in the way of each unresolved arrival."""
+        plan = self._coeff_plan(plan)
+        B = int(plan.B)
+        go, G = self._groups(groups, B)
+        start = None if start_rows is None else self._start_rows(start_rows, B)
+        held, targs = self._traffic_args(plan, traffic, traffic_groups, traffic_start_rows, go, G)      # (`held` keeps the pointers' tensors alive)
+        return self._conflict_list("uavac_minsnap_conflict_against_offsets_dev", "uavac_minsnap_conflicts_against_dev",
+                                   (*self._plan_args(plan), _ptr(go), G, *targs, _ptr(start), float(radius)), B)
+
     def stagger(self, plan, radius: float, groups=None, start_rows=None, step: int = 1, max_steps: int = 255,
                 priority=None, wide: bool = False, group_cap=None, airspaces: bool = False, traffic=None, traffic_groups=None,
                 traffic_start_rows=None) -> StaggerResult:

@@ -1026,6 +1026,86 @@ def separation_against_rows(rows, row_offsets, traffic_rows, traffic_row_offsets
     return sep, isep
 
 
+def conflicts_against_rows(rows, row_offsets, traffic_rows, traffic_row_offsets, radius, group_offsets=None, traffic_group_offsets=None,
+                           start_rows=None, traffic_start_rows=None):
+    """The CROSS conflict list recomputed from sampled rows -- the SPECIFICATION of `uavac_minsnap_conflict_against_offsets_dev` and
+    `uavac_minsnap_conflicts_against_dev` (csrc/minsnap_conflicts_against.hip), which are tested against it bit for bit.  NumPy on
+    the host; inputs, clock, groups, excluded missions, horizon and rounding exactly as in `separation_against_rows`: group g of the
+    plan meets group g of the traffic, H_g covers both sides, each mission stands at clamp(k - S, 0, N - 1), d^2 = (dx * dx + dy * dy)
+    + dz * dz, inside is strict.
+    Mission i of the plan lists every included traffic mission j of its group with d^2(i, j, k) < r^2 at some clock row k below H_g,
+    in ascending j.  Missions of the plan are never compared with each other; an excluded plan mission lists nothing, excluded
+    traffic is listed by nobody, a group without included traffic lists nothing.
+    -> (offsets (B + 1,) i64, pair_d (E,) f64, pair_i (CONF_ROWS, E) i32) with the layout of `conflicts_from_rows`: per entry the
+    partner (the TRAFFIC batch index), the first and the last clock row inside, the number of rows inside, the clock row of the
+    pair's minimum (the lowest one on a tie), and the minimum distance (the minimum of the squares, one sqrt)."""
+    rows = _host(rows)
+    ro = _host_i64(row_offsets)
+    B = len(ro) - 1
+    radius = _radius(radius)
+    go = _group_offsets(group_offsets, B)
+    S = _start_rows(start_rows, B, upper=None)
+    r2 = radius * radius
+    N = np.diff(ro)
+    pos = [rows[ro[b]:ro[b + 1], 0:3] for b in range(B)]
+    included = _included(pos.__getitem__, N, longest=None)
+    tpos, tN, tS, tgo, tinc = _traffic_side(traffic_rows, traffic_row_offsets, group_offsets, traffic_group_offsets, traffic_start_rows, go,
+                                            upper=None, longest=None)
+    per_mission = [[] for _ in range(B)]                                                  # (partner, first, last, inside, row of the minimum, d^2)
+    for g in range(len(go) - 1):
+        members = [b for b in range(int(go[g]), int(go[g + 1])) if included[b]]
+        partners = [j for j in range(int(tgo[g]), int(tgo[g + 1])) if tinc[j]]
+        if not members or not partners:
+            continue
+        k = np.arange(int(max(max(S[b] + N[b] for b in members), max(tS[j] + tN[j] for j in partners))))
+        T = np.stack([_at(tpos[j], k, tS[j]) for j in partners])                         # (n, H, 3): where the traffic stands at clock row k
+        for i in members:
+            own = _at(pos[i], k, S[i])
+            dx, dy, dz = (own[:, c][None, :] - T[:, :, c] for c in range(3))              # (n, H): partners first, rows ascending
+            d2 = (dx * dx + dy * dy) + dz * dz
+            inside = d2 < r2
+            for c in np.flatnonzero(inside.any(axis=1)):
+                hit = np.flatnonzero(inside[c])
+                low = int(np.argmin(d2[c]))                                               # the first minimum: the lowest row
+                per_mission[i].append((partners[c], hit[0], hit[-1], len(hit), low, d2[c, low]))
+    offsets = np.concatenate([[0], np.cumsum([len(p) for p in per_mission])]).astype(np.int64)
+    flat = [e for p in per_mission for e in p]
+    pair_i = np.array([e[:5] for e in flat], dtype=np.int32).reshape(-1, nat.CONF_ROWS).T.copy()
+    pair_d = np.sqrt(np.array([e[5] for e in flat], dtype=np.float64))
+    return offsets, pair_d, pair_i
+
+
+def conflicts_transposed(cl, n_partners):
+    """The CSR transpose of a conflict list between two sides, on the host: the list seen from the owners' side (`cl`: the tuple
+    `conflicts_against_rows` returns, or an `Engine.conflicts_against` -> ConflictList, or anything with its fields; tensors on any
+    device or arrays) -> the list seen from the partners' side, as the same tuple (offsets (n_partners + 1,) i64, pair_d (E,) f64,
+    pair_i (CONF_ROWS, E) i32): per partner the owners that list it, in ascending index, with the same five values.  The distance is
+    bit-symmetric, so the transpose of `plan against traffic` is `traffic against plan` with the sides and their groups swapped, bit
+    for bit: "which arrivals does committed mission j have to expect", without a second device call.  The cross-side counterpart of
+    `conflict_pairs`.  A list whose slices do not sum to its entries, or with a partner outside 0 .. n_partners - 1, is a ValueError."""
+    if not hasattr(cl, "offsets"):
+        off, dist, block = _host_i64(cl[0]), _host(cl[1]).reshape(-1), _host(cl[2], np.int64)
+        if block.ndim != 2 or block.shape[0] != nat.CONF_ROWS:
+            raise ValueError("pair_i holds CONF_ROWS rows")
+    else:
+        off, dist = _host_i64(cl.offsets), _host(cl.min_distance).reshape(-1)
+        block = np.stack([_host_i64(v).reshape(-1) for v in (cl.partner, cl.first_row, cl.last_row, cl.rows_inside, cl.min_row)])
+    n_partners = int(n_partners)
+    E = len(dist)
+    if len(off) < 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != E or block.shape[1] != E:
+        raise ValueError("a conflict list holds offsets[-1] entries in every field, in slices that ascend from 0")
+    partner = block[0]
+    if n_partners < 0 or (E and (partner.min() < 0 or partner.max() >= n_partners)):
+        raise ValueError("a partner lies outside 0 .. n_partners - 1")
+    owner = np.repeat(np.arange(len(off) - 1, dtype=np.int64), np.diff(off))
+    order = np.lexsort((owner, partner))                                                  # by partner, then by owner: both ascend
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(partner, minlength=n_partners))]).astype(np.int64)
+    pair_i = np.empty((nat.CONF_ROWS, E), dtype=np.int32)
+    pair_i[0] = owner[order]
+    pair_i[1:] = block[1:, order]
+    return offsets, dist[order].astype(np.float64), pair_i
+
+
 def stagger_against_rows(rows, row_offsets, traffic_rows, traffic_row_offsets, radius, group_offsets=None, traffic_group_offsets=None,
                          start_rows=None, traffic_start_rows=None, step=1, max_steps=255, max_group=None):
     """`stagger_from_rows` against committed TRAFFIC that never moves -- the SPECIFICATION of `uavac_minsnap_stagger_against_dev`
